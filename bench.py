@@ -12,9 +12,12 @@ RCCL, issued by the library on the sweep's own stream (pml_allreduce_loglik).
 N > 1: one process per GPU.  Either the launcher provides RANK / LOCAL_RANK / WORLD_SIZE (torch.distributed.run), or
 `python bench.py --gpus N` starts the N rank processes itself (before anything touches a GPU) and relays rank 0's line.
 
-Prints ONE JSON line on rank 0.  After the timed region the posteriors of EVERY column are validated on a strided
-node sample (rows sum to one, every node sees the column's total likelihood, observed tips keep their state), and,
-on one GPU, the other BASELINE configs are timed in the same process (`secondary`).
+Prints ONE JSON line on rank 0.  A plain run sets up, warms up, times --steps steps and prints the headline line
+(`metric`, `value`, `unit`, `ms_per_step`, ...; with --dump-outputs DIR it first writes what the last step computed).
+With --full the line also carries the CPU baseline and the roofline figures, and after the timed region the
+posteriors of EVERY column are validated on a strided node sample (rows sum to one, every node sees the column's total
+likelihood, observed tips keep their state), and, on one GPU, the other BASELINE configs are timed in the same process
+(`secondary`).
 """
 import argparse
 import json
@@ -65,7 +68,17 @@ def parse_args():
                    help='tree levels of the subtree the CPU baseline is timed on (default 18: 262 144 tips)')
     p.add_argument('--cpu-baseline-cores', type=int, default=None,
                    help='worker processes of the CPU baseline (default: the cores this process may run on, at most 32)')
-    return p.parse_args()
+    p.add_argument('--full', action='store_true',
+                   help='everything beyond the headline: the CPU baseline, the validation of every column, the roofline '
+                        'figures and, on one GPU, the other configs (`secondary`); the --no-* switches '
+                        'above leave parts of it out')
+    p.add_argument('--dump-outputs', metavar='DIR', default=None,
+                   help='after the timed steps, write what the last step computed to DIR/<name>.npy (float64; see '
+                        'dump_outputs)')
+    args = p.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        p.error('--steps must be at least 1 and --warmup at least 0')
+    return args
 
 
 # ---------------------------------------------------------------------------------------------------------------------
@@ -381,8 +394,9 @@ def library_source_digest():
 
 
 def run_cpu_baseline(args, levels, k, model):
-    """The CPU baseline of this run (None if switched off): called from a process that has not touched a GPU."""
-    if args.no_cpu_baseline or under_profiler():
+    """The CPU baseline of this run (None without --full or if switched off): called from a process that has not touched a
+    GPU."""
+    if not args.full or args.no_cpu_baseline or under_profiler():
         return None
     cl = args.cpu_baseline_levels
     if cl is None:
@@ -1023,6 +1037,36 @@ def custom_rates_optimisation(nwk, k=20):
 
 
 # ---------------------------------------------------------------------------------------------------------------------
+DUMP_NODE_STRIDE = 4099       # the validation's node sample: 512 of the 2 097 151 nodes of cfg4 (8.7 MB for 32 columns)
+DUMP_SAMPLE_BYTES = 48 << 20  # a wider shard samples fewer nodes: the dump stays below 64 MB
+
+
+def dump_stride(n_nodes, n_cols, k):
+    """Node stride of the sampled tables of dump_outputs: k + 2 doubles per sampled node and column."""
+    return max(DUMP_NODE_STRIDE, -(-n_nodes * n_cols * (k + 2) * 8 // DUMP_SAMPLE_BYTES))
+
+
+def dump_outputs(out_dir, eng, lnl, total, suffix=''):
+    """
+    What the last timed step computed, as out_dir/<name><suffix>.npy, all float64: `loglik` (the columns' ln L, what
+    marginal_pass hands back), `loglik_sum` (the all-reduced total), and of the tables the step leaves in HBM the rows of
+    every stride-th node of every column (node 0 first; a fixed sample -- a whole posterior table is N x k x 8 B per
+    column): `posterior_sample` [columns, rows, k], `lh_sum_sample` and `lh_sf_sample` [columns, rows] (the marginal
+    likelihoods as mantissa sum and log10 scale, pastml/ml.py:468-483).  Returns {name: shape}.
+    """
+    from pastml_amd import hip
+    n_cols = eng.n_cols
+    stride = dump_stride(eng.n_nodes, n_cols, eng.k)
+    arrays = dict(loglik=np.asarray(lnl, dtype=np.float64), loglik_sum=np.array([total], dtype=np.float64))
+    for name, buf in (('posterior_sample', hip.BUF_POSTERIOR), ('lh_sum_sample', hip.BUF_LH_SUM),
+                      ('lh_sf_sample', hip.BUF_LH_SF)):
+        arrays[name] = np.stack([eng.download_strided(buf, c, 0, stride) for c in range(n_cols)]).astype(np.float64)
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + suffix + '.npy'), a)
+    return {name: list(a.shape) for name, a in arrays.items()}
+
+
 def main():
     args = parse_args()
     if 'RANK' not in os.environ and args.gpus > 1:
@@ -1136,12 +1180,16 @@ def main():
     bu_ms, bu_launches = bul_ms + bu2_ms, bul_launches + bu2_launches
     td_ms, td_launches = tdl_ms + td2_ms, tdl_launches + td2_launches
     eng.profile_enable(False)
-    held, free = eng.memory()
     # A check that fails on one rank must not leave the others waiting in the closing collective: failures are collected,
     # agreed on by all ranks (all-reduce of a flag), and every rank leaves through the same barrier before it exits.
     failure = None
     validation = None
-    if not args.no_validate:
+    if args.dump_outputs:
+        try:
+            dump_outputs(args.dump_outputs, eng, lnl, total, '' if world == 1 else '_rank{}'.format(rank))
+        except OSError as e:
+            failure = 'could not write the outputs to {}: {}'.format(args.dump_outputs, e)
+    if args.full and not args.no_validate:
         try:
             validation = validate_columns(eng, flat, k, tip_states, lnl, chars=chars)
         except SystemExit as e:
@@ -1150,6 +1198,36 @@ def main():
     if rank == 0:
         units_per_step = N * k * cpg * world
         value = units_per_step * args.steps / dt
+        out = {
+            'metric': 'ACR nodes*states*chars/sec (full marginal pass: P(t) + bottom-up + top-down + posteriors)',
+            'value': value,
+            'unit': 'node*state*char/s',
+            'n_gpus': world,
+            'steps': args.steps,
+            'warmup': args.warmup,
+            'ms_per_step': dt / args.steps * 1e3,
+            'higher_is_better': True,
+            'scaling': 'weak',
+            'vs_baseline': None,
+            'dtype': 'f64',
+            'data': 'synthetic',
+            'config': {'workload': '{}: balanced tree, {} tips ({} nodes), k={} states, {}, '
+                                   '{} characters per GPU ({} in total), marginal (BU+TD+posteriors)'
+                                   .format({'cfg4': 'BASELINE config 4 shard', 'cfg2': 'BASELINE config 2',
+                                            'cfg4_small': 'reduced config 4 (16 384 tips)'}[args.workload],
+                                           flat.n_tips, N, k, model, cpg, cpg * world),
+                       'tips': int(flat.n_tips), 'nodes': int(N), 'states': k, 'chars_per_gpu': cpg,
+                       'chars_total': cpg * world, 'substitution_model': model,
+                       'sharding': 'characters over ranks, no data-path collective; 1 all-reduce (8 B) per step',
+                       'collective': comm.name, **{k_: v_ for k_, v_ in comm_report.items() if k_ != 'collective'}},
+            'per_rank': per_rank,
+            'loglik_sum': total,
+            'kernel_ms_per_step': {'bottom_up': bu_ms / args.steps, 'top_down': td_ms / args.steps,
+                                   'prep': prep_ms / args.steps},
+            # which sources the library that ran was compiled from (pml_build_digest) next to what the tree holds now
+            'library': {'build_digest': hip.build_digest(), 'source_digest': library_source_digest()},
+        }
+    if rank == 0 and args.full:
         # dominant kernel: the top-down + marginals level kernel (td_f81_kernel).  achieved = compulsory bytes of this
         # schedule (schedule_bytes: DESIGN.md 4b) / the kernel's own time
         sb = schedule_bytes(flat, k, cpg)
@@ -1212,30 +1290,7 @@ def main():
                     'frac_of_output_floor': OUTPUT_FLOOR_BYTES_PER_UNIT * per_s / 1e9 / HBM_PEAK_GBS,
                     'frac_of_output_floor_achievable': OUTPUT_FLOOR_BYTES_PER_UNIT * per_s / 1e9 / HBM_ACHIEVABLE_GBS,
                     'achievable_peak': HBM_ACHIEVABLE_GBS}
-        out = {
-            'metric': 'ACR nodes*states*chars/sec (full marginal pass: P(t) + bottom-up + top-down + posteriors)',
-            'value': value,
-            'unit': 'node*state*char/s',
-            'n_gpus': world,
-            'steps': args.steps,
-            'warmup': args.warmup,
-            'ms_per_step': dt / args.steps * 1e3,
-            'higher_is_better': True,
-            'scaling': 'weak',
-            'vs_baseline': None,
-            'dtype': 'f64',
-            'data': 'synthetic',
-            'config': {'workload': '{}: balanced tree, {} tips ({} nodes), k={} states, {}, '
-                                   '{} characters per GPU ({} in total), marginal (BU+TD+posteriors)'
-                                   .format({'cfg4': 'BASELINE config 4 shard', 'cfg2': 'BASELINE config 2',
-                                            'cfg4_small': 'reduced config 4 (16 384 tips)'}[args.workload],
-                                           flat.n_tips, N, k, model, cpg, cpg * world),
-                       'tips': int(flat.n_tips), 'nodes': int(N), 'states': k, 'chars_per_gpu': cpg,
-                       'chars_total': cpg * world, 'substitution_model': model,
-                       'sharding': 'characters over ranks, no data-path collective; 1 all-reduce (8 B) per step',
-                       'collective': comm.name, **{k_: v_ for k_, v_ in comm_report.items() if k_ != 'collective'}},
-            'per_rank': per_rank,
-            'loglik_sum': total,
+        out.update({
             'roofline': {
                 'bound': 'hbm', 'kernel': dom['name'],
                 'achieved': dom_gbs, 'peak': HBM_PEAK_GBS, 'unit': 'GB/s',
@@ -1290,16 +1345,12 @@ def main():
                                   'posterior vector of every node written and read back); a ratio above 1 says this '
                                   'schedule does not move that traffic -- that model is not a bound for it, the output floor is',
             },
-            'kernel_ms_per_step': {'bottom_up': bu_ms / args.steps, 'top_down': td_ms / args.steps,
-                                   'prep': prep_ms / args.steps},
             'prep_gbs': prep_gbs,
-            'device_memory_gb': held / 1e9,
+            'device_memory_gb': eng.memory()[0] / 1e9,
             'validation': validation,
-            # which sources the library that ran was compiled from (pml_build_digest) next to what the tree holds now and
-            # the stamp of the committed HBM counters
-            'library': {'build_digest': hip.build_digest(), 'source_digest': library_source_digest(),
-                        'traffic_stamp': traffic_stamp, 'kernel_sources_digest': csrc_digest()},
-        }
+        })
+        # and the stamp of the committed HBM counters
+        out['library'].update(traffic_stamp=traffic_stamp, kernel_sources_digest=csrc_digest())
         if cpu is not None:
             out['cpu_baseline'] = cpu
             out['speedup_vs_cpu_baseline'] = value / cpu['value']
@@ -1316,7 +1367,7 @@ def main():
             sys.stderr.write('bench.py, rank {}: {}\n'.format(rank, failure))
         sys.exit(3)
     if rank == 0:
-        if world == 1 and not args.no_secondary and args.workload == 'cfg4':
+        if args.full and world == 1 and not args.no_secondary and args.workload == 'cfg4':
             try:
                 out['secondary'] = secondary_measurements(gpu_index)
             except Exception as e:  # the headline line must survive a failure of the extras

@@ -8,7 +8,7 @@ timeout -k 10 900 python -m pytest $R/tests -m gpu -x -q > $O/r03_pytest.log 2>&
 cd /tmp && export TMPDIR=/tmp
 for v in nofold fold nofold2; do
   if [ $v = fold ]; then export PASTML_HIP_FOLD=1; else unset PASTML_HIP_FOLD; fi
-  timeout -k 10 300 python3 $R/bench.py --steps 10 --warmup 3 --no-cpu-baseline --no-secondary > $O/r03_bench_$v.json 2> $O/r03_bench_$v.err || exit 1
+  timeout -k 10 300 python3 $R/bench.py --steps 10 --warmup 3 --full --no-cpu-baseline --no-secondary > $O/r03_bench_$v.json 2> $O/r03_bench_$v.err || exit 1
   python3 -c "
 import json; d=json.load(open('$O/r03_bench_$v.json')); print('$v', round(d['ms_per_step'],3), d['kernel_ms_per_step'], 'bu frac', d['roofline_bottom_up']['frac'], 'td frac', d['roofline']['frac'])"
 done

@@ -12,7 +12,7 @@ for v in A B A2 B2; do
   echo "== $v"
   timeout -k 10 300 python3 $R/scripts/r04_ragged.py "$@" 2> $O/r04ab_$v.err || { cat $O/r04ab_$v.err; exit 1; }
   if [ -z "$NO_BENCH" ]; then
-  timeout -k 10 300 python3 $R/bench.py --steps 10 --warmup 3 --no-cpu-baseline --no-secondary > $O/libab_$v.json 2> $O/libab_$v.err || { tail -5 $O/libab_$v.err; exit 1; }
+  timeout -k 10 300 python3 $R/bench.py --steps 10 --warmup 3 --full --no-cpu-baseline --no-secondary > $O/libab_$v.json 2> $O/libab_$v.err || { tail -5 $O/libab_$v.err; exit 1; }
   python3 -c "
 import json; d=json.load(open('$O/libab_$v.json')); print('$v cfg4', round(d['ms_per_step'],3), d['kernel_ms_per_step'], 'bu frac', round(d['roofline_bottom_up']['frac'],4), 'td frac', round(d['roofline']['frac'],4))"
   fi

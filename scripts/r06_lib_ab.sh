@@ -5,7 +5,7 @@ out=$1; shift
 for rep in 1 2; do
   for lib in "$@"; do
     [ "$lib" = "base" ] && L="" || L=$PWD/scratch/r06/lib_$lib.so
-    PASTML_HIP_LIBRARY=$L timeout -k 10 200 python bench.py --steps 10 --warmup 3 --no-cpu-baseline --no-secondary --no-validate 2>/dev/null | python -c "
+    PASTML_HIP_LIBRARY=$L timeout -k 10 200 python bench.py --steps 10 --warmup 3 --full --no-cpu-baseline --no-secondary --no-validate 2>/dev/null | python -c "
 import json,sys
 d=json.loads(sys.stdin.read())
 b=d['roofline_bottom_up']; t=d['roofline_top_down']

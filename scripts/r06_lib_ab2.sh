@@ -6,7 +6,7 @@ for rep in 1 2; do
   for spec in "$@"; do
     set -- $spec; lib=$1; shift
     [ "$lib" = "base" ] && L="" || L=$PWD/scratch/r06/lib_$lib.so
-    env "$@" PASTML_HIP_LIBRARY=$L timeout -k 10 200 python bench.py --steps 10 --warmup 3 --no-cpu-baseline --no-secondary --no-validate 2>/dev/null | python -c "
+    env "$@" PASTML_HIP_LIBRARY=$L timeout -k 10 200 python bench.py --steps 10 --warmup 3 --full --no-cpu-baseline --no-secondary --no-validate 2>/dev/null | python -c "
 import json,sys
 d=json.loads(sys.stdin.read())
 b=d['roofline_bottom_up']; t=d['roofline_top_down']

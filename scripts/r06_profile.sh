@@ -3,14 +3,15 @@
 R=${GRAFT_REPO_ROOT:-$(pwd)}
 TAG=${1:-r06}
 cd $R || exit 1
-mkdir -p gpurun_out
-bash scripts/profile_cfg4.sh cfg4 > gpurun_out/${TAG}_profile_cfg4.log 2>&1
+export OUT=${OUT:-$R/scratch/profile}
+mkdir -p $OUT
+bash scripts/profile_cfg4.sh cfg4 > $OUT/${TAG}_profile_cfg4.log 2>&1
 echo "profile_cfg4 rc=$?"
 cd $R
-timeout -k 10 900 python bench.py > gpurun_out/${TAG}_bench_full.json 2> gpurun_out/${TAG}_bench_full.err
+timeout -k 10 900 python bench.py --full > $OUT/${TAG}_bench_full.json 2> $OUT/${TAG}_bench_full.err
 echo "bench rc=$?"
 python - <<PY
 import json
-d=json.load(open('gpurun_out/${TAG}_bench_full.json'))
+d=json.load(open('$OUT/${TAG}_bench_full.json'))
 print(d['ms_per_step'], d['roofline']['frac'], d['speedup_vs_cpu_baseline'])
 PY

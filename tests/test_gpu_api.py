@@ -1133,3 +1133,46 @@ def test_two_level_launches_where_the_byte_model_expects_them(monkeypatch):
             ran = [eng.profile_read(w)[1] for w in range(5)]
             eng.profile_enable(False)
         assert (ran[3] > 0) == expect and (ran[4] > 0) == expect, (k, C, ran)
+
+
+def test_bench_plain_run_dumps_what_its_last_step_computed(tmp_path):
+    """`bench.py` without --full prints the headline line alone (no CPU baseline, validation, roofline or other configs);
+    --dump-outputs writes what the last timed step computed: the same numbers as the engine run directly on the workload."""
+    import json
+    import subprocess
+    import sys
+    import bench
+    from conftest import REPO
+    from pastml_amd import synthetic
+    out_dir = str(tmp_path / 'outputs')
+    env = dict(os.environ)
+    for key in ('RANK', 'WORLD_SIZE', 'LOCAL_RANK', 'PASTML_AMD_RDZV_DIR'):
+        env.pop(key, None)
+    r = subprocess.run([sys.executable, os.path.join(REPO, 'bench.py'), '--gpus', '1', '--steps', '3', '--warmup', '1',
+                        '--workload', 'cfg4_small', '--dump-outputs', out_dir], env=env, capture_output=True, timeout=600)
+    assert r.returncode == 0, r.stderr.decode()[-2000:]
+    line = json.loads(r.stdout.decode().strip().splitlines()[-1])
+    L, k, C = bench.WORKLOADS['cfg4_small']
+    flat = synthetic.balanced_forest(L)
+    assert line['steps'] == 3 and line['warmup'] == 1 and line['dtype'] == 'f64' and line['higher_is_better'] is True
+    assert line['ms_per_step'] > 0
+    assert line['value'] == pytest.approx(flat.n_nodes * k * C / (line['ms_per_step'] * 1e-3), rel=1e-9)
+    for key in ('cpu_baseline', 'validation', 'roofline', 'secondary'):
+        assert key not in line
+    dumped = {name: np.load(os.path.join(out_dir, name + '.npy'))
+              for name in ('loglik', 'loglik_sum', 'posterior_sample', 'lh_sum_sample', 'lh_sf_sample')}
+    assert all(a.dtype == np.float64 for a in dumped.values())
+    assert sum(a.nbytes for a in dumped.values()) < 64 << 20
+    stride = bench.dump_stride(flat.n_nodes, C, k)
+    with hip.Engine(flat, C, k) as eng:
+        eng.set_models([(dict(kind=0, pi=synthetic.f81_frequencies(k, c)), (1.0, 0.0, 1.0)) for c in range(C)])
+        eng.set_tip_states(np.stack([synthetic.tip_states(flat.n_tips, k, c) for c in range(C)]))
+        lnl = eng.marginal_pass(posterior=False, lh=False)[0]
+        want = [np.stack([eng.download_strided(buf, c, 0, stride) for c in range(C)])
+                for buf in (hip.BUF_POSTERIOR, hip.BUF_LH_SUM, hip.BUF_LH_SF)]
+    np.testing.assert_allclose(dumped['loglik'], lnl, rtol=1e-13)
+    np.testing.assert_allclose(dumped['loglik_sum'], [line['loglik_sum']], rtol=1e-15)
+    np.testing.assert_allclose(dumped['loglik_sum'], [lnl.sum()], rtol=1e-13)
+    for name, w in zip(('posterior_sample', 'lh_sum_sample', 'lh_sf_sample'), want):
+        assert dumped[name].shape == w.shape
+        np.testing.assert_allclose(dumped[name], w, rtol=1e-12, atol=1e-300)

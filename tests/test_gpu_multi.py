@@ -119,7 +119,7 @@ def test_bench_two_ranks_started_directly(tmp_path):
     env.pop('RANK', None)
     env.pop('WORLD_SIZE', None)
     r = subprocess.run([sys.executable, os.path.join(REPO, 'bench.py'), '--gpus', '2', '--steps', '2', '--warmup', '1',
-                        '--workload', 'cfg4_small', '--chars-per-gpu', '2', '--cpu-baseline-levels', '11',
+                        '--workload', 'cfg4_small', '--chars-per-gpu', '2', '--full', '--cpu-baseline-levels', '11',
                         '--cpu-baseline-cores', '2'], env=env, capture_output=True, timeout=600)
     assert r.returncode == 0, r.stderr.decode()[-2000:]
     line = json.loads(r.stdout.decode().strip().splitlines()[-1])
@@ -141,8 +141,8 @@ def test_bench_four_ranks_of_32_characters(tmp_path):
     for key in ('RANK', 'WORLD_SIZE', 'LOCAL_RANK', 'PASTML_AMD_RDZV_DIR'):
         env.pop(key, None)
     r = subprocess.run([sys.executable, os.path.join(REPO, 'bench.py'), '--gpus', '4', '--steps', '2', '--warmup', '1',
-                        '--workload', 'cfg4_small', '--chars-per-gpu', '32', '--no-secondary', '--cpu-baseline-levels', '11',
-                        '--cpu-baseline-cores', '2'], env=env,
+                        '--workload', 'cfg4_small', '--chars-per-gpu', '32', '--full', '--no-secondary',
+                        '--cpu-baseline-levels', '11', '--cpu-baseline-cores', '2'], env=env,
                        capture_output=True, timeout=900)
     assert r.returncode == 0, r.stderr.decode()[-2000:]
     line = json.loads(r.stdout.decode().strip().splitlines()[-1])
@@ -188,7 +188,7 @@ def test_bench_two_ranks_under_torchrun(tmp_path):
     r = subprocess.run([sys.executable, '-m', 'torch.distributed.run', '--nnodes=1', '--nproc-per-node', '2',
                         '--master-addr', '127.0.0.1', '--master-port', str(_free_port()),
                         os.path.join(REPO, 'bench.py'), '--gpus', '2', '--steps', '2', '--warmup', '1',
-                        '--workload', 'cfg4_small', '--chars-per-gpu', '2', '--cpu-baseline-levels', '11',
+                        '--workload', 'cfg4_small', '--chars-per-gpu', '2', '--full', '--cpu-baseline-levels', '11',
                         '--cpu-baseline-cores', '2'], env=env, capture_output=True, timeout=900)
     assert r.returncode == 0, r.stderr.decode()[-3000:]
     lines = [l for l in r.stdout.decode().splitlines() if l.startswith('{')]

@@ -520,6 +520,54 @@ def test_bench_byte_model_knows_the_two_level_schedule():
     assert bench.schedule_bytes(FlatForest.from_trees([root]), 64, 128)['n_two_level'] == 0
 
 
+def test_bench_options(monkeypatch):
+    """A plain bench run leaves the extras off (--full turns them on); --steps sets the timed steps and must be positive."""
+    import bench
+    monkeypatch.setattr('sys.argv', ['bench.py', '--gpus', '1', '--steps', '7', '--warmup', '2'])
+    args = bench.parse_args()
+    assert (args.steps, args.warmup, args.full, args.dump_outputs) == (7, 2, False, None)
+    assert bench.run_cpu_baseline(args, 20, 64, 'F81') is None
+    monkeypatch.setattr('sys.argv', ['bench.py', '--full', '--dump-outputs', 'out'])
+    args = bench.parse_args()
+    assert args.full and args.dump_outputs == 'out'
+    monkeypatch.setattr('sys.argv', ['bench.py', '--steps', '0'])
+    with pytest.raises(SystemExit):
+        bench.parse_args()
+
+
+def test_bench_dump_outputs_stay_within_64_mb(tmp_path):
+    """dump_outputs writes float64 arrays of every column, sampled at every stride-th node from node 0 on; the stride grows
+    with the shard so that the whole dump stays below 64 MB (the headline shard: the validation's stride 4099)."""
+    import bench
+    from pastml_amd import hip
+    levels, k, cpg = bench.WORKLOADS['cfg4']
+    n_nodes = 2 ** (levels + 1) - 1
+    assert bench.dump_stride(n_nodes, cpg, k) == 4099
+    for n_cols, kk in ((cpg, k), (256, 64), (32, 256), (1, 4)):
+        rows = -(-n_nodes // bench.dump_stride(n_nodes, n_cols, kk))
+        assert rows * n_cols * (kk + 2) * 8 + 8 * (n_cols + 1) < 64 << 20
+
+    class Engine(object):
+        n_cols, n_nodes, k = 3, 10000, 5
+
+        def download_strided(self, what, col, first, stride):
+            rows = np.arange(first, self.n_nodes, stride, dtype=np.float64)
+            base = rows + 1e5 * col + 1e7 * what
+            return np.outer(base, np.arange(1, self.k + 1)) if what == hip.BUF_POSTERIOR else base
+
+    eng = Engine()
+    shapes = bench.dump_outputs(str(tmp_path), eng, np.array([-1.5, -2.5, -3.0]), -7.0)
+    got = {name: np.load(str(tmp_path / (name + '.npy'))) for name in shapes}
+    assert sorted(got) == ['lh_sf_sample', 'lh_sum_sample', 'loglik', 'loglik_sum', 'posterior_sample']
+    assert all(a.dtype == np.float64 and list(a.shape) == shapes[name] for name, a in got.items())
+    rows = np.arange(0, eng.n_nodes, 4099)
+    assert got['posterior_sample'].shape == (3, len(rows), 5) and got['lh_sf_sample'].shape == (3, len(rows))
+    assert np.array_equal(got['lh_sum_sample'][2], rows + 2e5 + 1e7 * hip.BUF_LH_SUM)
+    assert np.array_equal(got['loglik'], [-1.5, -2.5, -3.0]) and np.array_equal(got['loglik_sum'], [-7.0])
+    bench.dump_outputs(str(tmp_path), eng, np.zeros(3), 0.0, '_rank1')
+    assert os.path.exists(str(tmp_path / 'posterior_sample_rank1.npy'))
+
+
 def test_library_fd_points_are_numpys():
     """
     pml_host_f81_fd_points (the points of one forward-difference gradient, decoded, in one call into the library) ==
