@@ -276,6 +276,16 @@ int pml_marginal_counts(pml_ctx* ctx, int32_t col, int32_t n_repetitions, uint64
 int pml_marginal_counts_altered(pml_ctx* ctx, int32_t col, int32_t n_repetitions, uint64_t seed, const uint8_t* altered,
                                 double* sums_out, int32_t* state_counts_out, int32_t* same_out);
 
+/*
+ * n_repetitions scenarios of column col drawn forward from the roots (pastml/utilities/state_simulator.py:6-31):
+ * roots ~ pi, child ~ row (parent state) of P_n(t).  Draws keyed by (seed, caller's node id, rep_offset + r):
+ * results do not depend on launch geometry, chunking or the library's internal numbering.
+ * states_out[n_nodes][n_repetitions], caller's numbering; uint8 for k <= 256, else uint16.
+ * Needs a model (pml_model_set_*), no sweep.
+ */
+int pml_simulate_states(pml_ctx* ctx, int32_t col, int32_t n_repetitions, int32_t rep_offset, uint64_t seed,
+                        void* states_out);
+
 /* ---- multi-GPU (one process per GPU) ----------------------------------------------------------------------------------- */
 /*
  * The characters of a run are independent (pastml/acr.py:213-231 hands them to a pool one by one, each with its own

@@ -3070,6 +3070,33 @@ int pml_marginal_counts_altered(pml_ctx* ctx, int32_t col, int32_t n_repetitions
     return marginal_counts_impl(ctx, col, n_repetitions, seed, altered, sums_out, state_counts_out, same_out);
 }
 
+// n_repetitions scenarios of column col drawn forward from the roots (pml_launch_simulate.hip).  Needs a model, no sweep: the
+// per-branch e = exp(-mu t') (F81 family) or P(t) is prepared here.  The states are written in the caller's numbering on the
+// device, in rows padded to a multiple of 4 repetitions, and copied out without the padding.
+int pml_simulate_states(pml_ctx* ctx, int32_t col, int32_t n_repetitions, int32_t rep_offset, uint64_t seed, void* states_out) {
+    PML_TRY(require_model(ctx));
+    if (col < 0 || col >= ctx->C || !states_out) return fail(PML_ERR_INVALID, "bad column / output");
+    if (n_repetitions <= 0) return fail(PML_ERR_INVALID, "n_repetitions must be positive");
+    if (rep_offset < 0) return fail(PML_ERR_INVALID, "rep_offset must not be negative");
+    // (the sweeps may have left E / P(t) in registers only, or for other parameters: prepared afresh)
+    PML_TRY(run_prep(ctx, true));
+    const size_t es = ctx->k > 256 ? 2 : 1;
+    const size_t rs = ((size_t)n_repetitions + 3) / 4 * 4;
+    void* d_states = nullptr;
+    HIP_TRY(hipMalloc(&d_states, (size_t)ctx->N * rs * es));
+    int status = launch_simulate(ctx, col, n_repetitions, rep_offset, seed, d_states, rs);
+    hipError_t e = hipSuccess;
+    if (status == PML_OK)
+        e = hipMemcpy2DAsync(states_out, (size_t)n_repetitions * es, d_states, rs * es, (size_t)n_repetitions * es, (size_t)ctx->N,
+                             hipMemcpyDeviceToHost, ctx->stream);
+    const hipError_t e2 = hipStreamSynchronize(ctx->stream);
+    (void)hipFree(d_states);
+    PML_TRY(status);
+    if (e != hipSuccess) return fail(PML_ERR_HIP, "pml_simulate_states failed: %s", hipGetErrorString(e));
+    if (e2 != hipSuccess) return fail(PML_ERR_HIP, "pml_simulate_states failed: %s", hipGetErrorString(e2));
+    return PML_OK;
+}
+
 int pml_select_states(pml_ctx* ctx, int method, int force_joint, const uint64_t* lh_mask, uint64_t* masks_out,
                       int32_t* n_states_out) {
     PML_TRY(require_model(ctx));

@@ -320,6 +320,12 @@ struct pml_ctx {
     bool tip_post_missing = false; // the last top-down sweep left the observed tips' posteriors implicit
     const PmlUnit* units_override = nullptr;  // set around a dispatch_sweep on the block schedule's top lists
 
+    // forward simulation (pml_launch_simulate.hip): preorder node lists of the subtrees rooted at depth sim_depth (built on
+    // first use for that depth; a new tree resets them)
+    int sim_depth = -1, sim_n_lists = 0;
+    int4* d_sim_lists = nullptr;   // (internal id, caller's id, caller's id of the parent, 0) per node
+    int* d_sim_off = nullptr;
+
     PmlComm* comm = nullptr;   // RCCL communicator attached by pml_comm_init (survives tree uploads)
 };
 
@@ -369,6 +375,11 @@ static void free_all(pml_ctx* ctx) {
     if (ctx->d_stage) (void)hipFree(ctx->d_stage);
     ctx->d_stage = nullptr;
     ctx->stage_bytes = 0;
+    if (ctx->d_sim_lists) (void)hipFree(ctx->d_sim_lists);
+    if (ctx->d_sim_off) (void)hipFree(ctx->d_sim_off);
+    ctx->d_sim_lists = nullptr;
+    ctx->d_sim_off = nullptr;
+    ctx->sim_depth = -1;
     ctx->allocs.clear();
     ctx->held = 0;
 }

@@ -17,23 +17,7 @@
 // Nodes altered by the zero-branch handling (ml.py:352-387) follow other rules there: the host keeps that case.
 #pragma once
 #include "pml_kernels_pij.h"
-
-__device__ __forceinline__ void philox4x32_10(unsigned (&ctr)[4], unsigned k0, unsigned k1) {
-#pragma unroll
-    for (int round = 0; round < 10; ++round) {
-        const unsigned long long p0 = (unsigned long long)0xD2511F53u * ctr[0];
-        const unsigned long long p1 = (unsigned long long)0xCD9E8D57u * ctr[2];
-        const unsigned hi0 = (unsigned)(p0 >> 32), lo0 = (unsigned)p0;
-        const unsigned hi1 = (unsigned)(p1 >> 32), lo1 = (unsigned)p1;
-        const unsigned n0 = hi1 ^ ctr[1] ^ k0, n1 = lo1, n2 = hi0 ^ ctr[3] ^ k1, n3 = lo0;
-        ctr[0] = n0;
-        ctr[1] = n1;
-        ctr[2] = n2;
-        ctr[3] = n3;
-        k0 += 0x9E3779B9u;
-        k1 += 0xBB67AE85u;
-    }
-}
+#include "pml_philox.h"
 
 // uniform in [0, 1) with 53 random bits, a pure function of (seed, node, parent state, draw index)
 __device__ __forceinline__ double counts_uniform(u64 seed, unsigned node, unsigned state, unsigned draw) {

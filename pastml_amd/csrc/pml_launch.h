@@ -149,6 +149,9 @@ PML_INTERNAL int launch_eigen_joint(pml_ctx* ctx, const PmlUnit* units, const in
                                     const int* d_blk_start = nullptr, int n_blocks = 1);
 PML_INTERNAL int launch_eigen_joint_tips(pml_ctx* ctx);
 PML_INTERNAL int launch_pij_valu(pml_ctx* ctx);
+// ---- pml_launch_simulate.hip: forward simulation of a column along the forest (pml_simulate_states); d_states [N][rs] in the
+//      caller's numbering, uint8 for k <= 256, else uint16
+PML_INTERNAL int launch_simulate(pml_ctx* ctx, int col, int n_rep, int rep_offset, u64 seed, void* d_states, size_t rs);
 
 // More than 64 KB of dynamic LDS must be asked for: once per kernel, device and size (the largest asked for so far is what is
 // set) -- not per launch: the call is not free and should not sit inside a stream capture.  (A template: one table per kernel

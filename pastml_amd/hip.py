@@ -106,6 +106,7 @@ SIGNATURES = {
     'pml_marginal_counts': [_ctx_p, ctypes.c_int32, ctypes.c_int32, ctypes.c_uint64, _c_double_p],
     'pml_marginal_counts_altered': [_ctx_p, ctypes.c_int32, ctypes.c_int32, ctypes.c_uint64, ctypes.POINTER(ctypes.c_uint8),
                                     _c_double_p, _c_int32_p, _c_int32_p],
+    'pml_simulate_states': [_ctx_p, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_uint64, ctypes.c_void_p],
     'pml_download': [_ctx_p, ctypes.c_int, ctypes.c_int32, ctypes.c_void_p],
     'pml_comm_unique_id': [ctypes.POINTER(ctypes.c_ubyte)],
     'pml_comm_init': [_ctx_p, ctypes.c_int, ctypes.c_int, ctypes.POINTER(ctypes.c_ubyte)],
@@ -754,6 +755,19 @@ class Engine(BareContext):
                                                      _ptr(alt, ctypes.c_uint8), _ptr(sums, ctypes.c_double),
                                                      _ptr(counts, ctypes.c_int32), _ptr(same, ctypes.c_int32)))
         return sums, counts, same
+
+    def simulate_states(self, n_repetitions, seed, col=0, rep_offset=0):
+        """
+        n_repetitions scenarios of column col drawn forward from the roots under the column's model
+        (pastml/utilities/state_simulator.py:6-31): [n_nodes, n_repetitions] state ids in this engine's node numbering,
+        uint8 for k <= 256, else uint16.  Repetition r is drawn with the generator keyed by (seed, node, rep_offset + r),
+        so consecutive calls with consecutive rep_offsets make up one larger call.
+        """
+        dtype = np.uint8 if self.k <= 256 else np.uint16
+        out = np.empty((self.n_nodes, int(n_repetitions)), dtype=dtype)
+        _check(self._lib.pml_simulate_states(self._ctx, col, int(n_repetitions), int(rep_offset), ctypes.c_uint64(int(seed)),
+                                             out.ctypes.data_as(ctypes.c_void_p)))
+        return out
 
     def download(self, what, col=0):
         N, k = self.n_nodes, self.k
