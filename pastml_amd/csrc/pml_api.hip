@@ -25,104 +25,6 @@ int pml_fail(int code, const char* fmt, ...) {
     return code;
 }
 
-// ---------------------------------------------------------------------------------------------------------------------
-// Height-ordered numbering (round 5).  The C-ABI asks for breadth-first ids -- roots first, the children of a node
-// contiguous, every depth a contiguous id range -- which leaves the ORDER OF THE SIBLING GROUPS INSIDE A DEPTH free.  The
-// sweeps walk the nodes by fused height (bottom-up) and gather, per unit, 8-byte scalars of the unit's children (E, S, mask,
-// exponent) and of the tips under its cherry children; in plain breadth-first order the children of the units of ONE height
-// are scattered over their depth, so every gathered scalar costs a 128-byte line of its own (a random 262 144-tip tree moved
-// 28.8 GB per marginal pass where the schedule needs 22.2, profiles/r04b_*).  Here the sibling groups of a depth are ordered
-// by the height class of the unit that gathers them -- a stored node's children by its fused height, the tips of a cherry by
-// the fused height of the cherry's parent -- and, inside a class, in the order of their parents: the children of consecutive
-// units of a level are then consecutive in memory.  Same tree, same arithmetic per node, same bits (the order of a node's own
-// children is kept); k = 64: marginal pass 5.8 -> 5.2 ms, k = 12: 3.25 -> 2.48, k = 4: 2.39 -> 1.68 (262 144 random tips x 32
-// characters, profiles/r05e_height_order.txt).  A balanced tree is in this order already.
-// Returns false (and leaves the vectors empty) when the caller's numbering is the height order.
-// ---------------------------------------------------------------------------------------------------------------------
-// by_shape (round 6): inside a depth the sibling groups are ordered by (shape, height class) of the unit that gathers them instead of
-// by the class alone -- the level launches of wide units walk their lists sorted by shape (units_by_shape), so only then are the
-// children of CONSECUTIVE units of a launch consecutive in memory (the top-down lists are sorted by (shape, class) to match).
-static bool height_order(int N, int R, const int* parent, const int* first_child, const int* n_children,
-                         const int* td_offsets, int n_td_levels, bool fuse, bool by_shape, std::vector<int>& old_of_new,
-                         std::vector<int>& new_of_old) {
-    old_of_new.clear();
-    new_of_old.clear();
-    std::vector<int> cls(N, 0), fh(N, 0);
-    std::vector<char> stored(N, 0);
-    for (int i = 0; i < N; ++i) {
-        if (n_children[i] == 0) continue;
-        bool all_tips = true;
-        for (int j = 0; j < n_children[i]; ++j) all_tips &= n_children[first_child[i] + j] == 0;
-        stored[i] = !(fuse && all_tips && parent[i] >= 0);
-    }
-    for (int i = N - 1; i >= 0; --i) {  // children have larger ids than their parent
-        if (!stored[i]) continue;
-        int h = 0;
-        for (int j = 0; j < n_children[i]; ++j) {
-            const int ch = first_child[i] + j;
-            if (stored[ch] && fh[ch] > h) h = fh[ch];
-        }
-        fh[i] = h + 1;
-    }
-    for (int i = 0; i < N; ++i)
-        if (n_children[i] > 0) cls[i] = stored[i] ? fh[i] : fh[parent[i]];   // (a cherry is never a root)
-    // the shape of the gathering unit: describe_units' packed word of the stored node (of a cherry's parent for the tips of a cherry)
-    std::vector<long long> key(N, 0);
-    if (by_shape) {
-        auto packed_of = [&](int n) {
-            const int nc = n_children[n];
-            int packed = nc < 15 ? nc : 15;
-            bool cherries_ok = true, first_two = true;
-            for (int j = 0; j < 4 && j < nc; ++j) {
-                const int ch = first_child[n] + j;
-                int code = n_children[ch] == 0 ? 0 : 1;
-                if (n_children[ch] > 0 && !stored[ch]) {
-                    if (n_children[ch] > 4) {
-                        cherries_ok = false;
-                        code = 2;
-                    } else {
-                        code = 1 + n_children[ch];
-                    }
-                }
-                packed |= code << (8 + 3 * j);
-                if (j >= 2 && code == 1) first_two = false;
-            }
-            if (cherries_ok) packed |= 1 << 4;
-            if (first_two) packed |= 1 << 5;
-            return packed;
-        };
-        for (int i = 0; i < N; ++i)
-            if (n_children[i] > 0) key[i] = ((long long)packed_of(stored[i] ? i : parent[i]) << 32) | (unsigned)cls[i];
-    } else {
-        for (int i = 0; i < N; ++i) key[i] = cls[i];
-    }
-    std::vector<int> order;
-    order.reserve(N);
-    for (int i = 0; i < R; ++i) order.push_back(i);
-    size_t lo = 0;
-    bool identity = true;
-    std::vector<int> par;
-    for (int d = 0; d + 1 < n_td_levels; ++d) {
-        const size_t hi = order.size();
-        par.clear();
-        for (size_t q = lo; q < hi; ++q)
-            if (n_children[order[q]] > 0) par.push_back(order[q]);
-        std::stable_sort(par.begin(), par.end(), [&](int x, int y) { return key[x] < key[y]; });
-        for (int p : par)
-            for (int j = 0; j < n_children[p]; ++j) {
-                identity = identity && first_child[p] + j == (int)order.size();
-                order.push_back(first_child[p] + j);
-            }
-        lo = hi;
-    }
-    (void)td_offsets;
-    if (identity || (int)order.size() != N) return false;
-    old_of_new.swap(order);
-    new_of_old.assign(N, 0);
-    for (int q = 0; q < N; ++q) new_of_old[old_of_new[q]] = q;
-    return true;
-}
-
 // rows of `width` elements between the caller's numbering and the library's, for n_cols columns of N rows each
 template <typename T>
 static void rows_to_internal(const pml_ctx* ctx, const T* api, T* internal, size_t width, size_t n_cols) {
@@ -386,1090 +288,146 @@ int pml_sweep_schedule(pml_ctx* ctx, int32_t* kind, int32_t* n_blocks, int32_t* 
     return PML_OK;
 }
 
-// unit descriptors (PmlUnit, pml_kernels_f81.h) of a node list
-static int describe_units(const int* first_child, const int* n_children, const unsigned char* kind, const int* list, int count,
-                          bool use_kind, std::vector<PmlUnit>& out) {
-    out.resize(count > 0 ? count : 1);
-    for (int q = 0; q < count; ++q) {
-        const int n = list[q];
-        PmlUnit u;
-        u.n = n;
-        u.fc = first_child[n];
-        u.pad = 0;
-        const int nc = n_children[n];
-        int packed = nc < 15 ? nc : 15;
-        bool cherries_ok = true, stored_first_two_only = true;
-        for (int j = 0; j < 4; ++j) {
-            u.cfc[j] = 0;
-            if (j >= nc) continue;
-            const int ch = u.fc + j;
-            u.cfc[j] = first_child[ch];
-            const int kd = use_kind ? (int)kind[ch] : (n_children[ch] == 0 ? PML_KIND_TIP : PML_KIND_STORED);
-            int code = kd == PML_KIND_TIP ? 0 : 1;
-            if (kd == PML_KIND_CHERRY) {
-                if (n_children[ch] > 4) {
-                    cherries_ok = false;
-                    code = 2;
-                } else {
-                    code = 1 + n_children[ch];
-                }
-            }
-            packed |= code << (8 + 3 * j);
-            if (j >= 2 && code == 1) stored_first_two_only = false;
-        }
-        if (cherries_ok) packed |= 1 << 4;
-        if (stored_first_two_only) packed |= 1 << 5;
-        u.packed = packed;
-        out[q] = u;
-    }
-    return 0;
-}
-
-// the units of every level (offs) sorted by shape, stable (see pml_tree_upload)
-static std::vector<PmlUnit> units_by_shape(const std::vector<PmlUnit>& in, const std::vector<int>& offs, size_t count) {
-    auto shape_less = [](const PmlUnit& x, const PmlUnit& y) { return x.packed < y.packed; };
-    std::vector<PmlUnit> out(in);
-    for (size_t l = 0; l + 1 < offs.size(); ++l) {
-        const size_t a = (size_t)offs[l], b = std::min((size_t)offs[l + 1], count);
-        if (b > a + 1) std::stable_sort(out.begin() + a, out.begin() + b, shape_less);
-    }
-    return out;
-}
-
 // ---------------------------------------------------------------------------------------------------------------------
+// A tree: checked, numbered and planned on the host (pml_schedule.cpp), then the context is reset and every table of the
+// tree is put on the device.
 int pml_tree_upload(pml_ctx* ctx, int32_t n_nodes, int32_t n_roots, const int32_t* parent, const int32_t* first_child,
                     const int32_t* n_children, const double* dist, int32_t n_bu_levels, const int32_t* bu_offsets,
                     const int32_t* bu_order, int32_t n_td_levels, const int32_t* td_offsets,
                     const int32_t* td_parent_offsets, const int32_t* td_parents, const int32_t* post_rank) {
     if (!ctx) return fail(PML_ERR_INVALID, "ctx is NULL");
-    if (n_nodes <= 0 || n_roots <= 0 || n_roots > n_nodes) return fail(PML_ERR_INVALID, "bad node/root counts");
-    if (!parent || !first_child || !n_children || !dist || !bu_offsets || !td_offsets || !td_parent_offsets ||
-        !post_rank)
-        return fail(PML_ERR_INVALID, "NULL tree array");
-    if (n_bu_levels < 0 || n_td_levels < 1) return fail(PML_ERR_INVALID, "bad level counts");
-    // host-side validation of everything the kernels index with (a bad index would fault the GPU)
-    int n_internal = 0;
-    for (int i = 0; i < n_nodes; ++i) {
-        const int nc = n_children[i];
-        if (nc < 0) return fail(PML_ERR_INVALID, "n_children[%d] < 0", i);
-        if (nc > 0) {
-            ++n_internal;
-            const long long fc = first_child[i];
-            if (fc <= i || fc + nc > n_nodes) return fail(PML_ERR_INVALID, "children of node %d out of range", i);
-            for (int j = 0; j < nc; ++j)
-                if (parent[fc + j] != i) return fail(PML_ERR_INVALID, "parent/child arrays disagree at node %d", i);
-        }
-        if (i < n_roots ? parent[i] != -1 : (parent[i] < 0 || parent[i] >= i))
-            return fail(PML_ERR_INVALID, "parent[%d] = %d is not valid for level-ordered ids", i, parent[i]);
-        if (!(dist[i] >= 0.0)) return fail(PML_ERR_INVALID, "dist[%d] is negative or NaN", i);
-        if (post_rank[i] < 0 || post_rank[i] >= n_nodes) return fail(PML_ERR_INVALID, "post_rank[%d] out of range", i);
-    }
-    if (bu_offsets[0] != 0 || bu_offsets[n_bu_levels] != n_internal)
-        return fail(PML_ERR_INVALID, "bu_offsets must cover the %d internal nodes", n_internal);
-    if (td_parent_offsets[0] != 0 || td_parent_offsets[n_td_levels] != n_internal)
-        return fail(PML_ERR_INVALID, "td_parent_offsets must cover the %d internal nodes", n_internal);
-    if (td_offsets[0] != 0 || td_offsets[1] != n_roots || td_offsets[n_td_levels] != n_nodes)
-        return fail(PML_ERR_INVALID, "td_offsets must start with the roots and cover all nodes");
-    if (n_internal > 0 && (!bu_order || !td_parents)) return fail(PML_ERR_INVALID, "NULL level array");
-    {
-        std::vector<char> seen(n_nodes, 0);
-        std::vector<int> height(n_nodes, 0);
-        for (int l = 0; l < n_bu_levels; ++l) {
-            if (bu_offsets[l + 1] < bu_offsets[l]) return fail(PML_ERR_INVALID, "bu_offsets not monotone");
-            for (int q = bu_offsets[l]; q < bu_offsets[l + 1]; ++q) {
-                const int n = bu_order[q];
-                if (n < 0 || n >= n_nodes || n_children[n] == 0 || seen[n])
-                    return fail(PML_ERR_INVALID, "bu_order[%d] = %d is not a distinct internal node", q, n);
-                seen[n] = 1;
-                // every internal child must sit in an earlier level
-                for (int j = 0; j < n_children[n]; ++j) {
-                    const int ch = first_child[n] + j;
-                    if (n_children[ch] > 0 && (!seen[ch] || height[ch] >= l + 1))
-                        return fail(PML_ERR_INVALID, "bu level %d: node %d precedes its child %d", l, n, ch);
-                }
-                height[n] = l + 1;
-            }
-        }
-        std::fill(seen.begin(), seen.end(), 0);
-        for (int l = 0; l < n_td_levels; ++l) {
-            if (td_parent_offsets[l + 1] < td_parent_offsets[l] || td_offsets[l + 1] < td_offsets[l])
-                return fail(PML_ERR_INVALID, "td offsets not monotone");
-            for (int q = td_parent_offsets[l]; q < td_parent_offsets[l + 1]; ++q) {
-                const int n = td_parents[q];
-                if (n < td_offsets[l] || n >= td_offsets[l + 1] || n_children[n] == 0 || seen[n])
-                    return fail(PML_ERR_INVALID, "td_parents[%d] = %d is not a distinct internal node of depth %d", q,
-                                n, l);
-                seen[n] = 1;
-            }
-        }
-    }
-
-    // ---- the library's own numbering (height_order): from here on every array is in it
-    std::vector<int> perm_old_of_new, perm_new_of_old;
-    std::vector<int32_t> p_parent, p_first_child, p_n_children, p_bu_order, p_td_parents, p_post_rank;
-    std::vector<double> p_dist;
-    // Shape-aware order (round 6) for large forests without many polytomies: there the level launches walk shape-sorted lists
-    // and a depth's sibling groups follow them.  Measured, marginal pass, class-only -> shape-aware numbering, bits unchanged
-    // (profiles/r06q_shape_order.txt): random binary 262 144 tips x 32, k = 64 5.07 -> 4.94 ms, k = 12 2.29 -> 2.07, k = 8 1.91 ->
-    // 1.68, k = 4 1.46 -> 1.35 (the last two with their lists sorted by shape as well, which the old numbering punished);
-    // forests with polytomies lose 2 - 3 % (many shapes: short runs) and 40 000-tip trees 3 %: they keep the class-only order.
-    bool shape_order = false;
-    {
-        long long n_inner = 0, n34 = 0;   // (the polytomy rule of pml_chars_alloc)
-        for (int i = 0; i < n_nodes; ++i) {
-            const int nc = n_children[i];
-            bool inner = false;
-            for (int j = 0; j < nc && !inner; ++j) inner = n_children[first_child[i] + j] > 0;
-            if (!inner) continue;
-            ++n_inner;
-            n34 += nc == 3 || nc == 4;
-        }
-        const bool polytomies = n_inner > 0 && n34 * 100 >= 15 * n_inner;
-        shape_order = n_nodes >= 150000 && !polytomies;
-        if (ctx->tune.on(T_SHAPE_ORDER)) shape_order = ctx->tune.get(T_SHAPE_ORDER, 1) != 0;
-    }
-    if (!ctx->tune.on(T_NO_HEIGHT_ORDER) &&
-        height_order(n_nodes, n_roots, parent, first_child, n_children, td_offsets, n_td_levels, ctx->fuse, shape_order,
-                     perm_old_of_new, perm_new_of_old)) {
-        const std::vector<int>& o = perm_old_of_new;
-        const std::vector<int>& nw = perm_new_of_old;
-        p_parent.resize(n_nodes);
-        p_first_child.resize(n_nodes);
-        p_n_children.resize(n_nodes);
-        p_post_rank.resize(n_nodes);
-        p_dist.resize(n_nodes);
-        for (int q = 0; q < n_nodes; ++q) {
-            const int old = o[q];
-            p_parent[q] = parent[old] >= 0 ? nw[parent[old]] : -1;
-            p_n_children[q] = n_children[old];
-            // (a tip's entry is never read; it only has to pass for an id)
-            p_first_child[q] = n_children[old] > 0 ? nw[first_child[old]] : 0;
-            p_post_rank[q] = post_rank[old];
-            p_dist[q] = dist[old];
-        }
-        p_bu_order.assign(n_internal > 0 ? n_internal : 1, 0);
-        p_td_parents.assign(n_internal > 0 ? n_internal : 1, 0);
-        for (int l = 0; l < n_bu_levels; ++l) {
-            for (int q = bu_offsets[l]; q < bu_offsets[l + 1]; ++q) p_bu_order[q] = nw[bu_order[q]];
-            std::sort(p_bu_order.begin() + bu_offsets[l], p_bu_order.begin() + bu_offsets[l + 1]);
-        }
-        for (int l = 0; l < n_td_levels; ++l) {
-            for (int q = td_parent_offsets[l]; q < td_parent_offsets[l + 1]; ++q) p_td_parents[q] = nw[td_parents[q]];
-            std::sort(p_td_parents.begin() + td_parent_offsets[l], p_td_parents.begin() + td_parent_offsets[l + 1]);
-        }
-        parent = p_parent.data();
-        first_child = p_first_child.data();
-        n_children = p_n_children.data();
-        post_rank = p_post_rank.data();
-        dist = p_dist.data();
-        bu_order = p_bu_order.data();
-        td_parents = p_td_parents.data();
-    }
+    PmlTreeArrays t = {n_nodes,    n_roots,           n_bu_levels, n_td_levels, parent,    first_child, n_children,
+                       bu_offsets, bu_order,          td_offsets,  td_parent_offsets, td_parents, post_rank, dist};
+    const std::string bad = pml_check_tree(t);
+    if (!bad.empty()) return fail(PML_ERR_INVALID, "%s", bad.c_str());
+    // the library's own numbering (height_order): from here on every array is in it
+    PmlNumbering num;
+    PmlForest forest = pml_plan_forest(t, ctx->tune, ctx->fuse, num);
+    PmlTreePlan P = pml_plan_tree(forest, t, ctx->tune);
 
     HIP_TRY(hipSetDevice(ctx->device));
     HIP_TRY(hipStreamSynchronize(ctx->stream));
-    // a new tree resets everything the ctx holds
-    free_all(ctx);
-    hipStream_t stream = ctx->stream;
-    hipEvent_t e0 = ctx->ev0, e1 = ctx->ev1;
-    (void)prof_drain(ctx);
-    std::vector<hipEvent_t> prof_pool;
-    prof_pool.swap(ctx->prof_pool);
-    if (ctx->prof_open) prof_pool.push_back(ctx->prof_open);
-
-    int device = ctx->device;
-    const bool profile = ctx->profile;
-    const bool fuse = ctx->fuse, keep_td = ctx->keep_td, eig_fused_opt = ctx->eig_fused_opt, eigj_valu_opt = ctx->eigj_valu_opt,
-               implicit_tips = ctx->implicit_tips;
-    PmlComm* comm = ctx->comm;
-    const PmlTune tune = ctx->tune;
-    *ctx = pml_ctx();
-    ctx->tune = tune;
-    ctx->fuse = fuse;
-    ctx->keep_td = keep_td;
-    ctx->eig_fused_opt = eig_fused_opt;
-    ctx->eigj_valu_opt = eigj_valu_opt;
-    ctx->implicit_tips = implicit_tips;
-    ctx->comm = comm;
-    ctx->stream = stream;
-    ctx->ev0 = e0;
-    ctx->ev1 = e1;
-    ctx->prof_pool.swap(prof_pool);
-    ctx->profile = profile;
-    ctx->device = device;
-    ctx->old_of_new.swap(perm_old_of_new);
-    ctx->new_of_old.swap(perm_new_of_old);
-    ctx->shape_ordered = shape_order && !ctx->old_of_new.empty();
-
+    reset_for_tree(ctx);
+    ctx->old_of_new.swap(num.old_of_new);
+    ctx->new_of_old.swap(num.new_of_old);
     ctx->N = n_nodes;
     ctx->n_roots = n_roots;
     ctx->n_bu_levels = n_bu_levels;
     ctx->n_td_levels = n_td_levels;
-    ctx->bu_offsets.assign(bu_offsets, bu_offsets + n_bu_levels + 1);
-    ctx->td_offsets.assign(td_offsets, td_offsets + n_td_levels + 1);
-    ctx->td_parent_offsets.assign(td_parent_offsets, td_parent_offsets + n_td_levels + 1);
-    ctx->h_parent.assign(parent, parent + n_nodes);
-    ctx->h_n_children.assign(n_children, n_children + n_nodes);
-    PML_TRY(dev_alloc(ctx, &ctx->d_parent, n_nodes));
-    PML_TRY(dev_alloc(ctx, &ctx->d_first_child, n_nodes));
-    PML_TRY(dev_alloc(ctx, &ctx->d_n_children, n_nodes));
-    PML_TRY(dev_alloc(ctx, &ctx->d_post_rank, n_nodes));
-    PML_TRY(dev_alloc(ctx, &ctx->d_dist, n_nodes));
-    PML_TRY(dev_alloc(ctx, &ctx->d_bu_order, n_internal));
-    PML_TRY(dev_alloc(ctx, &ctx->d_td_parents, n_internal));
-    PML_TRY(upload(ctx, ctx->d_parent, parent, n_nodes));
+    ctx->forest = std::move(forest);
+    const PmlForest& f = ctx->forest;
+    const int n_internal = f.n_internal, n_stored = f.n_stored();
+    PML_TRY(put(ctx, &ctx->d_parent, t.parent, n_nodes));
+    PML_TRY(put(ctx, &ctx->d_first_child, t.first_child, n_nodes));
+    PML_TRY(put(ctx, &ctx->d_n_children, t.n_children, n_nodes));
+    PML_TRY(put(ctx, &ctx->d_post_rank, t.post_rank, n_nodes));
+    PML_TRY(put(ctx, &ctx->d_dist, t.dist, n_nodes));
+    PML_TRY(put(ctx, &ctx->d_bu_order, t.bu_order, n_internal));
+    PML_TRY(put(ctx, &ctx->d_td_parents, t.td_parents, n_internal));
     if (permuted(ctx)) {
-        PML_TRY(dev_alloc(ctx, &ctx->d_new_of_old, n_nodes));
-        PML_TRY(dev_alloc(ctx, &ctx->d_old_of_new, n_nodes));
-        PML_TRY(upload(ctx, ctx->d_new_of_old, ctx->new_of_old.data(), n_nodes));
-        PML_TRY(upload(ctx, ctx->d_old_of_new, ctx->old_of_new.data(), n_nodes));
+        PML_TRY(put(ctx, &ctx->d_new_of_old, ctx->new_of_old));
+        PML_TRY(put(ctx, &ctx->d_old_of_new, ctx->old_of_new));
     }
-    PML_TRY(upload(ctx, ctx->d_first_child, first_child, n_nodes));
-    PML_TRY(upload(ctx, ctx->d_n_children, n_children, n_nodes));
-    PML_TRY(upload(ctx, ctx->d_post_rank, post_rank, n_nodes));
-    PML_TRY(upload(ctx, ctx->d_dist, dist, n_nodes));
-    if (n_internal) {
-        PML_TRY(upload(ctx, ctx->d_bu_order, bu_order, n_internal));
-        PML_TRY(upload(ctx, ctx->d_td_parents, td_parents, n_internal));
+    PML_TRY(put(ctx, &ctx->d_bu_offsets, f.bu_offsets));
+    PML_TRY(put(ctx, &ctx->d_td_offsets, f.td_offsets));
+    ctx->n_tips = (int)P.tips.size();
+    PML_TRY(put(ctx, &ctx->d_tips, P.tips));
+    // cherry fusion: kind per node, level lists over the stored internal nodes, unit descriptors of the lists
+    ctx->n_cherries = (int)P.cherries.size();
+    PML_TRY(put(ctx, &ctx->d_kind, f.kind));
+    PML_TRY(put(ctx, &ctx->d_bu_order_f, f.order_f));
+    PML_TRY(put(ctx, &ctx->d_td_parents_f, f.tdp));
+    PML_TRY(put(ctx, &ctx->d_cherries, P.cherries));
+    PML_TRY(put(ctx, &ctx->d_bu_offsets_f, f.bu_offsets_f));
+    PML_TRY(put(ctx, &ctx->d_td_parent_offsets_f, f.td_parent_offsets_f));
+    PML_TRY(put(ctx, &ctx->d_cherry_units, P.cherry_units));
+    PML_TRY(put(ctx, &ctx->d_bu_units_f, P.bu_units_f));
+    PML_TRY(put(ctx, &ctx->d_td_units_f, P.td_units_f));
+    PML_TRY(put(ctx, &ctx->d_bu_units, P.bu_units));
+    if (P.shape_sort) {
+        PML_TRY(put(ctx, &ctx->d_bu_units_fs, P.bu_units_fs));
+        PML_TRY(put(ctx, &ctx->d_td_units_fs, P.td_units_fs));
     }
-    PML_TRY(dev_alloc(ctx, &ctx->d_bu_offsets, n_bu_levels + 1));
-    PML_TRY(dev_alloc(ctx, &ctx->d_td_offsets, n_td_levels + 1));
-    PML_TRY(upload(ctx, ctx->d_bu_offsets, bu_offsets, n_bu_levels + 1));
-    PML_TRY(upload(ctx, ctx->d_td_offsets, td_offsets, n_td_levels + 1));
-    {
-        std::vector<int> tips;
-        tips.reserve(n_nodes - n_internal);
-        for (int i = 0; i < n_nodes; ++i)
-            if (n_children[i] == 0) tips.push_back(i);
-        ctx->n_tips = (int)tips.size();
-        PML_TRY(dev_alloc(ctx, &ctx->d_tips, tips.size()));
-        if (!tips.empty()) PML_TRY(upload(ctx, ctx->d_tips, tips.data(), tips.size()));
-        HIP_TRY(hipStreamSynchronize(ctx->stream));  // the vector goes out of scope
+    ctx->bu_level_vec_f.swap(P.bu_level_vec_f);
+    ctx->bu_level_vec.swap(P.bu_level_vec);
+    ctx->td_cherry_prefix.swap(P.td_cherry_prefix);
+    ctx->small = P.small;
+    // the schedules: their geometry as planned, their tables on the device
+    pml_ctx::EigenTiers& E = ctx->eig_tiers;
+    E = P.eig.s;
+    if (E.ok) {
+        PML_TRY(put(ctx, &E.d_nodes, P.eig.t.list));
+        PML_TRY(put(ctx, &E.d_units, P.eig.units));
+        PML_TRY(put(ctx, &E.d_lv, P.eig.t.lv));
+        PML_TRY(put(ctx, &E.d_start, P.eig.t.start));
     }
-    // ---- cherry fusion tables: kind per node, level lists over the stored internal nodes
-    {
-        std::vector<unsigned char>& kind = ctx->h_kind;
-        kind.assign(n_nodes, PML_KIND_TIP);
-        std::vector<int> cherries, fh(n_nodes, 0);
-        for (int i = 0; i < n_nodes; ++i) {
-            if (n_children[i] == 0) continue;
-            bool all_tips = true;
-            for (int j = 0; j < n_children[i]; ++j) all_tips &= n_children[first_child[i] + j] == 0;
-            if (ctx->fuse && all_tips && parent[i] >= 0) {
-                kind[i] = PML_KIND_CHERRY;
-                cherries.push_back(i);
-            } else {
-                kind[i] = PML_KIND_STORED;
-            }
-        }
-        int max_h = 0;
-        for (int i = n_nodes - 1; i >= 0; --i) {  // children have larger ids than their parent
-            if (kind[i] != PML_KIND_STORED) continue;
-            int h = 0;
-            for (int j = 0; j < n_children[i]; ++j) {
-                const int ch = first_child[i] + j;
-                if (kind[ch] == PML_KIND_STORED && fh[ch] > h) h = fh[ch];
-            }
-            fh[i] = h + 1;
-            if (fh[i] > max_h) max_h = fh[i];
-        }
-        std::vector<int>& off = ctx->bu_offsets_f;
-        off.assign(max_h + 1, 0);
-        for (int i = 0; i < n_nodes; ++i)
-            if (kind[i] == PML_KIND_STORED) ++off[fh[i]];
-        // off[h] = count of height h (h >= 1) -> exclusive prefix: level l (0-based) = height l + 1
-        {
-            int run = 0;
-            for (int h = 1; h <= max_h; ++h) {
-                const int cnt = off[h];
-                off[h - 1] = run;
-                run += cnt;
-            }
-            off[max_h] = run;
-        }
-        const int n_stored = off[max_h];
-        std::vector<int> order(n_stored > 0 ? n_stored : 1), cursor(off.begin(), off.end());
-        for (int i = 0; i < n_nodes; ++i)
-            if (kind[i] == PML_KIND_STORED) order[cursor[fh[i] - 1]++] = i;
-        std::vector<int> tdp;
-        ctx->td_parent_offsets_f.assign(n_td_levels + 1, 0);
-        for (int l = 0; l < n_td_levels; ++l) {
-            for (int q = td_parent_offsets[l]; q < td_parent_offsets[l + 1]; ++q)
-                if (kind[td_parents[q]] == PML_KIND_STORED) tdp.push_back(td_parents[q]);
-            ctx->td_parent_offsets_f[l + 1] = (int)tdp.size();
-        }
-        ctx->n_cherries = (int)cherries.size();
-        {
-            // unit descriptors (PmlUnit, pml_kernels_f81.h) for the three node lists the F81 kernels walk
-            auto describe = [&](const int* list, int count, bool use_kind, std::vector<PmlUnit>& out) {
-                return describe_units(first_child, n_children, kind.data(), list, count, use_kind, out);
-            };
-            std::vector<PmlUnit> ub_f, ut_f, ub, uc;
-            describe(cherries.data(), (int)cherries.size(), false, uc);
-            PML_TRY(dev_alloc(ctx, &ctx->d_cherry_units, uc.size()));
-            PML_TRY(upload(ctx, ctx->d_cherry_units, uc.data(), uc.size()));
-            describe(order.data(), n_stored, true, ub_f);
-            ctx->bu_level_vec_f.assign(max_h > 0 ? max_h : 1, 0);
-            for (int l = 0; l < max_h; ++l)
-                for (int q = off[l]; q < off[l + 1] && !ctx->bu_level_vec_f[l]; ++q) {
-                    const int pk = ub_f[q].packed;
-                    if (((pk >> 8) & 7) == 1 || ((pk >> 11) & 7) == 1) ctx->bu_level_vec_f[l] = 1;
-                }
-            describe(tdp.data(), n_stored, true, ut_f);
-            ctx->td_cherry_prefix.assign(n_stored + 1, 0);
-            for (int q = 0; q < n_stored; ++q) {
-                const int pk = ut_f[q].packed;
-                ctx->td_cherry_prefix[q + 1] = ctx->td_cherry_prefix[q] + ((((pk >> 8) & 7) >= 2 || ((pk >> 11) & 7) >= 2) ? 1 : 0);
-            }
-            describe(bu_order, n_internal, false, ub);
-            {
-                pml_ctx::EigenTiers& E = ctx->eig_tiers;
-                E = pml_ctx::EigenTiers();
-                const int thin = (int)ctx->tune.get(T_EIGJ_TIER_THIN, 4096);
-                const int depth = std::max(2, (int)ctx->tune.get(T_EIGJ_TIER_DEPTH, 4));
-                const int top_nodes = 48;
-                int L0 = n_bu_levels;
-                while (L0 > 0 && bu_offsets[L0] - bu_offsets[L0 - 1] <= thin) --L0;
-                if (!ctx->tune.on(T_NO_EIGJ_TIERS) && n_bu_levels - L0 >= 6) {
-                    std::vector<int> level_of(n_nodes, -1);
-                    for (int l = 0; l < n_bu_levels; ++l)
-                        for (int q = bu_offsets[l]; q < bu_offsets[l + 1]; ++q) level_of[bu_order[q]] = l;
-                    std::vector<PmlUnit> tu;
-                    std::vector<int> lv, start, tnodes;
-                    int a = L0;
-                    std::vector<int> block_of(n_nodes, -1);
-                    // The depth of a tier is the largest (up to 12 levels) whose blocks still have at most 12 nodes per
-                    // level -- one pass of a workgroup per level step at k = 20 (three nodes per wavefront).  A
-                    // balanced binary tree gets tiers of four levels, ragged trees deeper ones (measured: HIV1C-shaped
-                    // and random 40 000-tip trees are 10 - 20 % faster with 6 - 8 levels than with 4, cfg3 slower).
-                    // PASTML_HIP_EIGJ_TIER_DEPTH fixes the depth.
-                    const bool fixed_depth = ctx->tune.on(T_EIGJ_TIER_DEPTH);
-                    while (a + 2 <= n_bu_levels && bu_offsets[a + 1] - bu_offsets[a] > top_nodes) {
-                        int use = 0, nb = 0;
-                        std::vector<std::vector<int>> cell;
-                        for (int dep = fixed_depth ? depth : 12; dep >= 2; --dep) {
-                            if (a + dep > n_bu_levels) {
-                                if (fixed_depth) break;
-                                continue;
-                            }
-                            const int b = a + dep;
-                            // block of a node: its highest ancestor below level b (higher levels come last in the list,
-                            // so walking it backwards meets parents before children)
-                            nb = 0;
-                            for (int q = bu_offsets[b]; q-- > bu_offsets[a];) {
-                                const int n = bu_order[q];
-                                const int p = parent[n];
-                                block_of[n] = (p >= 0 && level_of[p] >= 0 && level_of[p] < b) ? block_of[p] : nb++;
-                            }
-                            cell.assign((size_t)nb * dep, std::vector<int>());
-                            size_t widest_cell = 0;
-                            for (int q = bu_offsets[a]; q < bu_offsets[b]; ++q) {
-                                const int n = bu_order[q];
-                                std::vector<int>& cl = cell[(size_t)block_of[n] * dep + (level_of[n] - a)];
-                                cl.push_back(n);
-                                widest_cell = std::max(widest_cell, cl.size());
-                            }
-                            if (widest_cell <= 12 || dep == 2 || fixed_depth) {
-                                use = dep;
-                                break;
-                            }
-                        }
-                        if (use == 0) break;
-                        const int b = a + use;
-                        pml_ctx::EigenTiers::Tier T;
-                        T.first_block = (int)start.size();
-                        T.n_blocks = nb;
-                        T.depth = use;
-                        std::vector<int> flat_nodes;
-                        const int base = (int)tu.size();
-                        for (int bl = 0; bl < nb; ++bl) {
-                            start.push_back((int)lv.size());
-                            for (int d = 0; d < use; ++d) {
-                                lv.push_back(base + (int)flat_nodes.size());
-                                for (int n : cell[(size_t)bl * use + d]) flat_nodes.push_back(n);
-                            }
-                            lv.push_back(base + (int)flat_nodes.size());
-                        }
-                        std::vector<PmlUnit> part;
-                        describe(flat_nodes.data(), (int)flat_nodes.size(), false, part);
-                        part.resize(flat_nodes.size());
-                        tu.insert(tu.end(), part.begin(), part.end());
-                        tnodes.insert(tnodes.end(), flat_nodes.begin(), flat_nodes.end());
-                        E.tiers.push_back(T);
-                        for (int l = a; l < b; ++l) E.widest = std::max(E.widest, bu_offsets[l + 1] - bu_offsets[l]);
-                        a = b;
-                    }
-                    if (!E.tiers.empty()) {
-                        tu.push_back(ub[0]);  // (slack: an empty level at the end of the table is still addressed)
-                        tnodes.push_back(ub[0].n);
-                        PML_TRY(dev_alloc(ctx, &E.d_nodes, tnodes.size()));
-                        PML_TRY(upload(ctx, E.d_nodes, tnodes.data(), tnodes.size()));
-                        PML_TRY(dev_alloc(ctx, &E.d_units, tu.size()));
-                        PML_TRY(dev_alloc(ctx, &E.d_lv, lv.size()));
-                        PML_TRY(dev_alloc(ctx, &E.d_start, start.size()));
-                        PML_TRY(upload(ctx, E.d_units, tu.data(), tu.size()));
-                        PML_TRY(upload(ctx, E.d_lv, lv.data(), lv.size()));
-                        PML_TRY(upload(ctx, E.d_start, start.data(), start.size()));
-                        HIP_TRY(hipStreamSynchronize(ctx->stream));
-                        E.first_level = L0;
-                        E.top_level = a;
-                        E.ok = true;
-                    }
-                }
-            }
-            ctx->bu_level_vec.assign(n_bu_levels > 0 ? n_bu_levels : 1, 0);
-            for (int l = 0; l < n_bu_levels; ++l)
-                for (int q = bu_offsets[l]; q < bu_offsets[l + 1] && !ctx->bu_level_vec[l]; ++q) {
-                    const int pk = ub[q].packed;
-                    if (((pk >> 8) & 7) == 1 || ((pk >> 11) & 7) == 1) ctx->bu_level_vec[l] = 1;
-                }
-            {
-                // joint back-trace tiers: from the first depth of more than 1 024 nodes on, tiers of up to 10 depths whose
-                // subtrees keep at most 256 nodes per depth (one pass of a workgroup per step)
-                pml_ctx::BacktraceTiers& B = ctx->bt_tiers;
-                B = pml_ctx::BacktraceTiers();
-                int d1 = 1;
-                while (d1 < n_td_levels && td_offsets[d1 + 1] - td_offsets[d1] <= 1024) ++d1;
-                if (!ctx->tune.on(T_NO_BT_TIERS) && n_td_levels - d1 >= 2) {
-                    std::vector<int> depth_of(n_nodes, 0), anc(n_nodes, 0), tn, lv, start;
-                    for (int l = 0; l < n_td_levels; ++l)
-                        for (int i = td_offsets[l]; i < td_offsets[l + 1]; ++i) depth_of[i] = l;
-                    int da = d1;
-                    while (da < n_td_levels) {
-                        // one counting pass over up to 10 depths: nodes per (subtree, depth), the widest cell of every
-                        // depth; the tier takes the depths before the first one that is too wide
-                        const int dmax = std::min(10, n_td_levels - da);
-                        const int nb = td_offsets[da + 1] - td_offsets[da];
-                        std::vector<int> cnt10((size_t)nb * dmax, 0), widest(dmax, 0);
-                        for (int i = td_offsets[da]; i < td_offsets[da + dmax]; ++i) {
-                            const int dd = depth_of[i] - da;
-                            anc[i] = dd == 0 ? i - td_offsets[da] : anc[parent[i]];
-                            widest[dd] = std::max(widest[dd], ++cnt10[(size_t)anc[i] * dmax + dd]);
-                        }
-                        int use = 1;
-                        while (use < dmax && widest[use] <= 256) ++use;
-                        std::vector<int> cnt((size_t)nb * use);
-                        for (int b = 0; b < nb; ++b)
-                            for (int d = 0; d < use; ++d) cnt[(size_t)b * use + d] = cnt10[(size_t)b * dmax + d];
-                        // tables of the tier: per subtree its depth offsets into the node list
-                        pml_ctx::BacktraceTiers::Tier T;
-                        T.first_block = (int)start.size();
-                        T.n_blocks = nb;
-                        T.depth = use;
-                        const int base = (int)tn.size();
-                        std::vector<int> cell_start((size_t)nb * use + 1, 0);
-                        for (size_t q = 0; q < (size_t)nb * use; ++q) cell_start[q + 1] = cell_start[q] + cnt[q];
-                        tn.resize(base + cell_start.back());
-                        std::vector<int> cursor(cell_start.begin(), cell_start.end() - 1);
-                        for (int i = td_offsets[da]; i < td_offsets[da + use]; ++i)
-                            tn[base + cursor[(size_t)anc[i] * use + (depth_of[i] - da)]++] = i;
-                        for (int b = 0; b < nb; ++b) {
-                            start.push_back((int)lv.size());
-                            for (int d = 0; d <= use; ++d) lv.push_back(base + cell_start[(size_t)b * use + d]);
-                        }
-                        B.tiers.push_back(T);
-                        da += use;
-                    }
-                    if (!B.tiers.empty()) {
-                        tn.push_back(0);
-                        PML_TRY(dev_alloc(ctx, &B.d_nodes, tn.size()));
-                        PML_TRY(dev_alloc(ctx, &B.d_lv, lv.size()));
-                        PML_TRY(dev_alloc(ctx, &B.d_start, start.size()));
-                        PML_TRY(upload(ctx, B.d_nodes, tn.data(), tn.size()));
-                        PML_TRY(upload(ctx, B.d_lv, lv.data(), lv.size()));
-                        PML_TRY(upload(ctx, B.d_start, start.data(), start.size()));
-                        HIP_TRY(hipStreamSynchronize(ctx->stream));
-                        B.first_depth = d1;
-                        B.ok = true;
-                    }
-                }
-            }
-            // Units of one shape next to each other.  Within a level the order of the units is free, and a wavefront runs
-            // the union of its units' control flow: on a balanced tree every unit of a level has the same kinds of children
-            // (tip / stored node / cherry of m tips), on a ragged one a wave of 8 units met most combinations and ran them
-            // one after the other.  For the level launches of wide units (8 states per lane: 32 < k <= 64) every level's
-            // units are sorted by the descriptor's shape word -- stable, ids ascend inside a shape, neighbours still read
-            // neighbouring memory.  262 144-tip random binary tree x 32 characters, k = 64: marginal pass 6.5 -> 5.7 ms;
-            // 100 000 tips with polytomies: 2.86 -> 2.13 ms; narrow units (k = 4: 64 units per wave, every lane its own
-            // rows) lose 20 % to the scattered rows and keep id order.  PASTML_HIP_NO_SHAPE_SORT: id order everywhere.
-            auto shape_less = [](const PmlUnit& x, const PmlUnit& y) { return x.packed < y.packed; };
-            auto in_shape_order = [&](const std::vector<PmlUnit>& in, const std::vector<int>& offs, size_t count) {
-                for (size_t l = 0; l + 1 < offs.size(); ++l) {
-                    const size_t a = (size_t)offs[l], b = std::min((size_t)offs[l + 1], count);
-                    if (b > a + 1 && !std::is_sorted(in.begin() + a, in.begin() + b, shape_less)) return false;
-                }
-                return true;
-            };
-            auto by_shape = [&](const std::vector<PmlUnit>& in, const std::vector<int>& offs, size_t count) {
-                std::vector<PmlUnit> out(in);
-                for (size_t l = 0; l + 1 < offs.size(); ++l) {
-                    const size_t a = (size_t)offs[l], b = std::min((size_t)offs[l + 1], count);
-                    if (b > a + 1) std::stable_sort(out.begin() + a, out.begin() + b, shape_less);
-                }
-                return out;
-            };
-            // top-down lists: by (shape, height class) -- the order in which height_order lays the children of a depth's units out
-            // (bottom-up lists are per class already)
-            auto by_shape_class = [&](const std::vector<PmlUnit>& in, const std::vector<int>& offs, size_t count) {
-                if (!ctx->shape_ordered) return by_shape(in, offs, count);
-                std::vector<PmlUnit> out(in);
-                auto less = [&](const PmlUnit& x, const PmlUnit& y) {
-                    return x.packed != y.packed ? x.packed < y.packed : fh[x.n] < fh[y.n];
-                };
-                for (size_t l = 0; l + 1 < offs.size(); ++l) {
-                    const size_t a = (size_t)offs[l], b = std::min((size_t)offs[l + 1], count);
-                    if (b > a + 1) std::stable_sort(out.begin() + a, out.begin() + b, less);
-                }
-                return out;
-            };
-            // (a balanced tree is in shape order as it is: no second copy, the launches walk the id-ordered lists)
-            const bool shape_sort = !ctx->tune.on(T_NO_SHAPE_SORT) && n_stored > 0 &&
-                                    !(in_shape_order(ub_f, off, (size_t)n_stored) &&
-                                      in_shape_order(ut_f, ctx->td_parent_offsets_f, (size_t)n_stored));
-            if (shape_sort) {
-                const std::vector<PmlUnit> sb = by_shape(ub_f, off, (size_t)n_stored);
-                const std::vector<PmlUnit> st_ = by_shape_class(ut_f, ctx->td_parent_offsets_f, (size_t)n_stored);
-                PML_TRY(dev_alloc(ctx, &ctx->d_bu_units_fs, sb.size()));
-                PML_TRY(dev_alloc(ctx, &ctx->d_td_units_fs, st_.size()));
-                PML_TRY(upload(ctx, ctx->d_bu_units_fs, sb.data(), sb.size()));
-                PML_TRY(upload(ctx, ctx->d_td_units_fs, st_.data(), st_.size()));
-                HIP_TRY(hipStreamSynchronize(ctx->stream));  // the vectors go out of scope
-            }
-            PML_TRY(dev_alloc(ctx, &ctx->d_bu_units_f, ub_f.size()));
-            PML_TRY(dev_alloc(ctx, &ctx->d_td_units_f, ut_f.size()));
-            PML_TRY(dev_alloc(ctx, &ctx->d_bu_units, ub.size()));
-            PML_TRY(upload(ctx, ctx->d_bu_units_f, ub_f.data(), ub_f.size()));
-            PML_TRY(upload(ctx, ctx->d_td_units_f, ut_f.data(), ut_f.size()));
-            PML_TRY(upload(ctx, ctx->d_bu_units, ub.data(), ub.size()));
-            HIP_TRY(hipStreamSynchronize(ctx->stream));  // the vectors go out of scope
-        // ---- two-level units: stored nodes with two stored children that are each the parent of two cherries of two
-        // tips (ids of the four cherries and of the eight tips consecutive, as breadth-first numbering makes them)
-        {
-            pml_ctx::SuperSchedule& U = ctx->sup;
-            U = pml_ctx::SuperSchedule();
-            std::vector<char> pair(n_nodes, 0), sup(n_nodes, 0), gone(n_nodes, 0);
-            std::vector<int> sup_list;
-            if (ctx->fuse && !ctx->tune.on(T_NO_SUPER)) {
-                auto two = [&](int i) { return kind[i] == PML_KIND_STORED && n_children[i] == 2; };
-                for (int i = 0; i < n_nodes; ++i) {
-                    if (!two(i)) continue;
-                    const int a = first_child[i], b = a + 1;
-                    pair[i] = kind[a] == PML_KIND_CHERRY && kind[b] == PML_KIND_CHERRY && n_children[a] == 2 &&
-                              n_children[b] == 2 && first_child[b] == first_child[a] + 2;
-                }
-                for (int i = 0; i < n_nodes; ++i) {
-                    if (!two(i)) continue;
-                    const int a = first_child[i], b = a + 1;
-                    if (pair[a] && pair[b] && first_child[b] == first_child[a] + 2 &&
-                        first_child[first_child[b]] == first_child[first_child[a]] + 4) {
-                        sup[i] = 1;
-                        gone[i] = gone[a] = gone[b] = 1;
-                        sup_list.push_back(i);
-                    }
-                }
-            }
-            const bool env_min = ctx->tune.on(T_SUPER_MIN);
-            const int min_units = (int)ctx->tune.get(T_SUPER_MIN, 64);
-            // (a launch of its own per sweep: only where it carries a share of the work)
-            // (PASTML_HIP_SUPER_MIN given: whatever their share, for tests on ragged forests)
-            const bool use_sup = !sup_list.empty() && (int)sup_list.size() >= min_units &&
-                                 (env_min || (long long)sup_list.size() * 16 >= n_stored);
-            if (!use_sup) {  // (too few: no launch of their own; the stacked units below may still pay)
-                for (int n : sup_list) gone[n] = gone[first_child[n]] = gone[first_child[n] + 1] = 0;
-                sup_list.clear();
-            }
-            // (the rest-list schedule needs wide units and a forest beyond the subtree blocks' reach to be used at all:
-            // super_sweeps; here only the tree is known)
-            if (ctx->fuse && !ctx->tune.on(T_NO_SUPER) && n_stored > 0) {
-                std::vector<PmlUnit> us(std::max<size_t>(1, sup_list.size()));
-                {
-                    PmlUnit u;   // (padding element of the lists below when there are no two-level units)
-                    u.n = order[0];
-                    u.fc = first_child[order[0]];
-                    u.packed = 0;
-                    u.pad = 0;
-                    u.cfc[0] = u.cfc[1] = u.cfc[2] = u.cfc[3] = 0;
-                    us[0] = u;
-                }
-                for (size_t q = 0; q < sup_list.size(); ++q) {
-                    const int n = sup_list[q];
-                    PmlUnit u;
-                    u.n = n;
-                    u.fc = first_child[n];
-                    u.packed = PML_PACKED_TWO_STORED;
-                    u.cfc[0] = first_child[u.fc];
-                    u.cfc[1] = first_child[u.fc + 1];
-                    u.cfc[2] = u.cfc[3] = 0;
-                    u.pad = first_child[u.cfc[0]];
-                    us[q] = u;
-                }
-                // stacked units: ascending height, a node takes its two children over when both are plain units (not
-                // two-level nodes, not taken over, not stacked themselves) with two stored children whose vectors are in
-                // memory; only on levels of 1 024 .. 65 536 nodes (below: the narrow end's single launch; above: the
-                // streaming levels' other lane shape)
-                std::vector<char> stacked(n_nodes, 0), taken(n_nodes, 0), novec(n_nodes, 0);
-                std::vector<int> stack_list;
-                // (PASTML_HIP_STACK_MIN: smallest level that gets stacked units -- tests on small forests)
-                const int stack_min = (int)ctx->tune.get(T_STACK_MIN, 1024);
-                if (!ctx->tune.on(T_NO_STACK)) {
-                    for (int n : sup_list) novec[first_child[n]] = novec[first_child[n] + 1] = 1;
-                    auto level_size = [&](int node) { return off[fh[node]] - off[fh[node] - 1]; };
-                    auto has_vec = [&](int g) { return kind[g] == PML_KIND_STORED && !novec[g]; };
-                    auto plain2 = [&](int ch) {
-                        return kind[ch] == PML_KIND_STORED && !gone[ch] && !stacked[ch] && !taken[ch] && n_children[ch] == 2 &&
-                               has_vec(first_child[ch]) && has_vec(first_child[ch] + 1) && level_size(ch) <= 65536;
-                    };
-                    for (int q = 0; q < n_stored; ++q) {
-                        const int n = order[q];
-                        if (gone[n] || taken[n] || n_children[n] != 2 || level_size(n) < stack_min || level_size(n) > 65536) continue;
-                        const int a = first_child[n], b = a + 1;
-                        if (!plain2(a) || !plain2(b)) continue;
-                        stacked[n] = 1;
-                        taken[a] = taken[b] = novec[a] = novec[b] = 1;
-                        stack_list.push_back(n);
-                    }
-                }
-                // (A level with stacked units costs a launch more per sweep: they pay where they take most of what the
-                // two-level units leave -- the balanced part of a tree -- and not at a tenth of the nodes: a random binary
-                // tree of 262 144 tips had 6 132 of them, 10 % of its stored nodes, and was 3 % slower with them.
-                // PASTML_HIP_STACK_MIN given: whatever their share.)
-                if (!ctx->tune.on(T_STACK_MIN) &&
-                    (long long)stack_list.size() * 3 * 2 < (long long)n_stored - 3 * (long long)sup_list.size())
-                    stack_list.clear();
-                for (int n : stack_list) gone[n] = gone[first_child[n]] = gone[first_child[n] + 1] = 1;
-                if (!stack_list.empty()) {
-                    std::vector<int> depth_of(n_nodes, 0);
-                    for (int l = 0; l < n_td_levels; ++l)
-                        for (int i = td_offsets[l]; i < td_offsets[l + 1]; ++i) depth_of[i] = l;
-                    // by bottom-up level (stack_list is in that order already) and by depth
-                    U.stack_bu_offsets.assign(max_h + 1, 0);
-                    for (int n : stack_list) ++U.stack_bu_offsets[fh[n]];
-                    for (int l = 0; l < max_h; ++l) U.stack_bu_offsets[l + 1] += U.stack_bu_offsets[l];
-                    std::vector<int> by_depth(stack_list);
-                    std::stable_sort(by_depth.begin(), by_depth.end(), [&](int x, int y) { return depth_of[x] < depth_of[y]; });
-                    U.stack_td_offsets.assign(n_td_levels + 1, 0);
-                    for (int n : by_depth) ++U.stack_td_offsets[depth_of[n] + 1];
-                    for (int l = 0; l < n_td_levels; ++l) U.stack_td_offsets[l + 1] += U.stack_td_offsets[l];
-                    std::vector<PmlUnit> sb, sd, sc;
-                    describe(stack_list.data(), (int)stack_list.size(), true, sb);
-                    describe(by_depth.data(), (int)by_depth.size(), true, sd);
-                    std::vector<int> ch_list;
-                    for (int n : stack_list) {
-                        ch_list.push_back(first_child[n]);
-                        ch_list.push_back(first_child[n] + 1);
-                    }
-                    describe(ch_list.data(), (int)ch_list.size(), true, sc);
-                    PML_TRY(dev_alloc(ctx, &U.d_stack_bu, sb.size()));
-                    PML_TRY(dev_alloc(ctx, &U.d_stack_td, sd.size()));
-                    PML_TRY(dev_alloc(ctx, &U.d_stack_children, sc.size()));
-                    PML_TRY(upload(ctx, U.d_stack_bu, sb.data(), sb.size()));
-                    PML_TRY(upload(ctx, U.d_stack_td, sd.data(), sd.size()));
-                    PML_TRY(upload(ctx, U.d_stack_children, sc.data(), sc.size()));
-                    HIP_TRY(hipStreamSynchronize(ctx->stream));
-                    U.n_stack = (int)stack_list.size();
-                    if (ctx->tune.on(T_DEBUG)) fprintf(stderr, "pastml_hip: %d stacked units\n", U.n_stack);
-                }
-                if (!sup_list.empty() || !stack_list.empty()) {  // (else: the plain level lists, nothing to build)
-                // rest lists: the level structure of the fused lists, without the nodes the two-level units take over
-                std::vector<int> bu_r, td_r;
-                U.bu_offsets_r.assign(1, 0);
-                for (int l = 0; l < max_h; ++l) {
-                    for (int q = off[l]; q < off[l + 1]; ++q)
-                        if (!gone[order[q]]) bu_r.push_back(order[q]);
-                    U.bu_offsets_r.push_back((int)bu_r.size());
-                }
-                U.td_offsets_r.assign(1, 0);
-                for (int l = 0; l < n_td_levels; ++l) {
-                    for (int q = ctx->td_parent_offsets_f[l]; q < ctx->td_parent_offsets_f[l + 1]; ++q)
-                        if (!gone[tdp[q]]) td_r.push_back(tdp[q]);
-                    U.td_offsets_r.push_back((int)td_r.size());
-                }
-                std::vector<PmlUnit> ubr, utr, uch;
-                {
-                    std::vector<int> ch_list;
-                    for (int n : sup_list) {
-                        ch_list.push_back(first_child[n]);
-                        ch_list.push_back(first_child[n] + 1);
-                    }
-                    U.n_child_units = (int)ch_list.size();
-                    describe(ch_list.data(), (int)ch_list.size(), true, uch);  // (at least one element)
-                    PML_TRY(dev_alloc(ctx, &U.d_child_units, uch.size()));
-                    PML_TRY(upload(ctx, U.d_child_units, uch.data(), uch.size()));
-                }
-                describe(bu_r.data(), (int)bu_r.size(), true, ubr);
-                describe(td_r.data(), (int)td_r.size(), true, utr);
-                U.bu_level_vec_r.assign(max_h > 0 ? max_h : 1, 0);
-                for (int l = 0; l < max_h; ++l)
-                    for (int q = U.bu_offsets_r[l]; q < U.bu_offsets_r[l + 1] && !U.bu_level_vec_r[l]; ++q) {
-                        const int pk = ubr[q].packed;
-                        if (((pk >> 8) & 7) == 1 || ((pk >> 11) & 7) == 1) U.bu_level_vec_r[l] = 1;
-                    }
-                // (one element of slack: the walk over a level table reads the descriptor at a level's start even when
-                // the level is empty)
-                ubr.resize(bu_r.size() + 1, us[0]);
-                utr.resize(td_r.size() + 1, us[0]);
-                PML_TRY(dev_alloc(ctx, &U.d_units, us.size()));
-                PML_TRY(dev_alloc(ctx, &U.d_bu_units_r, ubr.size()));
-                PML_TRY(dev_alloc(ctx, &U.d_td_units_r, utr.size()));
-                PML_TRY(dev_alloc(ctx, &U.d_bu_offsets_r, U.bu_offsets_r.size()));
-                PML_TRY(dev_alloc(ctx, &U.d_td_offsets_r, U.td_offsets_r.size()));
-                PML_TRY(upload(ctx, U.d_units, us.data(), us.size()));
-                PML_TRY(upload(ctx, U.d_bu_units_r, ubr.data(), ubr.size()));
-                PML_TRY(upload(ctx, U.d_td_units_r, utr.data(), utr.size()));
-                if (shape_sort) {
-                    const std::vector<PmlUnit> sb = by_shape(ubr, U.bu_offsets_r, bu_r.size());
-                    const std::vector<PmlUnit> st_ = by_shape_class(utr, U.td_offsets_r, td_r.size());
-                    PML_TRY(dev_alloc(ctx, &U.d_bu_units_rs, sb.size()));
-                    PML_TRY(dev_alloc(ctx, &U.d_td_units_rs, st_.size()));
-                    PML_TRY(upload(ctx, U.d_bu_units_rs, sb.data(), sb.size()));
-                    PML_TRY(upload(ctx, U.d_td_units_rs, st_.data(), st_.size()));
-                    HIP_TRY(hipStreamSynchronize(ctx->stream));
-                }
-                PML_TRY(upload(ctx, U.d_bu_offsets_r, U.bu_offsets_r.data(), U.bu_offsets_r.size()));
-                PML_TRY(upload(ctx, U.d_td_offsets_r, U.td_offsets_r.data(), U.td_offsets_r.size()));
-                HIP_TRY(hipStreamSynchronize(ctx->stream));  // the vectors go out of scope
-                U.n = (int)sup_list.size();
-                // worth its lists: two-level units, or stacked units that take a sixteenth of the stored nodes over
-                U.ok = U.n > 0 || U.n_stack >= 64 || (U.n_stack > 0 && ctx->tune.on(T_STACK_MIN));
-                if (ctx->tune.on(T_DEBUG))
-                    fprintf(stderr, "pastml_hip: %d two-level units (%d of %d stored nodes)%s\n", U.n, 3 * U.n, n_stored,
-                            U.ok ? "" : " -- plain level lists");
-                }
-            }
-        }
-        // ---- subtree blocks: stored nodes -> blocks (maximal subtrees of <= S stored nodes) + top
-        {
-            const int S = (int)ctx->tune.get(T_BLOCK_NODES, 256);  // measured: 128-512 are within a few per cent, 1024+ loses at k >= 16
-            pml_ctx::BlockSchedule& B = ctx->blocks;
-            B = pml_ctx::BlockSchedule();
-            const int cap_stored = (int)ctx->tune.get(T_BLOCK_MAX_STORED, 1 << 17);  // beyond: the streaming level kernels
-            if (S > 0 && n_stored > S && n_stored <= cap_stored) {
-                std::vector<int> ssz(n_nodes, 0), blk(n_nodes, -1), depth(n_nodes, 0);
-                for (int l = 0; l < n_td_levels; ++l)
-                    for (int i = td_offsets[l]; i < td_offsets[l + 1]; ++i) depth[i] = l;
-                for (int i = n_nodes - 1; i >= 0; --i) {
-                    if (kind[i] != PML_KIND_STORED) continue;
-                    ssz[i] += 1;
-                    if (parent[i] >= 0) ssz[parent[i]] += ssz[i];
-                }
-                // Height cap.  All blocks run in one launch and the top starts after it: a sweep costs (levels of the
-                // tallest block) + (levels of the top).  Ragged trees have thin subtrees of few nodes and many levels;
-                // uncapped, such a block outlasts all others while the top's lowest levels wait for it (HIV1C: 47 + 27
-                // level steps for a tree of 57 levels).  Blocks therefore end below the lowest level of the top: what
-                // sticks out joins levels the top walks anyway, and blocks + top together are as many level steps as
-                // the forest has levels.  (PASTML_HIP_BLOCK_HEIGHT_CAP: 0 = no cap, n = cap at fused height n.)
-                int h_cap = max_h;
-                for (int q = 0; q < n_stored; ++q)
-                    if (ssz[order[q]] > S) h_cap = std::min(h_cap, fh[order[q]]);
-                if (ctx->tune.on(T_BLOCK_HEIGHT_CAP)) {
-                    const int v = (int)ctx->tune.get(T_BLOCK_HEIGHT_CAP, 0);
-                    h_cap = v > 0 ? v : max_h + 1;
-                }
-                int nb = 0;
-                for (int i = 0; i < n_nodes; ++i) {  // parents have smaller ids
-                    if (kind[i] != PML_KIND_STORED || ssz[i] > S || fh[i] >= h_cap) continue;
-                    const int p = parent[i];
-                    blk[i] = (p >= 0 && blk[p] >= 0) ? blk[p] : nb++;
-                }
-                // per block: its nodes by fused height (bottom-up) and by depth (top-down), each as consecutive levels
-                std::vector<std::vector<int>> members(nb);
-                for (int i = 0; i < n_nodes; ++i)
-                    if (blk[i] >= 0) members[blk[i]].push_back(i);
-                std::vector<int> bu_list, td_list, bu_start(nb), bu_levels(nb), bu_lv, td_start(nb), td_levels(nb), td_lv;
-                for (int b = 0; b < nb; ++b) {
-                    std::vector<int>& mem = members[b];  // ascending ids = non-decreasing depth
-                    td_start[b] = (int)td_lv.size();
-                    int nl = 0;
-                    for (size_t q = 0; q < mem.size(); ++q) {
-                        if (q == 0 || depth[mem[q]] != depth[mem[q - 1]]) {
-                            td_lv.push_back((int)td_list.size());
-                            ++nl;
-                        }
-                        td_list.push_back(mem[q]);
-                    }
-                    td_lv.push_back((int)td_list.size());
-                    td_levels[b] = nl;
-                    std::stable_sort(mem.begin(), mem.end(), [&](int x, int y) { return fh[x] < fh[y]; });
-                    bu_start[b] = (int)bu_lv.size();
-                    nl = 0;
-                    for (size_t q = 0; q < mem.size(); ++q) {
-                        if (q == 0 || fh[mem[q]] != fh[mem[q - 1]]) {
-                            bu_lv.push_back((int)bu_list.size());
-                            ++nl;
-                        }
-                        bu_list.push_back(mem[q]);
-                    }
-                    bu_lv.push_back((int)bu_list.size());
-                    bu_levels[b] = nl;
-                }
-                // the top: stored nodes outside the blocks, by fused height / by depth
-                std::vector<int> top_bu, top_td;
-                B.top_bu_offsets.assign(1, 0);
-                for (int l = 0; l < max_h; ++l) {
-                    for (int q = off[l]; q < off[l + 1]; ++q)
-                        if (blk[order[q]] < 0) top_bu.push_back(order[q]);
-                    if ((int)top_bu.size() > B.top_bu_offsets.back()) B.top_bu_offsets.push_back((int)top_bu.size());
-                }
-                B.top_td_offsets.assign(n_td_levels + 1, 0);
-                for (int l = 0; l < n_td_levels; ++l) {
-                    for (int q = ctx->td_parent_offsets_f[l]; q < ctx->td_parent_offsets_f[l + 1]; ++q)
-                        if (blk[tdp[q]] < 0) top_td.push_back(tdp[q]);
-                    B.top_td_offsets[l + 1] = (int)top_td.size();
-                }
-                const int n_top_levels = (int)B.top_bu_offsets.size() - 1;
-                if (nb > 0 && n_top_levels + 1 < max_h) {  // fewer dependent launches than the level schedule
-                    std::vector<PmlUnit> u1, u2, u3, u4;
-                    describe(bu_list.data(), (int)bu_list.size(), true, u1);
-                    describe(td_list.data(), (int)td_list.size(), true, u2);
-                    describe(top_bu.data(), (int)top_bu.size(), true, u3);
-                    describe(top_td.data(), (int)top_td.size(), true, u4);
-                    if (!ctx->tune.on(T_NO_SHAPE_SORT)) {
-                        // inside every level by shape (a wave of one shape runs that shape's code only: walk_levels); the
-                        // blocks' level tables lie one behind the other, so the whole array delimits the segments
-                        u1 = by_shape(u1, bu_lv, bu_list.size());
-                        u2 = by_shape(u2, td_lv, td_list.size());
-                        u3 = by_shape(u3, B.top_bu_offsets, top_bu.size());
-                        u4 = by_shape(u4, B.top_td_offsets, top_td.size());
-                    }
-                    B.top_bu_vec.assign(n_top_levels > 0 ? n_top_levels : 1, 0);
-                    for (int l = 0; l < n_top_levels; ++l)
-                        for (int q = B.top_bu_offsets[l]; q < B.top_bu_offsets[l + 1] && !B.top_bu_vec[l]; ++q) {
-                            const int pk = u3[q].packed;
-                            if (((pk >> 8) & 7) == 1 || ((pk >> 11) & 7) == 1) B.top_bu_vec[l] = 1;
-                        }
-                    auto put = [&](auto** dst, const auto& v) -> int {
-                        PML_TRY(dev_alloc(ctx, dst, v.size()));
-                        if (!v.empty()) PML_TRY(upload(ctx, *dst, v.data(), v.size()));
-                        return PML_OK;
-                    };
-                    PML_TRY(put(&B.d_bu_units, u1));
-                    PML_TRY(put(&B.d_td_units, u2));
-                    PML_TRY(put(&B.d_top_bu_units, u3));
-                    PML_TRY(put(&B.d_top_td_units, u4));
-                    PML_TRY(put(&B.d_bu_start, bu_start));
-                    PML_TRY(put(&B.d_bu_levels, bu_levels));
-                    PML_TRY(put(&B.d_bu_lv, bu_lv));
-                    PML_TRY(put(&B.d_td_start, td_start));
-                    PML_TRY(put(&B.d_td_levels, td_levels));
-                    PML_TRY(put(&B.d_td_lv, td_lv));
-                    PML_TRY(put(&B.d_top_bu_offsets, B.top_bu_offsets));
-                    PML_TRY(put(&B.d_top_td_offsets, B.top_td_offsets));
-                    HIP_TRY(hipStreamSynchronize(ctx->stream));  // the vectors go out of scope
-                    B.n_blocks = nb;
-                    for (int b = 0; b < nb; ++b) B.steps += bu_levels[b];
-                    if (ctx->tune.on(T_DEBUG))
-                        fprintf(stderr, "pastml_hip: %d stored nodes, %d subtree blocks, %lld block levels, %d top levels of %d\n",
-                                n_stored, nb, B.steps, n_top_levels, max_h);
-                    B.ok = true;
-                }
-            }
-        }
-        // (the thin ends of a large forest are cut into subtree blocks when the columns are known: build_thin_ends)
-        ctx->h_first_child.assign(first_child, first_child + n_nodes);
-        ctx->h_fh = fh;
-        ctx->h_order_f.assign(order.begin(), order.begin() + n_stored);
-        ctx->h_tdp = tdp;
-        ctx->thin = pml_ctx::ThinSchedule();
-        ctx->deep = pml_ctx::DeepSchedule();
-        }
-        PML_TRY(dev_alloc(ctx, &ctx->d_kind, n_nodes));
-        PML_TRY(dev_alloc(ctx, &ctx->d_bu_order_f, n_stored));
-        PML_TRY(dev_alloc(ctx, &ctx->d_td_parents_f, n_stored));
-        PML_TRY(dev_alloc(ctx, &ctx->d_cherries, cherries.size()));
-        PML_TRY(upload(ctx, ctx->d_kind, kind.data(), n_nodes));
-        if (n_stored) {
-            PML_TRY(upload(ctx, ctx->d_bu_order_f, order.data(), n_stored));
-            PML_TRY(upload(ctx, ctx->d_td_parents_f, tdp.data(), n_stored));
-        }
-        if (!cherries.empty()) PML_TRY(upload(ctx, ctx->d_cherries, cherries.data(), cherries.size()));
-        PML_TRY(dev_alloc(ctx, &ctx->d_bu_offsets_f, ctx->bu_offsets_f.size()));
-        PML_TRY(dev_alloc(ctx, &ctx->d_td_parent_offsets_f, ctx->td_parent_offsets_f.size()));
-        PML_TRY(upload(ctx, ctx->d_bu_offsets_f, ctx->bu_offsets_f.data(), ctx->bu_offsets_f.size()));
-        PML_TRY(upload(ctx, ctx->d_td_parent_offsets_f, ctx->td_parent_offsets_f.data(), ctx->td_parent_offsets_f.size()));
-        {
-            const int limit = (int)ctx->tune.get(T_SMALL_MAX_NODES, 2048);
-            ctx->small = n_nodes <= limit;
-        }
-        HIP_TRY(hipStreamSynchronize(ctx->stream));
+    pml_ctx::BacktraceTiers& T = ctx->bt_tiers;
+    T = P.bt.s;
+    if (T.ok) {
+        PML_TRY(put(ctx, &T.d_nodes, P.bt.t.list));
+        PML_TRY(put(ctx, &T.d_lv, P.bt.t.lv));
+        PML_TRY(put(ctx, &T.d_start, P.bt.t.start));
     }
-    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    pml_ctx::SuperSchedule& U = ctx->sup;
+    U = P.sup.s;
+    if (U.n_stack > 0) {
+        PML_TRY(put(ctx, &U.d_stack_bu, P.sup.stack_bu));
+        PML_TRY(put(ctx, &U.d_stack_td, P.sup.stack_td));
+        PML_TRY(put(ctx, &U.d_stack_children, P.sup.stack_children));
+    }
+    if (P.sup.lists) {
+        PML_TRY(put(ctx, &U.d_child_units, P.sup.child_units));
+        PML_TRY(put(ctx, &U.d_units, P.sup.units));
+        PML_TRY(put(ctx, &U.d_bu_units_r, P.sup.bu_units_r));
+        PML_TRY(put(ctx, &U.d_td_units_r, P.sup.td_units_r));
+        if (P.shape_sort) {
+            PML_TRY(put(ctx, &U.d_bu_units_rs, P.sup.bu_units_rs));
+            PML_TRY(put(ctx, &U.d_td_units_rs, P.sup.td_units_rs));
+        }
+        PML_TRY(put(ctx, &U.d_bu_offsets_r, U.bu_offsets_r));
+        PML_TRY(put(ctx, &U.d_td_offsets_r, U.td_offsets_r));
+    }
+    pml_ctx::BlockSchedule& B = ctx->blocks;
+    B = P.blocks.s;
+    if (B.ok) {
+        PML_TRY(put(ctx, &B.d_bu_units, P.blocks.bu_units));
+        PML_TRY(put(ctx, &B.d_td_units, P.blocks.td_units));
+        PML_TRY(put(ctx, &B.d_top_bu_units, P.blocks.top_bu_units));
+        PML_TRY(put(ctx, &B.d_top_td_units, P.blocks.top_td_units));
+        PML_TRY(put(ctx, &B.d_bu_start, P.blocks.bu.start));
+        PML_TRY(put(ctx, &B.d_bu_levels, P.blocks.bu.levels));
+        PML_TRY(put(ctx, &B.d_bu_lv, P.blocks.bu.lv));
+        PML_TRY(put(ctx, &B.d_td_start, P.blocks.td.start));
+        PML_TRY(put(ctx, &B.d_td_levels, P.blocks.td.levels));
+        PML_TRY(put(ctx, &B.d_td_lv, P.blocks.td.lv));
+        PML_TRY(put(ctx, &B.d_top_bu_offsets, B.top_bu_offsets));
+        PML_TRY(put(ctx, &B.d_top_td_offsets, B.top_td_offsets));
+    }
+    HIP_TRY(hipStreamSynchronize(ctx->stream));  // (the host tables go out of scope)
     return PML_OK;
 }
 
-// ---- thin ends of a large forest (thin_bottom_up / deep_top_down).
-// A ragged forest has many levels that hold a few hundred to a few thousand units: a launch of its own costs
-// 5 - 15 us each, a level step inside a workgroup's walk 2 us.  Bottom-up, the thin levels are the high ones
-// (every fused level from floor_level on holds at most THIN_UNITS units): subtree blocks + top over that part
-// of the forest, the blocks in ONE launch behind the wide levels' launches, the top in the narrow end's launch.
-// Top-down, they are the deep ones: the subtrees hanging at first_depth in ONE launch behind the wide depths.
-// Small subtrees share a workgroup (bins of up to THIN_BLOCK_NODES units; units of one level of different
-// subtrees do not depend on each other), so a workgroup's waves have work.
-// thin: the most units a thin level holds (pml_chars_alloc: by the bytes a level of that many units moves).
+// The thin ends of a large forest (pml_plan_thin_ends); thin: the most units a thin level holds (pml_chars_alloc: by the
+// bytes a level of that many units moves).
 static int build_thin_ends(pml_ctx* ctx, int thin) {
-    const int n_nodes = ctx->N, n_td_levels = ctx->n_td_levels;
-    const std::vector<int>& off = ctx->bu_offsets_f;
-    const int max_h = (int)off.size() - 1;
-    if (max_h <= 0) return PML_OK;
-    const int n_stored = off[max_h];
-    const std::vector<unsigned char>& kind = ctx->h_kind;
-    const std::vector<int>&parent = ctx->h_parent, &fh = ctx->h_fh, &order = ctx->h_order_f, &tdp = ctx->h_tdp;
-    auto describe = [&](const int* list, int count, bool use_kind, std::vector<PmlUnit>& out) {
-        describe_units(ctx->h_first_child.data(), ctx->h_n_children.data(), kind.data(), list, count, use_kind, out);
-    };
-    auto by_shape = [&](const std::vector<PmlUnit>& in, const std::vector<int>& offs, size_t count) { return units_by_shape(in, offs, count); };
+    PmlThinPlan P = pml_plan_thin_ends(ctx->forest, ctx->tune, thin);
     pml_ctx::ThinSchedule& H = ctx->thin;
-    H = pml_ctx::ThinSchedule();
     pml_ctx::DeepSchedule& D = ctx->deep;
-    D = pml_ctx::DeepSchedule();
-    const int S = std::max(8, (int)ctx->tune.get(T_THIN_BLOCK_NODES, 256));
-    const int narrow = std::min(128, std::max(1, thin / 32));  // (levels of about this many units are the single-workgroup launch's anyway)
-    auto put = [&](auto** dst, const auto& v) -> int {
-        PML_TRY(dev_alloc(ctx, dst, v.size()));
-        if (!v.empty()) PML_TRY(upload(ctx, *dst, v.data(), v.size()));
-        return PML_OK;
-    };
-    // bottom-up: levels [L0, Ltop) are thin and not yet narrow
-    int L0 = max_h, Ltop = max_h;
-    while (L0 > 0 && off[L0] - off[L0 - 1] <= thin) --L0;
-    while (Ltop > L0 && off[Ltop] - off[Ltop - 1] <= narrow) --Ltop;
-    if (thin > 0 && L0 > 0 && Ltop - L0 >= 3) {
-        std::vector<int> ssz(n_nodes), blk(n_nodes), bu_list, bu_start, bu_levels, bu_lv;
-        int a = L0;
-        while (a < Ltop) {
-            // the tier's nodes: fused height in (a, hc), hc = the lowest height at which a subtree of them exceeds S
-            std::fill(ssz.begin(), ssz.end(), 0);
-            for (int i = n_nodes - 1; i >= 0; --i) {
-                if (kind[i] != PML_KIND_STORED || fh[i] <= a) continue;
-                ssz[i] += 1;
-                if (parent[i] >= 0) ssz[parent[i]] += ssz[i];
-            }
-            int hc = max_h + 1;
-            for (int q = off[a]; q < n_stored; ++q)
-                if (ssz[order[q]] > S) hc = std::min(hc, fh[order[q]]);
-            // subtrees into bins: the open one while it fits (parents have smaller ids)
-            std::fill(blk.begin(), blk.end(), -1);
-            int nb = 0, fill = 0;
-            for (int i = 0; i < n_nodes; ++i) {
-                if (kind[i] != PML_KIND_STORED || fh[i] <= a || fh[i] >= hc) continue;
-                const int p = parent[i];
-                if (p >= 0 && blk[p] >= 0) {
-                    blk[i] = blk[p];
-                } else {
-                    if (nb == 0 || fill + ssz[i] > S) {
-                        ++nb;
-                        fill = 0;
-                    }
-                    fill += ssz[i];
-                    blk[i] = nb - 1;
-                }
-            }
-            std::vector<std::vector<int>> members(nb);
-            for (int q = off[a]; q < off[hc - 1]; ++q) members[blk[order[q]]].push_back(order[q]);   // (ascending height)
-            pml_ctx::ThinSchedule::Tier T;
-            T.first_block = (int)bu_start.size();
-            T.n_blocks = nb;
-            for (int b = 0; b < nb; ++b) {
-                const std::vector<int>& mem = members[b];
-                bu_start.push_back((int)bu_lv.size());
-                int nl = 0;
-                for (size_t q = 0; q < mem.size(); ++q) {
-                    if (q == 0 || fh[mem[q]] != fh[mem[q - 1]]) {
-                        bu_lv.push_back((int)bu_list.size());
-                        ++nl;
-                    }
-                    bu_list.push_back(mem[q]);
-                }
-                bu_lv.push_back((int)bu_list.size());
-                bu_levels.push_back(nl);
-            }
-            H.tiers.push_back(T);
-            if (ctx->tune.on(T_DEBUG))
-                fprintf(stderr, "pastml_hip: thin bottom-up tier: levels %d .. %d of %d, %d units in %d bins\n", a, hc - 2,
-                        max_h, off[hc - 1] - off[a], nb);
-            a = hc - 1;
-        }
-        if ((int)H.tiers.size() + 2 <= a - L0) {   // (launches saved)
-            std::vector<PmlUnit> u1;
-            describe(bu_list.data(), (int)bu_list.size(), true, u1);
-            if (!ctx->tune.on(T_NO_SHAPE_SORT)) u1 = by_shape(u1, bu_lv, bu_list.size());
-            u1.push_back(u1[0]);  // (slack: walk_levels fetches a level's first unit before it looks at its size)
-            PML_TRY(put(&H.d_units, u1));
-            PML_TRY(put(&H.d_start, bu_start));
-            PML_TRY(put(&H.d_levels, bu_levels));
-            PML_TRY(put(&H.d_lv, bu_lv));
-            HIP_TRY(hipStreamSynchronize(ctx->stream));  // the vectors go out of scope
-            H.floor_level = L0;
-            H.top_level = a;
-            H.ok = true;
-        }
+    H = P.thin;
+    D = P.deep;
+    if (H.ok) {
+        PML_TRY(put(ctx, &H.d_units, P.bu_units));
+        PML_TRY(put(ctx, &H.d_start, P.bu.start));
+        PML_TRY(put(ctx, &H.d_levels, P.bu.levels));
+        PML_TRY(put(ctx, &H.d_lv, P.bu.lv));
     }
-    // top-down: the depths behind the widest one
-    const std::vector<int>& toff = ctx->td_parent_offsets_f;
-    int widest = 0;
-    for (int l = 1; l < n_td_levels; ++l)
-        if (toff[l + 1] - toff[l] > toff[widest + 1] - toff[widest]) widest = l;
-    int D0 = n_td_levels;
-    while (D0 > widest + 1 && toff[D0] - toff[D0 - 1] <= thin) --D0;
-    int n_mid = 0;
-    for (int l = D0; l < n_td_levels; ++l) n_mid += toff[l + 1] - toff[l] > narrow;
-    if (thin > 0 && D0 > 0 && D0 < n_td_levels && n_mid >= 3) {
-        // a unit's bin: that of its parent's unit; the units of depth D0 open the subtrees
-        std::vector<int> bin(n_nodes, -1), size(n_nodes, 0);
-        for (int q = n_stored - 1; q >= toff[D0]; --q) {   // (the lists ascend in depth: children come later)
-            const int n = tdp[q];
-            size[n] += 1;
-            if (q >= toff[D0 + 1]) size[parent[n]] += size[n];
-        }
-        int nb = 0, fill = 0;
-        for (int q = toff[D0]; q < toff[D0 + 1]; ++q) {
-            const int n = tdp[q];
-            if (nb == 0 || fill + size[n] > S) {
-                ++nb;
-                fill = 0;
-            }
-            fill += size[n];
-            bin[n] = nb - 1;
-        }
-        std::vector<std::vector<int>> members(nb);
-        for (int q = toff[D0]; q < n_stored; ++q) {
-            const int n = tdp[q];
-            if (q >= toff[D0 + 1]) bin[n] = bin[parent[n]];
-            members[bin[n]].push_back(q);   // (positions: the depth of a unit is that of its list segment)
-        }
-        std::vector<int> depth_of_pos(n_stored - toff[D0]);
-        for (int l = D0; l < n_td_levels; ++l)
-            for (int q = toff[l]; q < toff[l + 1]; ++q) depth_of_pos[q - toff[D0]] = l;
-        std::vector<int> td_list, td_start(nb), td_levels(nb), td_lv;
-        for (int b = 0; b < nb; ++b) {
-            const std::vector<int>& mem = members[b];   // ascending positions = non-decreasing depth
-            td_start[b] = (int)td_lv.size();
-            int nl = 0;
-            for (size_t q = 0; q < mem.size(); ++q) {
-                if (q == 0 || depth_of_pos[mem[q] - toff[D0]] != depth_of_pos[mem[q - 1] - toff[D0]]) {
-                    td_lv.push_back((int)td_list.size());
-                    ++nl;
-                }
-                td_list.push_back(tdp[mem[q]]);
-            }
-            td_lv.push_back((int)td_list.size());
-            td_levels[b] = nl;
-        }
-        std::vector<PmlUnit> u2;
-        describe(td_list.data(), (int)td_list.size(), true, u2);
-        if (!ctx->tune.on(T_NO_SHAPE_SORT)) u2 = by_shape(u2, td_lv, td_list.size());
-        u2.push_back(u2[0]);
-        PML_TRY(put(&D.d_units, u2));
-        PML_TRY(put(&D.d_start, td_start));
-        PML_TRY(put(&D.d_levels, td_levels));
-        PML_TRY(put(&D.d_lv, td_lv));
-        HIP_TRY(hipStreamSynchronize(ctx->stream));
-        D.first_depth = D0;
-        D.n_blocks = nb;
-        D.ok = true;
-        if (ctx->tune.on(T_DEBUG))
-            fprintf(stderr, "pastml_hip: thin top-down depths from %d of %d: %d units in %d bins\n", D0, n_td_levels,
-                    (int)td_list.size(), nb);
+    if (D.ok) {
+        PML_TRY(put(ctx, &D.d_units, P.td_units));
+        PML_TRY(put(ctx, &D.d_start, P.td.start));
+        PML_TRY(put(ctx, &D.d_levels, P.td.levels));
+        PML_TRY(put(ctx, &D.d_lv, P.td.lv));
     }
+    HIP_TRY(hipStreamSynchronize(ctx->stream));  // (the host tables go out of scope)
     return PML_OK;
 }
 
@@ -1492,19 +450,7 @@ int pml_chars_alloc(pml_ctx* ctx, int32_t n_cols, int32_t k) {
         // Forests with many nodes of three or four children (15 % of the nodes with grandchildren) take 16 lanes per unit where
         // k allows it: the lane-parallel gather of a unit's children (Gather<G>) takes G / 4 of them -- two with 8 lanes, four
         // with 16 --, a unit with more walks them one after the other and holds up the other units of its wavefront.
-        bool polytomies = false;
-        {
-            long long n_inner = 0, n34 = 0;   // (nodes with a child that has children: what is a stored node under cherry fusion)
-            for (int i = 0; i < ctx->N; ++i) {
-                const int nc = ctx->h_n_children[i];
-                bool inner = false;
-                for (int j = 0; j < nc && !inner; ++j) inner = ctx->h_n_children[ctx->h_first_child[i] + j] > 0;
-                if (!inner) continue;
-                ++n_inner;
-                n34 += nc == 3 || nc == 4;
-            }
-            polytomies = n_inner > 0 && n34 * 100 >= 15 * n_inner;
-        }
+        const bool polytomies = ctx->forest.polytomies;
         auto shape = [&](int var, int dflt, int& G, int& R) {
             int rf = k >= 3 ? dflt : k;
             // Up to 8 states: two per lane (2 or 4 lanes per unit).  In the latency-bound schedules -- small and mid-size
@@ -1530,25 +476,9 @@ int pml_chars_alloc(pml_ctx* ctx, int32_t n_cols, int32_t k) {
             while (G < need) G <<= 1;
         };
         shape(T_F81_R, 4, ctx->Gf, ctx->Rf);
-        // Balanced parts: nodes whose two children each carry two cherries of two tips, ids consecutive (what pml_tree_upload
-        // makes two-level units of) -- counted on the topology alone, whatever the switches, so that the lane shape, and with
-        // it a column's bits, is a function of k and the forest.
-        bool balanced_parts = false;
-        {
-            const int* fc = ctx->h_first_child.data();
-            const int* nch = ctx->h_n_children.data();
-            auto tips2 = [&](int x) { return nch[x] == 2 && nch[fc[x]] == 0 && nch[fc[x] + 1] == 0; };
-            auto pair = [&](int x) { return nch[x] == 2 && tips2(fc[x]) && tips2(fc[x] + 1) && fc[fc[x] + 1] == fc[fc[x]] + 2; };
-            long long n_internal = 0, n_two = 0;
-            for (int i = 0; i < ctx->N; ++i) {
-                if (nch[i] == 0) continue;
-                ++n_internal;
-                if (nch[i] != 2) continue;
-                const int a = fc[i], b = a + 1;
-                if (pair(a) && pair(b) && fc[b] == fc[a] + 2 && fc[fc[b]] == fc[fc[a]] + 4) ++n_two;
-            }
-            balanced_parts = n_two > 0 && n_two * 32 >= n_internal;
-        }
+        // Balanced parts (PmlForest::balanced_parts): counted on the topology alone, whatever the switches, so that the lane
+        // shape, and with it a column's bits, is a function of k and the forest.
+        const bool balanced_parts = ctx->forest.balanced_parts;
         // 8 states per lane bottom-up (32 < k <= 64) where the forest has such parts (cfg4: the level that rebuilds cherries
         // 1.80 -> 1.58 ms; 262 144-tip balanced tree x 32: bottom-up 0.77 -> 0.63 ms) and few nodes of three or four children
         // (8 lanes gather two children in parallel, see below); elsewhere 4: polytomies x 16 columns bottom-up 0.64 -> 0.50 ms
@@ -1559,7 +489,7 @@ int pml_chars_alloc(pml_ctx* ctx, int32_t n_cols, int32_t k) {
         // Level launches walk the lists sorted by shape inside every level (pml_tree_upload) from 4 lanes per unit on: 262 144
         // tips x 32, marginal pass: k = 8 1.82 -> 1.78 ms, k = 12 2.35 -> 2.26, k = 16 2.38 -> 2.26, k = 20 3.49 -> 3.06, k = 32
         // 3.53 -> 3.11; polytomies k = 12 1.36 -> 1.28, k = 20 1.55 -> 1.36; two lanes per unit (k <= 4) lose 11 % and keep id order.
-        ctx->level_lists_sorted = ctx->Gf >= 4 || ctx->shape_ordered;   // (narrow units too where the numbering follows the shapes)
+        ctx->level_lists_sorted = ctx->Gf >= 4 || ctx->forest.shape_ordered;   // (narrow units too where the numbering follows the shapes)
         if (ctx->tune.on(T_SORT_LEVELS)) ctx->level_lists_sorted = ctx->tune.get(T_SORT_LEVELS, 1) != 0;
         // Top-down: 8 states per lane for 32 < k <= 64 (above) unless the forest has many nodes of three or four children
         // (15 % of those with grandchildren): the lane-parallel gather of a unit's children takes
@@ -1572,10 +502,10 @@ int pml_chars_alloc(pml_ctx* ctx, int32_t n_cols, int32_t k) {
         if (k >= 2 && (ctx->ks & 1)) ctx->ks += 1;  // 16-byte lane accesses
         {
             const int g = ctx->bu_wide_lanes ? 8 : ctx->Gf;
-            const int nl = (int)ctx->bu_offsets_f.size() - 1;
+            const int nl = (int)ctx->forest.bu_offsets_f.size() - 1;
             long long passes = 0;
             for (int l = 0; l < nl; ++l)
-                passes += ((long long)(ctx->bu_offsets_f[l + 1] - ctx->bu_offsets_f[l]) * g + PML_SMALL_BLOCK - 1) / PML_SMALL_BLOCK;
+                passes += ((long long)(ctx->forest.bu_offsets_f[l + 1] - ctx->forest.bu_offsets_f[l]) * g + PML_SMALL_BLOCK - 1) / PML_SMALL_BLOCK;
             // (up to 4 lanes per unit, k <= 16: with wider units one workgroup per column is too little parallelism --
             // HIV1C tree, 64 columns: k = 12 0.28 against 0.32 ms with level launches, k = 20 0.27 against 0.22)
             ctx->levels_fit_workgroup = nl > 0 && g <= 4 && passes * 4 <= (long long)nl * 5;
@@ -1637,7 +567,7 @@ int pml_chars_alloc(pml_ctx* ctx, int32_t n_cols, int32_t k) {
     // THIN_BYTES (20 MB) of state vectors over all columns -- beyond, the level kernels stream it faster than workgroups
     // that walk subtrees.  Measured (profiles/r05u_thin_ends.txt, THIN_UNITS sweeps): k = 4 x 32 columns 4 096 (16 384 loses
     // 20 %); k = 64: x 32 columns 1 024 - 2 048, x 16 2 048, x 8 4 096; k = 20 x 32 4 096.
-    if (!wide_states(ctx) && !ctx->bu_offsets_f.empty() && (ctx->bu_offsets_f.back() > 2048 || ctx->tune.on(T_THIN_UNITS)) && !ctx->tune.on(T_NO_THIN)) {
+    if (!wide_states(ctx) && !ctx->forest.bu_offsets_f.empty() && (ctx->forest.bu_offsets_f.back() > 2048 || ctx->tune.on(T_THIN_UNITS)) && !ctx->tune.on(T_NO_THIN)) {
         long long thin = ctx->tune.get(T_THIN_UNITS, 0);
         if (!ctx->tune.on(T_THIN_UNITS)) {
             const long long bytes = ctx->tune.get(T_THIN_BYTES, 20ll << 20);
@@ -1710,7 +640,7 @@ int pml_masks_from_tip_states(pml_ctx* ctx, int32_t col_begin, int32_t col_end, 
     const int nc = col_end - col_begin;
     std::vector<int32_t> own_ids;   // the caller's tip ids in the library's numbering
     for (int j = 0; j < n_tips; ++j)
-        if (tip_ids[j] < 0 || tip_ids[j] >= ctx->N || ctx->h_n_children[internal_id(ctx, tip_ids[j])] != 0)
+        if (tip_ids[j] < 0 || tip_ids[j] >= ctx->N || ctx->forest.n_children[internal_id(ctx, tip_ids[j])] != 0)
             return fail(PML_ERR_INVALID, "tip_ids[%d] = %d is not a tip", j, tip_ids[j]);
     if (permuted(ctx) && n_tips > 0) {
         own_ids.resize(n_tips);
@@ -2218,13 +1148,13 @@ static int enqueue_bottom_up(pml_ctx* ctx, int is_marginal, bool small_path, boo
         // end's single launch (in between, level launches where a level is still too wide for it)
         const pml_ctx::ThinSchedule& H = ctx->thin;
         auto level_launch = [&](int l) -> int {
-            const int a = ctx->bu_offsets_f[l], b = ctx->bu_offsets_f[l + 1];
+            const int a = ctx->forest.bu_offsets_f[l], b = ctx->forest.bu_offsets_f[l + 1];
             return dispatch_sweep(ctx, ctx->bu_level_vec_f[l] ? SW_BU_MARG_FUSED : SW_BU_MARG_FUSED_NOVEC, ctx->d_bu_order_f + a, b - a);
         };
         for (int l = 0; l < H.floor_level; ++l) PML_TRY(level_launch(l));
         for (size_t q = 0; q < H.tiers.size(); ++q) PML_TRY(dispatch_blocks_f81(ctx, true, 1 + (int)q));
-        const int nl = (int)ctx->bu_offsets_f.size() - 1;
-        int tail = std::min(nl - H.top_level, narrow_levels(ctx, ctx->bu_offsets_f, nl, false, ctx->sched_cols));
+        const int nl = (int)ctx->forest.bu_offsets_f.size() - 1;
+        int tail = std::min(nl - H.top_level, narrow_levels(ctx, ctx->forest.bu_offsets_f, nl, false, ctx->sched_cols));
         for (int l = H.top_level; l < nl - tail; ++l) PML_TRY(level_launch(l));
         PML_TRY(prof_end(ctx, 0, H.floor_level + (long long)H.tiers.size() + (nl - tail - H.top_level)));
         if (tail > 0) {
@@ -2232,10 +1162,10 @@ static int enqueue_bottom_up(pml_ctx* ctx, int is_marginal, bool small_path, boo
             loglik_done = true;
         }
     } else if (fused) {
-        const int nl = (int)ctx->bu_offsets_f.size() - 1;
-        const int tail = narrow_levels(ctx, ctx->bu_offsets_f, nl, false, ctx->sched_cols);
+        const int nl = (int)ctx->forest.bu_offsets_f.size() - 1;
+        const int tail = narrow_levels(ctx, ctx->forest.bu_offsets_f, nl, false, ctx->sched_cols);
         for (int l = 0; l < nl - tail; ++l) {
-            const int a = ctx->bu_offsets_f[l], b = ctx->bu_offsets_f[l + 1];
+            const int a = ctx->forest.bu_offsets_f[l], b = ctx->forest.bu_offsets_f[l + 1];
             PML_TRY(dispatch_sweep(ctx, ctx->bu_level_vec_f[l] ? SW_BU_MARG_FUSED : SW_BU_MARG_FUSED_NOVEC,
                                    ctx->d_bu_order_f + a, b - a));
         }
@@ -2247,9 +1177,9 @@ static int enqueue_bottom_up(pml_ctx* ctx, int is_marginal, bool small_path, boo
     } else if (!is_marginal && ctx->kind == PML_MODEL_F81 && ctx->fuse && !ctx->has_init && ctx->n_cherries > 0 &&
                ctx->W == 1) {
         // joint sweep over the cherry-fused lists (no altered nodes whose tables would need rewriting)
-        const int nl = (int)ctx->bu_offsets_f.size() - 1;
+        const int nl = (int)ctx->forest.bu_offsets_f.size() - 1;
         for (int l = 0; l < nl; ++l) {
-            const int a = ctx->bu_offsets_f[l], b = ctx->bu_offsets_f[l + 1];
+            const int a = ctx->forest.bu_offsets_f[l], b = ctx->forest.bu_offsets_f[l + 1];
             PML_TRY(dispatch_sweep(ctx, ctx->bu_level_vec_f[l] ? SW_BU_JOINT_FUSED : SW_BU_JOINT_FUSED_NOVEC,
                                    ctx->d_bu_order_f + a, b - a));
         }
@@ -2262,7 +1192,7 @@ static int enqueue_bottom_up(pml_ctx* ctx, int is_marginal, bool small_path, boo
         // (tiers only while their levels are thin for the whole batch: with many columns a level fills the chip)
         if (E.ok && (long long)E.widest * ctx->C <= 16384) {
             for (int l = 0; l < E.first_level; ++l) {
-                const int a = ctx->bu_offsets[l], b = ctx->bu_offsets[l + 1];
+                const int a = ctx->forest.bu_offsets[l], b = ctx->forest.bu_offsets[l + 1];
                 PML_TRY(launch_eigen_joint(ctx, ctx->d_bu_units + a, nullptr, 0, b - a));
             }
             for (const pml_ctx::EigenTiers::Tier& T : E.tiers)
@@ -2271,17 +1201,17 @@ static int enqueue_bottom_up(pml_ctx* ctx, int is_marginal, bool small_path, boo
             // the narrow end in one launch
             int l = E.top_level;
             long long extra = 0;
-            for (; l < ctx->n_bu_levels && ctx->bu_offsets[l + 1] - ctx->bu_offsets[l] > 48; ++l, ++extra) {
-                const int a = ctx->bu_offsets[l], b = ctx->bu_offsets[l + 1];
+            for (; l < ctx->n_bu_levels && ctx->forest.bu_offsets[l + 1] - ctx->forest.bu_offsets[l] > 48; ++l, ++extra) {
+                const int a = ctx->forest.bu_offsets[l], b = ctx->forest.bu_offsets[l + 1];
                 PML_TRY(launch_eigen_joint(ctx, ctx->d_bu_units + a, nullptr, 0, b - a));
             }
             PML_TRY(launch_eigen_joint(ctx, ctx->d_bu_units, ctx->d_bu_offsets, l, ctx->n_bu_levels - l));
             PML_TRY(prof_end(ctx, 0, E.first_level + 2 + extra + (long long)E.tiers.size()));
         } else {
-        const int tail = narrow_levels(ctx, ctx->bu_offsets, ctx->n_bu_levels, false, ctx->C,
+        const int tail = narrow_levels(ctx, ctx->forest.bu_offsets, ctx->n_bu_levels, false, ctx->C,
                                        PML_WAVES_PER_BLOCK * (64 / ctx->k));
         for (int l = 0; l < ctx->n_bu_levels - tail; ++l) {
-            const int a = ctx->bu_offsets[l], b = ctx->bu_offsets[l + 1];
+            const int a = ctx->forest.bu_offsets[l], b = ctx->forest.bu_offsets[l + 1];
             PML_TRY(launch_eigen_joint(ctx, ctx->d_bu_units + a, nullptr, 0, b - a));
         }
         PML_TRY(launch_eigen_joint(ctx, ctx->d_bu_units, ctx->d_bu_offsets, ctx->n_bu_levels - tail, tail));
@@ -2295,7 +1225,7 @@ static int enqueue_bottom_up(pml_ctx* ctx, int is_marginal, bool small_path, boo
         if (gemm_tiers && E.ok && (long long)E.widest * ctx->C <= 16384) {
             // thin levels in tiers of subtree blocks, as in the joint sweep (pml_ctx::EigenTiers)
             for (int l = 0; l < E.first_level; ++l) {
-                const int a = ctx->bu_offsets[l], b = ctx->bu_offsets[l + 1];
+                const int a = ctx->forest.bu_offsets[l], b = ctx->forest.bu_offsets[l + 1];
                 PML_TRY(launch_eigen_gemm(ctx, PML_EIGG_BU, ctx->d_bu_order + a, 0, b - a));
             }
             for (const pml_ctx::EigenTiers::Tier& T : E.tiers)
@@ -2303,17 +1233,17 @@ static int enqueue_bottom_up(pml_ctx* ctx, int is_marginal, bool small_path, boo
                                                  T.n_blocks));
             int l = E.top_level;
             long long extra = 0;
-            for (; l < ctx->n_bu_levels && ctx->bu_offsets[l + 1] - ctx->bu_offsets[l] > 2 * PML_WAVES_PER_BLOCK * 16; ++l, ++extra) {
-                const int a = ctx->bu_offsets[l], b = ctx->bu_offsets[l + 1];
+            for (; l < ctx->n_bu_levels && ctx->forest.bu_offsets[l + 1] - ctx->forest.bu_offsets[l] > 2 * PML_WAVES_PER_BLOCK * 16; ++l, ++extra) {
+                const int a = ctx->forest.bu_offsets[l], b = ctx->forest.bu_offsets[l + 1];
                 PML_TRY(launch_eigen_gemm(ctx, PML_EIGG_BU, ctx->d_bu_order + a, 0, b - a));
             }
             PML_TRY(launch_eigen_gemm_narrow(ctx, PML_EIGG_BU, ctx->d_bu_order, ctx->d_bu_offsets, l, ctx->n_bu_levels - l));
             PML_TRY(prof_end(ctx, 0, E.first_level + 2 + extra + (long long)E.tiers.size()));
         } else {
         // levels one workgroup finishes in a pass or two per wave (4 waves x 16 nodes) share one launch
-        const int tail = narrow_levels(ctx, ctx->bu_offsets, ctx->n_bu_levels, false, ctx->C, 2 * PML_WAVES_PER_BLOCK * 16);
+        const int tail = narrow_levels(ctx, ctx->forest.bu_offsets, ctx->n_bu_levels, false, ctx->C, 2 * PML_WAVES_PER_BLOCK * 16);
         for (int l = 0; l < ctx->n_bu_levels - tail; ++l) {
-            const int a = ctx->bu_offsets[l], b = ctx->bu_offsets[l + 1];
+            const int a = ctx->forest.bu_offsets[l], b = ctx->forest.bu_offsets[l + 1];
             PML_TRY(launch_eigen_gemm(ctx, PML_EIGG_BU, ctx->d_bu_order + a, 0, b - a));
         }
         PML_TRY(launch_eigen_gemm_narrow(ctx, PML_EIGG_BU, ctx->d_bu_order, ctx->d_bu_offsets, ctx->n_bu_levels - tail, tail));
@@ -2325,9 +1255,9 @@ static int enqueue_bottom_up(pml_ctx* ctx, int is_marginal, bool small_path, boo
         PML_TRY(launch_eigen_tips(ctx, is_marginal ? 0 : 1));
         {
         const int eig_nb = ((ctx->k + 3) / 4) % 4 == 0 ? 1 : (((ctx->k + 3) / 4) % 2 == 0 ? 2 : 4);  // EigShape::NB
-        const int tail = narrow_levels(ctx, ctx->bu_offsets, ctx->n_bu_levels, false, ctx->C, PML_WAVES_PER_BLOCK * eig_nb);
+        const int tail = narrow_levels(ctx, ctx->forest.bu_offsets, ctx->n_bu_levels, false, ctx->C, PML_WAVES_PER_BLOCK * eig_nb);
         for (int l = 0; l < ctx->n_bu_levels - tail; ++l) {
-            const int a = ctx->bu_offsets[l], b = ctx->bu_offsets[l + 1];
+            const int a = ctx->forest.bu_offsets[l], b = ctx->forest.bu_offsets[l + 1];
             PML_TRY(launch_eigen_fused(ctx, mode, ctx->d_bu_order + a, 0, b - a, 0));
         }
         PML_TRY(launch_eigen_narrow(ctx, mode, ctx->d_bu_order, ctx->d_bu_offsets, ctx->n_bu_levels - tail, tail));
@@ -2335,7 +1265,7 @@ static int enqueue_bottom_up(pml_ctx* ctx, int is_marginal, bool small_path, boo
         }
     } else {
         for (int l = 0; l < ctx->n_bu_levels; ++l) {
-            const int a = ctx->bu_offsets[l], b = ctx->bu_offsets[l + 1];
+            const int a = ctx->forest.bu_offsets[l], b = ctx->forest.bu_offsets[l + 1];
             const SweepKind sk = is_marginal ? SW_BU_MARG : (ctx->kind == PML_MODEL_F81 && !ctx->bu_level_vec[l]
                                                                      ? SW_BU_JOINT_NOVEC : SW_BU_JOINT);
             PML_TRY(dispatch_sweep(ctx, sk, ctx->d_bu_order + a, b - a));
@@ -2449,7 +1379,7 @@ static int submit_bottom_up(pml_ctx* ctx, int is_marginal, const uint8_t* active
     ctx->bu_mode = -1;
     ctx->td_valid = ctx->js_valid = false;
     // mid-size forests: the level launches are latency-bound, replay them as one hipGraph
-    const int n_launches = small_path ? 1 : (is_marginal && ctx->kind == PML_MODEL_F81 ? (int)ctx->bu_offsets_f.size() - 1
+    const int n_launches = small_path ? 1 : (is_marginal && ctx->kind == PML_MODEL_F81 ? (int)ctx->forest.bu_offsets_f.size() - 1
                                                                                           : ctx->n_bu_levels);
     const u64 generation_before = ctx->h_done ? *reinterpret_cast<volatile u64*>(ctx->h_done) : 0;  // (the stream is idle)
     if (ctx->graphs && !ctx->profile && n_launches >= 4) {  // (the block schedule's few launches replay as a graph too)
@@ -2511,7 +1441,7 @@ static int collect_bottom_up(pml_ctx* ctx, int is_marginal, double* loglik_out, 
         int ep = -1, ec = -1;
         if (err[c] != ~0ull && flags[c] != 0.0) {  // (a column that sat the sweep out reports nothing)
             ec = (int)(err[c] & 0xffffffffull);
-            ep = api_id(ctx, ctx->h_parent[ec]);
+            ep = api_id(ctx, ctx->forest.parent[ec]);
             ec = api_id(ctx, ec);
             if (status == PML_OK)
                 status = fail(PML_ZERO_LIKELIHOOD, "zero likelihood in column %d between parent %d and child %d", c, ep, ec);
@@ -2628,7 +1558,7 @@ static int run_top_down(pml_ctx* ctx) {
         }
         // F81 family: the roots and the levels right below them in one launch
         const int head = (td_fused && !td_small && ctx->n_roots <= 64)
-                             ? narrow_levels(ctx, ctx->td_parent_offsets_f, ctx->n_td_levels, true, ctx->C) : 0;
+                             ? narrow_levels(ctx, ctx->forest.td_parent_offsets_f, ctx->n_td_levels, true, ctx->C) : 0;
         if (!td_small && head == 0) PML_TRY(dispatch_sweep(ctx, SW_ROOTS, nullptr, ctx->n_roots));
         if (head > 0) PML_TRY(dispatch_small_f81(ctx, false, 0, 0, head));
         PML_TRY(prof_begin(ctx));  // the profile brackets the level kernel's launches only
@@ -2641,7 +1571,7 @@ static int run_top_down(pml_ctx* ctx) {
         if (eigen_gemm(ctx)) {
             int head = 0;
             {
-                std::vector<int> off(ctx->td_offsets.begin() + 1, ctx->td_offsets.end());
+                std::vector<int> off(ctx->forest.td_offsets.begin() + 1, ctx->forest.td_offsets.end());
                 head = narrow_levels(ctx, off, ctx->n_td_levels - 1, true, ctx->C, 2 * PML_WAVES_PER_BLOCK * 16);
             }
             if (head > 0) {
@@ -2649,7 +1579,7 @@ static int run_top_down(pml_ctx* ctx) {
                 ++n_launch;
             }
             for (int d = 1 + head; d < ctx->n_td_levels; ++d) {
-                const int a = ctx->td_offsets[d], b = ctx->td_offsets[d + 1];
+                const int a = ctx->forest.td_offsets[d], b = ctx->forest.td_offsets[d + 1];
                 PML_TRY(launch_eigen_gemm(ctx, PML_EIGG_TD, nullptr, a, b - a));
                 if (b > a) ++n_launch;
             }
@@ -2661,7 +1591,7 @@ static int run_top_down(pml_ctx* ctx) {
             // td_offsets[d] .. td_offsets[d + 1] = the nodes of depth d: the run of narrow depths below the roots
             int head = 0;
             {
-                std::vector<int> off(ctx->td_offsets.begin() + 1, ctx->td_offsets.end());
+                std::vector<int> off(ctx->forest.td_offsets.begin() + 1, ctx->forest.td_offsets.end());
                 const int ks4 = (ctx->k + 3) / 4;
                 const int eig_nb = ks4 % 4 == 0 ? 1 : (ks4 % 2 == 0 ? 2 : 4);  // EigShape::NB
                 head = narrow_levels(ctx, off, ctx->n_td_levels - 1, true, ctx->C, PML_WAVES_PER_BLOCK * eig_nb);
@@ -2671,7 +1601,7 @@ static int run_top_down(pml_ctx* ctx) {
                 ++n_launch;
             }
             for (int d = 1 + head; d < ctx->n_td_levels; ++d) {
-                const int a = ctx->td_offsets[d], b = ctx->td_offsets[d + 1];
+                const int a = ctx->forest.td_offsets[d], b = ctx->forest.td_offsets[d + 1];
                 PML_TRY(launch_eigen_fused(ctx, PML_EIG_TD, nullptr, a, b - a, 0));
                 if (b > a) ++n_launch;
             }
@@ -2687,7 +1617,7 @@ static int run_top_down(pml_ctx* ctx) {
         const bool deep = td_fused && !td_small && deep_top_down(ctx) && ctx->deep.first_depth > head;
         if (deep) {
             for (int l = head; l < ctx->deep.first_depth; ++l) {
-                const int a = ctx->td_parent_offsets_f[l], b = ctx->td_parent_offsets_f[l + 1];
+                const int a = ctx->forest.td_parent_offsets_f[l], b = ctx->forest.td_parent_offsets_f[l + 1];
                 PML_TRY(dispatch_sweep(ctx, SW_TD_FUSED, ctx->d_td_parents_f + a, b - a));
                 if (b > a) ++n_launch;
             }
@@ -2696,12 +1626,12 @@ static int run_top_down(pml_ctx* ctx) {
             return PML_OK;
         }
         if (td_fused && !td_small && ctx->Gt < 8 && !ctx->tune.on(T_NO_TD_TAIL)) {
-            tail = narrow_levels(ctx, ctx->td_parent_offsets_f, ctx->n_td_levels, false, ctx->C, 0, 1);
+            tail = narrow_levels(ctx, ctx->forest.td_parent_offsets_f, ctx->n_td_levels, false, ctx->C, 0, 1);
             if (tail > ctx->n_td_levels - head) tail = ctx->n_td_levels - head;
             if (tail < 2) tail = 0;
         }
         for (int l = head; l < (td_small ? 0 : ctx->n_td_levels - tail); ++l) {
-            const std::vector<int>& off = td_fused ? ctx->td_parent_offsets_f : ctx->td_parent_offsets;
+            const std::vector<int>& off = td_fused ? ctx->forest.td_parent_offsets_f : ctx->forest.td_parent_offsets;
             const int a = off[l], b = off[l + 1];
             PML_TRY(dispatch_sweep(ctx, td_fused ? SW_TD_FUSED : SW_TD,
                                    (td_fused ? ctx->d_td_parents_f : ctx->d_td_parents) + a, b - a));
@@ -2768,7 +1698,7 @@ static int materialize_td(pml_ctx* ctx) {
         st.td = ctx->d_td;  // state_of hides them when the option is off
         st.te = ctx->d_te;
         for (int d = 1; d < ctx->n_td_levels; ++d) {
-            const int a = ctx->td_offsets[d], b = ctx->td_offsets[d + 1];
+            const int a = ctx->forest.td_offsets[d], b = ctx->forest.td_offsets[d + 1];
             if (b <= a) continue;
             dim3 grid(grid_for(ctx, b - a, PML_WAVES_PER_BLOCK, ctx->C), ctx->C);
             hipLaunchKernelGGL(td_fill_kernel, grid, dim3(PML_BLOCK), 0, ctx->stream, tree_of(ctx, f81), cols_of(ctx), st,
@@ -2816,7 +1746,7 @@ int pml_marginal_pass(pml_ctx* ctx, double* loglik_out, int32_t* err_parent, int
     // between the last bottom-up kernel and the first top-down one.  (F81 family, once the buffers of a top-down sweep
     // exist: nothing may be allocated while a stream is captured.)
     const bool td_small = single_launch_sweeps(ctx) && ctx->kind == PML_MODEL_F81;
-    const int bu_launches = td_small ? 1 : (int)ctx->bu_offsets_f.size() - 1;
+    const int bu_launches = td_small ? 1 : (int)ctx->forest.bu_offsets_f.size() - 1;
     const bool one_graph = ctx->graphs && !ctx->profile && ctx->kind == PML_MODEL_F81 && ctx->d_post != nullptr &&
                            (!ctx->keep_td || ctx->d_td != nullptr) &&
                            (bu_launches >= 4 || (!td_small && ctx->n_td_levels >= 4));
@@ -2919,7 +1849,7 @@ int pml_marginal_pass(pml_ctx* ctx, double* loglik_out, int32_t* err_parent, int
 static int submit_joint_backtrace(pml_ctx* ctx) {
     int head = 0;
     {
-        std::vector<int> off(ctx->td_offsets.begin() + 1, ctx->td_offsets.end());
+        std::vector<int> off(ctx->forest.td_offsets.begin() + 1, ctx->forest.td_offsets.end());
         head = narrow_levels(ctx, off, ctx->n_td_levels - 1, true, ctx->C, 1024);
     }
     const pml_ctx::BacktraceTiers& B = ctx->bt_tiers;
@@ -2945,7 +1875,7 @@ static int submit_joint_backtrace(pml_ctx* ctx) {
             return PML_OK;
         }
         for (int l = 1 + head; l < ctx->n_td_levels; ++l) {
-            const int a = ctx->td_offsets[l], b = ctx->td_offsets[l + 1];
+            const int a = ctx->forest.td_offsets[l], b = ctx->forest.td_offsets[l + 1];
             if (b <= a) continue;
             dim3 grid(grid_for(ctx, b - a, PML_BLOCK, ctx->C), ctx->C);
             hipLaunchKernelGGL(joint_backtrace_kernel, grid, dim3(PML_BLOCK), 0, ctx->stream, tree_of(ctx), cols_of(ctx),
@@ -3032,7 +1962,7 @@ static int marginal_counts_impl(pml_ctx* ctx, int32_t col, int32_t n_repetitions
         hipLaunchKernelGGL(counts_roots_kernel, dim3(std::min(ctx->n_roots, 1024)), dim3(64), 0, ctx->stream, t, c, st, col,
                            n_repetitions, seed, d_counts, ctx->d_old_of_new);
         for (int l = 0; l < ctx->n_td_levels; ++l) {
-            const int a = ctx->td_parent_offsets[l], b = ctx->td_parent_offsets[l + 1];
+            const int a = ctx->forest.td_parent_offsets[l], b = ctx->forest.td_parent_offsets[l + 1];
             if (b <= a) continue;
             hipLaunchKernelGGL(counts_level_kernel, dim3(std::min(b - a, 65536)), dim3(64), 0, ctx->stream, t, c, st, m, P,
                                col, n_repetitions, seed, ctx->d_td_parents + a, b - a, d_counts, d_result, ctx->d_old_of_new,
@@ -3240,7 +2170,7 @@ static int download_internal(pml_ctx* ctx, int what, int32_t col, void* out) {
             std::vector<u64> m(N * ctx->W);
             HIP_TRY(hipMemcpy(m.data(), ctx->d_masks + (size_t)col * N * ctx->W, m.size() * sizeof(u64), hipMemcpyDeviceToHost));
             for (size_t n = 0; n < N; ++n)
-                if (ctx->h_n_children[n] == 0)
+                if (ctx->forest.n_children[n] == 0)
                     for (int s = 0; s < ctx->k; ++s) o[n * ctx->k + s] = (double)((m[n * ctx->W + (s >> 6)] >> (s & 63)) & 1ull);
             return PML_OK;
         }
@@ -3248,7 +2178,7 @@ static int download_internal(pml_ctx* ctx, int what, int32_t col, void* out) {
             if (ctx->bu_mode < 0) return fail(PML_ERR_INVALID, "no valid bottom-up sweep");
             PML_TRY(fetch_exponents(ctx, ctx->d_be, col, (double*)out));
             for (size_t n = 0; n < N; ++n)
-                if (ctx->h_n_children[n] == 0) ((double*)out)[n] = 0.0;
+                if (ctx->forest.n_children[n] == 0) ((double*)out)[n] = 0.0;
             return PML_OK;
         }
         case PML_BUF_TD:

@@ -21,6 +21,7 @@
 #include <vector>
 
 #include "pml_model.h"   // PmlTree, PmlCols, PmlState, PmlUnit, PmlModel (and the F81 / miscellaneous kernels' headers below it)
+#include "pml_schedule.h" // PmlTune, the schedules' host side, PmlForest
 
 struct PmlComm;  // pml_comm.h (pml_api.hip only)
 
@@ -45,60 +46,6 @@ PML_INTERNAL int pml_fail(int code, const char* fmt, ...) __attribute__((format(
         int _s = (expr);         \
         if (_s != PML_OK) return _s; \
     } while (0)
-
-// ---------------------------------------------------------------------------------------------------------------------
-// Every switch of the schedules in one table per context.  The defaults come from the environment (PASTML_HIP_<NAME>) when
-// the ctx is created, pml_ctx_set_tunable overrides them for that ctx -- there are no function-local statics: two contexts
-// of one process can run different schedules, and a test that sets a switch gets it (round 3 latched several of them at
-// their first use in the process).  FLAG: on when present (environment: whatever the value; set_tunable: value != 0).
-// TREE: read by pml_tree_upload / pml_chars_alloc, so it must be set before the tree is uploaded.
-// ---------------------------------------------------------------------------------------------------------------------
-#define PML_TUNABLES(X)                                                                                              \
-    X(GRID_CAP, 0, 0) X(SMALL_MANY_NODES, 0, 0) X(BLOCK_MAX_WORK, 0, 0)    \
-    X(NO_MFMA, 1, 0) X(NO_EIGEN_FUSED, 1, 0) X(NO_HKY_FUSED, 1, 0)      \
-    X(BLOCK_THREADS, 0, 0) X(EIG_BLOCKS, 0, 0) X(NO_EIGEN_GEMM, 1, 0) X(NO_EIGEN_JOINT_VALU, 1, 0) X(EIGJ_BLOCKS, 0, 0) \
-    X(EIGJ_TIP_BLOCKS, 0, 0) X(EIGJ_ONE_TIPS_KERNEL, 1, 0) X(EIGJ_TIER_THIN, 0, 1) X(EIGJ_TIER_DEPTH, 0, 1)            \
-    X(NO_EIGJ_TIERS, 1, 1) X(NO_BT_TIERS, 1, 1) X(NO_SHAPE_SORT, 1, 1) X(NO_SUPER, 1, 1) X(SUPER_MIN, 0, 1)            \
-    X(STACK_MIN, 0, 1) X(NO_STACK, 1, 1) X(DEBUG, 1, 0) X(BLOCK_NODES, 0, 1) X(BLOCK_MAX_STORED, 0, 1)                 \
-    X(BLOCK_HEIGHT_CAP, 0, 1) X(SMALL_MAX_NODES, 0, 1) X(F81_R, 0, 1) X(F81_TD_R, 0, 1) X(NO_GRAPH, 1, 1)              \
-    X(NARROW_UNITS, 0, 0) X(NO_EIGG_TIERS, 1, 0) X(NO_SPIN_WAIT, 1, 0)   \
-    X(PIJ_STAGE_ROWS, 0, 0) X(PIJ_BLOCKS, 0, 0) X(NO_HEIGHT_ORDER, 1, 1) X(NO_TD_TAIL, 1, 0) X(NO_PIJ_VALU, 1, 0) X(PIJ_VALU, 1, 0) X(NO_PIJ_WIDE, 1, 0) X(NO_EIGJ_PIPE, 1, 0) \
-    X(THIN_UNITS, 0, 1) X(THIN_BYTES, 0, 1) X(THIN_BLOCK_NODES, 0, 1) X(NO_THIN, 1, 0) X(NO_THIN_WIDE, 1, 0) X(BU_WIDE, 0, 1) X(SORT_LEVELS, 0, 1) X(NO_WIDE_LEAN, 1, 0) X(SHAPE_ORDER, 0, 1)
-enum PmlTunable {
-#define X(name, flag, tree) T_##name,
-    PML_TUNABLES(X)
-#undef X
-    T_COUNT
-};
-static const char* const kTunableName[T_COUNT] = {
-#define X(name, flag, tree) #name,
-    PML_TUNABLES(X)
-#undef X
-};
-static const bool kTunableFlag[T_COUNT] = {
-#define X(name, flag, tree) flag != 0,
-    PML_TUNABLES(X)
-#undef X
-};
-static const bool kTunableTree[T_COUNT] = {
-#define X(name, flag, tree) tree != 0,
-    PML_TUNABLES(X)
-#undef X
-};
-struct PmlTune {
-    long long val[T_COUNT];
-    bool has[T_COUNT];
-    PmlTune() {
-        for (int i = 0; i < T_COUNT; ++i) {
-            const std::string var = std::string("PASTML_HIP_") + kTunableName[i];
-            const char* e = getenv(var.c_str());
-            has[i] = e != nullptr;
-            val[i] = e ? atoll(e) : 0;
-        }
-    }
-    bool on(int i) const { return has[i]; }
-    long long get(int i, long long dflt) const { return has[i] ? val[i] : dflt; }
-};
 
 struct pml_ctx {
     int device = 0;
@@ -131,8 +78,7 @@ struct pml_ctx {
     double* d_msg = nullptr;  // fused eigen sweeps: messages of the bottom-up sweep
     int *d_tip_rest = nullptr, *d_tip_rest_count = nullptr;  // eigen joint sweep: [C][n_tips] tips that are not observed, [C]
     double* d_dist = nullptr;
-    std::vector<int> bu_offsets, td_offsets, td_parent_offsets, h_parent, h_n_children;
-    std::vector<int> h_first_child, h_fh, h_order_f, h_tdp;  // host copies for build_thin_ends (fused heights, fused lists)
+    PmlForest forest;  // the forest in the library's numbering (pml_plan_forest): level tables, kinds, fused lists, traits
     // Internal node numbering (height_order below): the library numbers the nodes of a ragged forest so that the sibling
     // groups a level's units gather lie next to each other; every per-node array that crosses the C-ABI is in the CALLER's
     // numbering and is permuted on the way in / out.  Both empty when the caller's numbering is kept (balanced trees, ...).
@@ -143,91 +89,27 @@ struct pml_ctx {
     // cherry fusion (F81 marginal sweeps): node kinds and level lists over the stored internal nodes only
     bool fuse = true;
     unsigned char* d_kind = nullptr;
-    std::vector<unsigned char> h_kind;
     int *d_bu_order_f = nullptr, *d_td_parents_f = nullptr, *d_cherries = nullptr;
     // unit descriptors of the F81 kernels, parallel to d_bu_order_f / d_td_parents_f / d_bu_order
     PmlUnit *d_bu_units_f = nullptr, *d_td_units_f = nullptr, *d_bu_units = nullptr, *d_cherry_units = nullptr;
     // the same fused lists with every level's units sorted by shape (level launches of wide units, see pml_tree_upload)
     PmlUnit *d_bu_units_fs = nullptr, *d_td_units_fs = nullptr;
     int *d_bu_offsets_f = nullptr, *d_td_parent_offsets_f = nullptr;  // level tables for the single-launch kernels
-    // subtree blocks (pml_kernels_f81.h, bottom): the stored nodes cut into subtrees of at most PML_BLOCK_NODES stored
-    // nodes, walked by one workgroup each, and the "top" above the cuts with level tables of its own
-    struct BlockSchedule {
-        bool ok = false;
-        int n_blocks = 0;
-        long long steps = 0;  // sum over the blocks of their levels: workgroup steps of one column's sweep
-        PmlUnit *d_bu_units = nullptr, *d_td_units = nullptr;          // units of the blocks, block by block
-        int *d_bu_start = nullptr, *d_bu_levels = nullptr, *d_bu_lv = nullptr;
-        int *d_td_start = nullptr, *d_td_levels = nullptr, *d_td_lv = nullptr;
-        PmlUnit *d_top_bu_units = nullptr, *d_top_td_units = nullptr;  // units of the top part, level by level
-        int *d_top_bu_offsets = nullptr, *d_top_td_offsets = nullptr;
-        std::vector<int> top_bu_offsets, top_td_offsets;               // host copies (launch geometry)
-        std::vector<char> top_bu_vec;                                   // per top level: stored node among children 0, 1
-    } blocks;
-    // Thin ends of a large ragged forest, units of fewer than 8 lanes (round 5).  Bottom-up: the fused levels from
-    // floor_level on (each of at most PASTML_HIP_THIN_UNITS units) in tiers of subtree blocks, like `blocks` but of that
-    // part of the forest only and with several small subtrees per workgroup; the wide levels below stay level launches.
-    struct ThinSchedule {
-        bool ok = false;
-        int floor_level = 0;  // the fused levels below stay level launches
-        int top_level = 0;    // ... and from this one on they are the narrow end's (level launches where still wide)
-        struct Tier { int first_block, n_blocks; };
-        std::vector<Tier> tiers;   // runs of levels, each cut into subtrees of at most THIN_BLOCK_NODES units: a launch per tier
-        PmlUnit* d_units = nullptr;
-        int *d_start = nullptr, *d_levels = nullptr, *d_lv = nullptr;
-    } thin;
-    // Top-down: the depths from first_depth on (each of at most THIN_UNITS parents): the subtrees hanging at first_depth,
-    // packed into bins of about THIN_BLOCK_NODES units, ONE launch walks them all, a workgroup per (bin, column).
-    struct DeepSchedule {
-        bool ok = false;
-        int first_depth = 0, n_blocks = 0;
-        PmlUnit* d_units = nullptr;
-        int *d_start = nullptr, *d_levels = nullptr, *d_lv = nullptr;
-    } deep;
-    // two-level units (pml_kernels_f81.h): nodes with two stored children that each carry two cherries of two tips run
-    // both levels in one unit; they and their children leave the level lists ("rest" lists, same level structure)
-    struct SuperSchedule {
-        bool ok = false;
-        int n = 0;
-        PmlUnit* d_units = nullptr;
-        PmlUnit* d_child_units = nullptr;  // the 2 n children of the two-level units, as units of their own (downloads)
-        PmlUnit *d_bu_units_r = nullptr, *d_td_units_r = nullptr;
-        PmlUnit *d_bu_units_rs = nullptr, *d_td_units_rs = nullptr;  // ... sorted by shape inside every level
-        // stacked units (pml_kernels_f81.h): nodes with two plain stored children of two stored children each, by
-        // bottom-up level and by depth; their children as units of their own for downloads
-        int n_child_units = 0;  // entries of d_child_units: the children of the two-level units
-        int n_stack = 0;
-        PmlUnit *d_stack_bu = nullptr, *d_stack_td = nullptr, *d_stack_children = nullptr;
-        std::vector<int> stack_bu_offsets, stack_td_offsets;
-        int *d_bu_offsets_r = nullptr, *d_td_offsets_r = nullptr;
-        std::vector<int> bu_offsets_r, td_offsets_r;
-        std::vector<char> bu_level_vec_r;
-    } sup;
-    // Joint sweep of the eigen models: the thin levels of a large forest (runs of levels of at most 4 096 nodes) in tiers
-    // of four levels; a tier is cut into subtree blocks and ONE launch walks them, a workgroup per (block, column) with a
-    // workgroup barrier between its levels -- a level costs a ~3.5 us pass instead of a ~7.5 us dependent launch.
-    struct EigenTiers {
-        bool ok = false;
-        int first_level = 0;   // plain bottom-up level the first tier starts at
-        int top_level = 0;     // ... and the level from which the single-workgroup launch takes over
-        struct Tier { int first_block, n_blocks, depth; };
-        std::vector<Tier> tiers;
-        PmlUnit* d_units = nullptr;
-        int *d_lv = nullptr, *d_start = nullptr;
-        int* d_nodes = nullptr;  // the node ids parallel to d_units (the sum sweeps walk node lists)
-        int widest = 0;        // nodes of the widest level inside the tiers
-    } eig_tiers;
-    // joint back-trace: the depths beyond its single-workgroup launch in tiers of subtrees (joint_backtrace_blocks_kernel)
-    struct BacktraceTiers {
-        bool ok = false;
-        int first_depth = 0;  // depths 1 .. first_depth - 1 stay with the single-workgroup launch
-        struct Tier { int first_block, n_blocks, depth; };
-        std::vector<Tier> tiers;
-        int *d_nodes = nullptr, *d_lv = nullptr, *d_start = nullptr;
-    } bt_tiers;
+    // the schedules the sweeps walk (pml_schedule.h): planned by pml_schedule.cpp, uploaded by pml_tree_upload / build_thin_ends
+    using BlockSchedule = PmlBlockSchedule;
+    using ThinSchedule = PmlThinSchedule;
+    using DeepSchedule = PmlDeepSchedule;
+    using SuperSchedule = PmlSuperSchedule;
+    using EigenTiers = PmlEigenTiers;
+    using BacktraceTiers = PmlBacktraceTiers;
+    BlockSchedule blocks;
+    ThinSchedule thin;
+    DeepSchedule deep;
+    SuperSchedule sup;
+    EigenTiers eig_tiers;
+    BacktraceTiers bt_tiers;
     bool small = false;  // forest small enough for the one-launch-per-sweep kernels
     bool levels_fit_workgroup = false;  // (nearly) every fused level is one pass of a 512-thread workgroup
-    std::vector<int> bu_offsets_f, td_parent_offsets_f;
     std::vector<char> bu_level_vec_f;  // per fused bottom-up level: some unit has a stored node as child 0 or 1
     std::vector<int> td_cherry_prefix; // over the fused top-down units: how many before it have a cherry as child 0 or 1
     std::vector<char> bu_level_vec;    // the same for the plain levels (joint sweep: every internal node is stored)
@@ -240,7 +122,6 @@ struct pml_ctx {
     int C = 0, k = 0, ks = 0, W = 0, G = 0, R = 0;
     int Gf = 0, Rf = 0;  // lane-group shape of the F81-family bottom-up kernels (chunked state ownership)
     bool bu_wide_lanes = false;  // 32 < k <= 64: most bottom-up levels run with 8 states per lane (see dispatch_sweep)
-    bool shape_ordered = false;   // the forest's numbering orders a depth's sibling groups by (shape, class) of the gathering unit
     bool level_lists_sorted = false;  // 32 < k <= 64: the level launches walk the lists sorted by shape (pml_tree_upload)
     int Gt = 0, Rt = 0;  // ... and of the F81-family top-down kernels
     u64 *d_masks = nullptr, *d_masks_init = nullptr;
@@ -360,6 +241,8 @@ static void drop_sweep_graphs(pml_ctx* ctx) {
     drop_graph(ctx->mp_graph);
 }
 
+static int prof_drain(pml_ctx* ctx);
+
 static void free_all(pml_ctx* ctx) {
     drop_sweep_graphs(ctx);
     drop_graph(ctx->bt_graph);
@@ -384,10 +267,46 @@ static void free_all(pml_ctx* ctx) {
     ctx->held = 0;
 }
 
+// A new tree: everything the ctx holds goes, except what belongs to the context rather than to a tree -- the device, the
+// settings (tunables, options, profiling), the stream and its events, the profiling event pool and the communicator.
+static void reset_for_tree(pml_ctx* ctx) {
+    free_all(ctx);
+    (void)prof_drain(ctx);
+    pml_ctx fresh;
+    fresh.device = ctx->device;
+    fresh.tune = ctx->tune;
+    fresh.fuse = ctx->fuse;
+    fresh.keep_td = ctx->keep_td;
+    fresh.eig_fused_opt = ctx->eig_fused_opt;
+    fresh.eigj_valu_opt = ctx->eigj_valu_opt;
+    fresh.implicit_tips = ctx->implicit_tips;
+    fresh.profile = ctx->profile;
+    fresh.stream = ctx->stream;
+    fresh.ev0 = ctx->ev0;
+    fresh.ev1 = ctx->ev1;
+    fresh.prof_pool.swap(ctx->prof_pool);
+    if (ctx->prof_open) fresh.prof_pool.push_back(ctx->prof_open);
+    fresh.comm = ctx->comm;
+    *ctx = std::move(fresh);
+}
+
 template <typename T>
 static int upload(pml_ctx* ctx, T* dst, const T* src, size_t count) {
     HIP_TRY(hipMemcpyAsync(dst, src, count * sizeof(T), hipMemcpyHostToDevice, ctx->stream));
     return PML_OK;
+}
+
+// a table of a tree on the device: allocated (at least one element) and its copy queued; the caller synchronises the
+// stream before the host table goes
+template <typename T>
+static int put(pml_ctx* ctx, T** dst, const T* src, size_t count) {
+    PML_TRY(dev_alloc(ctx, dst, count));
+    if (count) PML_TRY(upload(ctx, *dst, src, count));
+    return PML_OK;
+}
+template <typename T>
+static int put(pml_ctx* ctx, T** dst, const std::vector<T>& v) {
+    return put(ctx, dst, v.data(), v.size());
 }
 
 static void pick_group(const pml_ctx* ctx, int k, int& G, int& R) {
@@ -438,7 +357,7 @@ static bool block_schedule(const pml_ctx* c) {
     // times many columns ran in rounds of long-lived workgroups and lost to the level kernels.  The workgroups now
     // shrink until all are resident (launch_blocks_f81) and the blocks end below the top's lowest level
     // (pml_tree_upload): over scripts/schedule_sweep.py's grid the blocks never lose -- profiles/r03c_schedule_sweep.txt.)
-    return c->blocks.ok && !wide_states(c) && !c->bu_offsets_f.empty() && (long long)c->bu_offsets_f.back() * c->sched_cols <= limit;
+    return c->blocks.ok && !wide_states(c) && !c->forest.bu_offsets_f.empty() && (long long)c->forest.bu_offsets_f.back() * c->sched_cols <= limit;
 }
 
 static PmlTree tree_of(const pml_ctx* c, bool fused = false) {

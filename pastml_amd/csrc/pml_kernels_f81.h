@@ -12,10 +12,7 @@
 // shared by all its observed tips) and the parent's entry at s -- no per-tip reduction.
 #pragma once
 #include "pml_device.h"
-
-#define PML_KIND_TIP 0
-#define PML_KIND_CHERRY 1
-#define PML_KIND_STORED 2
+#include "pml_schedule.h"   // PmlUnit, PML_KIND_*, PML_PACKED_TWO_STORED
 
 typedef unsigned char pml_jt;  // entry of an arg-max table: a state index (k <= 256; beyond, the F81 family stores 16-bit entries
                                // in the same buffer: PmlState::jt16)
@@ -443,19 +440,7 @@ struct Gather {
     static constexpr bool enabled = G >= 8;
 };
 
-// Unit descriptor, built once per tree on the host (pml_tree_upload): everything about the topology around node n that
-// a unit needs, so that all data loads of a unit can be issued in one round trip (and the descriptor of the wave's next
-// unit is fetched while the current one is computed) instead of chasing n -> first_child -> children -> their children.
-//   packed: bits 0-3 number of children (15 = 15 or more), bit 4 = every cherry among the first four children has
-//           1..GC tips, bit 5 = no stored internal node among children 2 and 3 (the bottom-up pipeline prefetches the
-//           vectors of children 0 and 1), bits 8+3j..10+3j (j < 4) code of child j: 0 tip, 1 stored internal node,
-//           2+m cherry with m+1 tips
-//   cfc[j]: first child of child j (j < 4), i.e. where the tips of a cherry child start
-struct __attribute__((aligned(32))) PmlUnit {
-    int n, fc, packed, pad;
-    int cfc[4];
-};
-
+// Unit descriptors (PmlUnit, pml_schedule.h): the packed word's fields
 __device__ __forceinline__ int unit_nc(int packed) { return packed & 15; }
 __device__ __forceinline__ int unit_code(int packed, int j) { return (packed >> (8 + 3 * j)) & 7; }
 
@@ -1730,7 +1715,6 @@ bu_f81_kernel(PmlTree t, PmlCols c, PmlState st, const PmlUnit* __restrict__ uni
 // pad = t0 (the eight tips t0 .. t0 + 7).
 // ---------------------------------------------------------------------------------------------------------------------
 #define PML_PACKED_PAIR ((3 << 11) | (3 << 8) | (3 << 4) | 2)        // two children, both cherries of two tips
-#define PML_PACKED_TWO_STORED ((1 << 11) | (1 << 8) | (3 << 4) | 2)  // two children, both stored nodes
 
 struct SuperRegs {
     int n, fc, g0, t0;

@@ -36,7 +36,7 @@ int dispatch_small_f81(pml_ctx* ctx, bool bottom_up, int do_prep, int first_leve
                               const PmlUnit* units, const int* d_offsets, int skip_roots) {
     int g, r;
     multi_level_shape(ctx, bottom_up, g, r);
-    if (n_levels < 0) n_levels = bottom_up ? (int)ctx->bu_offsets_f.size() - 1 - first_level : ctx->n_td_levels;
+    if (n_levels < 0) n_levels = bottom_up ? (int)ctx->forest.bu_offsets_f.size() - 1 - first_level : ctx->n_td_levels;
     const int reset_err = (units == nullptr && first_level == 0) ? 1 : 0;
     if (units == nullptr) {
         // (the lists sorted by shape inside every level where the forest has them: a wave of one shape runs that shape's

@@ -14,7 +14,7 @@
 static int frontier_depth(const pml_ctx* ctx, int n_tiles) {
     const int L = ctx->n_td_levels;
     for (int d = 0; d < L; ++d) {
-        const long long cnt = ctx->td_offsets[d + 1] - ctx->td_offsets[d];
+        const long long cnt = ctx->forest.td_offsets[d + 1] - ctx->forest.td_offsets[d];
         if (cnt * n_tiles >= PML_SIM_ITEMS || d >= PML_SIM_MAX_TOP) return d;
     }
     return L;   // (a shallow forest: level launches only)
@@ -23,8 +23,8 @@ static int frontier_depth(const pml_ctx* ctx, int n_tiles) {
 // preorder lists of the subtrees rooted at depth D (entries: PmlSimArgs::lists), uploaded once per (tree, D)
 static int subtree_lists(pml_ctx* ctx, int D) {
     if (ctx->sim_depth == D) return PML_OK;
-    const int r0 = ctx->td_offsets[D], r1 = ctx->td_offsets[D + 1];
-    const int* fc = ctx->h_first_child.data();   // (the library's numbering: a node's children are fc[n] .. fc[n] + nc - 1)
+    const int r0 = ctx->forest.td_offsets[D], r1 = ctx->forest.td_offsets[D + 1];
+    const int* fc = ctx->forest.first_child.data();   // (the library's numbering: a node's children are fc[n] .. fc[n] + nc - 1)
     const bool perm = !ctx->old_of_new.empty();
     auto api = [&](int n) { return perm ? ctx->old_of_new[n] : n; };   // the caller's id of an internal node
     std::vector<int4> lists;
@@ -35,9 +35,9 @@ static int subtree_lists(pml_ctx* ctx, int D) {
         while (!stack.empty()) {
             const int n = stack.back();
             stack.pop_back();
-            const int p = ctx->h_parent[n];
+            const int p = ctx->forest.parent[n];
             lists.push_back(make_int4(n, api(n), p < 0 ? -1 : api(p), 0));
-            for (int j = ctx->h_n_children[n] - 1; j >= 0; --j) stack.push_back(fc[n] + j);
+            for (int j = ctx->forest.n_children[n] - 1; j >= 0; --j) stack.push_back(fc[n] + j);
         }
         off.push_back((int)lists.size());
     }
@@ -72,8 +72,8 @@ static int sim_run(pml_ctx* ctx, PmlSimArgs a, int threads, int D, size_t lds, l
     for (int d = 0; d < D; ++d) {
         a.lists = nullptr;
         a.list_off = nullptr;
-        a.first_node = ctx->td_offsets[d];
-        a.n_lists = ctx->td_offsets[d + 1] - ctx->td_offsets[d];
+        a.first_node = ctx->forest.td_offsets[d];
+        a.n_lists = ctx->forest.td_offsets[d + 1] - ctx->forest.td_offsets[d];
         PML_TRY((sim_launch<T, MODE>(ctx, a, threads, lds, max_blocks)));
     }
     if (D < ctx->n_td_levels) {
