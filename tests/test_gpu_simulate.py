@@ -7,6 +7,7 @@ import pytest
 from scipy import stats
 
 from conftest import GOLDEN, load_golden
+from sampler_ref import ALPHA, _check_transitions
 from pastml_amd import hip, ml
 from pastml_amd.acr import acr
 from pastml_amd.annotation import ForestStats, preannotate_forest
@@ -21,56 +22,11 @@ from pastml_amd.tree import FlatForest, read_tree
 from pastml_amd.utilities.state_simulator import simulate_states
 
 DATA = os.path.join(GOLDEN, 'data')
-# family-wise false-alarm probability of every chi-square family below (Bonferroni over its tests)
-ALPHA = 1e-6
 
 
 def _forest(flat):
     roots = flat.to_tree_nodes()
     return roots, flat
-
-
-def _pooled_chi2(observed, expected, min_expected=5.0):
-    """Pearson chi-square p-value with cells of small expectation pooled into one (None: fewer than 2 cells)."""
-    observed = np.asarray(observed, dtype=np.float64).ravel()
-    expected = np.asarray(expected, dtype=np.float64).ravel()
-    big = expected >= min_expected
-    obs = list(observed[big])
-    exp = list(expected[big])
-    rest_o, rest_e = observed[~big].sum(), expected[~big].sum()
-    if rest_e > 0:
-        obs.append(rest_o)
-        exp.append(rest_e)
-    if len(exp) < 2:
-        return None
-    obs, exp = np.array(obs), np.array(exp)
-    if exp.min() <= 0:
-        return None
-    chi2 = float(((obs - exp) ** 2 / exp).sum())
-    return float(stats.chi2.sf(chi2, len(exp) - 1))
-
-
-def _check_transitions(flat, model, sim, k):
-    """Roots against pi, every branch's (parent, child) table against n_a P[a][b] of the host model, Bonferroni."""
-    pi = np.asarray(model.frequencies, dtype=np.float64)
-    n_rep = sim.shape[1]
-    tests = []
-    for r in flat.roots:
-        tests.append((np.bincount(sim[r], minlength=k), n_rep * pi / pi.sum()))
-    for n in range(flat.n_nodes):
-        p = flat.parent[n]
-        if p < 0:
-            continue
-        P = np.maximum(model.get_Pij_t(float(flat.dist[n])), 0.0)
-        P = P / P.sum(axis=1, keepdims=True)
-        table = np.zeros((k, k))
-        np.add.at(table, (sim[p].astype(np.int64), sim[n].astype(np.int64)), 1)
-        n_a = table.sum(axis=1)
-        tests.append((table, n_a[:, None] * P))
-    pvals = [q for q in (_pooled_chi2(o, e) for o, e in tests) if q is not None]
-    assert pvals, 'no testable cell'
-    worst = min(pvals)
-    assert worst > ALPHA / len(pvals), 'min p = {:.3g} over {} tests'.format(worst, len(pvals))
 
 
 def _random_forest():
