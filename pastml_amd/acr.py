@@ -13,8 +13,10 @@ log-likelihoods over all ranks with the library's single RCCL all-reduce.
 Every prediction method of the reference is accepted: the likelihood methods (MPPA, MAP, JOINT, and the meta-methods
 ML and ALL) run their sweeps on the GPU; the parsimony methods (DOWNPASS, ACCTRAN, DELTRAN, MP; integer set work, no
 likelihoods) run on the host as level-wise array passes (pastml_amd.parsimony); COPY reports the annotation as it is.
-Polytomy resolution (tree editing) and the HTML side of the pipeline are out of scope and raise a
-clear error; ``pastml_amd.pipeline`` covers the file-to-file part.
+With ``resolve_polytomies`` the reconstruction is followed by the reference's tree editing (acr.py:234-278,
+pastml_amd.tree.resolve_trees / unresolve_trees): the edited forest is flattened again and every character re-run through
+the same batched path with its model frozen, until no polytomy resolution is removed.  The HTML side of the pipeline is
+out of scope; ``pastml_amd.pipeline`` covers the file-to-file part.
 """
 import logging
 import os
@@ -33,7 +35,7 @@ from pastml_amd.models.F81Model import F81Model, F81
 from pastml_amd.models.HKYModel import HKYModel, HKY, HKY_STATES
 from pastml_amd.models.JCModel import JCModel, JC
 from pastml_amd.models.JTTModel import JTTModel, JTT, JTT_STATES
-from pastml_amd.tree import TreeNode, get_flat_forest, AnnotationColumn
+from pastml_amd.tree import TreeNode, get_flat_forest, AnnotationColumn, resolve_trees, unresolve_trees
 
 MAX_STATES = 512   # = pastml_amd.hip.MAX_STATES = PML_MAX_STATES of the library (tests/test_host_logic.py checks); F81 family
 MAX_STATES_MATRIX = 256   # ... and the models with a transition matrix per branch (HKY has 4 states; JTT 20; CUSTOM_RATES any)
@@ -166,6 +168,36 @@ def _restrict_annotation_to(states, column, forest, flat=None):
                 n.add_feature(column, allowed & getattr(n, column))
 
 
+def _initial_annotations(flat, columns):
+    """
+    What the reference memorises before a run that may resolve polytomies (acr.py:163-170): every node's non-empty
+    annotation of every column, here as one AnnotationColumn per column over ``flat``.  Columnar annotations are taken as
+    they are (empty values become "not annotated", as the reference keeps only non-empty sets); values set node by node
+    are collected with one walk.
+    """
+    from pastml_amd.tree import _DICT_FEATURE_NAMES
+    out = {}
+    for c in columns:
+        col = flat.columns.get(c)
+        shadowed = c in _DICT_FEATURE_NAMES and any(c in n.__dict__ for n in flat.nodes)
+        if isinstance(col, AnnotationColumn) and col.absent is None and not shadowed:
+            out[c] = AnnotationColumn(np.where(col.codes == -1, -2, col.codes), col.values, col.multi)
+            continue
+        sets = [getattr(n, c, set()) for n in flat.nodes]
+        values = np.array(sorted({v for vs in sets if vs for v in vs}, key=str), dtype=object)
+        index = {v: j for j, v in enumerate(values.tolist())}
+        codes = np.full(flat.n_nodes, -2, dtype=np.int64)
+        multi = {}
+        for i, vs in enumerate(sets):
+            if vs:
+                js = {index[v] for v in vs}
+                codes[i] = min(js)
+                if len(js) > 1:
+                    multi[i] = js
+        out[c] = AnnotationColumn(codes, values, multi)
+    return out
+
+
 def total_log_likelihood(results):
     """
     Sum of the log-likelihoods of all characters of a run.  Under a multi-process launch every rank passes the results
@@ -206,9 +238,12 @@ def acr(forest, df=None, columns=None, column2states=None, prediction_method=MPP
     """
     from pastml_amd import sharding
     from pastml_amd.batch import Task, run_tasks
-    if resolve_polytomies:
-        raise NotImplementedError('resolve_polytomies (tree editing, pastml/tree.py:344-492) is outside the '
-                                  'accelerated likelihood path')
+    comm = sharding.communicator()
+    if resolve_polytomies and comm is not None and comm.world > 1:
+        # every rank holds only its own block of the characters, while the tree editing needs all their predictions
+        raise NotImplementedError('resolve_polytomies is not supported under a multi-process launch ({} ranks): the '
+                                  'polytomies are resolved from the predictions of all characters, and each rank has '
+                                  'only its own; run it in a single process'.format(comm.world))
     if isinstance(forest, TreeNode):
         forest = [forest]
     logger = logging.getLogger('pastml')
@@ -225,6 +260,8 @@ def acr(forest, df=None, columns=None, column2states=None, prediction_method=MPP
 
     forest_stats = ForestStats(forest)
     flat = get_flat_forest(forest)   # once per call: the characters below all work on these arrays
+    # if polytomies are to be resolved, the runs after the editing start again from the initial annotations
+    initial = _initial_annotations(flat, columns) if resolve_polytomies else None
     logger.debug('\n=============ACR===============================')
     column2parameters = column2parameters or {}
     column2rates = column2rates or {}
@@ -291,21 +328,57 @@ def acr(forest, df=None, columns=None, column2states=None, prediction_method=MPP
     seeds_all = np.random.randint(0, 2 ** 31 - 1, size=n_ml) if n_ml else np.zeros(0, dtype=np.int64)
     ml_rank = np.cumsum([item[0] == 'ml' for item in plan]) - 1
     # one process per GPU: this rank's contiguous block of the characters
-    comm = sharding.communicator()
     mine = range(len(plan))
     if comm is not None and comm.world > 1:
         mine = sharding.shard_characters(len(plan), comm.rank, comm.world)
     seeds = np.array([seeds_all[ml_rank[i]] for i in mine if plan[i][0] == 'ml'], dtype=np.int64)
     plan = [plan[i] for i in mine]
     tasks = [item[3] for item in plan if item[0] == 'ml']
-    ml_results = iter(run_tasks(forest, tasks, force_joint=force_joint, flat=flat, seeds=seeds)) if tasks else iter(())
-    results = []
-    for kind, character, method, payload in plan:
-        if kind == 'ml':
-            results.append(next(ml_results))
-        elif kind == 'mp':
-            results.append(parsimonious_acr(forest, character, method, payload, forest_stats.num_nodes,
-                                            forest_stats.num_tips))
-        else:
-            results.append({CHARACTER: character, STATES: payload, METHOD: method})
-    return flatten_lists(results)
+
+    def run_all(flat, forest_stats):
+        ml_results = iter(run_tasks(forest, tasks, force_joint=force_joint, flat=flat, seeds=seeds)) if tasks else iter(())
+        results = []
+        for kind, character, method, payload in plan:
+            if kind == 'ml':
+                results.append(next(ml_results))
+            elif kind == 'mp':
+                results.append(parsimonious_acr(forest, character, method, payload, forest_stats.num_nodes,
+                                                forest_stats.num_tips))
+            else:
+                results.append({CHARACTER: character, STATES: payload, METHOD: method})
+        return flatten_lists(results)
+
+    results = run_all(flat, forest_stats)
+    if not resolve_polytomies:
+        return results
+
+    # Polytomy resolution (acr.py:234-278).  Re-runs keep the restart seeds drawn above (frozen models never restart)
+    # and go through the same batched device path on the edited forest.
+    column2states = {r[CHARACTER]: r[STATES] for r in results}
+    column2copy = {r[CHARACTER]: r[METHOD] == COPY for r in results}
+    if not resolve_trees(column2states, forest):
+        return results
+    level = logger.level
+    logger.setLevel(logging.ERROR)
+    try:
+        # back to the initial annotations: a COPY column keeps the state of the polytomy nodes (there is no way to
+        # compute one), every other prediction is deleted
+        flat = get_flat_forest(forest)
+        for c in columns:
+            flat.set_column(c, initial[c].taken(flat.inherited_rows if column2copy.get(c) else flat.carried_rows))
+        forest_stats = ForestStats(forest)
+        for t in tasks:
+            t.model.freeze()
+            t.model.forest_stats = forest_stats
+        results = run_all(flat, forest_stats)
+        logger.setLevel(level)
+        while unresolve_trees(column2states, forest):
+            logger.setLevel(logging.ERROR)
+            # as in the reference, the statistics of the forest as resolved stay in force (node counts of the results,
+            # tau factor of the models): they are not recomputed after an unresolve step.  Nor are the annotations
+            # restored: these runs start from the predictions of the run before, which the columns still hold
+            results = run_all(get_flat_forest(forest), forest_stats)
+            logger.setLevel(level)
+    finally:
+        logger.setLevel(level)
+    return results

@@ -7,8 +7,9 @@ Two representations live here:
   ``acr()`` / ``ml.py`` touch (``traverse``, ``children``, ``up``, ``dist``, ``name``,
   ``is_root``, ``is_leaf``, ``add_feature(s)``, ``del_feature``, ``features``, leaf iteration).  ete3 itself is not
   installed on our boxes, so callers build trees with :func:`read_tree` / :func:`read_forest`
-  (reference: ``pastml/tree.py:176-222``).  Only newick reading/naming is provided; tree editing, dates, polytomy
-  resolution and nexus (``pastml/tree.py`` rest) are out of scope.
+  (reference: ``pastml/tree.py:176-222``).  Newick reading/naming and the polytomy resolution of ``acr()``
+  (:func:`resolve_trees` / :func:`unresolve_trees`, ``pastml/tree.py:344-492``) are provided; dates and nexus
+  (``pastml/tree.py`` rest) are out of scope.
 
 * :class:`FlatForest` -- the structure-of-arrays form that is uploaded to the GPU: nodes are renumbered in
   breadth-first (level) order over the whole forest so that (i) the children of a node are contiguous,
@@ -18,11 +19,13 @@ Two representations live here:
 """
 from collections import deque, Counter
 
+import logging
 import re
 
 import numpy as np
 
 DEFAULT_DIST = 1.0
+IS_POLYTOMY = 'polytomy'   # feature of the nodes that resolve_trees adds (pastml/tree.py:29)
 
 
 class NewickError(ValueError):
@@ -57,6 +60,28 @@ class NodeColumn(object):
             self.absent = np.zeros(n_nodes, dtype=bool)
         self.absent[i] = True
 
+    def taken(self, rows):
+        """
+        This column over another set of nodes (an edited tree flattened again): row i of the result is row ``rows[i]``
+        here; ``rows[i] < 0`` -- a node this column knows nothing of -- is absent.
+        """
+        rows = np.asarray(rows, dtype=np.int64)
+        new = rows < 0
+        safe = np.where(new, 0, rows)
+        out = self._take(safe, new)
+        absent = out._new_absent(new)
+        if self.absent is not None:
+            absent = absent | self.absent[safe]
+        if absent.any():
+            out.absent = absent
+        return out
+
+    def _new_absent(self, new):
+        return new
+
+    def _take(self, safe, new):
+        raise NotImplementedError
+
 
 class ArrayColumn(NodeColumn):
     """values[i] (a scalar or a row of a 2-d array); ``convert`` is applied to what is handed out."""
@@ -70,6 +95,9 @@ class ArrayColumn(NodeColumn):
             return ABSENT
         v = self.values[i]
         return self.convert(v) if self.convert is not None else v
+
+    def _take(self, safe, new):
+        return ArrayColumn(np.asarray(self.values)[safe], self.convert)
 
 
 class MaskColumn(NodeColumn):
@@ -85,6 +113,9 @@ class MaskColumn(NodeColumn):
         b = np.ascontiguousarray(self.words[i]).view(np.uint8)
         return np.unpackbits(b, bitorder='little')[:self.k].astype(int)
 
+    def _take(self, safe, new):
+        return MaskColumn(self.words[safe], self.k)
+
 
 class StateSetColumn(NodeColumn):
     """Packed state words [N, W] handed out as sets of state names (pastml/ml.py:923-928)."""
@@ -99,6 +130,9 @@ class StateSetColumn(NodeColumn):
         b = np.ascontiguousarray(self.words[i]).view(np.uint8)
         bits = np.unpackbits(b, bitorder='little')[:len(self.states)].astype(bool)
         return set(self.states[bits])
+
+    def _take(self, safe, new):
+        return StateSetColumn(self.words[safe], self.states)
 
 
 class AnnotationColumn(NodeColumn):
@@ -124,6 +158,19 @@ class AnnotationColumn(NodeColumn):
         if i in self.multi:
             return {self.values[j] for j in self.multi[i]}
         return {self.values[c]}
+
+    def _take(self, safe, new):
+        # new nodes are "not in the table" (code -2), which reads as absent without an absent mask
+        codes = np.where(new, -2, self.codes[safe])
+        multi = {}
+        if self.multi:
+            olds = np.fromiter(self.multi.keys(), dtype=np.int64, count=len(self.multi))
+            for i in np.flatnonzero(np.isin(safe, olds) & ~new).tolist():
+                multi[i] = self.multi[int(safe[i])]
+        return AnnotationColumn(codes, self.values, multi)
+
+    def _new_absent(self, new):
+        return np.zeros(len(new), dtype=bool)
 
 
 class TreeNode(object):
@@ -489,6 +536,8 @@ def name_tree(tree, suffix=""):
         n_nodes += 1
         if _.name:
             existing_names[_.name] += 1
+            if '.polytomy_' in _.name:   # a tree written after polytomy resolution (pastml/tree.py:91-92)
+                _.add_feature(IS_POLYTOMY, 1)
     if n_nodes == len(existing_names):
         return
     i = 0
@@ -534,7 +583,7 @@ class FlatForest(object):
     ``nodes`` (optional) is the list of TreeNode objects in id order.
     """
 
-    def __init__(self, parent, n_children, first_child, dist, roots, nodes=None):
+    def __init__(self, parent, n_children, first_child, dist, roots, nodes=None, carry=None):
         self.parent = np.ascontiguousarray(parent, dtype=np.int32)
         self.n_children = np.ascontiguousarray(n_children, dtype=np.int32)
         self.first_child = np.ascontiguousarray(first_child, dtype=np.int32)
@@ -545,11 +594,36 @@ class FlatForest(object):
         self.columns = {}   # columnar node features: name -> NodeColumn (see the top of this module)
         self._derive()
         if nodes is not None:
-            self.adopt_nodes()
+            self.adopt_nodes(carry)
 
     # ------------------------------------------------------------------------------------------------------------------
-    def adopt_nodes(self):
-        """Points the TreeNode objects at this forest: ``node.<feature>`` then resolves through ``self.columns``."""
+    def adopt_nodes(self, carry=None):
+        """
+        Points the TreeNode objects at this forest: ``node.<feature>`` then resolves through ``self.columns``.
+        ``carry``: the forest of the same trees before an edit (resolve_trees / unresolve_trees).  Its columns are
+        re-indexed onto this one instead of being moved onto the nodes one by one; ``carried_rows[i]`` is node i's row
+        there (-1: the node is new).
+        """
+        if carry is not None:
+            rows = []
+            for i, n in enumerate(self.nodes):
+                old = n._cols
+                if old is carry:
+                    rows.append(n._idx)
+                else:
+                    rows.append(-1)
+                    if old is not None and old is not self and old.columns:
+                        for name, col in old.columns.items():
+                            if name not in n.__dict__:
+                                v = col.get(n._idx)
+                                if v is not ABSENT:
+                                    n.add_feature(name, v)
+                n._cols = self
+                n._idx = i
+            self.carried_rows = np.asarray(rows, dtype=np.int64)
+            for name, col in carry.columns.items():
+                self.columns[name] = col.taken(self.carried_rows)
+            return
         for i, n in enumerate(self.nodes):
             old = n._cols
             if old is not None and old is not self and old.columns:
@@ -681,8 +755,11 @@ class FlatForest(object):
 
     # ------------------------------------------------------------------------------------------------------------------
     @classmethod
-    def from_trees(cls, forest):
-        """Flattens TreeNode trees (one tree or a list). Node ids follow forest-wide level order."""
+    def from_trees(cls, forest, carry=None):
+        """
+        Flattens TreeNode trees (one tree or a list). Node ids follow forest-wide level order.  ``carry``: see
+        :meth:`adopt_nodes`.
+        """
         if isinstance(forest, TreeNode):
             forest = [forest]
         nodes = list(forest)
@@ -698,7 +775,7 @@ class FlatForest(object):
                 nodes.append(c)
                 parent.append(i)
             i += 1
-        return cls(parent, n_children, first_child, dist, np.arange(len(forest)), nodes=nodes)
+        return cls(parent, n_children, first_child, dist, np.arange(len(forest)), nodes=nodes, carry=carry)
 
     @classmethod
     def balanced(cls, n_levels, seed=42, lo=0.01, hi=0.2):
@@ -820,3 +897,203 @@ def get_flat_forest(forest):
     # ids must follow per-tree level order for single trees; for forests the order is forest-wide level order
     holder._flat_cache = (key_roots, flat)
     return flat
+
+
+# =====================================================================================================================
+# Polytomy resolution (pastml/tree.py:344-492)
+# =====================================================================================================================
+class _Predictions(object):
+    """
+    The selected states of every node of ``flat`` in the result columns of a run, as packed words per column (the
+    reference's ``get_prediction`` / ``states_are_different`` on node attributes, tree.py:358-360, 383-387): ``key[i]``
+    numbers node i's combination of state sets over all columns, ``different(a, b)`` tells whether two nodes share no
+    state in some column.  A node without the feature counts as the empty set.
+    """
+
+    def __init__(self, flat, columns, column2states):
+        from pastml_amd.batch import annotation_words
+        self.states = [np.asarray(column2states[c]) for c in columns]
+        self.words = [annotation_words(flat, c, states)[0] for c, states in zip(columns, self.states)]
+        if self.words:
+            _, key = np.unique(np.concatenate(self.words, axis=1), axis=0, return_inverse=True)
+            self.key = np.asarray(key).reshape(-1)
+        else:
+            self.key = np.zeros(flat.n_nodes, dtype=np.int64)
+
+    def different(self, a, b):
+        a, b = np.atleast_1d(a), np.atleast_1d(b)
+        out = np.zeros(len(a), dtype=bool)
+        for w in self.words:
+            out |= ~(w[a] & w[b]).any(axis=1)
+        return out
+
+    def key_string(self, i):
+        """'.'-joined per column, '-'-joined indices of the node's states in the column's state list (tree.py:358-360)."""
+        parts = []
+        for w, states in zip(self.words, self.states):
+            bits = np.unpackbits(np.ascontiguousarray(w[i]).view(np.uint8), bitorder='little')[:len(states)]
+            parts.append('-'.join(str(j) for j in np.flatnonzero(bits)))
+        return '.'.join(parts)
+
+
+def _polytomy_flags(flat):
+    """bool[N]: the nodes with a true IS_POLYTOMY feature (the column resolve_trees keeps, or values set node by node)."""
+    flags = np.zeros(flat.n_nodes, dtype=bool)
+    col = flat.columns.get(IS_POLYTOMY)
+    if isinstance(col, ArrayColumn):
+        flags = np.asarray(col.values).astype(bool)
+        if col.absent is not None:
+            flags = flags & ~col.absent
+    if IS_POLYTOMY in _DICT_FEATURE_NAMES and flat.nodes is not None:
+        for i, n in enumerate(flat.nodes):
+            if IS_POLYTOMY in n.__dict__:
+                flags[i] = bool(n.__dict__[IS_POLYTOMY])
+    return flags
+
+
+def _reflatten(forest, old, inherit=(), inherit_columns=()):
+    """
+    Flattens the edited trees again and caches the result for get_flat_forest: the columns of ``old`` move over row
+    by row (FlatForest.adopt_nodes).  ``inherit``: (new node, row in ``old``) pairs whose columns in ``inherit_columns``
+    take that row's values (a new polytomy node takes its child's selected states, tree.py:411-412).
+    ``inherited_rows`` of the result is ``carried_rows`` with those rows filled in.
+    """
+    holder = forest[0]
+    holder._flat_cache = None
+    flat = FlatForest.from_trees(forest, carry=old)
+    rows = flat.carried_rows
+    if inherit:
+        rows = rows.copy()
+        for node, row in inherit:
+            rows[node._idx] = row
+        for name in inherit_columns:
+            if name in old.columns:
+                flat.columns[name] = old.columns[name].taken(rows)
+    flat.inherited_rows = rows
+    holder._flat_cache = (tuple(id(t) for t in forest), flat)
+    return flat
+
+
+def resolve_trees(column2states, forest):
+    """
+    Resolves polytomies from the state predictions (reference: pastml/tree.py:344-380): when a node with more than 2
+    children has m >= 2 children with the same selected states in all columns (and more than one such group), the m
+    children get a new parent ``<node>.polytomy_<states>`` at the distance of the closest of them -- provided its
+    states differ from the node's in some column.
+
+    :param column2states: character -> its states (the result columns of a run, meta-method columns included)
+    :param forest: a TreeNode tree or a list of them, edited in place
+    :return: number of newly created nodes.
+
+    The reference walks every node; a node's outcome depends only on its own children, so here the groups of all
+    nodes are formed at once on the flat forest and only the new nodes are built one by one.  Node features that live
+    in columns move to the re-flattened forest (the new nodes take their child's selected states, nothing else).
+    """
+    if isinstance(forest, TreeNode):
+        forest = [forest]
+    columns = sorted(column2states.keys())
+    flat = get_flat_forest(forest)
+    num_new_nodes = 0
+    parent = flat.parent
+    under = np.flatnonzero((parent >= 0) & (flat.n_children[np.maximum(parent, 0)] > 2))
+    inherit = []
+    if len(under):
+        preds = _Predictions(flat, columns, column2states)
+        p, key = parent[under], preds.key[under]
+        # groups: (parent, prediction); inside one, the closest child first, ties to the leftmost (min() over the
+        # reference's list, tree.py:396)
+        order = np.lexsort((under, flat.dist[under], key, p))
+        ids, ps, ks = under[order], p[order], key[order]
+        start = np.flatnonzero(np.concatenate(([True], (ps[1:] != ps[:-1]) | (ks[1:] != ks[:-1]))))
+        size = np.diff(np.append(start, len(ids)))
+        gp, closest = ps[start], ids[start]
+        first = np.minimum.reduceat(ids, start)   # where the group starts among the children: insertion order
+        groups_of_parent = np.bincount(gp, minlength=flat.n_nodes)[gp]
+        take = np.flatnonzero((size >= 2) & (groups_of_parent > 1))
+        take = take[preds.different(gp[take], closest[take])]
+        take = take[np.lexsort((first[take], gp[take]))]
+        nodes = flat.nodes
+        for g in take.tolist():
+            n, child = nodes[gp[g]], nodes[closest[g]]
+            members = [nodes[i] for i in np.sort(ids[start[g]:start[g] + size[g]]).tolist()]
+            dist = child.dist
+            pol = n.add_child(dist=dist, name='{}.polytomy_{}'.format(n.name, preds.key_string(closest[g])))
+            for c in columns:
+                if c in child.__dict__:   # a value set on the node itself; columnar ones are inherited below
+                    pol.add_feature(c, child.__dict__[c])
+            for c in members:
+                n.remove_child(c)
+                pol.add_child(c, dist=c.dist - dist)
+            inherit.append((pol, int(closest[g])))
+            num_new_nodes += 1
+    if num_new_nodes:
+        new = _reflatten(forest, flat, inherit, columns)
+        flags = _polytomy_flags(new)   # earlier polytomy nodes keep theirs
+        flags[[pol._idx for pol, _ in inherit]] = True
+        col = ArrayColumn(np.ones(new.n_nodes, dtype=np.int8), convert=int)
+        col.absent = ~flags
+        new.columns[IS_POLYTOMY] = col
+        logging.getLogger('pastml').debug('Created {} new internal nodes while resolving polytomies'.format(num_new_nodes))
+    else:
+        logging.getLogger('pastml').debug('Could not resolve any polytomy')
+    return num_new_nodes
+
+
+def unresolve_trees(column2states, forest):
+    """
+    Removes the polytomy resolutions that no longer agree with the predictions (reference: pastml/tree.py:417-492):
+    in post-order, a polytomy node whose children all share its states is kept unless its parent has them too; any
+    other is removed, its children moving up to its parent with their branches extended by its own.
+
+    :param column2states: character -> its states
+    :param forest: a TreeNode tree or a list of them, edited in place
+    :return: number of removed nodes.
+    """
+    if isinstance(forest, TreeNode):
+        forest = [forest]
+    columns = sorted(column2states.keys())
+    flat = get_flat_forest(forest)
+    num_removed_nodes = 0
+    num_new_nodes = 0
+    pols = np.flatnonzero(_polytomy_flags(flat))
+    num_polytomies = len(pols)
+    if num_polytomies:
+        preds = _Predictions(flat, columns, column2states)
+        nodes = flat.nodes
+
+        def remove_node(n):
+            parent = n.up
+            for c in n.children:
+                parent.add_child(c, dist=c.dist + n.dist)
+            parent.remove_child(n)
+            n.children = []
+
+        # Removing a node only moves children that were already visited, so the walk visits the nodes of the
+        # original post-order (post_rank: tree by tree, each in post-order, as the reference's loops)
+        for i in pols[np.argsort(flat.post_rank[pols], kind='stable')].tolist():
+            n = nodes[i]
+            kids = [c._idx for c in n.children]
+            parent = n.up
+            # if the state is the same as all the child states, it's still a good polytomy resolution
+            if len(set(preds.key[kids].tolist())) == 1 and not preds.different(i, kids[0])[0]:
+                # ... unless the parent has it too (then the polytomy is not needed)
+                if not preds.different(i, parent._idx)[0]:
+                    num_removed_nodes += 1
+                    remove_node(n)
+                continue
+            num_removed_nodes += 1
+            remove_node(n)
+            # The reference then tries to group the parent's children anew ("new polytomies above", tree.py:475-483),
+            # but it fills the node's own state2children instead of above_state2children, so the loop over the latter
+            # never runs and no node is created.  Reproduced as written: nothing is created here either.
+    if num_removed_nodes:
+        _reflatten(forest, flat)
+        logging.getLogger('pastml').debug(
+            'Removed {} polytomy resolution{} as inconsistent with model parameters.'
+            .format(num_removed_nodes, 's' if num_removed_nodes > 1 else ''))
+        if num_new_nodes:
+            logging.getLogger('pastml').debug(
+                'Created {} new polytomy resolution{}.'.format(num_new_nodes, 's' if num_new_nodes > 1 else ''))
+    elif num_polytomies - num_removed_nodes + num_new_nodes:
+        logging.getLogger('pastml').debug('All the polytomy resolutions are consistent with model parameters.')
+    return num_removed_nodes
