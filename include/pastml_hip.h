@@ -277,6 +277,26 @@ int pml_marginal_counts_altered(pml_ctx* ctx, int32_t col, int32_t n_repetitions
                                 double* sums_out, int32_t* state_counts_out, int32_t* same_out);
 
 /*
+ * Maximum parsimony of n_cols characters of k states (k <= 512) on the uploaded forest: the bottom-up pass
+ * (pastml/parsimony.py:92-122) and, per bit of methods, ACCTRAN (:125-158), DOWNPASS (:161-210) and DELTRAN (:213-242, on
+ * the DOWNPASS sets), each with the number of state changes its sets need (:360-380, summed over the trees) and the number
+ * of nodes by size of their set (what parsimonious_acr's num_scenarios / unresolved nodes / states per node are made of,
+ * :280-290).  Needs pml_tree_upload only -- no pml_chars_alloc, no model; the scratch of the call (at most 7 x
+ * n_cols * n_nodes * W * 8 bytes; the columns are walked in chunks if that does not fit, PASTML_HIP_PARS_MAX_COLS bounds a
+ * chunk) is released before it returns.  Integer arithmetic only: results do not depend on launch geometry, chunking or the
+ * library's numbering.
+ *   given          [n_cols][n_nodes][W]  annotated states as masks, caller's numbering; all-zero words = node not annotated
+ *   sets_out       [n_methods][n_cols][n_nodes][W], the requested methods in the order ACCTRAN, DOWNPASS, DELTRAN
+ *   steps_out      [n_methods][n_cols]
+ *   size_hist_out  [n_methods][n_cols][k + 1]: nodes by number of states kept
+ * pml_parsimony_info: kernel launches of the last call and the time of its passes (HIP events; without transfers).
+ */
+enum { PML_PARS_ACCTRAN = 1, PML_PARS_DOWNPASS = 2, PML_PARS_DELTRAN = 4 };
+int pml_parsimony(pml_ctx* ctx, int32_t n_cols, int32_t k, const uint64_t* given, int methods, uint64_t* sets_out,
+                  int64_t* steps_out, int64_t* size_hist_out);
+int pml_parsimony_info(pml_ctx* ctx, int64_t* launches, double* passes_ms);
+
+/*
  * n_repetitions scenarios of column col drawn forward from the roots (pastml/utilities/state_simulator.py:6-31):
  * roots ~ pi, child ~ row (parent state) of P_n(t).  Draws keyed by (seed, caller's node id, rep_offset + r):
  * results do not depend on launch geometry, chunking or the library's internal numbering.

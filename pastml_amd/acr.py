@@ -42,7 +42,7 @@ MAX_STATES_MATRIX = 256   # ... and the models with a transition matrix per bran
 
 model2class = {F81: F81Model, JC: JCModel, CUSTOM_RATES: CustomRatesModel, HKY: HKYModel, JTT: JTTModel, EFT: EFTModel}
 
-from pastml_amd.parsimony import is_parsimonious, parsimonious_acr, MP_METHODS, ACCTRAN, DELTRAN, DOWNPASS, MP  # noqa: E402,F401
+from pastml_amd.parsimony import is_parsimonious, parsimonious_acr, parsimonious_acr_many, MP_METHODS, ACCTRAN, DELTRAN, DOWNPASS, MP  # noqa: E402,F401
 
 COPY = 'COPY'
 
@@ -337,13 +337,16 @@ def acr(forest, df=None, columns=None, column2states=None, prediction_method=MPP
 
     def run_all(flat, forest_stats):
         ml_results = iter(run_tasks(forest, tasks, force_joint=force_joint, flat=flat, seeds=seeds)) if tasks else iter(())
+        # the parsimonious characters of the call together: one device call, or the host path one by one (choose_path)
+        mp = [item for item in plan if item[0] == 'mp']
+        mp_results = iter(parsimonious_acr_many(forest, [item[1] for item in mp], [item[2] for item in mp],
+                                                [item[3] for item in mp], forest_stats.num_nodes, forest_stats.num_tips))
         results = []
         for kind, character, method, payload in plan:
             if kind == 'ml':
                 results.append(next(ml_results))
             elif kind == 'mp':
-                results.append(parsimonious_acr(forest, character, method, payload, forest_stats.num_nodes,
-                                                forest_stats.num_tips))
+                results.append(next(mp_results))
             else:
                 results.append({CHARACTER: character, STATES: payload, METHOD: method})
         return flatten_lists(results)

@@ -1293,10 +1293,13 @@ def reconstruct(batch, tasks, lnl, force_joint=True):
             if method == ml.ALL:
                 # the parsimonious reconstructions of the annotation, and the likelihood restricted to each of them
                 # (ml.py:718-733); a selection that leaves some zero-length branch without a common state has none
-                from pastml_amd.parsimony import parsimonious_acr, MP
-                mp_results = [parsimonious_acr(batch.flat.nodes[:len(flat.roots)], t.character, MP, t.model.states,
-                                               t.model.forest_stats.num_nodes, t.model.forest_stats.num_tips)
-                              for t in tasks]
+                # (all characters of the group in one device call on the group's own context, or the host path one by one:
+                # parsimony.choose_path)
+                from pastml_amd.parsimony import parsimonious_acr_many, MP
+                stats = tasks[0].model.forest_stats
+                mp_results = parsimonious_acr_many(batch.flat.nodes[:len(flat.roots)], [t.character for t in tasks],
+                                                   [MP] * m, [t.model.states for t in tasks], stats.num_nodes,
+                                                   stats.num_tips, engine=batch.engine)
                 for c in range(m):
                     results[c].extend(mp_results[c])
                 for which in range(len(mp_results[0])):

@@ -2027,6 +2027,26 @@ int pml_simulate_states(pml_ctx* ctx, int32_t col, int32_t n_repetitions, int32_
     return PML_OK;
 }
 
+// Maximum parsimony of n_cols characters on the uploaded forest (pml_launch_parsimony.hip).  Needs the tree only: no columns,
+// no model, no likelihood vectors -- the scratch of the call is freed before it returns.
+int pml_parsimony(pml_ctx* ctx, int32_t n_cols, int32_t k, const uint64_t* given, int methods, uint64_t* sets_out,
+                  int64_t* steps_out, int64_t* size_hist_out) {
+    if (!ctx || ctx->N == 0) return fail(PML_ERR_INVALID, "upload the tree first");
+    if (n_cols <= 0) return fail(PML_ERR_INVALID, "n_cols must be positive");
+    if (k <= 0) return fail(PML_ERR_INVALID, "k must be positive");
+    if (k > PML_MAX_STATES) return fail(PML_ERR_UNSUPPORTED, "k = %d states; at most %d are supported", k, PML_MAX_STATES);
+    if (methods <= 0 || methods > 7) return fail(PML_ERR_INVALID, "methods must be a combination of PML_PARS_ACCTRAN / _DOWNPASS / _DELTRAN");
+    if (!given || !sets_out || !steps_out || !size_hist_out) return fail(PML_ERR_INVALID, "NULL array");
+    return launch_parsimony(ctx, n_cols, k, (const u64*)given, methods, (u64*)sets_out, (i64*)steps_out, (i64*)size_hist_out);
+}
+
+int pml_parsimony_info(pml_ctx* ctx, int64_t* launches, double* passes_ms) {
+    if (!ctx) return fail(PML_ERR_INVALID, "ctx is NULL");
+    if (launches) *launches = ctx->pars_launches;
+    if (passes_ms) *passes_ms = ctx->pars_ms;
+    return PML_OK;
+}
+
 int pml_select_states(pml_ctx* ctx, int method, int force_joint, const uint64_t* lh_mask, uint64_t* masks_out,
                       int32_t* n_states_out) {
     PML_TRY(require_model(ctx));

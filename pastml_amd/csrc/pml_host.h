@@ -25,7 +25,7 @@
 
 struct PmlComm;  // pml_comm.h (pml_api.hip only)
 
-#define PML_VERSION 102
+#define PML_VERSION 103
 
 // internal linkage across the library's translation units (not part of the C-ABI)
 #define PML_INTERNAL __attribute__((visibility("hidden")))
@@ -206,6 +206,10 @@ struct pml_ctx {
     int sim_depth = -1, sim_n_lists = 0;
     int4* d_sim_lists = nullptr;   // (internal id, caller's id, caller's id of the parent, 0) per node
     int* d_sim_off = nullptr;
+
+    // parsimony (pml_launch_parsimony.hip): kernel launches and event time of the passes of the last pml_parsimony
+    long long pars_launches = 0;
+    double pars_ms = 0;
 
     PmlComm* comm = nullptr;   // RCCL communicator attached by pml_comm_init (survives tree uploads)
 };

@@ -152,6 +152,9 @@ PML_INTERNAL int launch_pij_valu(pml_ctx* ctx);
 // ---- pml_launch_simulate.hip: forward simulation of a column along the forest (pml_simulate_states); d_states [N][rs] in the
 //      caller's numbering, uint8 for k <= 256, else uint16
 PML_INTERNAL int launch_simulate(pml_ctx* ctx, int col, int n_rep, int rep_offset, u64 seed, void* d_states, size_t rs);
+// ---- pml_launch_parsimony.hip: the parsimony passes on packed state sets (pml_parsimony); host arrays in the caller's numbering
+PML_INTERNAL int launch_parsimony(pml_ctx* ctx, int n_cols, int k, const u64* given, int methods, u64* sets_out, i64* steps_out,
+                                  i64* hist_out);
 
 // More than 64 KB of dynamic LDS must be asked for: once per kernel, device and size (the largest asked for so far is what is
 // set) -- not per launch: the call is not free and should not sit inside a stream capture.  (A template: one table per kernel

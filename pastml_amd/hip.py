@@ -31,6 +31,7 @@ OPT_KEEP_TD = 2
 OPT_EIGEN_FUSED = 3
 OPT_EIGEN_JOINT_VALU = 4
 OPT_IMPLICIT_TIP_POSTERIORS = 5
+PARS_ACCTRAN, PARS_DOWNPASS, PARS_DELTRAN = 1, 2, 4   # pml_parsimony's methods
 COMM_ID_BYTES = 128
 COMM_SUM, COMM_MAX = 0, 1
 
@@ -107,6 +108,9 @@ SIGNATURES = {
     'pml_marginal_counts_altered': [_ctx_p, ctypes.c_int32, ctypes.c_int32, ctypes.c_uint64, ctypes.POINTER(ctypes.c_uint8),
                                     _c_double_p, _c_int32_p, _c_int32_p],
     'pml_simulate_states': [_ctx_p, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_uint64, ctypes.c_void_p],
+    'pml_parsimony': [_ctx_p, ctypes.c_int32, ctypes.c_int32, _c_uint64_p, ctypes.c_int, _c_uint64_p,
+                      ctypes.POINTER(ctypes.c_int64), ctypes.POINTER(ctypes.c_int64)],
+    'pml_parsimony_info': [_ctx_p, ctypes.POINTER(ctypes.c_int64), _c_double_p],
     'pml_download': [_ctx_p, ctypes.c_int, ctypes.c_int32, ctypes.c_void_p],
     'pml_comm_unique_id': [ctypes.POINTER(ctypes.c_ubyte)],
     'pml_comm_init': [_ctx_p, ctypes.c_int, ctypes.c_int, ctypes.POINTER(ctypes.c_ubyte)],
@@ -485,7 +489,8 @@ class Engine(BareContext):
                 flat.n_bu_levels, _ptr(arrays['bu_offsets'], i32), _ptr(arrays['bu_order'], i32),
                 flat.n_td_levels, _ptr(arrays['td_offsets'], i32), _ptr(arrays['td_parent_offsets'], i32),
                 _ptr(arrays['td_parents'], i32), _ptr(arrays['post_rank'], i32)))
-            _check(lib.pml_chars_alloc(self._ctx, n_cols, k))
+            if n_cols:   # (n_cols = 0: the tree alone -- Engine.tree_only, what the parsimony passes need)
+                _check(lib.pml_chars_alloc(self._ctx, n_cols, k))
         except Exception:
             self.close()
             raise
@@ -768,6 +773,39 @@ class Engine(BareContext):
         _check(self._lib.pml_simulate_states(self._ctx, col, int(n_repetitions), int(rep_offset), ctypes.c_uint64(int(seed)),
                                              out.ctypes.data_as(ctypes.c_void_p)))
         return out
+
+    @classmethod
+    def tree_only(cls, flat, device=None, tune=None):
+        """A context that holds the forest and no columns: no likelihood vectors are allocated (``parsimony`` needs no more)."""
+        return cls(flat, 0, 0, device=device, tune=tune)
+
+    def parsimony(self, given, k, methods):
+        """
+        Maximum parsimony of several characters in one call (pml_parsimony).  given: uint64 [n, N, W] annotated states
+        (all-zero words: none); methods: a combination of PARS_ACCTRAN / PARS_DOWNPASS / PARS_DELTRAN.  Returns (sets uint64
+        [n_methods, n, N, W], steps int64 [n_methods, n], size_hist int64 [n_methods, n, k + 1]), the methods in the order
+        ACCTRAN, DOWNPASS, DELTRAN.  Works on any context with a tree, whatever its columns.
+        """
+        W = (k + 63) // 64
+        given = _as(given, np.uint64)
+        if given.ndim == 2:
+            given = given[None]
+        if given.shape[1:] != (self.n_nodes, W):
+            raise ValueError('given must be [n, {}, {}], got {}'.format(self.n_nodes, W, given.shape))
+        n = given.shape[0]
+        n_methods = bin(int(methods) & 7).count('1')
+        sets = np.empty((n_methods, n, self.n_nodes, W), dtype=np.uint64)
+        steps = np.empty((n_methods, n), dtype=np.int64)
+        hist = np.empty((n_methods, n, k + 1), dtype=np.int64)
+        _check(self._lib.pml_parsimony(self._ctx, n, int(k), _ptr(given, ctypes.c_uint64), int(methods),
+                                       _ptr(sets, ctypes.c_uint64), _ptr(steps, ctypes.c_int64), _ptr(hist, ctypes.c_int64)))
+        return sets, steps, hist
+
+    def parsimony_info(self):
+        """(kernel launches, milliseconds of the passes by HIP events) of the last ``parsimony`` call."""
+        launches, ms = ctypes.c_int64(0), ctypes.c_double(0)
+        _check(self._lib.pml_parsimony_info(self._ctx, ctypes.byref(launches), ctypes.byref(ms)))
+        return launches.value, ms.value
 
     def download(self, what, col=0):
         N, k = self.n_nodes, self.k

@@ -1,14 +1,20 @@
 """
 Maximum-parsimony reconstruction (DOWNPASS, ACCTRAN, DELTRAN, MP): what pastml/parsimony.py computes, on the flattened
-forest.  Integer set work, no likelihoods: it stays on the host, but as array operations per tree level instead of
-per-node Python sets -- state sets are 0/1 rows of an [N, k] array, "the most common states among these sets"
-(parsimony.py:73-87) is a segment sum over the contiguous children of each parent followed by a row maximum, and the
-passes run level by level over the height / depth ranges the device sweeps use too.
+forest.  Integer set work, no likelihoods.  Two paths compute the same sets:
+
+* the host path (``parsimonious_acr``): array operations per tree level instead of per-node Python sets -- state sets are
+  0/1 rows of an [N, k] array, "the most common states among these sets" (parsimony.py:73-87) is a segment sum over the
+  contiguous children of each parent followed by a row maximum, and the passes run level by level over the height / depth
+  ranges the device sweeps use too.  One character at a time, any number of states;
+* the device path (``parsimonious_acr_batch`` -> ``hip.Engine.parsimony`` -> pml_parsimony): all characters of a forest
+  in one call, on packed state sets, up to 512 states.  ``PASTML_AMD_PARSIMONY`` = auto / host / device chooses
+  (``choose_path``).
 
 It is here because the ``ALL`` meta-method of ``ml_acr`` (pastml/ml.py:718-733) evaluates the likelihood restricted to
 each parsimonious reconstruction, and so that ``acr()`` accepts every prediction method of the reference.
 """
 import logging
+import os
 
 import numpy as np
 
@@ -23,6 +29,18 @@ DELTRAN = 'DELTRAN'
 MP = 'MP'
 
 MP_METHODS = {DOWNPASS, ACCTRAN, DELTRAN}
+
+PATH_VARIABLE = 'PASTML_AMD_PARSIMONY'
+AUTO, HOST, DEVICE = 'auto', 'host', 'device'
+MAX_DEVICE_STATES = 512   # the device path's bound (W <= 8 words per set); the host path has none
+# `auto` takes the device from this much work on, nodes x characters x words per set.  Measured (scripts/parsimony_scale.py,
+# profiles/parsimony_scale.txt): with ONE character -- the case that favours the host most, the device's fixed cost of a
+# context, the tree upload and the call being spread over nothing -- the two paths meet at 31 999 nodes (0.0256 s against
+# 0.0266 s); rounded up to the next power of two.  With more characters the device wins from less work on (5 443 nodes x 91
+# characters, work 495 313: 56 times faster), so the constant errs towards the host.  Inside the ALL meta-method the
+# group's context holds the tree already; that call site was not measured on its own and shares the constant.
+AUTO_MIN_WORK = 1 << 16
+AUTO_MIN_WORK_WITH_CONTEXT = 1 << 16
 META_MP_METHODS = {MP}
 
 
@@ -214,3 +232,141 @@ def parsimonious_acr(forest, character, prediction_method, states, num_nodes, nu
             report(DELTRAN, sets)
     logger.debug("Parsimonious reconstruction for {} requires {} state changes.".format(character, result[STEPS]))
     return results
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+def parsimony_path():
+    """The value of PASTML_AMD_PARSIMONY: 'auto' (default), 'host' or 'device'."""
+    value = os.environ.get(PATH_VARIABLE, AUTO).strip().lower() or AUTO
+    if value not in (AUTO, HOST, DEVICE):
+        raise ValueError('{} must be one of {}, {} or {}, not {!r}'.format(PATH_VARIABLE, AUTO, HOST, DEVICE, value))
+    return value
+
+
+def _device_ready():
+    from pastml_amd import hip
+    try:
+        return hip.device_count() > 0
+    except (hip.HipUnavailableError, OSError):
+        return False
+
+
+def choose_path(n_nodes, characters, states, has_context=False):
+    """
+    HOST or DEVICE for these characters of one forest (``states``: their state arrays).  'device' insists: it raises
+    HipUnavailableError without the library or a gfx950 device and ValueError for a character of more than 512 states.
+    'auto' takes the device when it is there, every character fits and the job (nodes x characters x words per set) is large
+    enough; under a multi-process launch it stays on the host, as before.
+    """
+    from pastml_amd import hip, sharding
+    path = parsimony_path()
+    if path == HOST or not len(characters):
+        return HOST
+    if path == DEVICE:
+        for character, s in zip(characters, states):
+            if len(s) > MAX_DEVICE_STATES:
+                raise ValueError('Character {} has {} states: the device path of the parsimonious methods supports at most '
+                                 '{} ({}=device); the host path has no bound.'
+                                 .format(character, len(s), MAX_DEVICE_STATES, PATH_VARIABLE))
+        hip.load_library()   # HipUnavailableError without it
+        if hip.device_count() < 1:
+            raise hip.HipUnavailableError('{}=device, but no HIP device is visible: the device path of the parsimonious '
+                                          'methods needs an MI355X (gfx950)'.format(PATH_VARIABLE))
+        return DEVICE
+    comm = sharding.communicator()
+    if comm is not None and comm.world > 1:
+        return HOST
+    if any(len(s) > MAX_DEVICE_STATES for s in states):
+        return HOST
+    work = sum(n_nodes * ((len(s) + 63) // 64) for s in states)
+    if work < (AUTO_MIN_WORK_WITH_CONTEXT if has_context else AUTO_MIN_WORK):
+        return HOST
+    return DEVICE if _device_ready() else HOST
+
+
+_METHOD_BITS = ((ACCTRAN, 1), (DOWNPASS, 2), (DELTRAN, 4))
+
+
+def _reported(prediction_method):
+    """The methods a prediction method reports, in the order of parsimonious_acr."""
+    return [m for m, _ in _METHOD_BITS if prediction_method in (m, MP)]
+
+
+def parsimonious_acr_batch(forest, characters, prediction_methods, states, num_nodes, num_tips, engine=None):
+    """
+    ``parsimonious_acr`` for several characters of one forest on the device: their annotations are packed, every group of
+    characters with the same number of states is ONE pml_parsimony call, and per character the same node features, log
+    lines and result dictionaries come back (a list of result lists, in the order of ``characters``).  engine: a context
+    that holds this forest (whatever its columns); without one a tree-only context is made for the call.
+    """
+    from pastml_amd import hip
+    from pastml_amd.batch import annotation_words
+    from pastml_amd.tree import TreeNode, get_flat_forest, StateSetColumn
+    if isinstance(forest, TreeNode):
+        forest = [forest]
+    logger = logging.getLogger('pastml')
+    flat = get_flat_forest(forest)
+    states = [np.asarray(s) for s in states]
+    for character, s in zip(characters, states):
+        if len(s) > MAX_DEVICE_STATES:
+            raise ValueError('Character {} has {} states: the device path of the parsimonious methods supports at most {}.'
+                             .format(character, len(s), MAX_DEVICE_STATES))
+    results = [None] * len(characters)
+    own = engine is None
+    if own:
+        engine = hip.Engine.tree_only(flat)
+    try:
+        for k in sorted({len(s) for s in states}):
+            group = [i for i, s in enumerate(states) if len(s) == k]
+            bits = 0
+            for i in group:
+                for m, bit in _METHOD_BITS:
+                    # (DELTRAN works on the DOWNPASS sets, which the library computes for it without reporting them)
+                    bits |= bit if m in _reported(prediction_methods[i]) else 0
+            slot = {m: j for j, m in enumerate(m for m, bit in _METHOD_BITS if bits & bit)}
+            given = np.stack([annotation_words(flat, characters[i], states[i])[0] for i in group])
+            sets, steps, hist = engine.parsimony(given, k, bits)
+            sizes = np.arange(k + 1)
+            for c, i in enumerate(group):
+                character, prediction_method = characters[i], prediction_methods[i]
+                out = []
+                for method in _reported(prediction_method):
+                    j = slot[method]
+                    name = character if prediction_method == method else get_personalized_feature_name(character, method)
+                    flat.set_column(name, StateSetColumn(sets[j, c], states[i]))
+                    h = hist[j, c]
+                    scenarios = 1
+                    for size in range(2, k + 1):
+                        if h[size]:
+                            scenarios *= size ** int(h[size])
+                    res = {STATES: states[i], NUM_NODES: num_nodes, NUM_TIPS: num_tips, STEPS: int(steps[j, c])}
+                    res[NUM_SCENARIOS] = scenarios
+                    res[NUM_UNRESOLVED_NODES] = int(h[2:].sum())
+                    res[NUM_STATES_PER_NODE] = int((h * sizes).sum()) / num_nodes
+                    res[PERC_UNRESOLVED] = res[NUM_UNRESOLVED_NODES] * 100 / num_nodes
+                    logger.debug('{} node{} unresolved ({:.2f}%) for {} by {}, i.e. {:.4f} state{} per node in average.'
+                                 .format(res[NUM_UNRESOLVED_NODES], 's are' if res[NUM_UNRESOLVED_NODES] != 1 else ' is',
+                                         res[PERC_UNRESOLVED], character, method, res[NUM_STATES_PER_NODE],
+                                         's' if res[NUM_STATES_PER_NODE] > 1 else ''))
+                    res[CHARACTER], res[METHOD] = name, method
+                    out.append(res)
+                logger.debug("Parsimonious reconstruction for {} requires {} state changes."
+                             .format(character, out[-1][STEPS]))
+                results[i] = out
+    finally:
+        if own:
+            engine.close()
+    return results
+
+
+def parsimonious_acr_many(forest, characters, prediction_methods, states, num_nodes, num_tips, engine=None):
+    """The parsimonious reconstructions of several characters by the path PASTML_AMD_PARSIMONY selects (``choose_path``)."""
+    from pastml_amd.tree import TreeNode, get_flat_forest
+    if isinstance(forest, TreeNode):
+        forest = [forest]
+    if not len(characters):
+        return []
+    flat = get_flat_forest(forest)
+    if choose_path(flat.n_nodes, characters, states, has_context=engine is not None) == DEVICE:
+        return parsimonious_acr_batch(forest, characters, prediction_methods, states, num_nodes, num_tips, engine=engine)
+    return [parsimonious_acr(forest, c, m, s, num_nodes, num_tips) for c, m, s in zip(characters, prediction_methods, states)]
