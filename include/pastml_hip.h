@@ -277,6 +277,27 @@ int pml_marginal_counts_altered(pml_ctx* ctx, int32_t col, int32_t n_repetitions
                                 double* sums_out, int32_t* state_counts_out, int32_t* same_out);
 
 /*
+ * The exact counterpart of pml_marginal_counts for the columns [col_begin, col_end): the limit of its estimate for
+ * n_repetitions -> infinity, in closed form from the vectors of the marginal pass (needs pml_bottom_up (marginal) and
+ * pml_top_down_marginals first, PML_ERR_INVALID otherwise).  Per column, in units "per scenario", with
+ *   w_n[b] = BU_n[b] pi_b mask_n[b],  M_n[a][b] = w_n[b] P_n[b][a] / sum_b' w_n[b'] P_n[b'][a]      (pastml/ml.py:819-824)
+ * and q_n = the marginal posterior of node n (the scheme draws the root from it, ml.py:794-798, and a child from q_parent . M_n,
+ * which for a reversible model is the child's posterior):
+ *   pair (p, n), neither end altered:  counts[a][b] += q_p[a] M_n[a][b],  same_p[a] += q_p[a] M_n[a][a]   (rows with q_p[a] == 0 unused)
+ *   after the children of p:           counts[i][i] -= min(q_p[i], same_p[i])                              (ml.py:859-860)
+ * altered ([n_nodes], 1 = altered by the zero-branch handling, ml.py:352-387; or NULL): the pairs with an altered end are left out
+ * of counts_out, their parents keep their diagonal correction, and same_out carries those parents' same_p over their other
+ * children (rows of other nodes are zero) -- the contract of pml_marginal_counts_altered, with the reference's rules for those
+ * pairs (ml.py:806-812, 840-855: ps = to_initial(q_p) if p is altered else q_p, ci likewise, norm = ci / sum(ci), counts[i][:] +=
+ * norm ps[i], same_p[i] += norm[i] ps[i]) left to the caller: pastml_amd.ml.expected_counts.
+ * counts_out[n_cols][k][k]; same_out[n_cols][n_nodes][k] or NULL.  F81 family: k <= 512, the sum over the branches runs on the FP64
+ * matrix cores; HKY / eigen models: k <= 256.  No atomics: the result does not depend on launch geometry, on the schedule
+ * switches, on the library's numbering or on the column a character sits in.
+ */
+int pml_expected_counts(pml_ctx* ctx, int32_t col_begin, int32_t col_end, const uint8_t* altered, double* counts_out,
+                        double* same_out);
+
+/*
  * Maximum parsimony of n_cols characters of k states (k <= 512) on the uploaded forest: the bottom-up pass
  * (pastml/parsimony.py:92-122) and, per bit of methods, ACCTRAN (:125-158), DOWNPASS (:161-210) and DELTRAN (:213-242, on
  * the DOWNPASS sets), each with the number of state changes its sets need (:360-380, summed over the trees) and the number

@@ -364,6 +364,26 @@ class CharacterBatch(object):
             first = int(np.flatnonzero(e.err_child >= 0)[0])
             raise LikelihoodError(first, int(e.err_parent[first]), int(e.err_child[first]))
 
+    def marginal_pass_resident(self, models):
+        """
+        What marginal_counts / expected_counts need before they count: zero-branch alteration of the characters with
+        tau == 0 (kept: alter=False semantics of ml.py:700-703 afterwards), then the marginal pass with every result left on the
+        device (nothing is copied out).  Returns the altered (character, node) flags, bool [m, N].
+        """
+        rows = np.array([0 == mdl.tau for mdl in models], dtype=bool)
+        altered = self.alter(rows) if rows.any() else np.zeros((self.m, self.N), dtype=bool)
+        eng = self.engine
+        self._upload_models(eng, models)
+        self._upload_masks()
+        eng.set_initial_masks(None)
+        self.n_sweeps += self.m
+        try:
+            eng.marginal_pass(posterior=False, lh=False)
+        except hip.ZeroLikelihoodError as e:
+            first = int(np.flatnonzero(e.err_child >= 0)[0])
+            raise LikelihoodError(first, int(e.err_parent[first]), int(e.err_child[first]))
+        return altered
+
     def joint_states(self):
         """Joint state of every node after a joint sweep (ml.py:598-622): int64 [m, N]."""
         return self.engine.joint_backtrace().astype(np.int64)

@@ -2000,6 +2000,55 @@ int pml_marginal_counts_altered(pml_ctx* ctx, int32_t col, int32_t n_repetitions
     return marginal_counts_impl(ctx, col, n_repetitions, seed, altered, sums_out, state_counts_out, same_out);
 }
 
+// Exact expected transition counts of the columns [col_begin, col_end) (pml_launch_expected.hip): the limit of the sampler above
+// for n_repetitions -> infinity, from the vectors the marginal pass left on the device.  altered (caller's ids, or null): the
+// pairs with an altered end are left out and their parents' same-state sums go to same_out, as in pml_marginal_counts_altered.
+int pml_expected_counts(pml_ctx* ctx, int32_t col_begin, int32_t col_end, const uint8_t* altered, double* counts_out,
+                        double* same_out) {
+    PML_TRY(require_model(ctx));
+    PML_TRY(check_cols(ctx, col_begin, col_end));
+    if (!counts_out) return fail(PML_ERR_INVALID, "counts_out is NULL");
+    if (ctx->bu_mode != 1 || !ctx->td_valid)
+        return fail(PML_ERR_INVALID, "pml_expected_counts needs a marginal pml_bottom_up and pml_top_down_marginals first");
+    if (ctx->kind != PML_MODEL_F81 && ctx->k > 256)
+        return fail(PML_ERR_UNSUPPORTED, "k = %d: the matrix models hold at most 256 states", ctx->k);
+    HIP_TRY(hipStreamSynchronize(ctx->stream));   // (a pass that ended in a spin on the completion word may have left the stream busy)
+    ctx->wait_signal = false;
+    PML_TRY(materialize_cherries(ctx));  // the conditional probabilities need every bottom-up vector
+    PML_TRY(materialize_tip_posteriors(ctx));
+    PML_TRY(run_prep(ctx));  // P(t) of every branch (the fused sweeps never materialise it) / exp(-mu t')
+    const size_t k = ctx->k, N = (size_t)ctx->N, cols = (size_t)(col_end - col_begin);
+    const bool with_same = altered != nullptr && same_out != nullptr;
+    double *d_out = nullptr, *d_same = nullptr;
+    unsigned char* d_alt = nullptr;
+    std::vector<unsigned char> alt;
+    hipError_t e = hipMalloc((void**)&d_out, cols * k * k * sizeof(double));
+    if (e == hipSuccess && altered != nullptr) {
+        alt.assign(N, 0);
+        for (size_t i = 0; i < N; ++i) alt[(size_t)internal_id(ctx, (int)i)] = altered[i] ? 1 : 0;
+        e = hipMalloc((void**)&d_alt, N);
+        if (e == hipSuccess) e = hipMemcpyAsync(d_alt, alt.data(), N, hipMemcpyHostToDevice, ctx->stream);
+    }
+    if (e == hipSuccess && with_same) {
+        e = hipMalloc((void**)&d_same, cols * N * k * sizeof(double));
+        if (e == hipSuccess) e = hipMemsetAsync(d_same, 0, cols * N * k * sizeof(double), ctx->stream);
+    }
+    int status = PML_OK;
+    if (e == hipSuccess) status = launch_expected(ctx, col_begin, col_end, d_alt, d_out, d_same);
+    if (e == hipSuccess && status == PML_OK)
+        e = hipMemcpyAsync(counts_out, d_out, cols * k * k * sizeof(double), hipMemcpyDeviceToHost, ctx->stream);
+    if (e == hipSuccess && status == PML_OK && with_same)
+        e = hipMemcpyAsync(same_out, d_same, cols * N * k * sizeof(double), hipMemcpyDeviceToHost, ctx->stream);
+    const hipError_t e2 = hipStreamSynchronize(ctx->stream);
+    if (d_out) (void)hipFree(d_out);
+    if (d_alt) (void)hipFree(d_alt);
+    if (d_same) (void)hipFree(d_same);
+    PML_TRY(status);
+    if (e != hipSuccess) return fail(PML_ERR_HIP, "pml_expected_counts failed: %s", hipGetErrorString(e));
+    if (e2 != hipSuccess) return fail(PML_ERR_HIP, "pml_expected_counts failed: %s", hipGetErrorString(e2));
+    return PML_OK;
+}
+
 // n_repetitions scenarios of column col drawn forward from the roots (pml_launch_simulate.hip).  Needs a model, no sweep: the
 // per-branch e = exp(-mu t') (F81 family) or P(t) is prepared here.  The states are written in the caller's numbering on the
 // device, in rows padded to a multiple of 4 repetitions, and copied out without the padding.

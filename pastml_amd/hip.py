@@ -107,6 +107,7 @@ SIGNATURES = {
     'pml_marginal_counts': [_ctx_p, ctypes.c_int32, ctypes.c_int32, ctypes.c_uint64, _c_double_p],
     'pml_marginal_counts_altered': [_ctx_p, ctypes.c_int32, ctypes.c_int32, ctypes.c_uint64, ctypes.POINTER(ctypes.c_uint8),
                                     _c_double_p, _c_int32_p, _c_int32_p],
+    'pml_expected_counts': [_ctx_p, ctypes.c_int32, ctypes.c_int32, ctypes.POINTER(ctypes.c_uint8), _c_double_p, _c_double_p],
     'pml_simulate_states': [_ctx_p, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_uint64, ctypes.c_void_p],
     'pml_parsimony': [_ctx_p, ctypes.c_int32, ctypes.c_int32, _c_uint64_p, ctypes.c_int, _c_uint64_p,
                       ctypes.POINTER(ctypes.c_int64), ctypes.POINTER(ctypes.c_int64)],
@@ -760,6 +761,29 @@ class Engine(BareContext):
                                                      _ptr(alt, ctypes.c_uint8), _ptr(sums, ctypes.c_double),
                                                      _ptr(counts, ctypes.c_int32), _ptr(same, ctypes.c_int32)))
         return sums, counts, same
+
+    def expected_counts(self, col_begin=0, col_end=None, altered=None):
+        """
+        Exact expected numbers of state changes per scenario of the columns [col_begin, col_end) after a marginal pass
+        (pml_expected_counts: the n_repetitions -> infinity limit of marginal_counts, no sampling): [cols, k, k].
+        altered (0/1 array [N]): the pairs with an altered end are left out and the parents of such pairs keep their diagonal
+        correction; returns (counts, same [cols, N, k]) then, same holding those parents' same-state sums over their other
+        children -- pastml_amd.ml.expected_counts adds the rest.
+        """
+        col_end = self.n_cols if col_end is None else col_end
+        if not 0 <= col_begin < col_end <= self.n_cols:
+            raise ValueError('bad column range')
+        out = np.empty((col_end - col_begin, self.k, self.k), dtype=np.float64)
+        if altered is None:
+            _check(self._lib.pml_expected_counts(self._ctx, col_begin, col_end, None, _ptr(out, ctypes.c_double), None))
+            return out
+        alt = np.ascontiguousarray(altered, dtype=np.uint8)
+        if alt.shape != (self.n_nodes,):
+            raise ValueError('one flag per node expected')
+        same = np.empty((col_end - col_begin, self.n_nodes, self.k), dtype=np.float64)
+        _check(self._lib.pml_expected_counts(self._ctx, col_begin, col_end, _ptr(alt, ctypes.c_uint8),
+                                             _ptr(out, ctypes.c_double), _ptr(same, ctypes.c_double)))
+        return out, same
 
     def simulate_states(self, n_repetitions, seed, col=0, rep_offset=0):
         """

@@ -538,7 +538,7 @@ def marginal_counts(forest, character, model, n_repetitions=1_000, device_sampli
                 c = cnt * initial[n]
                 if np.count_nonzero(c):
                     return n_repetitions * c / c.sum()
-                return n_repetitions * initial[n] / initial[n].sum()
+                return n_repetitions * initial[n].astype(np.float64) / initial[n].sum()   # (int8 masks: the product must not be formed in int8)
 
             result = sums
             internal = np.flatnonzero(flat.n_children > 0)
@@ -574,7 +574,7 @@ def marginal_counts(forest, character, model, n_repetitions=1_000, device_sampli
             c = counts * initial[n]
             if np.count_nonzero(c):
                 return n_repetitions * c / c.sum()
-            return n_repetitions * initial[n] / initial[n].sum()
+            return n_repetitions * initial[n].astype(np.float64) / initial[n].sum()   # (int8 masks: the product must not be formed in int8)
 
         result = np.zeros((k, k), dtype=float)
         state_counts = np.zeros((problem.N, k), dtype=np.int64)
@@ -614,3 +614,114 @@ def marginal_counts(forest, character, model, n_repetitions=1_000, device_sampli
         return result / n_repetitions
     finally:
         problem.close()
+
+
+# =====================================================================================================================
+# expected_counts
+# =====================================================================================================================
+
+def add_altered_pairs(flat, counts, same, posterior, is_altered, initial):
+    """
+    The host part of expected_counts for one character with nodes altered by the zero-branch handling: the (parent, child)
+    pairs with an altered end (pastml/ml.py:806-812, 840-855) and the diagonal correction of their parents (:859-860), for
+    all affected parents at once.
+
+    :param counts: [k, k] the device's sums over all other pairs (diagonal corrected for all other parents)
+    :param same: [N, k] the affected parents' same-state sums over their other children (pml_expected_counts' same_out)
+    :param posterior: [N, k] marginal posteriors = the per-scenario state frequencies q of the nodes
+    :param is_altered: [N] bool; initial: [N, k] 0/1 masks the altered nodes had before
+    :return: [k, k]
+    """
+    result = np.array(counts, dtype=np.float64)
+    parent = flat.parent
+    has_parent = parent >= 0
+    child = np.flatnonzero(has_parent & (is_altered | is_altered[np.where(has_parent, parent, 0)]))
+    if not len(child):
+        return result
+    par = parent[child]
+
+    def states_of(nodes):
+        # to_initial(q, x) for the altered nodes: q restricted to the states x had and renormalised, or those states evenly
+        q = posterior[nodes]
+        init = initial[nodes].astype(np.float64)
+        c = q * init
+        s = c.sum(axis=1, keepdims=True)
+        restricted = np.where(s > 0, c / np.where(s > 0, s, 1.0), init / np.maximum(init.sum(axis=1, keepdims=True), 1.0))
+        return np.where(is_altered[nodes][:, None], restricted, q)
+
+    ps = states_of(par)
+    ci = states_of(child)
+    norm = ci / ci.sum(axis=1, keepdims=True)
+    result += ps.T.dot(norm)   # (rows i with ps[i] == 0 add nothing, ml.py:851)
+    same = np.array(same, dtype=np.float64)
+    np.add.at(same, par, ps * norm)
+    dirty = np.unique(par)
+    result[np.diag_indices_from(result)] -= np.minimum(states_of(dirty), same[dirty]).sum(axis=0)
+    return result
+
+
+def expected_counts(forest, characters, models):
+    """
+    Exact expected numbers of state changes i -> j along the trees, per scenario: what marginal_counts (pastml/ml.py:753-862)
+    estimates, in closed form -- its limit for n_repetitions -> infinity, term by term, diagonal correction and the fractional
+    counts around altered nodes included; nothing is sampled.
+
+    The quantity, for one character, nodes in level order.  M_n[a][b] is the reference's conditional (ml.py:819-824):
+    w_n[b] = BU_n[b] * pi_b * mask_n[b], M_n[a][b] = w_n[b] * P_n[b][a] / sum_b' w_n[b'] * P_n[b'][a]; rows a with
+    q_parent[a] == 0 are never used (ml.py:831).  Masks are the ones the marginal pass ran with (altered where tau == 0).
+    q_root = marginal posterior of the root (ml.py:794-798), q_n = q_parent . M_n for every other node (the models are
+    reversible, so q_n is the marginal posterior of n and is read from the posterior table).  A pair (p, n) with neither end
+    altered adds q_p[a] * M_n[a][b] to result[a][b] and q_p[a] * M_n[a][a] to same_p[a].  A pair with an altered end
+    (ml.py:806-812, 840-855): ps = to_initial(q_p, p) if p is altered else q_p, ci likewise for n, norm = ci / sum(ci); for
+    every i with ps[i] > 0 result[i][:] += norm * ps[i], same_p[i] += norm[i] * ps[i]; to_initial(q, x) = q * initial_mask_x
+    renormalised, or initial_mask_x / its sum if that product is all zero.  After the children of p (ml.py:859-860):
+    result[i][i] -= min(ps[i], same_p[i]).
+
+    Characters are grouped by (number of states, model kind); a group is one batch on the device: one marginal pass and
+    ``pml_expected_counts`` over its columns (HIP, all characters at once; include/pastml_hip.h), the pairs around altered
+    nodes are added here from posterior rows.  F81 family: up to 512 states; HKY and the eigen models: up to 256.
+
+    :param characters: a character (feature name) or a list of them; models: a model or a list, one per character
+    :return: a k x k array, entry [i, j] = expected number of i -> j changes per scenario -- or a list of them
+    """
+    from pastml_amd.batch import CharacterBatch, LikelihoodError, annotation_words, likelihood_error
+    if isinstance(forest, TreeNode):
+        forest = [forest]
+    single = isinstance(characters, str)
+    if single:
+        characters, models = [characters], [models]
+    characters, models = list(characters), list(models)
+    if len(characters) != len(models):
+        raise ValueError('one model per character expected')
+    flat = get_flat_forest(forest)
+    groups = {}
+    for i, model in enumerate(models):
+        groups.setdefault((len(model.states), model.kernel_spec()['kind']), []).append(i)
+    results = [None] * len(characters)
+    for (k, _), members in groups.items():
+        group_models = [models[i] for i in members]
+        with CharacterBatch(flat, k, len(members)) as batch:
+            for c, i in enumerate(members):
+                batch.set_annotation(c, *annotation_words(flat, characters[i], models[i].states))
+            batch.initialize_allowed_states()
+            try:
+                altered = batch.marginal_pass_resident(group_models)
+            except LikelihoodError as e:
+                raise likelihood_error(flat, e)
+            eng = batch.engine
+            dirty = altered.any(axis=1)
+            c = 0
+            while c < len(members):
+                if dirty[c]:
+                    counts, same = eng.expected_counts(c, c + 1, altered=altered[c])
+                    results[members[c]] = add_altered_pairs(flat, counts[0], same[0], eng.download(hip.BUF_POSTERIOR, c),
+                                                            altered[c], hip.unpack_masks(batch.init_masks[c], k))
+                    c += 1
+                    continue
+                e = c
+                while e < len(members) and not dirty[e]:
+                    e += 1
+                for j, counts in enumerate(eng.expected_counts(c, e)):
+                    results[members[c + j]] = counts
+                c = e
+    return results[0] if single else results
