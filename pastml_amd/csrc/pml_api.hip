@@ -403,6 +403,29 @@ int pml_tree_upload(pml_ctx* ctx, int32_t n_nodes, int32_t n_roots, const int32_
         PML_TRY(put(ctx, &B.d_top_bu_offsets, B.top_bu_offsets));
         PML_TRY(put(ctx, &B.d_top_td_offsets, B.top_td_offsets));
     }
+    // the unit lists and their level tables by PmlList; a list sorted by shape is the plain one where the forest has none
+    auto or_else = [](const PmlUnit* sorted, const PmlUnit* plain) { return sorted ? sorted : plain; };
+    const PmlUnit** L = ctx->d_unit_lists;
+    L[L_BU_FUSED] = ctx->d_bu_units_f;
+    L[L_BU_FUSED_SORTED] = or_else(ctx->d_bu_units_fs, ctx->d_bu_units_f);
+    L[L_TD_FUSED] = ctx->d_td_units_f;
+    L[L_TD_FUSED_SORTED] = or_else(ctx->d_td_units_fs, ctx->d_td_units_f);
+    L[L_BU_PLAIN] = ctx->d_bu_units;
+    L[L_CHERRIES] = ctx->d_cherry_units;
+    L[L_TOP_BU] = B.d_top_bu_units;
+    L[L_TOP_TD] = B.d_top_td_units;
+    L[L_REST_BU] = U.d_bu_units_r;
+    L[L_REST_BU_SORTED] = or_else(U.d_bu_units_rs, U.d_bu_units_r);
+    L[L_REST_TD] = U.d_td_units_r;
+    L[L_REST_TD_SORTED] = or_else(U.d_td_units_rs, U.d_td_units_r);
+    L[L_CHILD_UNITS] = U.d_child_units;
+    L[L_STACK_CHILDREN] = U.d_stack_children;
+    ctx->d_list_offsets[L_BU_FUSED] = ctx->d_bu_offsets_f;
+    ctx->d_list_offsets[L_TD_FUSED] = ctx->d_td_parent_offsets_f;
+    ctx->d_list_offsets[L_TOP_BU] = B.d_top_bu_offsets;
+    ctx->d_list_offsets[L_TOP_TD] = B.d_top_td_offsets;
+    ctx->d_list_offsets[L_REST_BU] = U.d_bu_offsets_r;
+    ctx->d_list_offsets[L_REST_TD] = U.d_td_offsets_r;
     HIP_TRY(hipStreamSynchronize(ctx->stream));  // (the host tables go out of scope)
     return PML_OK;
 }
@@ -906,11 +929,11 @@ static int ensure_transition_storage(pml_ctx* ctx) {
     return PML_OK;
 }
 
-static int run_prep(pml_ctx* ctx, bool force = false) {
+static int run_prep(pml_ctx* ctx, bool force = false, bool bu_sweep = false) {
     if (!ctx->capturing) PML_TRY(params_push(ctx));  // (callers outside a sweep: pml_pij_batch, pml_marginal_counts, downloads)
     if (!ctx->prep_dirty && !force) return PML_OK;
     const PmlTree t = tree_of(ctx);
-    const PmlCols c = cols_of(ctx);
+    const PmlCols c = cols_of(ctx, bu_sweep);
     const PmlModel m = model_of(ctx);
     PML_TRY(ensure_transition_storage(ctx));
     PML_TRY(prof_begin(ctx));
@@ -1028,258 +1051,180 @@ int pml_pij_batch(pml_ctx* ctx, double* P_out) {
     return PML_OK;
 }
 
-// The narrow end of a large forest (the levels near the roots hold a handful of nodes each) is walked by ONE launch
-// with a workgroup barrier between levels instead of one latency-bound launch per level: returns the number of
-// consecutive levels, counted from the root end, that hold at most `limit` units each (0 if fewer than two do).
-// Measured on MI355X: with one column (cfg2, 65 536 tips) 512 units per level is the best cut (0.205 -> 0.181 ms per
-// marginal pass); one workgroup per column walks the levels, so with many columns the level kernels, which spread a
-// level over the whole chip, win earlier: the limit shrinks with the number of columns.
-// The fused eigen sweeps pass their own limit: a pass of theirs is a ~10 us dependent chain, so only levels that one
-// workgroup finishes in a single pass per wave belong to the narrow end.
-static int narrow_levels(const pml_ctx* ctx, const std::vector<int>& off, int n_levels, bool from_front, int C, int fixed_limit = 0,
-                         int top_down = -1) {
-    if (wide_states(ctx)) return 0;   // (no multi-level kernels beyond 256 states)
-    const int limit_env = (int)ctx->tune.get(T_NARROW_UNITS, 0);
-    int limit = fixed_limit > 0 ? fixed_limit : (limit_env > 0 ? limit_env : std::max(8, 512 / std::max(1, C)));
-    if (fixed_limit <= 0 && limit_env <= 0 && ctx->kind == PML_MODEL_F81) {
-        // ... but never below half a pass of the walking workgroup (512 threads, g lanes per unit): such a level is one
-        // wavefront's work per SIMD either way, and a launch of its own costs 5 - 10 us where a level step inside the
-        // walk costs 2.  Random 262 144-tip tree x 32 characters, marginal pass: k = 4 1.66 -> 1.52 ms, k = 12 2.56 -> 2.37,
-        // k = 64 unchanged (profiles/r05j_narrow_units.txt, r05l_narrow_ab.txt); same bits (multi_level_shape).
-        const bool td = top_down < 0 ? from_front : top_down != 0;   // (which sweep's lane shape walks the levels)
-        const int g = td ? ctx->Gt : (ctx->bu_wide_lanes ? 8 : ctx->Gf);
-        limit = std::max(limit, 256 / std::max(1, g));
-    }
-    int n = 0;
-    for (int q = 0; q < n_levels; ++q) {
-        const int l = from_front ? q : n_levels - 1 - q;
-        if (off[l + 1] - off[l] > limit) break;
-        ++n;
-    }
-    return n >= 2 ? n : 0;
+// ---------------------------------------------------------------------------------------------------------------------
+// Everything the planners of the sweeps' launch sequences read of a context (pml_schedule.h): the predicates are
+// evaluated here, once per plan.
+static PmlSweepTraits sweep_traits(const pml_ctx* ctx) {
+    PmlSweepTraits t;
+    t.f81 = ctx->kind == PML_MODEL_F81;
+    t.eigen_fused = eigen_fused(ctx);
+    t.eigen_gemm = eigen_gemm(ctx);
+    t.eigen_joint_valu = eigen_joint_valu(ctx);
+    t.hky_fused = hky_fused(ctx);
+    t.wide_states = wide_states(ctx);
+    t.k = ctx->k;
+    t.W = ctx->W;
+    t.C = ctx->C;
+    t.sched_cols = ctx->sched_cols;
+    t.n_roots = ctx->n_roots;
+    t.n_cherries = ctx->n_cherries;
+    t.has_init = ctx->has_init;
+    t.fuse = ctx->fuse;
+    t.Gf = ctx->Gf;
+    t.Gt = ctx->Gt;
+    t.bu_wide_lanes = ctx->bu_wide_lanes;
+    t.level_lists_sorted = ctx->level_lists_sorted;
+    t.single_launch = single_launch_sweeps(ctx);
+    t.blocks = block_schedule(ctx);
+    t.super = super_sweeps(ctx);
+    t.thin = thin_bottom_up(ctx);
+    t.deep = deep_top_down(ctx);
+    t.narrow_units = (int)ctx->tune.get(T_NARROW_UNITS, 0);
+    t.no_td_tail = ctx->tune.on(T_NO_TD_TAIL);
+    t.no_eigg_tiers = ctx->tune.on(T_NO_EIGG_TIERS);
+    t.no_spin_wait = ctx->tune.on(T_NO_SPIN_WAIT);
+    t.waves = PML_WAVES_PER_BLOCK;
+    const int ks4 = (ctx->k + 3) / 4;
+    t.eig_nb = ks4 % 4 == 0 ? 1 : (ks4 % 2 == 0 ? 2 : 4);   // EigShape::NB (pml_kernels_eigen_mfma.h)
+    return t;
 }
 
-// ---------------------------------------------------------------------------------------------------------------------
-// Everything a bottom-up sweep puts on the stream, without host synchronisation (so that it can be captured).
-static int enqueue_bottom_up(pml_ctx* ctx, int is_marginal, bool small_path, bool force_prep) {
-    struct Scope {
-        pml_ctx* c;
-        explicit Scope(pml_ctx* x) : c(x) { c->in_bu_enqueue = true; }
-        ~Scope() { c->in_bu_enqueue = false; }
-    } scope(ctx);
-    ctx->enqueue_signals = false;
-    const bool eig = eigen_fused(ctx);
-    const bool gemm = is_marginal && eigen_gemm(ctx);
-    const bool eigj = !is_marginal && eigen_joint_valu(ctx);
-    PML_TRY(params_push(ctx));  // what the last model update left in the pinned mirror (part of the graph when captured)
-    if (!small_path) {  // the single-launch kernel resets the error words itself
-        hipLaunchKernelGGL(reset_err_kernel, dim3((ctx->C + 63) / 64), dim3(64), 0, ctx->stream, ctx->d_err, ctx->C,
-                           eigj ? ctx->d_tip_rest_count : nullptr);
-        HIP_TRY(hipGetLastError());
-        // the fused eigen sweeps build P(t) themselves, the two-GEMM sweeps never need it
-        if (!eig && !gemm && !eigj && !hky_fused(ctx)) PML_TRY(run_prep(ctx, force_prep));
-    }
-    PML_TRY(prof_begin(ctx));
-    const bool fused = is_marginal && ctx->kind == PML_MODEL_F81;
-    bool loglik_done = small_path;
-    bool joint_fused = false;
-    if (small_path) {
-        // prep + every level + ln L in one launch
-        PML_TRY(dispatch_small_f81(ctx, true, (ctx->prep_dirty || force_prep) ? 1 : 0));
-        PML_TRY(prof_end(ctx, 0, 1));
-    } else if (fused && block_schedule(ctx)) {
-        // subtree blocks in one launch, then the top part: level launches, its narrow end (and ln L) in one launch
-        const pml_ctx::BlockSchedule& B = ctx->blocks;
-        PML_TRY(dispatch_blocks_f81(ctx, true));
-        const int nl = (int)B.top_bu_offsets.size() - 1;
-        const int tail = narrow_levels(ctx, B.top_bu_offsets, nl, false, ctx->sched_cols);
-        for (int l = 0; l < nl - tail; ++l) {
-            const int a = B.top_bu_offsets[l], b = B.top_bu_offsets[l + 1];
-            ctx->units_override = B.d_top_bu_units + a;
-            const int status = dispatch_sweep(ctx, B.top_bu_vec[l] ? SW_BU_MARG_FUSED : SW_BU_MARG_FUSED_NOVEC,
-                                              ctx->d_bu_order_f, b - a);
-            ctx->units_override = nullptr;
-            PML_TRY(status);
+static PmlSchedules schedules_of(const pml_ctx* ctx) {
+    return {&ctx->blocks, &ctx->thin, &ctx->deep, &ctx->sup, &ctx->eig_tiers, &ctx->bt_tiers, &ctx->bu_level_vec_f,
+            &ctx->bu_level_vec, &ctx->td_cherry_prefix};
+}
+
+// Puts the launches of a plan on the stream, in order and without host synchronisation (so that they can be captured):
+// one call of a launcher per record.  bottom_up: they are a bottom-up sweep's, which looks at the flags of the active
+// columns.  The profile brackets open and close where a record's bracket differs from the one before it, and a bracket's
+// launches are its records.  n_signals: the launches that raise the completion word are added to it.
+static int run_plan(pml_ctx* ctx, const std::vector<PmlLaunch>& plan, bool bottom_up, int is_marginal, bool force_prep,
+                    int* n_signals) {
+    const pml_ctx::EigenTiers& E = ctx->eig_tiers;
+    const pml_ctx::BacktraceTiers& B = ctx->bt_tiers;
+    const int* order = bottom_up ? ctx->d_bu_order : nullptr;   // (top-down: the nodes of a depth are a contiguous id range)
+    const int* offsets = bottom_up ? ctx->d_bu_offsets : ctx->d_td_offsets;
+    const int gemm_mode = bottom_up ? PML_EIGG_BU : PML_EIGG_TD;
+    const int eig_mode = !bottom_up ? PML_EIG_TD : (is_marginal ? PML_EIG_BU_MARG : PML_EIG_BU_JOINT);
+    int open = PML_NO_BRACKET;
+    long long launches = 0;
+    for (const PmlLaunch& r : plan) {
+        if (ctx->tune.on(T_DEBUG))
+            fprintf(stderr, "pml plan: branch %d op %d list %d kind %d first %d count %d arg %d bracket %d signal %d\n", r.branch,
+                    r.op, r.list, r.kind, r.first, r.count, r.arg, r.bracket, (int)r.signal);
+        if (r.bracket != open) {
+            if (open != PML_NO_BRACKET) PML_TRY(prof_end(ctx, open, launches));
+            if (r.bracket != PML_NO_BRACKET) PML_TRY(prof_begin(ctx));
+            open = r.bracket;
+            launches = 0;
         }
-        PML_TRY(prof_end(ctx, 0, 1 + nl - tail));
-        if (tail > 0) {
-            PML_TRY(dispatch_small_f81(ctx, true, 0, 0, tail, B.d_top_bu_units, B.d_top_bu_offsets + (nl - tail)));
-            loglik_done = true;
-        }
-    } else if (fused && super_sweeps(ctx)) {
-        // the two-level units first (they depend on tips only), then the levels of what is left
-        const pml_ctx::SuperSchedule& U = ctx->sup;
-        PML_TRY(dispatch_super_f81(ctx, true));
-        PML_TRY(prof_end(ctx, 4, U.n > 0 ? 1 : 0));
-        PML_TRY(prof_begin(ctx));
-        const int nl = (int)U.bu_offsets_r.size() - 1;
-        int tail = narrow_levels(ctx, U.bu_offsets_r, nl, false, ctx->sched_cols);
-        // (the narrow end's single launch walks the rest lists only: it starts above the last level with stacked units)
-        for (int l = nl - 1; l >= 0 && U.n_stack > 0; --l)
-            if (U.stack_bu_offsets[l + 1] > U.stack_bu_offsets[l]) {
-                tail = std::min(tail, nl - 1 - l);
+        ++launches;
+        if (r.signal) ++*n_signals;
+        const bool joint = r.kind == EIG_JOINT, gemm = r.kind == EIG_GEMM;   // (of the eigen ops; else the fused matrix-core kernels)
+        switch (r.op) {
+            case OP_RESET_ERR:
+                hipLaunchKernelGGL(reset_err_kernel, dim3((ctx->C + 63) / 64), dim3(64), 0, ctx->stream, ctx->d_err, ctx->C,
+                                   r.arg ? ctx->d_tip_rest_count : nullptr);
+                HIP_TRY(hipGetLastError());
+                break;
+            case OP_PREP:   // (brackets itself: other callers run it outside a sweep)
+                PML_TRY(run_prep(ctx, force_prep, true));
+                break;
+            case OP_LOGLIK:
+                // ln L and the error words are written straight into pinned host memory by the last kernel
+                hipLaunchKernelGGL(loglik_kernel, dim3((ctx->C + PML_BLOCK - 1) / PML_BLOCK), dim3(PML_BLOCK), 0, ctx->stream,
+                                   tree_of(ctx), cols_of(ctx, true), state_of(ctx), ctx->C, is_marginal ? 1 : 0, ctx->h_loglik,
+                                   ctx->h_err);
+                HIP_TRY(hipGetLastError());
+                break;
+            case OP_LEVEL:
+                PML_TRY(dispatch_sweep(ctx, (SweepKind)r.kind, r.list, r.first, r.count, r.cherries, bottom_up));
+                break;
+            case OP_ROOTS:
+                PML_TRY(dispatch_sweep(ctx, SW_ROOTS, L_NONE, 0, r.count));
+                break;
+            case OP_LEVELS: {
+                // (the fused lists of the whole forest are the launcher's default: it picks the sorted ones where they pay)
+                const bool whole = r.list == L_BU_FUSED || r.list == L_TD_FUSED;
+                const int do_prep = (bottom_up && r.arg && (ctx->prep_dirty || force_prep)) ? 1 : 0;
+                PML_TRY(dispatch_small_f81(ctx, bottom_up, r.signal, do_prep, whole ? r.first : 0, r.count,
+                                           whole ? nullptr : ctx->d_unit_lists[r.list], whole ? nullptr : ctx->d_list_offsets[r.list] + r.first,
+                                           bottom_up ? 0 : r.arg));
                 break;
             }
-        if (tail < 2) tail = 0;
-        long long n_launch = 0;
-        for (int l = 0; l < nl - tail; ++l) {
-            const int a = U.bu_offsets_r[l], b = U.bu_offsets_r[l + 1];
-            if (b > a) {
-                ctx->units_override = (ctx->level_lists_sorted && U.d_bu_units_rs ? U.d_bu_units_rs : U.d_bu_units_r) + a;
-                const int status = dispatch_sweep(ctx, U.bu_level_vec_r[l] ? SW_BU_MARG_FUSED : SW_BU_MARG_FUSED_NOVEC,
-                                                  ctx->d_bu_order_f, b - a);
-                ctx->units_override = nullptr;
-                PML_TRY(status);
-                ++n_launch;
+            case OP_BLOCKS:
+                PML_TRY(dispatch_blocks_f81(ctx, bottom_up, r.first, r.signal));
+                break;
+            case OP_SUPER:
+                PML_TRY(dispatch_super_f81(ctx, bottom_up));
+                break;
+            case OP_STACK:
+                PML_TRY(dispatch_stack_f81(ctx, bottom_up, r.first));
+                break;
+            case OP_EIG_TIPS:
+                if (joint) PML_TRY(launch_eigen_joint_tips(ctx));
+                else if (gemm) PML_TRY(launch_eigen_gemm(ctx, PML_EIGG_TIPS, ctx->d_tips, 0, ctx->n_tips));
+                else PML_TRY(launch_eigen_tips(ctx, is_marginal ? 0 : 1));
+                break;
+            case OP_EIG_LEVEL: {
+                const int* nodes = order ? order + r.first : nullptr;
+                const int first = order ? 0 : r.first;
+                if (joint) PML_TRY(launch_eigen_joint(ctx, ctx->d_bu_units + r.first, nullptr, 0, r.count));
+                else if (gemm) PML_TRY(launch_eigen_gemm(ctx, gemm_mode, nodes, first, r.count));
+                else PML_TRY(launch_eigen_fused(ctx, eig_mode, nodes, first, r.count, 0));
+                break;
             }
-            // the level's stacked units (they read vectors of two levels down: independent of the launch above)
-            if (U.n_stack > 0 && U.stack_bu_offsets[l + 1] > U.stack_bu_offsets[l]) {
-                PML_TRY(dispatch_stack_f81(ctx, true, l));
-                ++n_launch;
+            case OP_EIG_NARROW:
+                if (joint) PML_TRY(launch_eigen_joint(ctx, ctx->d_bu_units, offsets, r.first, r.count));
+                else if (gemm) PML_TRY(launch_eigen_gemm_narrow(ctx, gemm_mode, order, offsets, r.first, r.count));
+                else PML_TRY(launch_eigen_narrow(ctx, eig_mode, order, offsets, r.first, r.count));
+                break;
+            case OP_EIG_TIER: {   // thin levels in tiers of subtree blocks (pml_ctx::EigenTiers)
+                const pml_ctx::EigenTiers::Tier& T = E.tiers[r.first];
+                if (joint) PML_TRY(launch_eigen_joint(ctx, E.d_units, E.d_lv, 0, T.depth, E.d_start + T.first_block, T.n_blocks));
+                else PML_TRY(launch_eigen_gemm_narrow(ctx, PML_EIGG_BU, E.d_nodes, E.d_lv, 0, T.depth, E.d_start + T.first_block,
+                                                      T.n_blocks));
+                break;
             }
-        }
-        PML_TRY(prof_end(ctx, 0, n_launch));
-        if (tail > 0) {
-            PML_TRY(dispatch_small_f81(ctx, true, 0, 0, tail, U.d_bu_units_r, U.d_bu_offsets_r + (nl - tail)));
-            loglik_done = true;
-        }
-    } else if (fused && thin_bottom_up(ctx)) {
-        // the wide levels one launch each, the thin ones in tiers of subtree blocks (a launch per tier), then the narrow
-        // end's single launch (in between, level launches where a level is still too wide for it)
-        const pml_ctx::ThinSchedule& H = ctx->thin;
-        auto level_launch = [&](int l) -> int {
-            const int a = ctx->forest.bu_offsets_f[l], b = ctx->forest.bu_offsets_f[l + 1];
-            return dispatch_sweep(ctx, ctx->bu_level_vec_f[l] ? SW_BU_MARG_FUSED : SW_BU_MARG_FUSED_NOVEC, ctx->d_bu_order_f + a, b - a);
-        };
-        for (int l = 0; l < H.floor_level; ++l) PML_TRY(level_launch(l));
-        for (size_t q = 0; q < H.tiers.size(); ++q) PML_TRY(dispatch_blocks_f81(ctx, true, 1 + (int)q));
-        const int nl = (int)ctx->forest.bu_offsets_f.size() - 1;
-        int tail = std::min(nl - H.top_level, narrow_levels(ctx, ctx->forest.bu_offsets_f, nl, false, ctx->sched_cols));
-        for (int l = H.top_level; l < nl - tail; ++l) PML_TRY(level_launch(l));
-        PML_TRY(prof_end(ctx, 0, H.floor_level + (long long)H.tiers.size() + (nl - tail - H.top_level)));
-        if (tail > 0) {
-            PML_TRY(dispatch_small_f81(ctx, true, 0, nl - tail, tail));
-            loglik_done = true;
-        }
-    } else if (fused) {
-        const int nl = (int)ctx->forest.bu_offsets_f.size() - 1;
-        const int tail = narrow_levels(ctx, ctx->forest.bu_offsets_f, nl, false, ctx->sched_cols);
-        for (int l = 0; l < nl - tail; ++l) {
-            const int a = ctx->forest.bu_offsets_f[l], b = ctx->forest.bu_offsets_f[l + 1];
-            PML_TRY(dispatch_sweep(ctx, ctx->bu_level_vec_f[l] ? SW_BU_MARG_FUSED : SW_BU_MARG_FUSED_NOVEC,
-                                   ctx->d_bu_order_f + a, b - a));
-        }
-        PML_TRY(prof_end(ctx, 0, nl - tail));  // the profile brackets the level kernel's launches only
-        if (tail > 0) {  // the levels next to the roots and ln L in one launch
-            PML_TRY(dispatch_small_f81(ctx, true, 0, nl - tail, tail));
-            loglik_done = true;
-        }
-    } else if (!is_marginal && ctx->kind == PML_MODEL_F81 && ctx->fuse && !ctx->has_init && ctx->n_cherries > 0 &&
-               ctx->W == 1) {
-        // joint sweep over the cherry-fused lists (no altered nodes whose tables would need rewriting)
-        const int nl = (int)ctx->forest.bu_offsets_f.size() - 1;
-        for (int l = 0; l < nl; ++l) {
-            const int a = ctx->forest.bu_offsets_f[l], b = ctx->forest.bu_offsets_f[l + 1];
-            PML_TRY(dispatch_sweep(ctx, ctx->bu_level_vec_f[l] ? SW_BU_JOINT_FUSED : SW_BU_JOINT_FUSED_NOVEC,
-                                   ctx->d_bu_order_f + a, b - a));
-        }
-        PML_TRY(prof_end(ctx, 0, nl));
-        joint_fused = true;
-    } else if (eigj) {
-        // joint sweep of an eigen model on the vector units (pml_kernels_eigen_joint.h): the tips, then the levels
-        PML_TRY(launch_eigen_joint_tips(ctx));
-        const pml_ctx::EigenTiers& E = ctx->eig_tiers;
-        // (tiers only while their levels are thin for the whole batch: with many columns a level fills the chip)
-        if (E.ok && (long long)E.widest * ctx->C <= 16384) {
-            for (int l = 0; l < E.first_level; ++l) {
-                const int a = ctx->forest.bu_offsets[l], b = ctx->forest.bu_offsets[l + 1];
-                PML_TRY(launch_eigen_joint(ctx, ctx->d_bu_units + a, nullptr, 0, b - a));
+            case OP_BT_NARROW:
+                hipLaunchKernelGGL(joint_backtrace_narrow_kernel, dim3(1, ctx->C), dim3(PML_BLOCK), 0, ctx->stream,
+                                   tree_of(ctx), cols_of(ctx), state_of(ctx), ctx->d_td_offsets, r.first, r.count);
+                HIP_TRY(hipGetLastError());
+                break;
+            case OP_BT_TIER: {
+                const pml_ctx::BacktraceTiers::Tier& T = B.tiers[r.first];
+                hipLaunchKernelGGL(joint_backtrace_blocks_kernel, dim3(T.n_blocks, ctx->C), dim3(PML_BLOCK), 0, ctx->stream,
+                                   tree_of(ctx), cols_of(ctx), state_of(ctx), B.d_nodes, B.d_lv, B.d_start + T.first_block,
+                                   T.depth);
+                HIP_TRY(hipGetLastError());
+                break;
             }
-            for (const pml_ctx::EigenTiers::Tier& T : E.tiers)
-                PML_TRY(launch_eigen_joint(ctx, E.d_units, E.d_lv, 0, T.depth, E.d_start + T.first_block, T.n_blocks));
-            // what is left above the tiers: levels of a launch each while they are wide (a forest of many trees), then
-            // the narrow end in one launch
-            int l = E.top_level;
-            long long extra = 0;
-            for (; l < ctx->n_bu_levels && ctx->forest.bu_offsets[l + 1] - ctx->forest.bu_offsets[l] > 48; ++l, ++extra) {
-                const int a = ctx->forest.bu_offsets[l], b = ctx->forest.bu_offsets[l + 1];
-                PML_TRY(launch_eigen_joint(ctx, ctx->d_bu_units + a, nullptr, 0, b - a));
+            case OP_BT_LEVEL: {
+                dim3 grid(grid_for(ctx, r.count, PML_BLOCK, ctx->C), ctx->C);
+                hipLaunchKernelGGL(joint_backtrace_kernel, grid, dim3(PML_BLOCK), 0, ctx->stream, tree_of(ctx), cols_of(ctx),
+                                   state_of(ctx), r.first, r.first + r.count);
+                HIP_TRY(hipGetLastError());
+                break;
             }
-            PML_TRY(launch_eigen_joint(ctx, ctx->d_bu_units, ctx->d_bu_offsets, l, ctx->n_bu_levels - l));
-            PML_TRY(prof_end(ctx, 0, E.first_level + 2 + extra + (long long)E.tiers.size()));
-        } else {
-        const int tail = narrow_levels(ctx, ctx->forest.bu_offsets, ctx->n_bu_levels, false, ctx->C,
-                                       PML_WAVES_PER_BLOCK * (64 / ctx->k));
-        for (int l = 0; l < ctx->n_bu_levels - tail; ++l) {
-            const int a = ctx->forest.bu_offsets[l], b = ctx->forest.bu_offsets[l + 1];
-            PML_TRY(launch_eigen_joint(ctx, ctx->d_bu_units + a, nullptr, 0, b - a));
+            default:
+                return fail(PML_ERR_INVALID, "unknown launch op %d", r.op);
         }
-        PML_TRY(launch_eigen_joint(ctx, ctx->d_bu_units, ctx->d_bu_offsets, ctx->n_bu_levels - tail, tail));
-        PML_TRY(prof_end(ctx, 0, ctx->n_bu_levels + 1 - tail + (tail > 0 ? 1 : 0)));
-        }
-    } else if (gemm) {
-        // marginal sweep: P(t) is never formed, msg = A (e o (A^-1 v)) as two small GEMMs per 16 nodes
-        PML_TRY(launch_eigen_gemm(ctx, PML_EIGG_TIPS, ctx->d_tips, 0, ctx->n_tips));
-        const pml_ctx::EigenTiers& E = ctx->eig_tiers;
-        const bool gemm_tiers = !ctx->tune.on(T_NO_EIGG_TIERS);
-        if (gemm_tiers && E.ok && (long long)E.widest * ctx->C <= 16384) {
-            // thin levels in tiers of subtree blocks, as in the joint sweep (pml_ctx::EigenTiers)
-            for (int l = 0; l < E.first_level; ++l) {
-                const int a = ctx->forest.bu_offsets[l], b = ctx->forest.bu_offsets[l + 1];
-                PML_TRY(launch_eigen_gemm(ctx, PML_EIGG_BU, ctx->d_bu_order + a, 0, b - a));
-            }
-            for (const pml_ctx::EigenTiers::Tier& T : E.tiers)
-                PML_TRY(launch_eigen_gemm_narrow(ctx, PML_EIGG_BU, E.d_nodes, E.d_lv, 0, T.depth, E.d_start + T.first_block,
-                                                 T.n_blocks));
-            int l = E.top_level;
-            long long extra = 0;
-            for (; l < ctx->n_bu_levels && ctx->forest.bu_offsets[l + 1] - ctx->forest.bu_offsets[l] > 2 * PML_WAVES_PER_BLOCK * 16; ++l, ++extra) {
-                const int a = ctx->forest.bu_offsets[l], b = ctx->forest.bu_offsets[l + 1];
-                PML_TRY(launch_eigen_gemm(ctx, PML_EIGG_BU, ctx->d_bu_order + a, 0, b - a));
-            }
-            PML_TRY(launch_eigen_gemm_narrow(ctx, PML_EIGG_BU, ctx->d_bu_order, ctx->d_bu_offsets, l, ctx->n_bu_levels - l));
-            PML_TRY(prof_end(ctx, 0, E.first_level + 2 + extra + (long long)E.tiers.size()));
-        } else {
-        // levels one workgroup finishes in a pass or two per wave (4 waves x 16 nodes) share one launch
-        const int tail = narrow_levels(ctx, ctx->forest.bu_offsets, ctx->n_bu_levels, false, ctx->C, 2 * PML_WAVES_PER_BLOCK * 16);
-        for (int l = 0; l < ctx->n_bu_levels - tail; ++l) {
-            const int a = ctx->forest.bu_offsets[l], b = ctx->forest.bu_offsets[l + 1];
-            PML_TRY(launch_eigen_gemm(ctx, PML_EIGG_BU, ctx->d_bu_order + a, 0, b - a));
-        }
-        PML_TRY(launch_eigen_gemm_narrow(ctx, PML_EIGG_BU, ctx->d_bu_order, ctx->d_bu_offsets, ctx->n_bu_levels - tail, tail));
-        PML_TRY(prof_end(ctx, 0, ctx->n_bu_levels + 1 - tail + (tail > 0 ? 1 : 0)));
-        }
-    } else if (eig) {
-        // every node once, in the launch of its level: the tips first, then the internal nodes by height
-        const int mode = is_marginal ? PML_EIG_BU_MARG : PML_EIG_BU_JOINT;
-        PML_TRY(launch_eigen_tips(ctx, is_marginal ? 0 : 1));
-        {
-        const int eig_nb = ((ctx->k + 3) / 4) % 4 == 0 ? 1 : (((ctx->k + 3) / 4) % 2 == 0 ? 2 : 4);  // EigShape::NB
-        const int tail = narrow_levels(ctx, ctx->forest.bu_offsets, ctx->n_bu_levels, false, ctx->C, PML_WAVES_PER_BLOCK * eig_nb);
-        for (int l = 0; l < ctx->n_bu_levels - tail; ++l) {
-            const int a = ctx->forest.bu_offsets[l], b = ctx->forest.bu_offsets[l + 1];
-            PML_TRY(launch_eigen_fused(ctx, mode, ctx->d_bu_order + a, 0, b - a, 0));
-        }
-        PML_TRY(launch_eigen_narrow(ctx, mode, ctx->d_bu_order, ctx->d_bu_offsets, ctx->n_bu_levels - tail, tail));
-        PML_TRY(prof_end(ctx, 0, ctx->n_bu_levels + 1 - tail + (tail > 0 ? 1 : 0)));
-        }
-    } else {
-        for (int l = 0; l < ctx->n_bu_levels; ++l) {
-            const int a = ctx->forest.bu_offsets[l], b = ctx->forest.bu_offsets[l + 1];
-            const SweepKind sk = is_marginal ? SW_BU_MARG : (ctx->kind == PML_MODEL_F81 && !ctx->bu_level_vec[l]
-                                                                     ? SW_BU_JOINT_NOVEC : SW_BU_JOINT);
-            PML_TRY(dispatch_sweep(ctx, sk, ctx->d_bu_order + a, b - a));
-        }
-        PML_TRY(prof_end(ctx, 0, ctx->n_bu_levels));
     }
-    if (!loglik_done) {
-        hipLaunchKernelGGL(loglik_kernel, dim3((ctx->C + PML_BLOCK - 1) / PML_BLOCK), dim3(PML_BLOCK), 0, ctx->stream,
-                           tree_of(ctx), cols_of(ctx), state_of(ctx), ctx->C, is_marginal ? 1 : 0, ctx->h_loglik,
-                           ctx->h_err);
-        HIP_TRY(hipGetLastError());
-    }
-    ctx->bu_fused_joint = joint_fused;
-    return PML_OK;  // ln L and the error words are written straight into pinned host memory by the last kernel
+    if (open != PML_NO_BRACKET) PML_TRY(prof_end(ctx, open, launches));
+    return PML_OK;
+}
+
+// Everything a bottom-up sweep puts on the stream, without host synchronisation (so that it can be captured), as
+// pml_plan_bottom_up lists it.  signals: its last launch raises the completion word.
+static int enqueue_bottom_up(pml_ctx* ctx, int is_marginal, bool force_prep, bool* signals) {
+    PML_TRY(params_push(ctx));  // what the last model update left in the pinned mirror (part of the graph when captured)
+    const std::vector<PmlLaunch> plan = pml_plan_bottom_up(ctx->forest, schedules_of(ctx), sweep_traits(ctx), is_marginal != 0);
+    int n_signals = 0;
+    PML_TRY(run_plan(ctx, plan, true, is_marginal, force_prep, &n_signals));
+    ctx->signals_enqueued += n_signals;
+    *signals = n_signals > 0;
+    ctx->bu_fused_joint = plan.front().branch == BU_FUSED_JOINT;
+    return PML_OK;
 }
 
 // Captures fn's stream work once and replays it afterwards; falls back to direct submission if capture fails.
@@ -1339,6 +1284,22 @@ static void set_active_columns(pml_ctx* ctx, const uint8_t* active) {
     if (changed) ctx->params_dirty = true;
 }
 
+// the sweep never reads the batch of P(t): the fused eigen sweeps build it in registers, the two-GEMM sweeps never form it
+static bool sweep_without_p(const pml_ctx* ctx, int is_marginal) {
+    return eigen_fused(ctx) || (is_marginal && eigen_gemm(ctx)) || (!is_marginal && eigen_joint_valu(ctx)) || hky_fused(ctx);
+}
+
+// what a bottom-up sweep leaves behind (a replayed pml_marginal_pass runs no submit_bottom_up)
+static void note_bottom_up(pml_ctx* ctx, int is_marginal) {
+    const bool f81_marginal = is_marginal && ctx->kind == PML_MODEL_F81;
+    ctx->js_valid = false;
+    if (!sweep_without_p(ctx, is_marginal)) ctx->prep_dirty = false;   // (else no batch ran)
+    ctx->bu_fused = (f81_marginal && ctx->n_cherries > 0) || ctx->bu_fused_joint;
+    // (a sweep of some of the columns says nothing about the others: where an earlier sweep of the level schedule left the
+    // children of their two-level units out of memory they still are -- rebuilding rows that are in memory is harmless)
+    ctx->bu_absorbed = (f81_marginal && super_sweeps(ctx)) || (ctx->active_partial && ctx->bu_absorbed);
+}
+
 static int submit_bottom_up(pml_ctx* ctx, int is_marginal, const uint8_t* active = nullptr) {
     set_active_columns(ctx, active);
     if (ctx->wait_signal) {  // a sweep was submitted and never collected: the generation below must be read on an idle stream
@@ -1366,8 +1327,6 @@ static int submit_bottom_up(pml_ctx* ctx, int is_marginal, const uint8_t* active
         PML_TRY(dev_alloc(ctx, &ctx->d_J, CN * ctx->ks * (ctx->k > 256 ? 2 : 1)));
         PML_TRY(dev_alloc(ctx, &ctx->d_js, CN));
     }
-    const bool no_p = eigen_fused(ctx) || (is_marginal && eigen_gemm(ctx)) || (!is_marginal && eigen_joint_valu(ctx)) ||
-                      hky_fused(ctx);
     if (eigen_fused(ctx) || eigen_gemm(ctx) || eigen_joint_valu(ctx)) {
         if (!ctx->d_msg) PML_TRY(dev_alloc(ctx, &ctx->d_msg, CN * ctx->ks));
     }
@@ -1375,7 +1334,7 @@ static int submit_bottom_up(pml_ctx* ctx, int is_marginal, const uint8_t* active
         PML_TRY(dev_alloc(ctx, &ctx->d_tip_rest, (size_t)ctx->C * std::max(1, ctx->n_tips)));
         PML_TRY(dev_alloc(ctx, &ctx->d_tip_rest_count, (size_t)ctx->C));
     }
-    if (!no_p) PML_TRY(ensure_transition_storage(ctx));
+    if (!sweep_without_p(ctx, is_marginal)) PML_TRY(ensure_transition_storage(ctx));
     ctx->bu_mode = -1;
     ctx->td_valid = ctx->js_valid = false;
     // mid-size forests: the level launches are latency-bound, replay them as one hipGraph
@@ -1387,23 +1346,17 @@ static int submit_bottom_up(pml_ctx* ctx, int is_marginal, const uint8_t* active
         pml_ctx::GraphSlot& graph = few ? ctx->bu_graph_few : ctx->bu_graph[slot];
         bool& signals = few ? ctx->bu_signals_few : ctx->bu_signals[slot];
         const bool replay = graph.exec != nullptr;
-        PML_TRY(run_captured(ctx, graph, [&]() { return enqueue_bottom_up(ctx, is_marginal, small_path, true); }));
-        if (!replay) signals = ctx->enqueue_signals;  // (a replay runs what was captured)
+        bool enqueued = false;
+        PML_TRY(run_captured(ctx, graph, [&]() { return enqueue_bottom_up(ctx, is_marginal, true, &enqueued); }));
+        if (!replay) signals = enqueued;  // (a replay runs what was captured)
         ctx->wait_signal = signals;
     } else {
         // (inside the capture of a whole marginal pass the per-branch pass must be part of the graph)
-        PML_TRY(enqueue_bottom_up(ctx, is_marginal, small_path, ctx->in_outer_capture));
-        ctx->wait_signal = ctx->enqueue_signals;
+        PML_TRY(enqueue_bottom_up(ctx, is_marginal, ctx->in_outer_capture, &ctx->wait_signal));
     }
     ctx->done_expect = generation_before + 1;
     if (ctx->in_outer_capture || ctx->tune.on(T_NO_SPIN_WAIT)) ctx->wait_signal = false;
-    // the fused eigen sweeps build P(t) in registers, the two-GEMM sweeps never form it: no batch ran
-    if (!no_p) ctx->prep_dirty = false;
-    ctx->bu_fused = (is_marginal && ctx->kind == PML_MODEL_F81 && ctx->n_cherries > 0) || ctx->bu_fused_joint;
-    // (a sweep of some of the columns says nothing about the others: where an earlier sweep of the level schedule left the
-    // children of their two-level units out of memory they still are -- rebuilding rows that are in memory is harmless)
-    ctx->bu_absorbed = (is_marginal && ctx->kind == PML_MODEL_F81 && !small_path && super_sweeps(ctx)) ||
-                       (ctx->active_partial && ctx->bu_absorbed);
+    note_bottom_up(ctx, is_marginal);
     return PML_OK;
 }
 
@@ -1480,8 +1433,18 @@ int pml_bottom_up_collect(pml_ctx* ctx, int is_marginal, double* loglik_out, int
     return collect_bottom_up(ctx, is_marginal, loglik_out, err_parent, err_child);
 }
 
-// the top-down launches (shared by pml_top_down_marginals and the lazy TD materialisation of pml_download)
-static int run_top_down(pml_ctx* ctx) {
+// what a top-down sweep leaves behind (a replayed pml_marginal_pass runs no run_top_down)
+static void note_top_down(pml_ctx* ctx) {
+    ctx->td_valid = true;
+    ctx->td_vec_valid = ctx->kind != PML_MODEL_F81 || ctx->keep_td;
+    ctx->td_filled = false;
+    ctx->post_ever = true;
+    ctx->tip_post_missing = state_of(ctx).implicit_tips;
+}
+
+// the top-down launches (shared by pml_top_down_marginals and the lazy TD materialisation of pml_download), as
+// pml_plan_top_down lists them; wants_signal: the caller waits on the completion word of the last launch
+static int run_top_down(pml_ctx* ctx, bool wants_signal = false) {
     const size_t CN = (size_t)ctx->C * ctx->N;
     const bool td_stored = ctx->kind != PML_MODEL_F81 || ctx->keep_td;
     if (td_stored && !ctx->d_td) {
@@ -1494,151 +1457,12 @@ static int run_top_down(pml_ctx* ctx) {
         PML_TRY(dev_alloc(ctx, &ctx->d_lhe, CN));
     }
     const bool td_small = single_launch_sweeps(ctx) && ctx->kind == PML_MODEL_F81;
-    const bool td_fused = ctx->kind == PML_MODEL_F81;
-    auto enqueue = [&]() -> int {
-        if (td_fused && !td_small && block_schedule(ctx)) {
-            // block schedule: the top part (roots, its narrow end in one launch, its wide levels one launch each),
-            // then all subtree blocks in one launch
-            const pml_ctx::BlockSchedule& B = ctx->blocks;
-            const int head = ctx->n_roots <= 64 ? narrow_levels(ctx, B.top_td_offsets, ctx->n_td_levels, true, ctx->C) : 0;
-            if (head == 0) PML_TRY(dispatch_sweep(ctx, SW_ROOTS, nullptr, ctx->n_roots));
-            if (head > 0) PML_TRY(dispatch_small_f81(ctx, false, 0, 0, head, B.d_top_td_units, B.d_top_td_offsets));
-            PML_TRY(prof_begin(ctx));
-            long long n_launch = 0;
-            for (int l = head; l < ctx->n_td_levels; ++l) {
-                const int a = B.top_td_offsets[l], b = B.top_td_offsets[l + 1];
-                if (b <= a) continue;
-                ctx->units_override = B.d_top_td_units + a;
-                const int status = dispatch_sweep(ctx, SW_TD_FUSED, ctx->d_td_parents_f, b - a);
-                ctx->units_override = nullptr;
-                PML_TRY(status);
-                ++n_launch;
-            }
-            ctx->signal_next_td = ctx->mp_wants_signal;  // (the last launch of the pass)
-            PML_TRY(dispatch_blocks_f81(ctx, false));
-            PML_TRY(prof_end(ctx, 1, n_launch + 1));
-            return PML_OK;
-        }
-        if (td_fused && !td_small && super_sweeps(ctx)) {
-            // the levels of the rest lists, then every two-level unit in one launch (it needs its node's row only, and
-            // that comes from a unit of the rest lists or from the roots)
-            const pml_ctx::SuperSchedule& U = ctx->sup;
-            int head = ctx->n_roots <= 64 ? narrow_levels(ctx, U.td_offsets_r, ctx->n_td_levels, true, ctx->C) : 0;
-            // (... and the single launch below the roots ends above the first depth with stacked nodes)
-            for (int l = 0; l < ctx->n_td_levels && U.n_stack > 0; ++l)
-                if (U.stack_td_offsets[l + 1] > U.stack_td_offsets[l]) {
-                    head = std::min(head, l);
-                    break;
-                }
-            if (head < 2) head = 0;
-            if (head == 0) PML_TRY(dispatch_sweep(ctx, SW_ROOTS, nullptr, ctx->n_roots));
-            if (head > 0) PML_TRY(dispatch_small_f81(ctx, false, 0, 0, head, U.d_td_units_r, U.d_td_offsets_r));
-            PML_TRY(prof_begin(ctx));
-            long long n_launch = 0;
-            for (int l = head; l < ctx->n_td_levels; ++l) {
-                const int a = U.td_offsets_r[l], b = U.td_offsets_r[l + 1];
-                if (b > a) {
-                    ctx->units_override = (ctx->level_lists_sorted && U.d_td_units_rs ? U.d_td_units_rs : U.d_td_units_r) + a;
-                    const int status = dispatch_sweep(ctx, SW_TD_FUSED, ctx->d_td_parents_f, b - a);
-                    ctx->units_override = nullptr;
-                    PML_TRY(status);
-                    ++n_launch;
-                }
-                // the children of the stacked nodes of this depth (their rows come from the depth above)
-                if (U.n_stack > 0 && U.stack_td_offsets[l + 1] > U.stack_td_offsets[l]) {
-                    PML_TRY(dispatch_stack_f81(ctx, false, l));
-                    ++n_launch;
-                }
-            }
-            PML_TRY(prof_end(ctx, 1, n_launch));
-            PML_TRY(prof_begin(ctx));
-            PML_TRY(dispatch_super_f81(ctx, false));
-            PML_TRY(prof_end(ctx, 3, U.n > 0 ? 1 : 0));
-            return PML_OK;
-        }
-        // F81 family: the roots and the levels right below them in one launch
-        const int head = (td_fused && !td_small && ctx->n_roots <= 64)
-                             ? narrow_levels(ctx, ctx->forest.td_parent_offsets_f, ctx->n_td_levels, true, ctx->C) : 0;
-        if (!td_small && head == 0) PML_TRY(dispatch_sweep(ctx, SW_ROOTS, nullptr, ctx->n_roots));
-        if (head > 0) PML_TRY(dispatch_small_f81(ctx, false, 0, 0, head));
-        PML_TRY(prof_begin(ctx));  // the profile brackets the level kernel's launches only
-        long long n_launch = 0;
-        if (td_small) {
-            ctx->signal_next_td = ctx->mp_wants_signal;  // (the last launch of the pass)
-            PML_TRY(dispatch_small_f81(ctx, false, 0));
-            n_launch = 1;
-        }
-        if (eigen_gemm(ctx)) {
-            int head = 0;
-            {
-                std::vector<int> off(ctx->forest.td_offsets.begin() + 1, ctx->forest.td_offsets.end());
-                head = narrow_levels(ctx, off, ctx->n_td_levels - 1, true, ctx->C, 2 * PML_WAVES_PER_BLOCK * 16);
-            }
-            if (head > 0) {
-                PML_TRY(launch_eigen_gemm_narrow(ctx, PML_EIGG_TD, nullptr, ctx->d_td_offsets, 1, head));
-                ++n_launch;
-            }
-            for (int d = 1 + head; d < ctx->n_td_levels; ++d) {
-                const int a = ctx->forest.td_offsets[d], b = ctx->forest.td_offsets[d + 1];
-                PML_TRY(launch_eigen_gemm(ctx, PML_EIGG_TD, nullptr, a, b - a));
-                if (b > a) ++n_launch;
-            }
-            PML_TRY(prof_end(ctx, 1, n_launch));
-            return PML_OK;
-        }
-        if (eigen_fused(ctx)) {
-            // child-centric: the nodes of a depth are a contiguous id range (roots are depth 0, done above)
-            // td_offsets[d] .. td_offsets[d + 1] = the nodes of depth d: the run of narrow depths below the roots
-            int head = 0;
-            {
-                std::vector<int> off(ctx->forest.td_offsets.begin() + 1, ctx->forest.td_offsets.end());
-                const int ks4 = (ctx->k + 3) / 4;
-                const int eig_nb = ks4 % 4 == 0 ? 1 : (ks4 % 2 == 0 ? 2 : 4);  // EigShape::NB
-                head = narrow_levels(ctx, off, ctx->n_td_levels - 1, true, ctx->C, PML_WAVES_PER_BLOCK * eig_nb);
-            }
-            if (head > 0) {
-                PML_TRY(launch_eigen_narrow(ctx, PML_EIG_TD, nullptr, ctx->d_td_offsets, 1, head));
-                ++n_launch;
-            }
-            for (int d = 1 + head; d < ctx->n_td_levels; ++d) {
-                const int a = ctx->forest.td_offsets[d], b = ctx->forest.td_offsets[d + 1];
-                PML_TRY(launch_eigen_fused(ctx, PML_EIG_TD, nullptr, a, b - a, 0));
-                if (b > a) ++n_launch;
-            }
-            PML_TRY(prof_end(ctx, 1, n_launch));
-            return PML_OK;
-        }
-        // F81 family: the thin depths at the DEEP end of a ragged forest (a handful of parents each) in one launch as well
-        // -- a launch of their own costs 9 - 11 us each, a level step of the walk 2 - 3 (round 5)
-        int tail = 0;
-        // (units of fewer than 8 lanes only: at k = 64 a level step inside the walk costs what the launch does)
-        // ... and when many of the deep depths are thin, all of them: the subtrees hanging at the first one, a workgroup per
-        // (bin of subtrees, column) walking its depths (pml_tree_upload, "thin ends")
-        const bool deep = td_fused && !td_small && deep_top_down(ctx) && ctx->deep.first_depth > head;
-        if (deep) {
-            for (int l = head; l < ctx->deep.first_depth; ++l) {
-                const int a = ctx->forest.td_parent_offsets_f[l], b = ctx->forest.td_parent_offsets_f[l + 1];
-                PML_TRY(dispatch_sweep(ctx, SW_TD_FUSED, ctx->d_td_parents_f + a, b - a));
-                if (b > a) ++n_launch;
-            }
-            PML_TRY(dispatch_blocks_f81(ctx, false, 1));
-            PML_TRY(prof_end(ctx, 1, n_launch + 1));
-            return PML_OK;
-        }
-        if (td_fused && !td_small && ctx->Gt < 8 && !ctx->tune.on(T_NO_TD_TAIL)) {
-            tail = narrow_levels(ctx, ctx->forest.td_parent_offsets_f, ctx->n_td_levels, false, ctx->C, 0, 1);
-            if (tail > ctx->n_td_levels - head) tail = ctx->n_td_levels - head;
-            if (tail < 2) tail = 0;
-        }
-        for (int l = head; l < (td_small ? 0 : ctx->n_td_levels - tail); ++l) {
-            const std::vector<int>& off = td_fused ? ctx->forest.td_parent_offsets_f : ctx->forest.td_parent_offsets;
-            const int a = off[l], b = off[l + 1];
-            PML_TRY(dispatch_sweep(ctx, td_fused ? SW_TD_FUSED : SW_TD,
-                                   (td_fused ? ctx->d_td_parents_f : ctx->d_td_parents) + a, b - a));
-            if (b > a) ++n_launch;
-        }
-        PML_TRY(prof_end(ctx, 1, n_launch));
-        if (tail > 0) PML_TRY(dispatch_small_f81(ctx, false, 0, ctx->n_td_levels - tail, tail, nullptr, nullptr, 1));
+    auto enqueue = [&]() -> int {   // (a replayed graph plans nothing)
+        const std::vector<PmlLaunch> plan = pml_plan_top_down(ctx->forest, schedules_of(ctx), sweep_traits(ctx), wants_signal);
+        int n_signals = 0;
+        PML_TRY(run_plan(ctx, plan, false, 1, false, &n_signals));
+        ctx->signals_enqueued += n_signals;
+        ctx->td_final_signals = n_signals > 0;
         return PML_OK;
     };
     if (ctx->graphs && !ctx->profile && !td_small && ctx->n_td_levels >= 4) {
@@ -1646,11 +1470,7 @@ static int run_top_down(pml_ctx* ctx) {
     } else {
         PML_TRY(enqueue());
     }
-    ctx->td_valid = true;
-    ctx->td_vec_valid = td_stored;
-    ctx->td_filled = false;
-    ctx->post_ever = true;
-    ctx->tip_post_missing = state_of(ctx).implicit_tips;
+    note_top_down(ctx);
     return PML_OK;
 }
 
@@ -1770,13 +1590,11 @@ int pml_marginal_pass(pml_ctx* ctx, double* loglik_out, int32_t* err_parent, int
             ctx->td_final_signals = false;
             PML_TRY(run_captured(ctx, ctx->mp_graph, [&]() {
                 ctx->in_outer_capture = true;
-                ctx->mp_wants_signal = true;
                 int status = submit_bottom_up(ctx, 1);
                 if (status == PML_OK) {
                     ctx->bu_mode = 1;
-                    status = run_top_down(ctx);
+                    status = run_top_down(ctx, true);
                 }
-                ctx->mp_wants_signal = false;
                 ctx->in_outer_capture = false;
                 return status;
             }));
@@ -1786,16 +1604,9 @@ int pml_marginal_pass(pml_ctx* ctx, double* loglik_out, int32_t* err_parent, int
         n_signals = ctx->mp_signals;
         final_signals = ctx->mp_final;
         // the bookkeeping of submit_bottom_up / run_top_down (a replay runs neither)
-        ctx->js_valid = false;
-        ctx->prep_dirty = false;
-        ctx->bu_fused = ctx->n_cherries > 0;
         ctx->bu_fused_joint = false;
-        ctx->bu_absorbed = super_sweeps(ctx);
-        ctx->td_valid = true;
-        ctx->td_vec_valid = ctx->keep_td;
-        ctx->td_filled = false;
-        ctx->post_ever = true;
-        ctx->tip_post_missing = state_of(ctx).implicit_tips;
+        note_bottom_up(ctx, 1);
+        note_top_down(ctx);
     } else {
         PML_TRY(submit_bottom_up(ctx, 1));
         n_signals = ctx->wait_signal ? 1 : 0;  // (its last launch signals)
@@ -1803,10 +1614,7 @@ int pml_marginal_pass(pml_ctx* ctx, double* loglik_out, int32_t* err_parent, int
         ctx->bu_mode = 1;  // provisional, for run_top_down's bookkeeping; collect_bottom_up has the last word
         ctx->signals_enqueued = 0;
         ctx->td_final_signals = false;
-        ctx->mp_wants_signal = td_small;  // (the single launch is enqueued afresh every time; level sweeps may replay a graph)
-        const int td_status = run_top_down(ctx);
-        ctx->mp_wants_signal = false;
-        PML_TRY(td_status);
+        PML_TRY(run_top_down(ctx, td_small));  // (the single launch is enqueued afresh every time; level sweeps may replay a graph)
         n_signals += ctx->signals_enqueued;
         final_signals = ctx->td_final_signals;
     }
@@ -1844,46 +1652,11 @@ int pml_marginal_pass(pml_ctx* ctx, double* loglik_out, int32_t* err_parent, int
     return fetched;
 }
 
-// the back-trace launches (no host synchronisation): the narrow depths below the roots in one launch, the wide ones one
-// launch each
+// the back-trace launches (no host synchronisation), as pml_plan_backtrace lists them
 static int submit_joint_backtrace(pml_ctx* ctx) {
-    int head = 0;
-    {
-        std::vector<int> off(ctx->forest.td_offsets.begin() + 1, ctx->forest.td_offsets.end());
-        head = narrow_levels(ctx, off, ctx->n_td_levels - 1, true, ctx->C, 1024);
-    }
-    const pml_ctx::BacktraceTiers& B = ctx->bt_tiers;
-    // (tiers while one column's narrow end is the limit they were cut for: with many columns the narrow end is shorter
-    // and the depths in between keep their launches)
-    bool tiers = B.ok && 1 + head >= B.first_depth;
-    for (const pml_ctx::BacktraceTiers::Tier& T : B.tiers)
-        tiers = tiers && (long long)T.n_blocks * ctx->C <= 8192;  // (a workgroup per subtree and column: only while few)
-    auto enqueue = [&]() -> int {
-        if (head > 0) {
-            hipLaunchKernelGGL(joint_backtrace_narrow_kernel, dim3(1, ctx->C), dim3(PML_BLOCK), 0, ctx->stream,
-                               tree_of(ctx), cols_of(ctx), state_of(ctx), ctx->d_td_offsets, 1,
-                               tiers ? B.first_depth - 1 : head);
-            HIP_TRY(hipGetLastError());
-        }
-        if (tiers) {
-            for (const pml_ctx::BacktraceTiers::Tier& T : B.tiers) {
-                hipLaunchKernelGGL(joint_backtrace_blocks_kernel, dim3(T.n_blocks, ctx->C), dim3(PML_BLOCK), 0, ctx->stream,
-                                   tree_of(ctx), cols_of(ctx), state_of(ctx), B.d_nodes, B.d_lv, B.d_start + T.first_block,
-                                   T.depth);
-                HIP_TRY(hipGetLastError());
-            }
-            return PML_OK;
-        }
-        for (int l = 1 + head; l < ctx->n_td_levels; ++l) {
-            const int a = ctx->forest.td_offsets[l], b = ctx->forest.td_offsets[l + 1];
-            if (b <= a) continue;
-            dim3 grid(grid_for(ctx, b - a, PML_BLOCK, ctx->C), ctx->C);
-            hipLaunchKernelGGL(joint_backtrace_kernel, grid, dim3(PML_BLOCK), 0, ctx->stream, tree_of(ctx), cols_of(ctx),
-                               state_of(ctx), a, b);
-            HIP_TRY(hipGetLastError());
-        }
-        return PML_OK;
-    };
+    int head = 0, n_signals = 0;
+    const std::vector<PmlLaunch> plan = pml_plan_backtrace(ctx->forest, schedules_of(ctx), sweep_traits(ctx), &head);
+    auto enqueue = [&]() -> int { return run_plan(ctx, plan, false, 0, false, &n_signals); };
     if (ctx->graphs && !ctx->profile && ctx->n_td_levels - head >= 4) {
         PML_TRY(run_captured(ctx, ctx->bt_graph, enqueue));
     } else {
@@ -2173,24 +1946,16 @@ static int fetch_exponents(pml_ctx* ctx, const i64* src, int col, double* out) {
 static int materialize_cherries(pml_ctx* ctx) {
     if (ctx->bu_absorbed) {
         // the children of the two-level units: their own units (two cherries of two tips), from the tips
-        ctx->units_override = ctx->sup.d_child_units;
-        const int status = dispatch_sweep(ctx, SW_BU_MARG_FUSED_NOVEC, ctx->d_bu_order_f, ctx->sup.n_child_units);  // (nothing if 0)
-        ctx->units_override = nullptr;
-        PML_TRY(status);
+        PML_TRY(dispatch_sweep(ctx, SW_BU_MARG_FUSED_NOVEC, L_CHILD_UNITS, 0, ctx->sup.n_child_units));  // (nothing if 0)
         // ... and the children of the stacked units (two stored children each; in chunks of at most 65 536 units: the
         // lane shape, hence the rounding of pi . v, of the levels they were taken from)
-        for (int a = 0; a < 2 * ctx->sup.n_stack; a += 65536) {
-            ctx->units_override = ctx->sup.d_stack_children + a;
-            const int st2 = dispatch_sweep(ctx, SW_BU_MARG_FUSED, ctx->d_bu_order_f, std::min(65536, 2 * ctx->sup.n_stack - a));
-            ctx->units_override = nullptr;
-            PML_TRY(st2);
-        }
+        for (int a = 0; a < 2 * ctx->sup.n_stack; a += 65536)
+            PML_TRY(dispatch_sweep(ctx, SW_BU_MARG_FUSED, L_STACK_CHILDREN, a, std::min(65536, 2 * ctx->sup.n_stack - a)));
         HIP_TRY(hipStreamSynchronize(ctx->stream));
         ctx->bu_absorbed = false;
     }
     if (!ctx->bu_fused) return PML_OK;
-    PML_TRY(dispatch_sweep(ctx, ctx->bu_fused_joint ? SW_BU_CHERRIES_JOINT : SW_BU_CHERRIES, ctx->d_cherries,
-                           ctx->n_cherries));
+    PML_TRY(dispatch_sweep(ctx, ctx->bu_fused_joint ? SW_BU_CHERRIES_JOINT : SW_BU_CHERRIES, L_CHERRIES, 0, ctx->n_cherries));
     HIP_TRY(hipStreamSynchronize(ctx->stream));
     ctx->bu_fused = false;
     return PML_OK;

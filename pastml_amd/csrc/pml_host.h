@@ -130,7 +130,6 @@ struct pml_ctx {
     double *d_pi = nullptr, *d_mu = nullptr, *d_kappa = nullptr, *d_d = nullptr, *d_A = nullptr, *d_Ainv = nullptr;
     double* d_active = nullptr;   // last array of the parameter block: 0.0 = the column sits the next bottom-up sweep out
     bool active_partial = false;  // ... some column does (pml_bottom_up_submit_columns)
-    bool in_bu_enqueue = false;   // the launches being enqueued are a bottom-up sweep's: they look at the flags
     int n_active = 0;             // columns that take part in the next sweep
     int sched_cols = 0;           // the number of columns the schedule of a sweep is chosen for (C; 32 for a few active ones)
     bool bu_signals_few = false;
@@ -183,13 +182,12 @@ struct pml_ctx {
     u64* h_done = nullptr;      // pinned: generation of the last finished launch
     u64* d_done = nullptr;      // device: [0] columns done in the running launch, [1] generation
     u64 done_expect = 0;        // what *h_done shows when the sweep submitted last has finished
-    bool enqueue_signals = false;          // set by the launcher while a sweep is enqueued
     bool bu_signals[2] = {false, false};   // per captured sweep (joint / marginal): its last launch signals
     bool wait_signal = false;              // the sweep submitted last signals
     // the same for a whole marginal pass: its last top-down launch signals where the schedule ends in a multi-level
     // kernel (single-launch sweeps, subtree blocks); signals_enqueued counts the signalling launches of what is being
-    // enqueued (the bottom-up sweep's and the top-down sweep's), mp_signals / mp_final keep them for the captured pass
-    bool signal_next_td = false, td_final_signals = false, mp_final = false, mp_wants_signal = false;
+    // enqueued (run_plan: the bottom-up sweep's and the top-down sweep's), mp_signals / mp_final keep them for the captured pass
+    bool td_final_signals = false, mp_final = false;
     int signals_enqueued = 0, mp_signals = 0;
     bool td_valid = false, js_valid = false;
     bool keep_td = false;      // PML_OPT_KEEP_TD (or a pml_download of the TD vectors asked for them)
@@ -199,7 +197,8 @@ struct pml_ctx {
     bool eigj_valu_opt = true; // PML_OPT_EIGEN_JOINT_VALU
     bool implicit_tips = false;    // PML_OPT_IMPLICIT_TIP_POSTERIORS
     bool tip_post_missing = false; // the last top-down sweep left the observed tips' posteriors implicit
-    const PmlUnit* units_override = nullptr;  // set around a dispatch_sweep on the block schedule's top lists
+    const PmlUnit* d_unit_lists[L_COUNT] = {};   // the unit lists of the F81 kernels by PmlList (pml_tree_upload)
+    const int* d_list_offsets[L_COUNT] = {};     // ... and the level tables of those that several-level launches walk
 
     // forward simulation (pml_launch_simulate.hip): preorder node lists of the subtrees rooted at depth sim_depth (built on
     // first use for that depth; a new tree resets them)
@@ -377,7 +376,8 @@ static PmlTree tree_of(const pml_ctx* c, bool fused = false) {
     return t;
 }
 
-static PmlCols cols_of(const pml_ctx* c) {
+// bu_sweep: the launch is part of a bottom-up sweep, which looks at the flags of the active columns
+static PmlCols cols_of(const pml_ctx* c, bool bu_sweep = false) {
     PmlCols s;
     s.k = c->k;
     s.ks = c->ks;
@@ -386,7 +386,7 @@ static PmlCols cols_of(const pml_ctx* c) {
     s.masks = c->d_masks;
     s.masks_init = c->has_init ? c->d_masks_init : nullptr;
     s.pi = c->d_pi;
-    s.active = c->in_bu_enqueue ? c->d_active : nullptr;  // (only the sweep itself: downloads rebuild what they need for all)
+    s.active = bu_sweep ? c->d_active : nullptr;  // (only the sweep itself: downloads rebuild what they need for all)
     return s;
 }
 

@@ -19,14 +19,6 @@
     X(64, 2)             \
     X(64, 4)
 
-enum SweepKind {
-    SW_BU_MARG, SW_BU_JOINT, SW_TD, SW_ROOTS, SW_BU_MARG_FUSED, SW_TD_FUSED, SW_BU_CHERRIES,
-    SW_BU_MARG_FUSED_NOVEC,  // a fused level none of whose units has a stored node among its first two children
-    SW_BU_JOINT_NOVEC,       // the same for a level of the joint sweep (the level whose children are all tips)
-    SW_BU_JOINT_FUSED, SW_BU_JOINT_FUSED_NOVEC,  // joint sweep over the cherry-fused level lists
-    SW_BU_CHERRIES_JOINT     // materialises the cherries' vectors after a fused joint sweep
-};
-
 
 #define PML_F81_CASES(X) \
     X(2, 2)              \
@@ -118,15 +110,16 @@ static bool eigen_joint_valu(const pml_ctx* c) {
 // ---- pml_launch_matrix.hip: sweeps of the models with a materialised (or closed-form 4 x 4) P(t), state selection
 PML_INTERNAL int dispatch_sweep_matrix(pml_ctx* ctx, SweepKind what, const int* level, int n_level);
 PML_INTERNAL int dispatch_select(pml_ctx* ctx, int method, int force_joint, const u64* d_lh_mask);
-// ---- pml_launch_f81_level.hip: F81-family level launches
-PML_INTERNAL int dispatch_sweep_f81(pml_ctx* ctx, SweepKind what, const int* level, int n_level);
+// ---- pml_launch_f81_level.hip: F81-family level launches over n_level units.  cherries: the top-down staging hint (some unit
+//      has a cherry among its first two children); bu_sweep: part of a bottom-up sweep, which looks at the active-column flags
+PML_INTERNAL int dispatch_sweep_f81(pml_ctx* ctx, SweepKind what, const PmlUnit* units, int n_level, bool cherries, bool bu_sweep);
 // ---- pml_launch_f81_wide.hip: the same for more than 256 states (64 lanes x 8 states)
-PML_INTERNAL int dispatch_sweep_f81_wide(pml_ctx* ctx, SweepKind what, const int* level, int n_level);
+PML_INTERNAL int dispatch_sweep_f81_wide(pml_ctx* ctx, SweepKind what, const PmlUnit* units, int n_level, bool cherries, bool bu_sweep);
 // ---- pml_launch_f81_small.hip / pml_launch_f81_blocks.hip: several levels in one launch (whole sweeps of small forests and
-//      the narrow ends; subtree blocks and the thin ends)
-PML_INTERNAL int dispatch_small_f81(pml_ctx* ctx, bool bottom_up, int do_prep, int first_level = 0, int n_levels = -1,
+//      the narrow ends; subtree blocks and the thin ends).  signal: the launch raises the completion word
+PML_INTERNAL int dispatch_small_f81(pml_ctx* ctx, bool bottom_up, bool signal, int do_prep, int first_level, int n_levels,
                                     const PmlUnit* units = nullptr, const int* d_offsets = nullptr, int skip_roots = 0);
-PML_INTERNAL int dispatch_blocks_f81(pml_ctx* ctx, bool bottom_up, int which = 0);
+PML_INTERNAL int dispatch_blocks_f81(pml_ctx* ctx, bool bottom_up, int which, bool signal);
 // ---- pml_launch_f81_super.hip: two-level and stacked units
 PML_INTERNAL int dispatch_super_f81(pml_ctx* ctx, bool bottom_up);
 PML_INTERNAL int dispatch_stack_f81(pml_ctx* ctx, bool bottom_up, int level);
@@ -183,7 +176,11 @@ static inline int with_lds(const pml_ctx* ctx, K kernel, size_t bytes) {
     return PML_OK;
 }
 
-static inline int dispatch_sweep(pml_ctx* ctx, SweepKind what, const int* level, int n_level) {
+// a level launch over the entries first .. first + n_level of a list: its unit descriptors (F81 family) or its node ids
+static inline int dispatch_sweep(pml_ctx* ctx, SweepKind what, int list, int first, int n_level, bool cherries = true,
+                                 bool bu_sweep = false) {
     if (n_level <= 0) return PML_OK;
-    return ctx->kind == PML_MODEL_F81 ? dispatch_sweep_f81(ctx, what, level, n_level) : dispatch_sweep_matrix(ctx, what, level, n_level);
+    if (ctx->kind == PML_MODEL_F81) return dispatch_sweep_f81(ctx, what, ctx->d_unit_lists[list] + first, n_level, cherries, bu_sweep);
+    const int* nodes = list == L_BU_PLAIN ? ctx->d_bu_order : (list == L_TD_PLAIN ? ctx->d_td_parents : nullptr);
+    return dispatch_sweep_matrix(ctx, what, nodes ? nodes + first : nullptr, n_level);
 }

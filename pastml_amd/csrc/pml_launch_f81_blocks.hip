@@ -22,9 +22,9 @@ static BlockTables block_tables(const pml_ctx* ctx, bool bottom_up, int which) {
 }
 
 template <int G, int R>
-static void launch_blocks_f81(pml_ctx* ctx, bool bottom_up, int which) {
+static void launch_blocks_f81(pml_ctx* ctx, bool bottom_up, int which, bool signal) {
     const PmlTree t = tree_of(ctx, true);
-    const PmlCols c = cols_of(ctx);
+    const PmlCols c = cols_of(ctx, bottom_up);
     const PmlState st = state_of(ctx);
     const BlockTables B = block_tables(ctx, bottom_up, which);
     // Workgroup size: 512 threads while every (block, column) workgroup is resident at once; with more workgroups than
@@ -52,23 +52,18 @@ static void launch_blocks_f81(pml_ctx* ctx, bool bottom_up, int which) {
     dim3 grid(B.n_blocks, ctx->C), block(threads);
     if (bottom_up)
         hipLaunchKernelGGL((bu_f81_blocks_kernel<G, R>), grid, block, 0, ctx->stream, t, c, st, B.units, B.start, B.levels, B.lv);
-    else {
-        const bool signal = ctx->signal_next_td && ctx->C <= 64 && !ctx->tune.on(T_NO_SPIN_WAIT);
-        ctx->signal_next_td = false;
+    else
         hipLaunchKernelGGL((td_f81_blocks_kernel<G, R>), grid, block, 0, ctx->stream, t, c, st, B.units, B.start, B.levels,
                            B.lv, signal ? ctx->d_done : nullptr, signal ? ctx->h_done : nullptr);
-        ctx->td_final_signals = signal;
-        if (signal) ++ctx->signals_enqueued;
-    }
 }
 
 
-int dispatch_blocks_f81(pml_ctx* ctx, bool bottom_up, int which) {
+int dispatch_blocks_f81(pml_ctx* ctx, bool bottom_up, int which, bool signal) {
     int g, r;
     multi_level_shape(ctx, bottom_up, g, r);
 #define X(G_, R_)                                           \
     if (g == G_ && r == R_) {                               \
-        launch_blocks_f81<G_, R_>(ctx, bottom_up, which);   \
+        launch_blocks_f81<G_, R_>(ctx, bottom_up, which, signal);   \
         HIP_TRY(hipGetLastError());                         \
         return PML_OK;                                      \
     }

@@ -5,28 +5,16 @@
 
 // F81-family sweeps: chunked state ownership (pml_kernels_f81.h), their own (G, R)
 template <int G, int R>
-static void launch_sweep_f81(pml_ctx* ctx, SweepKind what, const int* level, int n_level) {
+static void launch_sweep_f81(pml_ctx* ctx, SweepKind what, const PmlUnit* units, int n_level, bool cherries, bool bu_sweep) {
     const bool fused_lists = what == SW_BU_MARG_FUSED || what == SW_BU_MARG_FUSED_NOVEC ||
                              what == SW_BU_JOINT_FUSED || what == SW_BU_JOINT_FUSED_NOVEC;
     const PmlTree t = tree_of(ctx, fused_lists || what == SW_TD_FUSED);
-    const PmlCols c = cols_of(ctx);
+    const PmlCols c = cols_of(ctx, bu_sweep);
     const PmlState st = state_of(ctx);
     const int upb = PML_WAVES_PER_BLOCK * (64 / G);
     const bool pipelined = fused_lists || what == SW_BU_MARG || what == SW_BU_CHERRIES || what == SW_BU_JOINT ||
                            what == SW_BU_JOINT_NOVEC || what == SW_BU_CHERRIES_JOINT;
     dim3 grid(grid_for(ctx, n_level, upb, ctx->C, pipelined), ctx->C), block(PML_BLOCK);
-    // the level is given as a position in one of the node lists; the kernels read the descriptor list parallel to it
-    const PmlUnit* units = nullptr;
-    // (level launches of wide units walk the lists sorted by shape, pml_tree_upload)
-    const bool sorted = ctx->level_lists_sorted && ctx->d_bu_units_fs != nullptr;
-    if (fused_lists) units = ctx->d_bu_units_f + (level - ctx->d_bu_order_f);
-    if (sorted && (what == SW_BU_MARG_FUSED || what == SW_BU_MARG_FUSED_NOVEC))
-        units = ctx->d_bu_units_fs + (level - ctx->d_bu_order_f);
-    if (what == SW_BU_MARG || what == SW_BU_JOINT || what == SW_BU_JOINT_NOVEC)
-        units = ctx->d_bu_units + (level - ctx->d_bu_order);
-    if (what == SW_TD_FUSED) units = (sorted ? ctx->d_td_units_fs : ctx->d_td_units_f) + (level - ctx->d_td_parents_f);
-    if (what == SW_BU_CHERRIES || what == SW_BU_CHERRIES_JOINT) units = ctx->d_cherry_units + (level - ctx->d_cherries);
-    if (ctx->units_override != nullptr) units = ctx->units_override;  // a level of the block schedule's top part
     switch (what) {
         case SW_BU_MARG_FUSED:
         case SW_BU_MARG:
@@ -59,11 +47,6 @@ static void launch_sweep_f81(pml_ctx* ctx, SweepKind what, const int* level, int
                 const bool scalars = true;   // (the rows' sums and exponents are staged with them)
                 stage = 3;
                 // bit 2: some unit of the level has a cherry among its first two children (tip slots in use)
-                bool cherries = true;
-                if (ctx->units_override == nullptr && !ctx->td_cherry_prefix.empty()) {
-                    const size_t a = (size_t)(level - ctx->d_td_parents_f), b = a + (size_t)n_level;
-                    if (b < ctx->td_cherry_prefix.size()) cherries = ctx->td_cherry_prefix[b] != ctx->td_cherry_prefix[a];
-                }
                 if (cherries) stage |= 4;
                 lds = (size_t)PML_WAVES_PER_BLOCK * td_stage_doubles(64 / G, c.ks, scalars) * sizeof(double);
             }

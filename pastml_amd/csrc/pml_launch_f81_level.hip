@@ -1,7 +1,7 @@
 // Launchers of the F81-family level kernels (one launch per fused height / depth).
 #include "pml_launch_f81_level.h"
 
-int dispatch_sweep_f81(pml_ctx* ctx, SweepKind what, const int* level, int n_level) {
+int dispatch_sweep_f81(pml_ctx* ctx, SweepKind what, const PmlUnit* units, int n_level, bool cherries, bool bu_sweep) {
     if (n_level <= 0) return PML_OK;
     if (what == SW_TD) return fail(PML_ERR_INVALID, "the F81 kernels walk descriptor lists: SW_TD has none");
     const bool td = what == SW_TD_FUSED || what == SW_ROOTS;
@@ -18,12 +18,12 @@ int dispatch_sweep_f81(pml_ctx* ctx, SweepKind what, const int* level, int n_lev
     }
 #define X(G_, R_)                                                \
 if (g == G_ && r == R_) {                                    \
-    launch_sweep_f81<G_, R_>(ctx, what, level, n_level);     \
+    launch_sweep_f81<G_, R_>(ctx, what, units, n_level, cherries, bu_sweep);     \
     HIP_TRY(hipGetLastError());                              \
     return PML_OK;                                           \
 }
     PML_F81_CASES(X)
 #undef X
-    if (g == 64 && r == 8) return dispatch_sweep_f81_wide(ctx, what, level, n_level);   // (more than 256 states)
+    if (g == 64 && r == 8) return dispatch_sweep_f81_wide(ctx, what, units, n_level, cherries, bu_sweep);   // (more than 256 states)
     return fail(PML_ERR_UNSUPPORTED, "no F81 kernel for G=%d R=%d", g, r);
 }

@@ -4,7 +4,7 @@
 template <int G, int R>
 static void launch_super_f81(pml_ctx* ctx, bool bottom_up) {
     const PmlTree t = tree_of(ctx, true);
-    const PmlCols c = cols_of(ctx);
+    const PmlCols c = cols_of(ctx, bottom_up);
     const PmlState st = state_of(ctx);
     const int upb = PML_WAVES_PER_BLOCK * (64 / G);
     // (top-down: one unit per child of a two-level node)
@@ -19,7 +19,7 @@ static void launch_super_f81(pml_ctx* ctx, bool bottom_up) {
 template <int G, int R>
 static void launch_stack_f81(pml_ctx* ctx, bool bottom_up, int a, int n) {
     const PmlTree t = tree_of(ctx, true);
-    const PmlCols c = cols_of(ctx);
+    const PmlCols c = cols_of(ctx, bottom_up);
     const PmlState st = state_of(ctx);
     const int upb = PML_WAVES_PER_BLOCK * (64 / G);
     dim3 grid(grid_for(ctx, bottom_up ? n : 2 * n, upb, ctx->C), ctx->C), block(PML_BLOCK);

@@ -3,9 +3,9 @@
 // (pastml/ml.py:134); the other lane shapes stop at 256.  These contexts run the plain level schedule (pml_host.h, wide_states).
 #include "pml_launch_f81_level.h"
 
-int dispatch_sweep_f81_wide(pml_ctx* ctx, SweepKind what, const int* level, int n_level) {
+int dispatch_sweep_f81_wide(pml_ctx* ctx, SweepKind what, const PmlUnit* units, int n_level, bool cherries, bool bu_sweep) {
     if (n_level <= 0) return PML_OK;
-    launch_sweep_f81<64, 8>(ctx, what, level, n_level);
+    launch_sweep_f81<64, 8>(ctx, what, units, n_level, cherries, bu_sweep);
     HIP_TRY(hipGetLastError());
     return PML_OK;
 }

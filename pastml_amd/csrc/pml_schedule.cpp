@@ -855,3 +855,321 @@ PmlThinPlan pml_plan_thin_ends(const PmlForest& f, const PmlTune& tune, int thin
     plan_thin_top_down(f, tune, thin, S, narrow, P);
     return P;
 }
+
+// ---------------------------------------------------------------------------------------------------------------------
+// The sweeps' launch sequences (pml_schedule.h, PmlLaunch)
+// ---------------------------------------------------------------------------------------------------------------------
+// The narrow end of a large forest (the levels near the roots hold a handful of nodes each) is walked by ONE launch
+// with a workgroup barrier between levels instead of one latency-bound launch per level: returns the number of
+// consecutive levels, counted from the root end, that hold at most `limit` units each (0 if fewer than two do).
+// Measured on MI355X: with one column (cfg2, 65 536 tips) 512 units per level is the best cut (0.205 -> 0.181 ms per
+// marginal pass); one workgroup per column walks the levels, so with many columns the level kernels, which spread a
+// level over the whole chip, win earlier: the limit shrinks with the number of columns.
+// The fused eigen sweeps pass their own limit: a pass of theirs is a ~10 us dependent chain, so only levels that one
+// workgroup finishes in a single pass per wave belong to the narrow end.
+static int narrow_levels(const PmlSweepTraits& t, const std::vector<int>& off, int n_levels, bool from_front, int C, int fixed_limit = 0,
+                         int top_down = -1, int skip = 0) {
+    if (t.wide_states) return 0;   // (no multi-level kernels beyond 256 states)
+    int limit = fixed_limit > 0 ? fixed_limit : (t.narrow_units > 0 ? t.narrow_units : std::max(8, 512 / std::max(1, C)));
+    if (fixed_limit <= 0 && t.narrow_units <= 0 && t.f81) {
+        // ... but never below half a pass of the walking workgroup (512 threads, g lanes per unit): such a level is one
+        // wavefront's work per SIMD either way, and a launch of its own costs 5 - 10 us where a level step inside the
+        // walk costs 2.  Random 262 144-tip tree x 32 characters, marginal pass: k = 4 1.66 -> 1.52 ms, k = 12 2.56 -> 2.37,
+        // k = 64 unchanged (profiles/r05j_narrow_units.txt, r05l_narrow_ab.txt); same bits (multi_level_shape).
+        const bool td = top_down < 0 ? from_front : top_down != 0;   // (which sweep's lane shape walks the levels)
+        const int g = td ? t.Gt : (t.bu_wide_lanes ? 8 : t.Gf);
+        limit = std::max(limit, 256 / std::max(1, g));
+    }
+    int n = 0;
+    for (int q = 0; q < n_levels; ++q) {
+        const int l = skip + (from_front ? q : n_levels - 1 - q);
+        if (off[l + 1] - off[l] > limit) break;
+        ++n;
+    }
+    return n >= 2 ? n : 0;
+}
+// the run of narrow depths right below the roots (td_offsets[d] .. td_offsets[d + 1] = the nodes of depth d; the roots are depth 0)
+static int narrow_depths(const PmlSweepTraits& t, const PmlForest& f, int limit) {
+    return narrow_levels(t, f.td_offsets, (int)f.td_offsets.size() - 2, true, t.C, limit, -1, 1);
+}
+
+namespace {
+struct Plan {
+    std::vector<PmlLaunch> v;
+    int branch = 0, bracket = PML_NO_BRACKET;
+    PmlLaunch& add(int op, int list = L_NONE, int first = 0, int count = 0, int kind = 0) {
+        v.push_back(PmlLaunch{(unsigned char)op, (unsigned char)list, (unsigned char)kind, (unsigned char)bracket,
+                              (unsigned char)branch, false, true, first, count, 0});
+        return v.back();
+    }
+    // a launch per level l0 .. l1 - 1 of an offsets table; an empty level keeps its record (the launcher returns at once and the
+    // profile counts it) or is skipped; after(l): what else level l launches
+    template <class K, class A>
+    void levels(int op, int list, const std::vector<int>& off, int l0, int l1, bool keep_empty, K kind, A after) {
+        for (int l = l0; l < l1; ++l) {
+            if (keep_empty || off[l + 1] > off[l]) add(op, list, off[l], off[l + 1] - off[l], kind(l));
+            after(l);
+        }
+    }
+    template <class K>
+    void levels(int op, int list, const std::vector<int>& off, int l0, int l1, bool keep_empty, K kind) {
+        levels(op, list, off, l0, l1, keep_empty, kind, [](int) {});
+    }
+};
+const auto no_kind = [](int) { return 0; };
+const auto td_fused_kind = [](int) { return (int)SW_TD_FUSED; };
+}  // namespace
+
+// the stacked units of level / depth l, if any
+static void add_stack(Plan& p, const PmlSuperSchedule& U, const std::vector<int>& off, int l) {
+    if (U.n_stack > 0 && off[l + 1] > off[l]) p.add(OP_STACK, L_NONE, l, off[l + 1] - off[l]);
+}
+
+// Bottom-up sweep of an eigen model: the tips, then the levels -- the thin ones in tiers of subtree blocks where the forest has
+// them (pml_ctx::EigenTiers; only while their levels are thin for the whole batch: with many columns a level fills the chip),
+// what is left above the tiers a launch each while wider than `wide` (a forest of many trees), then the narrow end in one launch
+// (E: the tiers, or null where the sweep has none)
+static void eigen_bottom_up(Plan& p, const PmlForest& f, const PmlSweepTraits& t, int family, const PmlEigenTiers* E, int wide,
+                            int narrow_limit) {
+    const int nb = (int)f.bu_offsets.size() - 1;
+    const auto fam = [family](int) { return family; };
+    p.add(OP_EIG_TIPS, L_NONE, 0, 0, family);
+    if (E != nullptr) {
+        p.levels(OP_EIG_LEVEL, L_BU_PLAIN, f.bu_offsets, 0, E->first_level, true, fam);
+        for (size_t q = 0; q < E->tiers.size(); ++q) p.add(OP_EIG_TIER, L_NONE, (int)q, E->tiers[q].n_blocks, family);
+        int l = E->top_level;
+        while (l < nb && f.bu_offsets[l + 1] - f.bu_offsets[l] > wide) ++l;
+        p.levels(OP_EIG_LEVEL, L_BU_PLAIN, f.bu_offsets, E->top_level, l, true, fam);
+        p.add(OP_EIG_NARROW, L_BU_PLAIN, l, nb - l, family);   // (counted by the profile even where no level is left for it)
+        return;
+    }
+    const int tail = narrow_levels(t, f.bu_offsets, nb, false, t.C, narrow_limit);
+    p.levels(OP_EIG_LEVEL, L_BU_PLAIN, f.bu_offsets, 0, nb - tail, true, fam);
+    if (tail > 0) p.add(OP_EIG_NARROW, L_BU_PLAIN, nb - tail, tail, family);
+}
+
+std::vector<PmlLaunch> pml_plan_bottom_up(const PmlForest& f, const PmlSchedules& s, const PmlSweepTraits& t, bool is_marginal) {
+    const bool eig = t.eigen_fused, gemm = is_marginal && t.eigen_gemm, eigj = !is_marginal && t.eigen_joint_valu;
+    const bool fused = is_marginal && t.f81;
+    Plan p;
+    p.branch = fused ? (t.single_launch ? BU_ONE_LAUNCH : t.blocks ? BU_BLOCKS : t.super ? BU_SUPER : t.thin ? BU_THIN : BU_FUSED)
+               : (t.f81 && t.fuse && !t.has_init && t.n_cherries > 0 && t.W == 1) ? BU_FUSED_JOINT
+               : eigj ? BU_EIGJ : gemm ? BU_GEMM : eig ? BU_EIG_FUSED : BU_PLAIN;
+    // (eigen tiers only while their levels are thin for the whole batch: with many columns a level fills the chip)
+    const bool tiers = s.eig->ok && (long long)s.eig->widest * t.C <= 16384 && !(gemm && !eigj && t.no_eigg_tiers);
+    if (tiers && p.branch == BU_EIGJ) p.branch = BU_EIGJ_TIERS;
+    if (tiers && p.branch == BU_GEMM) p.branch = BU_GEMM_TIERS;
+    if (p.branch != BU_ONE_LAUNCH) {  // the single-launch kernel resets the error words itself
+        p.add(OP_RESET_ERR).arg = eigj ? 1 : 0;
+        // the fused eigen sweeps build P(t) themselves, the two-GEMM sweeps never need it
+        if (!eig && !gemm && !eigj && !t.hky_fused) p.add(OP_PREP);
+    }
+    p.bracket = 0;
+    const int nl = (int)f.bu_offsets_f.size() - 1;
+    const int fused_list = t.level_lists_sorted ? L_BU_FUSED_SORTED : L_BU_FUSED;
+    auto marg_kind = [](const std::vector<char>& vec) {
+        return [&vec](int l) { return (int)(vec[l] ? SW_BU_MARG_FUSED : SW_BU_MARG_FUSED_NOVEC); };
+    };
+    // the levels next to the roots and ln L in one launch: the last of the sweep, outside the profile's bracket
+    auto narrow_end = [&](int list, int first_level, int tail) {
+        p.bracket = PML_NO_BRACKET;
+        if (tail > 0) p.add(OP_LEVELS, list, first_level, tail).signal = t.sched_cols <= 64 && !t.no_spin_wait;
+    };
+    switch (p.branch) {
+        case BU_ONE_LAUNCH: {   // prep + every level + ln L in one launch
+            PmlLaunch& r = p.add(OP_LEVELS, L_BU_FUSED, 0, nl);
+            r.arg = 1;
+            r.signal = t.sched_cols <= 64 && !t.no_spin_wait;
+            break;
+        }
+        case BU_BLOCKS: {   // subtree blocks in one launch, then the top part: level launches, its narrow end (and ln L) in one launch
+            const PmlBlockSchedule& B = *s.blocks;
+            p.add(OP_BLOCKS, L_NONE, 0, B.n_blocks);
+            const int n = (int)B.top_bu_offsets.size() - 1;
+            const int tail = narrow_levels(t, B.top_bu_offsets, n, false, t.sched_cols);
+            p.levels(OP_LEVEL, L_TOP_BU, B.top_bu_offsets, 0, n - tail, true, marg_kind(B.top_bu_vec));
+            narrow_end(L_TOP_BU, n - tail, tail);
+            break;
+        }
+        case BU_SUPER: {   // the two-level units first (they depend on tips only), then the levels of what is left
+            const PmlSuperSchedule& U = *s.sup;
+            p.bracket = 4;
+            if (U.n > 0) p.add(OP_SUPER, L_NONE, 0, U.n);
+            p.bracket = 0;
+            const int n = (int)U.bu_offsets_r.size() - 1;
+            int tail = narrow_levels(t, U.bu_offsets_r, n, false, t.sched_cols);
+            // (the narrow end's single launch walks the rest lists only: it starts above the last level with stacked units)
+            for (int l = n - 1; l >= 0 && U.n_stack > 0; --l)
+                if (U.stack_bu_offsets[l + 1] > U.stack_bu_offsets[l]) {
+                    tail = std::min(tail, n - 1 - l);
+                    break;
+                }
+            if (tail < 2) tail = 0;
+            // (a level's stacked units read vectors of two levels down: independent of the level's own launch)
+            p.levels(OP_LEVEL, t.level_lists_sorted ? L_REST_BU_SORTED : L_REST_BU, U.bu_offsets_r, 0, n - tail, false,
+                     marg_kind(U.bu_level_vec_r), [&](int l) { add_stack(p, U, U.stack_bu_offsets, l); });
+            narrow_end(L_REST_BU, n - tail, tail);
+            break;
+        }
+        case BU_THIN: {
+            // the wide levels one launch each, the thin ones in tiers of subtree blocks (a launch per tier), then the narrow
+            // end's single launch (in between, level launches where a level is still too wide for it)
+            const PmlThinSchedule& H = *s.thin;
+            p.levels(OP_LEVEL, fused_list, f.bu_offsets_f, 0, H.floor_level, true, marg_kind(*s.bu_level_vec_f));
+            for (size_t q = 0; q < H.tiers.size(); ++q) p.add(OP_BLOCKS, L_NONE, 1 + (int)q, H.tiers[q].n_blocks);
+            const int tail = std::min(nl - H.top_level, narrow_levels(t, f.bu_offsets_f, nl, false, t.sched_cols));
+            p.levels(OP_LEVEL, fused_list, f.bu_offsets_f, H.top_level, nl - tail, true, marg_kind(*s.bu_level_vec_f));
+            narrow_end(L_BU_FUSED, nl - tail, tail);
+            break;
+        }
+        case BU_FUSED: {
+            const int tail = narrow_levels(t, f.bu_offsets_f, nl, false, t.sched_cols);
+            p.levels(OP_LEVEL, fused_list, f.bu_offsets_f, 0, nl - tail, true, marg_kind(*s.bu_level_vec_f));
+            narrow_end(L_BU_FUSED, nl - tail, tail);
+            break;
+        }
+        case BU_FUSED_JOINT:   // joint sweep over the cherry-fused lists (no altered nodes whose tables would need rewriting)
+            p.levels(OP_LEVEL, L_BU_FUSED, f.bu_offsets_f, 0, nl, true,
+                     [&](int l) { return (int)((*s.bu_level_vec_f)[l] ? SW_BU_JOINT_FUSED : SW_BU_JOINT_FUSED_NOVEC); });
+            break;
+        case BU_EIGJ_TIERS:
+        case BU_EIGJ:   // joint sweep of an eigen model on the vector units (pml_kernels_eigen_joint.h)
+            eigen_bottom_up(p, f, t, EIG_JOINT, tiers ? s.eig : nullptr, 48, t.waves * (64 / t.k));
+            break;
+        case BU_GEMM_TIERS:
+        case BU_GEMM:
+            // marginal sweep: P(t) is never formed, msg = A (e o (A^-1 v)) as two small GEMMs per 16 nodes; levels one
+            // workgroup finishes in a pass or two per wave (4 waves x 16 nodes) share one launch
+            eigen_bottom_up(p, f, t, EIG_GEMM, tiers ? s.eig : nullptr, 2 * t.waves * 16, 2 * t.waves * 16);
+            break;
+        case BU_EIG_FUSED:   // every node once, in the launch of its level: the tips first, then the internal nodes by height
+            eigen_bottom_up(p, f, t, EIG_FUSED, nullptr, 0, t.waves * t.eig_nb);
+            break;
+        default:
+            p.levels(OP_LEVEL, L_BU_PLAIN, f.bu_offsets, 0, (int)f.bu_offsets.size() - 1, true, [&](int l) {
+                return (int)(is_marginal ? SW_BU_MARG : (t.f81 && !(*s.bu_level_vec)[l] ? SW_BU_JOINT_NOVEC : SW_BU_JOINT));
+            });
+    }
+    p.bracket = PML_NO_BRACKET;
+    if (p.v.back().op != OP_LEVELS) p.add(OP_LOGLIK);   // (the launch that walks the last levels writes ln L itself)
+    return p.v;
+}
+
+// Top-down sweep of an eigen model below the roots: the run of narrow depths in one launch, then a launch per depth
+static void eigen_top_down(Plan& p, const PmlForest& f, const PmlSweepTraits& t, int family, int limit) {
+    const int head = narrow_depths(t, f, limit);
+    if (head > 0) p.add(OP_EIG_NARROW, L_IDS, 1, head, family);
+    p.levels(OP_EIG_LEVEL, L_IDS, f.td_offsets, 1 + head, (int)f.td_offsets.size() - 1, false, [family](int) { return family; });
+}
+
+std::vector<PmlLaunch> pml_plan_top_down(const PmlForest& f, const PmlSchedules& s, const PmlSweepTraits& t, bool wants_signal) {
+    const int nd = (int)f.td_offsets.size() - 1;
+    const bool td_small = t.single_launch && t.f81;
+    const bool levels_f81 = t.f81 && !td_small;
+    const bool signal = wants_signal && t.C <= 64 && !t.no_spin_wait;   // (the last launch of the pass)
+    Plan p;
+    // the roots, or the roots and the `head` levels right below them in one launch
+    auto roots = [&](int list, int head) {
+        if (head == 0) p.add(OP_ROOTS, L_NONE, 0, t.n_roots);
+        else p.add(OP_LEVELS, list, 0, head);
+        p.bracket = 1;
+    };
+    if (levels_f81 && t.blocks) {
+        // block schedule: the top part (roots, its narrow end in one launch, its wide levels one launch each),
+        // then all subtree blocks in one launch
+        const PmlBlockSchedule& B = *s.blocks;
+        p.branch = TD_BLOCKS;
+        const int head = t.n_roots <= 64 ? narrow_levels(t, B.top_td_offsets, nd, true, t.C) : 0;
+        roots(L_TOP_TD, head);
+        p.levels(OP_LEVEL, L_TOP_TD, B.top_td_offsets, head, nd, false, td_fused_kind);
+        p.add(OP_BLOCKS, L_NONE, 0, B.n_blocks).signal = signal;
+        return p.v;
+    }
+    if (levels_f81 && t.super) {
+        // the levels of the rest lists, then every two-level unit in one launch (it needs its node's row only, and
+        // that comes from a unit of the rest lists or from the roots)
+        const PmlSuperSchedule& U = *s.sup;
+        p.branch = TD_SUPER;
+        int head = t.n_roots <= 64 ? narrow_levels(t, U.td_offsets_r, nd, true, t.C) : 0;
+        // (... and the single launch below the roots ends above the first depth with stacked nodes)
+        for (int l = 0; l < nd && U.n_stack > 0; ++l)
+            if (U.stack_td_offsets[l + 1] > U.stack_td_offsets[l]) {
+                head = std::min(head, l);
+                break;
+            }
+        if (head < 2) head = 0;
+        roots(L_REST_TD, head);
+        // (the children of the stacked nodes of a depth: their rows come from the depth above)
+        p.levels(OP_LEVEL, t.level_lists_sorted ? L_REST_TD_SORTED : L_REST_TD, U.td_offsets_r, head, nd, false, td_fused_kind,
+                 [&](int l) { add_stack(p, U, U.stack_td_offsets, l); });
+        p.bracket = 3;
+        if (U.n > 0) p.add(OP_SUPER, L_NONE, 0, U.n);
+        return p.v;
+    }
+    // F81 family: the roots and the levels right below them in one launch
+    const int head = (levels_f81 && t.n_roots <= 64) ? narrow_levels(t, f.td_parent_offsets_f, nd, true, t.C) : 0;
+    const bool deep = levels_f81 && t.deep && s.deep->first_depth > head;
+    p.branch = td_small ? TD_ONE_LAUNCH : deep ? TD_DEEP : t.eigen_gemm ? TD_GEMM : t.eigen_fused ? TD_EIG_FUSED : TD_LEVELS;
+    if (td_small) p.bracket = 1;
+    else roots(L_TD_FUSED, head);
+    if (td_small) p.add(OP_LEVELS, L_TD_FUSED, 0, nd).signal = signal;
+    // eigen models, child-centric: the nodes of a depth are a contiguous id range (roots are depth 0, done above)
+    else if (t.eigen_gemm) eigen_top_down(p, f, t, EIG_GEMM, 2 * t.waves * 16);
+    else if (t.eigen_fused) eigen_top_down(p, f, t, EIG_FUSED, t.waves * t.eig_nb);
+    if (p.branch != TD_LEVELS && p.branch != TD_DEEP) return p.v;
+    const int fused_list = t.level_lists_sorted ? L_TD_FUSED_SORTED : L_TD_FUSED;
+    // the staging hint of a level of the whole forest's fused list
+    auto hint = [&](size_t from) {
+        const std::vector<int>& pre = *s.td_cherry_prefix;
+        for (size_t i = from; i < p.v.size(); ++i) {
+            const size_t a = (size_t)p.v[i].first, b = a + (size_t)p.v[i].count;
+            if (!pre.empty() && b < pre.size()) p.v[i].cherries = pre[b] != pre[a];
+        }
+    };
+    // F81 family: the thin depths at the DEEP end of a ragged forest (a handful of parents each) in one launch as well
+    // -- a launch of their own costs 9 - 11 us each, a level step of the walk 2 - 3 (round 5) --, and when many of the deep
+    // depths are thin, all of them: the subtrees hanging at the first one, a workgroup per (bin of subtrees, column)
+    // walking its depths (pml_plan_thin_ends)
+    const size_t from = p.v.size();
+    if (deep) {
+        p.levels(OP_LEVEL, fused_list, f.td_parent_offsets_f, head, s.deep->first_depth, false, td_fused_kind);
+        hint(from);
+        p.add(OP_BLOCKS, L_NONE, 1, s.deep->n_blocks);
+        return p.v;
+    }
+    int tail = 0;
+    // (units of fewer than 8 lanes only: at k = 64 a level step inside the walk costs what the launch does)
+    if (t.f81 && t.Gt < 8 && !t.no_td_tail) {
+        tail = std::min(nd - head, narrow_levels(t, f.td_parent_offsets_f, nd, false, t.C, 0, 1));
+        if (tail < 2) tail = 0;
+    }
+    if (t.f81) {
+        p.levels(OP_LEVEL, fused_list, f.td_parent_offsets_f, head, nd - tail, false, td_fused_kind);
+        hint(from);
+    } else {
+        p.levels(OP_LEVEL, L_TD_PLAIN, f.td_parent_offsets, head, nd, false, [](int) { return (int)SW_TD; });
+    }
+    p.bracket = PML_NO_BRACKET;
+    if (tail > 0) p.add(OP_LEVELS, L_TD_FUSED, nd - tail, tail).arg = 1;
+    return p.v;
+}
+
+// the back-trace launches: the narrow depths below the roots in one launch, the wide ones one launch each or in tiers
+std::vector<PmlLaunch> pml_plan_backtrace(const PmlForest& f, const PmlSchedules& s, const PmlSweepTraits& t, int* head_out) {
+    const int head = narrow_depths(t, f, 1024);
+    const PmlBacktraceTiers& B = *s.bt;
+    // (tiers while one column's narrow end is the limit they were cut for: with many columns the narrow end is shorter
+    // and the depths in between keep their launches)
+    bool tiers = B.ok && 1 + head >= B.first_depth;
+    for (const PmlBacktraceTiers::Tier& T : B.tiers)
+        tiers = tiers && (long long)T.n_blocks * t.C <= 8192;  // (a workgroup per subtree and column: only while few)
+    Plan p;
+    p.branch = tiers ? BT_TIERS : BT_LEVELS;
+    if (head > 0) p.add(OP_BT_NARROW, L_IDS, 1, tiers ? B.first_depth - 1 : head);
+    if (tiers)
+        for (size_t q = 0; q < B.tiers.size(); ++q) p.add(OP_BT_TIER, L_NONE, (int)q, B.tiers[q].n_blocks);
+    else
+        p.levels(OP_BT_LEVEL, L_IDS, f.td_offsets, 1 + head, (int)f.td_offsets.size() - 1, false, no_kind);
+    if (head_out) *head_out = head;
+    return p.v;
+}

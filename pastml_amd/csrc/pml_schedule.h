@@ -260,6 +260,74 @@ struct PmlThinPlan {
     std::vector<PmlUnit> bu_units, td_units;
 };
 
+// ---------------------------------------------------------------------------------------------------------------------
+// A sweep's launch sequence as data: pml_plan_bottom_up / _top_down / _backtrace decide which launches a sweep consists of
+// and in what order, run_plan (pml_api.hip) issues them.  PASTML_HIP_DEBUG prints a plan, one line per record.
+// ---------------------------------------------------------------------------------------------------------------------
+enum SweepKind {
+    SW_BU_MARG, SW_BU_JOINT, SW_TD, SW_ROOTS, SW_BU_MARG_FUSED, SW_TD_FUSED, SW_BU_CHERRIES,
+    SW_BU_MARG_FUSED_NOVEC,  // a fused level none of whose units has a stored node among its first two children
+    SW_BU_JOINT_NOVEC,       // the same for a level of the joint sweep (the level whose children are all tips)
+    SW_BU_JOINT_FUSED, SW_BU_JOINT_FUSED_NOVEC,  // joint sweep over the cherry-fused level lists
+    SW_BU_CHERRIES_JOINT     // materialises the cherries' vectors after a fused joint sweep
+};
+enum PmlEigenFamily { EIG_JOINT, EIG_GEMM, EIG_FUSED };   // which eigen kernels an OP_EIG_* launch runs (pml_launch.h)
+enum PmlOp {
+    OP_RESET_ERR, OP_PREP, OP_LOGLIK,
+    OP_LEVEL,    // one level launch: entries first .. first + count of the list
+    OP_LEVELS,   // several levels in one launch, a workgroup per column: levels first .. first + count of the list's table
+    OP_BLOCKS,   // subtree blocks; first = 0: the block schedule's, q + 1: tier q of the thin ends (top-down: the deep bins)
+    OP_SUPER, OP_STACK,   // every two-level unit; the stacked units of level / depth `first`
+    OP_ROOTS,
+    OP_EIG_TIPS, OP_EIG_LEVEL, OP_EIG_NARROW, OP_EIG_TIER,   // eigen models (level: entries; narrow: levels; tier `first`)
+    OP_BT_NARROW, OP_BT_TIER, OP_BT_LEVEL,                   // joint back-trace, the same
+    OP_COUNT
+};
+// which unit / node list a launch walks (pml_ctx::d_unit_lists).  The _SORTED lists are sorted by shape inside every level.
+enum PmlList {
+    L_NONE, L_BU_FUSED, L_BU_FUSED_SORTED, L_TD_FUSED, L_TD_FUSED_SORTED, L_BU_PLAIN, L_TD_PLAIN, L_CHERRIES, L_TOP_BU, L_TOP_TD,
+    L_REST_BU, L_REST_BU_SORTED, L_REST_TD, L_REST_TD_SORTED, L_CHILD_UNITS, L_STACK_CHILDREN,
+    L_IDS,   // a contiguous range of node ids (the nodes of a depth)
+    L_COUNT
+};
+enum PmlBranch {
+    BU_ONE_LAUNCH, BU_BLOCKS, BU_SUPER, BU_THIN, BU_FUSED, BU_FUSED_JOINT, BU_EIGJ_TIERS, BU_EIGJ, BU_GEMM_TIERS, BU_GEMM,
+    BU_EIG_FUSED, BU_PLAIN, TD_ONE_LAUNCH, TD_BLOCKS, TD_SUPER, TD_GEMM, TD_EIG_FUSED, TD_DEEP, TD_LEVELS, BT_TIERS, BT_LEVELS,
+    PML_BRANCH_COUNT
+};
+#define PML_NO_BRACKET 255
+struct PmlLaunch {
+    unsigned char op, list, kind;   // PmlOp, PmlList, SweepKind (OP_EIG_*: PmlEigenFamily)
+    unsigned char bracket;          // profile bracket (pml_profile_read's `which`) the launch is counted in, or PML_NO_BRACKET
+    unsigned char branch;           // the schedule branch that planned it (for the plan's reader and the tests; not executed)
+    bool signal;                    // raises the completion word (the last launch of its sweep)
+    bool cherries;                  // top-down staging hint: some unit has a cherry among its first two children
+    int first, count;
+    int arg;                        // OP_LEVELS: 1 = with the per-branch prep (bottom-up) / the roots are done (top-down); OP_RESET_ERR: 1 = eigen joint
+};
+// Everything the planners read besides the forest and its schedules; filled from a context by sweep_traits (pml_api.hip).
+struct PmlSweepTraits {
+    bool f81, eigen_fused, eigen_gemm, eigen_joint_valu, hky_fused, wide_states;   // model kind and path
+    int k, W, C, sched_cols, n_roots, n_cherries;
+    bool has_init, fuse;
+    int Gf, Gt;
+    bool bu_wide_lanes, level_lists_sorted;
+    bool single_launch, blocks, super, thin, deep;   // single_launch_sweeps, block_schedule, super_sweeps, thin_bottom_up, deep_top_down
+    int narrow_units;                                // NARROW_UNITS (0: not set)
+    bool no_td_tail, no_eigg_tiers, no_spin_wait;
+    int waves, eig_nb;                               // PML_WAVES_PER_BLOCK, EigShape::NB
+};
+struct PmlSchedules {
+    const PmlBlockSchedule* blocks;
+    const PmlThinSchedule* thin;
+    const PmlDeepSchedule* deep;
+    const PmlSuperSchedule* sup;
+    const PmlEigenTiers* eig;
+    const PmlBacktraceTiers* bt;
+    const std::vector<char>*bu_level_vec_f, *bu_level_vec;
+    const std::vector<int>* td_cherry_prefix;
+};
+
 #define PML_PLAN __attribute__((visibility("hidden")))   // (internal to the library, like pml_host.h's PML_INTERNAL)
 // "" when the arrays describe a forest the kernels can index safely, else the reason
 PML_PLAN std::string pml_check_tree(const PmlTreeArrays& t);
@@ -269,3 +337,8 @@ PML_PLAN PmlForest pml_plan_forest(PmlTreeArrays& t, const PmlTune& tune, bool f
 PML_PLAN PmlTreePlan pml_plan_tree(const PmlForest& f, const PmlTreeArrays& t, const PmlTune& tune);
 // thin: the most units a thin level holds
 PML_PLAN PmlThinPlan pml_plan_thin_ends(const PmlForest& f, const PmlTune& tune, int thin);
+// the launches of a sweep, in the order they are issued (wants_signal: the pass waits on the top-down sweep's completion word;
+// head: the narrow depths below the roots, which decide whether the back-trace replays as a graph)
+PML_PLAN std::vector<PmlLaunch> pml_plan_bottom_up(const PmlForest& f, const PmlSchedules& s, const PmlSweepTraits& t, bool is_marginal);
+PML_PLAN std::vector<PmlLaunch> pml_plan_top_down(const PmlForest& f, const PmlSchedules& s, const PmlSweepTraits& t, bool wants_signal);
+PML_PLAN std::vector<PmlLaunch> pml_plan_backtrace(const PmlForest& f, const PmlSchedules& s, const PmlSweepTraits& t, int* head);
