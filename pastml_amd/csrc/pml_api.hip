@@ -563,8 +563,7 @@ int pml_chars_alloc(pml_ctx* ctx, int32_t n_cols, int32_t k) {
     *ctx->h_done = 0;
     PML_TRY(dev_alloc(ctx, &ctx->d_done, 2));
     HIP_TRY(hipMemsetAsync(ctx->d_done, 0, 2 * sizeof(u64), ctx->stream));
-    ctx->done_expect = 0;
-    ctx->wait_signal = false;
+    ctx->pending = {};
     ctx->graphs = !ctx->tune.on(T_NO_GRAPH);
     PML_TRY(dev_alloc(ctx, &ctx->d_bu, CN * ctx->ks));
     PML_TRY(dev_alloc(ctx, &ctx->d_S, CN));
@@ -784,12 +783,14 @@ static int params_flush(pml_ctx* ctx) {
     return PML_OK;
 }
 
-static int params_push(pml_ctx* ctx) {
-    if (!ctx->capturing && !ctx->params_dirty) return PML_OK;
+// (captured: the copy is recorded whatever the mirror holds now, and the sequence's outcome says that it is part of it --
+// the mirror counts as sent whenever the graph is launched, run_captured)
+static int params_push(pml_ctx* ctx, PmlCapture capture = CAP_NONE, PmlSweepOutcome* outcome = nullptr) {
+    if (capture == CAP_NONE && !ctx->params_dirty) return PML_OK;
     HIP_TRY(hipMemcpyAsync(ctx->d_params, ctx->h_params, ctx->n_params * sizeof(double), hipMemcpyHostToDevice,
                            ctx->stream));
-    if (ctx->capturing) ctx->capture_saw_params = true;
-    else ctx->params_dirty = false;
+    if (capture == CAP_NONE) ctx->params_dirty = false;
+    else if (outcome) outcome->has_params = true;
     return PML_OK;
 }
 
@@ -930,7 +931,9 @@ static int ensure_transition_storage(pml_ctx* ctx) {
 }
 
 static int run_prep(pml_ctx* ctx, bool force = false, bool bu_sweep = false) {
-    if (!ctx->capturing) PML_TRY(params_push(ctx));  // (callers outside a sweep: pml_pij_batch, pml_marginal_counts, downloads)
+    // (callers outside a sweep: pml_pij_batch, pml_marginal_counts, downloads; a sweep's own copy went out, or into the
+    // capture, before its first launch: enqueue_bottom_up)
+    if (!bu_sweep) PML_TRY(params_push(ctx));
     if (!ctx->prep_dirty && !force) return PML_OK;
     const PmlTree t = tree_of(ctx);
     const PmlCols c = cols_of(ctx, bu_sweep);
@@ -1097,9 +1100,8 @@ static PmlSchedules schedules_of(const pml_ctx* ctx) {
 // Puts the launches of a plan on the stream, in order and without host synchronisation (so that they can be captured):
 // one call of a launcher per record.  bottom_up: they are a bottom-up sweep's, which looks at the flags of the active
 // columns.  The profile brackets open and close where a record's bracket differs from the one before it, and a bracket's
-// launches are its records.  n_signals: the launches that raise the completion word are added to it.
-static int run_plan(pml_ctx* ctx, const std::vector<PmlLaunch>& plan, bool bottom_up, int is_marginal, bool force_prep,
-                    int* n_signals) {
+// launches are its records.  (What the launches leave behind: pml_plan_outcome.)
+static int run_plan(pml_ctx* ctx, const std::vector<PmlLaunch>& plan, bool bottom_up, int is_marginal, bool force_prep) {
     const pml_ctx::EigenTiers& E = ctx->eig_tiers;
     const pml_ctx::BacktraceTiers& B = ctx->bt_tiers;
     const int* order = bottom_up ? ctx->d_bu_order : nullptr;   // (top-down: the nodes of a depth are a contiguous id range)
@@ -1119,7 +1121,6 @@ static int run_plan(pml_ctx* ctx, const std::vector<PmlLaunch>& plan, bool botto
             launches = 0;
         }
         ++launches;
-        if (r.signal) ++*n_signals;
         const bool joint = r.kind == EIG_JOINT, gemm = r.kind == EIG_GEMM;   // (of the eigen ops; else the fused matrix-core kernels)
         switch (r.op) {
             case OP_RESET_ERR:
@@ -1215,28 +1216,25 @@ static int run_plan(pml_ctx* ctx, const std::vector<PmlLaunch>& plan, bool botto
 }
 
 // Everything a bottom-up sweep puts on the stream, without host synchronisation (so that it can be captured), as
-// pml_plan_bottom_up lists it.  signals: its last launch raises the completion word.
-static int enqueue_bottom_up(pml_ctx* ctx, int is_marginal, bool force_prep, bool* signals) {
-    PML_TRY(params_push(ctx));  // what the last model update left in the pinned mirror (part of the graph when captured)
+// pml_plan_bottom_up lists it.
+static int enqueue_bottom_up(pml_ctx* ctx, int is_marginal, bool force_prep, PmlCapture capture, PmlSweepOutcome* outcome) {
     const std::vector<PmlLaunch> plan = pml_plan_bottom_up(ctx->forest, schedules_of(ctx), sweep_traits(ctx), is_marginal != 0);
-    int n_signals = 0;
-    PML_TRY(run_plan(ctx, plan, true, is_marginal, force_prep, &n_signals));
-    ctx->signals_enqueued += n_signals;
-    *signals = n_signals > 0;
-    ctx->bu_fused_joint = plan.front().branch == BU_FUSED_JOINT;
-    return PML_OK;
+    *outcome = pml_plan_outcome(plan);
+    PML_TRY(params_push(ctx, capture, outcome));  // what the last model update left in the pinned mirror (part of the graph when captured)
+    return run_plan(ctx, plan, true, is_marginal, force_prep);
 }
 
-// Captures fn's stream work once and replays it afterwards; falls back to direct submission if capture fails.
-static int run_captured(pml_ctx* ctx, pml_ctx::GraphSlot& slot, const std::function<int()>& enqueue) {
-    if (ctx->in_outer_capture) return enqueue();  // part of a larger capture
+// Captures enqueue's stream work once and replays it afterwards; outcome: of what now runs on the stream, captured just
+// now or replayed.  capture: CAP_PASS -- the stream is being captured already, the work becomes part of that graph.
+using PmlEnqueue = std::function<int(PmlCapture, PmlSweepOutcome*)>;
+static int run_captured(pml_ctx* ctx, pml_ctx::GraphSlot& slot, PmlCapture capture, const PmlEnqueue& enqueue,
+                        PmlSweepOutcome* outcome) {
+    if (capture == CAP_PASS) return enqueue(CAP_PASS, outcome);
     if (slot.exec && slot.has_init != ctx->has_init) drop_graph(slot);
     if (!slot.exec) {
         HIP_TRY(hipStreamBeginCapture(ctx->stream, hipStreamCaptureModeThreadLocal));
-        ctx->capturing = true;
-        ctx->capture_saw_params = false;
-        const int status = enqueue();
-        ctx->capturing = false;
+        slot.outcome = {};
+        const int status = enqueue(CAP_OWN, &slot.outcome);
         hipGraph_t graph = nullptr;
         const hipError_t e = hipStreamEndCapture(ctx->stream, &graph);
         if (status != PML_OK) {
@@ -1253,14 +1251,13 @@ static int run_captured(pml_ctx* ctx, pml_ctx::GraphSlot& slot, const std::funct
         slot.graph = graph;
         slot.exec = exec;
         slot.has_init = ctx->has_init;
-        slot.has_params = ctx->capture_saw_params;
     }
     HIP_TRY(hipGraphLaunch(slot.exec, ctx->stream));
-    if (slot.has_params) ctx->params_dirty = false;
+    if (slot.outcome.has_params) ctx->params_dirty = false;
+    *outcome = slot.outcome;
     return PML_OK;
 }
 
-// puts a bottom-up sweep on the stream (no host synchronisation)
 // Which columns the next bottom-up sweep computes (nullptr: all).  The flags travel with the parameter block (params_push:
 // inside the captured sweep when it is replayed), so they are written while no sweep is in flight, like the parameters.
 static void set_active_columns(pml_ctx* ctx, const uint8_t* active) {
@@ -1290,9 +1287,10 @@ static bool sweep_without_p(const pml_ctx* ctx, int is_marginal) {
 }
 
 // what a bottom-up sweep leaves behind (a replayed pml_marginal_pass runs no submit_bottom_up)
-static void note_bottom_up(pml_ctx* ctx, int is_marginal) {
+static void note_bottom_up(pml_ctx* ctx, int is_marginal, const PmlSweepOutcome& outcome) {
     const bool f81_marginal = is_marginal && ctx->kind == PML_MODEL_F81;
     ctx->js_valid = false;
+    ctx->bu_fused_joint = outcome.fused_joint;
     if (!sweep_without_p(ctx, is_marginal)) ctx->prep_dirty = false;   // (else no batch ran)
     ctx->bu_fused = (f81_marginal && ctx->n_cherries > 0) || ctx->bu_fused_joint;
     // (a sweep of some of the columns says nothing about the others: where an earlier sweep of the level schedule left the
@@ -1300,12 +1298,48 @@ static void note_bottom_up(pml_ctx* ctx, int is_marginal) {
     ctx->bu_absorbed = (f81_marginal && super_sweeps(ctx)) || (ctx->active_partial && ctx->bu_absorbed);
 }
 
-static int submit_bottom_up(pml_ctx* ctx, int is_marginal, const uint8_t* active = nullptr) {
-    set_active_columns(ctx, active);
-    if (ctx->wait_signal) {  // a sweep was submitted and never collected: the generation below must be read on an idle stream
-        HIP_TRY(hipStreamSynchronize(ctx->stream));
-        ctx->wait_signal = false;
+// Waits for what was submitted last (a bottom-up sweep, a marginal pass).  Where its last launch raises the pinned word
+// (pml_signal_done) the host spins on that word -- the results lie in pinned memory behind it -- instead of asking the
+// runtime, which notices the end of a short launch sequence ~4 us later (scripts/ub/syncwait.hip); after 2 ms, or for
+// anything else, it is hipStreamSynchronize.  Everything queued afterwards is ordered behind the sweep by the stream as
+// before.  idle: the caller needs the stream idle, not just the results (the word is raised before its kernel has ended:
+// blocking copies on the NULL stream, the generation the next submission reads).
+static int wait_pending(pml_ctx* ctx, bool idle = false) {
+    const bool spin = ctx->pending.spin && !idle && ctx->h_done;
+    ctx->pending.spin = false;
+    if (spin) {
+        const u64* flag = ctx->h_done;
+        const auto t0 = std::chrono::steady_clock::now();
+        for (unsigned spins = 0;; ++spins) {
+            // (acquire: the results the host reads next were written before the word was raised)
+            if (__atomic_load_n(flag, __ATOMIC_ACQUIRE) >= ctx->pending.expect) return PML_OK;
+#if defined(__x86_64__)
+            __builtin_ia32_pause();
+#endif
+            if ((spins & 1023u) == 1023u &&
+                std::chrono::steady_clock::now() - t0 > std::chrono::milliseconds(2))
+                break;
+        }
     }
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    return PML_OK;
+}
+
+// Opens a submission: the generation the completion word shows before it.  (A sweep submitted and never collected is
+// waited for first: the word is read on an idle stream.)
+static int generation_before(pml_ctx* ctx, u64* generation) {
+    if (ctx->pending.spin) PML_TRY(wait_pending(ctx, true));
+    *generation = ctx->h_done ? *reinterpret_cast<volatile u64*>(ctx->h_done) : 0;
+    return PML_OK;
+}
+
+// puts a bottom-up sweep on the stream (no host synchronisation).  may_spin: whoever waits for the sweep reads nothing but
+// what lies behind its completion word (wait_pending); capture: CAP_NONE, or CAP_PASS inside the graph of a marginal pass
+static int submit_bottom_up(pml_ctx* ctx, int is_marginal, const uint8_t* active, bool may_spin, PmlCapture capture,
+                            PmlSweepOutcome* outcome) {
+    set_active_columns(ctx, active);
+    u64 generation = 0;
+    PML_TRY(generation_before(ctx, &generation));
     // A sweep of a few columns of a context of many is scheduled as a context of few would be (the workgroups of the
     // other columns return at once): subtree blocks instead of one workgroup per column walking every level, the
     // completion word -- HIV1C tree, 6 of 246 binary columns: 0.15 -> 0.10 ms per sweep.  Two schedules, two captured
@@ -1340,48 +1374,22 @@ static int submit_bottom_up(pml_ctx* ctx, int is_marginal, const uint8_t* active
     // mid-size forests: the level launches are latency-bound, replay them as one hipGraph
     const int n_launches = small_path ? 1 : (is_marginal && ctx->kind == PML_MODEL_F81 ? (int)ctx->forest.bu_offsets_f.size() - 1
                                                                                           : ctx->n_bu_levels);
-    const u64 generation_before = ctx->h_done ? *reinterpret_cast<volatile u64*>(ctx->h_done) : 0;  // (the stream is idle)
     if (ctx->graphs && !ctx->profile && n_launches >= 4) {  // (the block schedule's few launches replay as a graph too)
-        const int slot = is_marginal ? 1 : 0;
-        pml_ctx::GraphSlot& graph = few ? ctx->bu_graph_few : ctx->bu_graph[slot];
-        bool& signals = few ? ctx->bu_signals_few : ctx->bu_signals[slot];
-        const bool replay = graph.exec != nullptr;
-        bool enqueued = false;
-        PML_TRY(run_captured(ctx, graph, [&]() { return enqueue_bottom_up(ctx, is_marginal, true, &enqueued); }));
-        if (!replay) signals = enqueued;  // (a replay runs what was captured)
-        ctx->wait_signal = signals;
+        pml_ctx::GraphSlot& graph = few ? ctx->bu_graph_few : ctx->bu_graph[is_marginal ? 1 : 0];
+        PML_TRY(run_captured(ctx, graph, capture, [&](PmlCapture c, PmlSweepOutcome* o) -> int { return enqueue_bottom_up(ctx, is_marginal, true, c, o); },
+                             outcome));
     } else {
         // (inside the capture of a whole marginal pass the per-branch pass must be part of the graph)
-        PML_TRY(enqueue_bottom_up(ctx, is_marginal, ctx->in_outer_capture, &ctx->wait_signal));
+        PML_TRY(enqueue_bottom_up(ctx, is_marginal, capture == CAP_PASS, capture, outcome));
     }
-    ctx->done_expect = generation_before + 1;
-    if (ctx->in_outer_capture || ctx->tune.on(T_NO_SPIN_WAIT)) ctx->wait_signal = false;
-    note_bottom_up(ctx, is_marginal);
+    ctx->pending = {generation + 1, outcome->final_signals && may_spin && capture == CAP_NONE && !ctx->tune.on(T_NO_SPIN_WAIT)};
+    note_bottom_up(ctx, is_marginal, *outcome);
     return PML_OK;
 }
-
-// Waits for the bottom-up sweep submitted last.  Where its last launch raises the pinned word (bu_f81_small_kernel) the
-// host spins on that word -- the results lie in pinned memory behind it -- instead of asking the runtime, which notices
-// the end of a short launch sequence ~4 us later (scripts/ub/syncwait.hip); after 2 ms, or for any other sweep, it is
-// hipStreamSynchronize.  Everything queued afterwards is ordered behind the sweep by the stream as before.
-static int wait_bottom_up(pml_ctx* ctx) {
-    if (ctx->wait_signal && ctx->h_done) {
-        ctx->wait_signal = false;
-        const u64* flag = ctx->h_done;
-        const auto t0 = std::chrono::steady_clock::now();
-        for (unsigned spins = 0;; ++spins) {
-            // (acquire: the results the host reads next were written before the word was raised)
-            if (__atomic_load_n(flag, __ATOMIC_ACQUIRE) >= ctx->done_expect) return PML_OK;
-#if defined(__x86_64__)
-            __builtin_ia32_pause();
-#endif
-            if ((spins & 1023u) == 1023u &&
-                std::chrono::steady_clock::now() - t0 > std::chrono::milliseconds(2))
-                break;
-        }
-    }
-    HIP_TRY(hipStreamSynchronize(ctx->stream));
-    return PML_OK;
+// a sweep of its own, waited for by wait_pending (pml_bottom_up, pml_bottom_up_submit / _collect)
+static int submit_bottom_up(pml_ctx* ctx, int is_marginal, const uint8_t* active = nullptr) {
+    PmlSweepOutcome outcome;
+    return submit_bottom_up(ctx, is_marginal, active, true, CAP_NONE, &outcome);
 }
 
 // after the stream has been synchronised: log-likelihoods and zero-likelihood reports of the last sweep
@@ -1410,7 +1418,7 @@ int pml_bottom_up(pml_ctx* ctx, int is_marginal, double* loglik_out, int32_t* er
     PML_TRY(require_model(ctx));
     if (!loglik_out) return fail(PML_ERR_INVALID, "loglik_out is NULL");
     PML_TRY(submit_bottom_up(ctx, is_marginal));
-    PML_TRY(wait_bottom_up(ctx));
+    PML_TRY(wait_pending(ctx));
     return collect_bottom_up(ctx, is_marginal, loglik_out, err_parent, err_child);
 }
 
@@ -1429,7 +1437,7 @@ int pml_bottom_up_collect(pml_ctx* ctx, int is_marginal, double* loglik_out, int
     if (!ctx || ctx->C == 0) return fail(PML_ERR_INVALID, "allocate the columns first");
     if (!loglik_out) return fail(PML_ERR_INVALID, "loglik_out is NULL");
     HIP_TRY(hipSetDevice(ctx->device));
-    PML_TRY(wait_bottom_up(ctx));
+    PML_TRY(wait_pending(ctx));
     return collect_bottom_up(ctx, is_marginal, loglik_out, err_parent, err_child);
 }
 
@@ -1444,7 +1452,7 @@ static void note_top_down(pml_ctx* ctx) {
 
 // the top-down launches (shared by pml_top_down_marginals and the lazy TD materialisation of pml_download), as
 // pml_plan_top_down lists them; wants_signal: the caller waits on the completion word of the last launch
-static int run_top_down(pml_ctx* ctx, bool wants_signal = false) {
+static int run_top_down(pml_ctx* ctx, bool wants_signal = false, PmlCapture capture = CAP_NONE, PmlSweepOutcome* outcome = nullptr) {
     const size_t CN = (size_t)ctx->C * ctx->N;
     const bool td_stored = ctx->kind != PML_MODEL_F81 || ctx->keep_td;
     if (td_stored && !ctx->d_td) {
@@ -1457,19 +1465,18 @@ static int run_top_down(pml_ctx* ctx, bool wants_signal = false) {
         PML_TRY(dev_alloc(ctx, &ctx->d_lhe, CN));
     }
     const bool td_small = single_launch_sweeps(ctx) && ctx->kind == PML_MODEL_F81;
-    auto enqueue = [&]() -> int {   // (a replayed graph plans nothing)
+    auto enqueue = [&](PmlCapture, PmlSweepOutcome* o) -> int {   // (a replayed graph plans nothing)
         const std::vector<PmlLaunch> plan = pml_plan_top_down(ctx->forest, schedules_of(ctx), sweep_traits(ctx), wants_signal);
-        int n_signals = 0;
-        PML_TRY(run_plan(ctx, plan, false, 1, false, &n_signals));
-        ctx->signals_enqueued += n_signals;
-        ctx->td_final_signals = n_signals > 0;
-        return PML_OK;
+        *o = pml_plan_outcome(plan);
+        return run_plan(ctx, plan, false, 1, false);
     };
+    PmlSweepOutcome done;
     if (ctx->graphs && !ctx->profile && !td_small && ctx->n_td_levels >= 4) {
-        PML_TRY(run_captured(ctx, ctx->td_graph, enqueue));
+        PML_TRY(run_captured(ctx, ctx->td_graph, capture, enqueue, &done));
     } else {
-        PML_TRY(enqueue());
+        PML_TRY(enqueue(capture, &done));
     }
+    if (outcome) *outcome = done;
     note_top_down(ctx);
     return PML_OK;
 }
@@ -1571,56 +1578,33 @@ int pml_marginal_pass(pml_ctx* ctx, double* loglik_out, int32_t* err_parent, int
                            (!ctx->keep_td || ctx->d_td != nullptr) &&
                            (bu_launches >= 4 || (!td_small && ctx->n_td_levels >= 4));
     // Where the pass ends in a multi-level kernel and has few columns, that kernel says when it is done (pml_signal_done)
-    // and the wait at the end of this call is a spin on the word it raises (wait_signals) -- as for a bottom-up sweep.
+    // and the wait at the end of this call is a spin on the word it raises (wait_pending) -- as for a bottom-up sweep.
     // The word counts the signalling launches (the bottom-up sweep's last one may be one too).
-    if (ctx->wait_signal) {  // (a sweep submitted and never collected: the count below is read on an idle stream)
-        HIP_TRY(hipStreamSynchronize(ctx->stream));
-        ctx->wait_signal = false;
-    }
+    u64 generation = 0;
+    PML_TRY(generation_before(ctx, &generation));
     set_active_columns(ctx, nullptr);  // (the replayed pass does not go through submit_bottom_up)
-    const u64 generation_before = ctx->h_done ? *reinterpret_cast<volatile u64*>(ctx->h_done) : 0;
-    int n_signals = 0;
-    bool final_signals = false;
+    PmlSweepOutcome pass;
     if (one_graph) {
-        if (ctx->mp_graph.exec && ctx->mp_graph.has_init == ctx->has_init) {
-            HIP_TRY(hipGraphLaunch(ctx->mp_graph.exec, ctx->stream));
-            if (ctx->mp_graph.has_params) ctx->params_dirty = false;
-        } else {
-            ctx->signals_enqueued = 0;
-            ctx->td_final_signals = false;
-            PML_TRY(run_captured(ctx, ctx->mp_graph, [&]() {
-                ctx->in_outer_capture = true;
-                int status = submit_bottom_up(ctx, 1);
-                if (status == PML_OK) {
-                    ctx->bu_mode = 1;
-                    status = run_top_down(ctx, true);
-                }
-                ctx->in_outer_capture = false;
-                return status;
-            }));
-            ctx->mp_signals = ctx->signals_enqueued;
-            ctx->mp_final = ctx->td_final_signals;
-        }
-        n_signals = ctx->mp_signals;
-        final_signals = ctx->mp_final;
+        PML_TRY(run_captured(ctx, ctx->mp_graph, CAP_NONE, [&](PmlCapture, PmlSweepOutcome* o) -> int {
+            PmlSweepOutcome td;
+            PML_TRY(submit_bottom_up(ctx, 1, nullptr, false, CAP_PASS, o));
+            ctx->bu_mode = 1;
+            PML_TRY(run_top_down(ctx, true, CAP_PASS, &td));
+            o->then(td);
+            return PML_OK;
+        }, &pass));
         // the bookkeeping of submit_bottom_up / run_top_down (a replay runs neither)
-        ctx->bu_fused_joint = false;
-        note_bottom_up(ctx, 1);
+        note_bottom_up(ctx, 1, pass);
         note_top_down(ctx);
     } else {
-        PML_TRY(submit_bottom_up(ctx, 1));
-        n_signals = ctx->wait_signal ? 1 : 0;  // (its last launch signals)
-        ctx->wait_signal = false;  // (this call waits for the whole pass: fetch_marginals)
+        PmlSweepOutcome td;
+        PML_TRY(submit_bottom_up(ctx, 1, nullptr, false, CAP_NONE, &pass));  // (this call waits for the whole pass)
         ctx->bu_mode = 1;  // provisional, for run_top_down's bookkeeping; collect_bottom_up has the last word
-        ctx->signals_enqueued = 0;
-        ctx->td_final_signals = false;
-        PML_TRY(run_top_down(ctx, td_small));  // (the single launch is enqueued afresh every time; level sweeps may replay a graph)
-        n_signals += ctx->signals_enqueued;
-        final_signals = ctx->td_final_signals;
+        PML_TRY(run_top_down(ctx, td_small, CAP_NONE, &td));  // (the single launch is enqueued afresh every time; level sweeps may replay a graph)
+        pass.then(td);
     }
-    const bool spin = final_signals && ctx->comm == nullptr && !posterior_out && !lh_sum_out && !lh_sf_out &&
-                      !ctx->tune.on(T_NO_SPIN_WAIT);
-    ctx->done_expect = generation_before + (u64)n_signals;
+    ctx->pending = {generation + (u64)pass.n_signals, pass.final_signals && ctx->comm == nullptr && !posterior_out && !lh_sum_out &&
+                                                          !lh_sf_out && !ctx->tune.on(T_NO_SPIN_WAIT)};
     // a communicator is attached: the one collective of the path goes on the stream right here, behind the sweeps --
     // the rank's sum formed on the device from the values the sweep left in pinned memory, all-reduced over RCCL, copied
     // back; the single wait of this call (fetch_marginals) covers it.  pml_loglik_total hands the result out.
@@ -1637,9 +1621,8 @@ int pml_marginal_pass(pml_ctx* ctx, double* loglik_out, int32_t* err_parent, int
         cm->total_fresh = true;
     }
     int fetched = PML_OK;
-    if (spin) {
-        ctx->wait_signal = true;
-        fetched = wait_bottom_up(ctx);  // (nothing to copy: the spin on the last launch's word, or the stream)
+    if (ctx->pending.spin) {
+        fetched = wait_pending(ctx);  // (nothing to copy: the spin on the last launch's word, or the stream)
     } else {
         fetched = fetch_marginals(ctx, posterior_out, lh_sum_out, lh_sf_out);  // synchronises
     }
@@ -1654,15 +1637,15 @@ int pml_marginal_pass(pml_ctx* ctx, double* loglik_out, int32_t* err_parent, int
 
 // the back-trace launches (no host synchronisation), as pml_plan_backtrace lists them
 static int submit_joint_backtrace(pml_ctx* ctx) {
-    int head = 0, n_signals = 0;
+    int head = 0;
     const std::vector<PmlLaunch> plan = pml_plan_backtrace(ctx->forest, schedules_of(ctx), sweep_traits(ctx), &head);
-    auto enqueue = [&]() -> int { return run_plan(ctx, plan, false, 0, false, &n_signals); };
-    if (ctx->graphs && !ctx->profile && ctx->n_td_levels - head >= 4) {
-        PML_TRY(run_captured(ctx, ctx->bt_graph, enqueue));
-    } else {
-        PML_TRY(enqueue());
-    }
-    return PML_OK;
+    auto enqueue = [&](PmlCapture, PmlSweepOutcome* o) -> int {
+        *o = pml_plan_outcome(plan);
+        return run_plan(ctx, plan, false, 0, false);
+    };
+    PmlSweepOutcome done;   // (no launch of the back-trace signals: fetch_joint_states waits on the stream)
+    if (ctx->graphs && !ctx->profile && ctx->n_td_levels - head >= 4) return run_captured(ctx, ctx->bt_graph, CAP_NONE, enqueue, &done);
+    return enqueue(CAP_NONE, &done);
 }
 
 static int fetch_joint_states(pml_ctx* ctx, int32_t* joint_state_out) {
@@ -1684,8 +1667,8 @@ int pml_joint_pass(pml_ctx* ctx, double* loglik_out, int32_t* err_parent, int32_
     PML_TRY(require_model(ctx));
     if (!loglik_out) return fail(PML_ERR_INVALID, "loglik_out is NULL");
     // joint sweep and back-trace submitted together: one host round trip
-    PML_TRY(submit_bottom_up(ctx, 0));
-    ctx->wait_signal = false;  // (fetch_joint_states waits for both)
+    PmlSweepOutcome sweep;
+    PML_TRY(submit_bottom_up(ctx, 0, nullptr, false, CAP_NONE, &sweep));  // (fetch_joint_states waits for both)
     PML_TRY(submit_joint_backtrace(ctx));
     const int fetched = fetch_joint_states(ctx, joint_state_out);  // synchronises
     const int status = collect_bottom_up(ctx, 0, loglik_out, err_parent, err_child);
@@ -1785,8 +1768,7 @@ int pml_expected_counts(pml_ctx* ctx, int32_t col_begin, int32_t col_end, const 
         return fail(PML_ERR_INVALID, "pml_expected_counts needs a marginal pml_bottom_up and pml_top_down_marginals first");
     if (ctx->kind != PML_MODEL_F81 && ctx->k > 256)
         return fail(PML_ERR_UNSUPPORTED, "k = %d: the matrix models hold at most 256 states", ctx->k);
-    HIP_TRY(hipStreamSynchronize(ctx->stream));   // (a pass that ended in a spin on the completion word may have left the stream busy)
-    ctx->wait_signal = false;
+    PML_TRY(wait_pending(ctx, true));   // (a pass that ended in a spin on the completion word may have left the stream busy)
     PML_TRY(materialize_cherries(ctx));  // the conditional probabilities need every bottom-up vector
     PML_TRY(materialize_tip_posteriors(ctx));
     PML_TRY(run_prep(ctx));  // P(t) of every branch (the fused sweeps never materialise it) / exp(-mu t')
@@ -1991,8 +1973,7 @@ static int download_internal(pml_ctx* ctx, int what, int32_t col, void* out) {
     if (col < 0 || col >= ctx->C || !out) return fail(PML_ERR_INVALID, "bad column / output");
     // (a pass that ended in a spin on the completion word may have left the stream busy, and the blocking copies below run
     // on the NULL stream, which a non-blocking stream is not ordered with)
-    HIP_TRY(hipStreamSynchronize(ctx->stream));
-    ctx->wait_signal = false;
+    PML_TRY(wait_pending(ctx, true));
     if (what == PML_BUF_BU || what == PML_BUF_BU_SF) PML_TRY(materialize_cherries(ctx));
     const size_t N = ctx->N;
     const double nan = std::numeric_limits<double>::quiet_NaN();

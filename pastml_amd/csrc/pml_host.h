@@ -25,6 +25,10 @@
 
 struct PmlComm;  // pml_comm.h (pml_api.hip only)
 
+// How the stream is being captured while a sweep is enqueued: not at all (the sweep may replay a graph of its own), into the
+// sweep's own graph, or into the one graph of a whole marginal pass (the sweeps inside it keep no graphs of their own).
+enum PmlCapture { CAP_NONE, CAP_OWN, CAP_PASS };
+
 #define PML_VERSION 103
 
 // internal linkage across the library's translation units (not part of the C-ABI)
@@ -116,7 +120,7 @@ struct pml_ctx {
     int n_cherries = 0;
     bool bu_fused = false;  // the last bottom-up sweep left the cherries unmaterialised
     bool bu_absorbed = false;  // ... and the children of the two-level units
-    bool bu_fused_joint = false;  // ... and it was a joint sweep
+    bool bu_fused_joint = false;  // ... and it was a joint sweep (note_bottom_up, from the sweep's outcome)
 
     // columns
     int C = 0, k = 0, ks = 0, W = 0, G = 0, R = 0;
@@ -132,7 +136,6 @@ struct pml_ctx {
     bool active_partial = false;  // ... some column does (pml_bottom_up_submit_columns)
     int n_active = 0;             // columns that take part in the next sweep
     int sched_cols = 0;           // the number of columns the schedule of a sweep is chosen for (C; 32 for a few active ones)
-    bool bu_signals_few = false;
     double* d_Asym = nullptr;   // [C][k][k], 65 <= k <= 128: the one matrix of the sum sweeps (eig_sym_kernel)
     double* d_eigT = nullptr;   // [C][k][k]: scratch of that kernel
     std::vector<double> h_symA; // [C][k k + k]: the A and pi d_Asym was made from (an unchanged model is not orthonormalised again)
@@ -161,34 +164,29 @@ struct pml_ctx {
         hipGraph_t graph = nullptr;
         hipGraphExec_t exec = nullptr;
         bool has_init = false;
-        bool has_params = false;  // the captured sequence starts with the copy of the parameter block (params_push)
+        PmlSweepOutcome outcome;  // of the captured sequence (run_captured hands it out, captured just now or replayed)
     };
-    bool capture_saw_params = false;
     GraphSlot bu_graph[2], td_graph, bt_graph;
     GraphSlot bu_graph_few;        // the marginal sweep as scheduled for a few active columns (submit_bottom_up)
     GraphSlot mp_graph;            // bottom-up + top-down of pml_marginal_pass as ONE graph
-    bool in_outer_capture = false; // the sweeps are being captured into mp_graph: no graphs of their own
     bool graphs = true;
     double* h_loglik = nullptr;  // pinned staging of the per-column results
     // pi, sf, tau, tau factor, mu, kappa of all columns live in ONE device block with a pinned host mirror of the same
     // layout: a parameter update (every optimiser step) is one asynchronous copy and no synchronisation
     double *d_params = nullptr, *h_params = nullptr;
     bool params_dirty = false;  // the pinned mirror holds values the device block has not seen (params_push sends them)
-    bool capturing = false;     // a sweep's launch sequence is being captured into a graph
     size_t n_params = 0;
     u64* h_err = nullptr;
     // completion of a bottom-up sweep whose last launch is the single-workgroup-per-column kernel: that kernel raises a
     // word in pinned memory when its last column is done (bu_f81_small_kernel), and the collect spins on it
     u64* h_done = nullptr;      // pinned: generation of the last finished launch
     u64* d_done = nullptr;      // device: [0] columns done in the running launch, [1] generation
-    u64 done_expect = 0;        // what *h_done shows when the sweep submitted last has finished
-    bool bu_signals[2] = {false, false};   // per captured sweep (joint / marginal): its last launch signals
-    bool wait_signal = false;              // the sweep submitted last signals
     // the same for a whole marginal pass: its last top-down launch signals where the schedule ends in a multi-level
-    // kernel (single-launch sweeps, subtree blocks); signals_enqueued counts the signalling launches of what is being
-    // enqueued (run_plan: the bottom-up sweep's and the top-down sweep's), mp_signals / mp_final keep them for the captured pass
-    bool td_final_signals = false, mp_final = false;
-    int signals_enqueued = 0, mp_signals = 0;
+    // kernel (single-launch sweeps, subtree blocks); the word counts the signalling launches (PmlSweepOutcome::n_signals)
+    struct Pending {
+        u64 expect = 0;     // what *h_done shows when what was submitted last has finished
+        bool spin = false;  // its end raises the word and nobody has waited for it yet: wait_pending spins
+    } pending;
     bool td_valid = false, js_valid = false;
     bool keep_td = false;      // PML_OPT_KEEP_TD (or a pml_download of the TD vectors asked for them)
     bool td_vec_valid = false; // the TD vectors of the last top-down sweep are in d_td

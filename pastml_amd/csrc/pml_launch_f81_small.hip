@@ -11,7 +11,7 @@ static void launch_small_f81(pml_ctx* ctx, bool bottom_up, bool signal, int do_p
     const PmlCols c = cols_of(ctx, bottom_up);
     const PmlState st = state_of(ctx);
     dim3 grid(1, ctx->C), block(PML_SMALL_BLOCK);
-    // signal: the completion word (bu_f81_small_kernel, wait_bottom_up) for sweeps of few columns, where the host's wait is
+    // signal: the completion word (bu_f81_small_kernel, wait_pending) for sweeps of few columns, where the host's wait is
     // a tenth of the sweep (HIV1C tree, k = 12: 14 columns 0.1265 -> 0.1127 ms per sweep; at 128 columns the
     // system-scope fences in 128 workgroups cost what the spin saves: 0.203 against 0.207 ms)
     if (bottom_up)

@@ -1173,3 +1173,11 @@ std::vector<PmlLaunch> pml_plan_backtrace(const PmlForest& f, const PmlSchedules
     if (head_out) *head_out = head;
     return p.v;
 }
+
+PmlSweepOutcome pml_plan_outcome(const std::vector<PmlLaunch>& plan) {
+    PmlSweepOutcome o;
+    for (const PmlLaunch& r : plan) o.n_signals += r.signal ? 1 : 0;
+    o.final_signals = o.n_signals > 0;   // (only a plan's last launch signals)
+    o.fused_joint = !plan.empty() && plan.front().branch == BU_FUSED_JOINT;
+    return o;
+}

@@ -305,6 +305,21 @@ struct PmlLaunch {
     int first, count;
     int arg;                        // OP_LEVELS: 1 = with the per-branch prep (bottom-up) / the roots are done (top-down); OP_RESET_ERR: 1 = eigen joint
 };
+// What an enqueued launch sequence leaves behind for the host that waits for it and reads its results.  A captured graph keeps
+// the outcome of what it holds (pml_ctx::GraphSlot): a replay runs none of the code that enqueued it.
+struct PmlSweepOutcome {
+    int n_signals = 0;           // launches that raise the completion word
+    bool final_signals = false;  // the sequence's end raises it
+    bool has_params = false;     // the copy of the parameter block is part of the (captured) sequence
+    bool fused_joint = false;    // the bottom-up sweep ran the cherry-fused joint branch: the cherries are not in memory
+    // this sequence followed by `next` on the same stream
+    void then(const PmlSweepOutcome& next) {
+        n_signals += next.n_signals;
+        final_signals = next.final_signals;
+        has_params = has_params || next.has_params;
+        fused_joint = fused_joint || next.fused_joint;
+    }
+};
 // Everything the planners read besides the forest and its schedules; filled from a context by sweep_traits (pml_api.hip).
 struct PmlSweepTraits {
     bool f81, eigen_fused, eigen_gemm, eigen_joint_valu, hky_fused, wide_states;   // model kind and path
@@ -342,3 +357,5 @@ PML_PLAN PmlThinPlan pml_plan_thin_ends(const PmlForest& f, const PmlTune& tune,
 PML_PLAN std::vector<PmlLaunch> pml_plan_bottom_up(const PmlForest& f, const PmlSchedules& s, const PmlSweepTraits& t, bool is_marginal);
 PML_PLAN std::vector<PmlLaunch> pml_plan_top_down(const PmlForest& f, const PmlSchedules& s, const PmlSweepTraits& t, bool wants_signal);
 PML_PLAN std::vector<PmlLaunch> pml_plan_backtrace(const PmlForest& f, const PmlSchedules& s, const PmlSweepTraits& t, int* head);
+// the part of a plan's outcome the plan decides (has_params is the enqueuer's)
+PML_PLAN PmlSweepOutcome pml_plan_outcome(const std::vector<PmlLaunch>& plan);

@@ -1,5 +1,6 @@
 // Host-only check of the sweeps' launch plans (pastml_amd/csrc/pml_schedule.h): plans forests with pml_schedule.cpp and, over
-// a grid of PmlSweepTraits, checks every plan for coverage, order, once-only launches and the per-bracket launch counts.
+// a grid of PmlSweepTraits, checks every plan for coverage, order, once-only launches, the per-bracket launch counts and the
+// outcome the host keeps of it (pml_plan_outcome).
 // Built and run by tests/test_sweep_plan_host.py; prints FAIL lines and exits 1, or one OK line.
 #include "../pastml_amd/csrc/pml_schedule.h"
 
@@ -385,8 +386,23 @@ static void check_rules(const Planned& F, const std::vector<PmlLaunch>& plan, co
     }
 }
 
+// ---- what a plan leaves behind for the host (pml_plan_outcome): the completion word's count, the cherry-fused joint branch
+static PmlSweepOutcome check_outcome(const std::vector<PmlLaunch>& plan, bool joint_bottom_up) {
+    const PmlSweepOutcome o = pml_plan_outcome(plan);
+    int n_signal = 0;
+    for (const PmlLaunch& r : plan) n_signal += r.signal ? 1 : 0;
+    CHECK(o.n_signals == n_signal, "outcome counts %d signalling launches, the plan holds %d", o.n_signals, n_signal);
+    CHECK(o.final_signals == (n_signal > 0 && plan.back().signal), "outcome: final_signals %d with %d signal records", (int)o.final_signals, n_signal);
+    const bool fused_joint = !plan.empty() && plan.front().branch == BU_FUSED_JOINT;
+    CHECK(o.fused_joint == fused_joint, "outcome: fused_joint %d for a plan of branch %d", (int)o.fused_joint, plan.empty() ? -1 : plan.front().branch);
+    CHECK(!o.fused_joint || joint_bottom_up, "outcome: fused_joint for a plan that is no joint bottom-up sweep");
+    CHECK(!o.has_params, "outcome: a plan holds no copy of the parameter block");
+    return o;
+}
+
 static void run_case(const Planned& F, const PmlSweepTraits& t, const char* what) {
     long long got[5], want[5];
+    PmlSweepOutcome marginal_sweep;
     for (int marginal = 0; marginal < 2; ++marginal) {
         g_case = std::string(what) + (marginal ? " bottom-up marginal" : " bottom-up joint");
         const std::vector<PmlLaunch> plan = pml_plan_bottom_up(F.f, F.S, t, marginal != 0);
@@ -395,6 +411,8 @@ static void run_case(const Planned& F, const PmlSweepTraits& t, const char* what
         check_rules(F, plan, t);
         expected_counts(F, plan, t, want);
         for (int i = 0; i < 5; ++i) CHECK(got[i] == want[i], "bracket %d: %lld records, the sweep counted %lld launches", i, got[i], want[i]);
+        const PmlSweepOutcome o = check_outcome(plan, !marginal);
+        if (marginal) marginal_sweep = o;
     }
     for (int wants = 0; wants < 2; ++wants) {
         g_case = std::string(what) + " top-down";
@@ -406,11 +424,18 @@ static void run_case(const Planned& F, const PmlSweepTraits& t, const char* what
         bool signals = false;
         for (const PmlLaunch& r : plan) signals = signals || r.signal;
         CHECK(!signals || (wants && t.C <= 64 && !t.no_spin_wait), "a top-down launch signals unasked");
+        // a marginal pass: the bottom-up sweep, then this one
+        const PmlSweepOutcome td = check_outcome(plan, false);
+        PmlSweepOutcome pass = marginal_sweep;
+        pass.then(td);
+        CHECK(pass.n_signals == marginal_sweep.n_signals + td.n_signals && pass.final_signals == td.final_signals && !pass.fused_joint,
+              "the outcome of a pass: %d signals, final %d, fused_joint %d", pass.n_signals, (int)pass.final_signals, (int)pass.fused_joint);
     }
     g_case = std::string(what) + " back-trace";
     int head = -1;
     const std::vector<PmlLaunch> plan = pml_plan_backtrace(F.f, F.S, t, &head);
     if (F.nd() > 1) check_plan(F, plan, 2, false, got);
+    check_outcome(plan, false);
     CHECK(head >= 0, "no head");
 }
 

@@ -1292,6 +1292,46 @@ def test_completion_word_wait_returns_what_the_stream_wait_returns(n_tips, cols)
         assert np.array_equal(x, y)
 
 
+def test_replayed_sweep_leaves_what_the_captured_sweep_left():
+    """What a bottom-up sweep leaves behind -- here: whether the cherries' vectors were left out of memory by the
+    cherry-fused JOINT branch or by a marginal sweep -- belongs to the launch sequence, and a replayed graph runs none of the
+    code that enqueued it: marginal (capture), joint (capture), marginal (replay) must rebuild the cherries of a MARGINAL
+    sweep for a download or the counts sampler, and a joint sweep replayed after it those of a joint sweep.  The engine
+    that replays graphs against one that enqueues every sweep afresh (NO_GRAPH), bit for bit.  (Ambiguous tips: with one
+    allowed state per tip the sum and the maximum over a cherry's tips are the same number.)"""
+    k, cols, seed = 4, 2, 20261
+    rng = np.random.default_rng(1500)
+    flat = FlatForest.random(1500, seed=1500, max_arity=2, zero_frac=0.0)
+    children = np.flatnonzero(flat.parent >= 0)
+    tip_children = np.bincount(flat.parent[children], weights=flat.is_tip[children], minlength=flat.n_nodes)
+    n_cherries = int(np.sum((flat.n_children > 0) & (tip_children == flat.n_children)))
+    assert flat.n_nodes > 2048 and n_cherries > 0
+    specs = [(random_spec('F81', k, rng), (float(rng.uniform(0.5, 3)), 0.0, 1.0)) for _ in range(cols)]
+    masks = np.stack([random_masks(flat, k, rng, missing=0.2, multi=0.2, internal=0.0) for _ in range(cols)])
+    results = {}
+    for name, tune in (('graphs', {}), ('direct', dict(NO_GRAPH=1))):
+        out = []
+        with hip.Engine(flat, cols, k, tune=tune) as eng:
+            eng.set_models(specs)
+            eng.set_masks(masks)
+            # (a single-launch sweep is enqueued afresh every time: nothing would be replayed)
+            assert eng.sweep_schedule()[0] != hip.SCHEDULE_SINGLE_LAUNCH
+            out += [eng.bottom_up(True), eng.bottom_up(False), eng.bottom_up(True)]
+            for c in range(cols):
+                out += [eng.download(hip.BUF_BU, c), eng.download(hip.BUF_BU_SF, c)]
+            eng.top_down_marginals()
+            out.append(eng.marginal_counts(100, seed, col=0))
+            out.append(eng.bottom_up(False))
+            for c in range(cols):
+                # (the roots' arg-max tables are undefined: no sweep writes those rows of the device buffer)
+                out += [eng.download(hip.BUF_BU, c), eng.download(hip.BUF_BU_SF, c),
+                        np.ascontiguousarray(eng.download(hip.BUF_JOINT_TABLE, c)[flat.parent >= 0])]
+        results[name] = out
+    assert len(results['graphs']) == len(results['direct'])
+    for i, (x, y) in enumerate(zip(results['graphs'], results['direct'])):
+        assert x.shape == y.shape and x.tobytes() == y.tobytes(), i
+
+
 @pytest.mark.parametrize('k', [2, 4, 12, 64])
 def test_block_schedule_gives_the_bits_of_the_level_schedule(k):
     """Mid-size forests: subtree blocks walked by one workgroup each + the top above the cuts (a handful of launches)

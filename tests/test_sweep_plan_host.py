@@ -5,7 +5,9 @@ loaded -- and plans ten forests over a grid of PmlSweepTraits.  Every plan is ch
 in exactly one launch), order (no launch reads a vector before the launch that writes it), the once-only launches (ln L, the
 completion word) and the per-bracket launch counts the profile reported before the plans existed; over the whole input set
 every op and every schedule branch of the three planners must be reached; the narrow ends, the level kinds, the choice of the
-sorted lists, the staging hint and the completion word are checked against the rules restated in the driver.  (A sanitizer
+sorted lists, the staging hint and the completion word are checked against the rules restated in the driver; the outcome
+the host keeps of every plan (pml_plan_outcome) must count the plan's signal records and name the cherry-fused joint branch
+exactly for BU_FUSED_JOINT plans.  (A sanitizer
 build of the same driver is for running by hand: add -fsanitize=address,undefined to FLAGS.  UBSan then reports misaligned
 PmlUnit accesses inside the std::stable_sort of units_by_shape -- libstdc++'s temporary buffer ignores the 32-byte alignment --,
 which are the tree planner's, not the launch plans'.)"""
