@@ -318,6 +318,30 @@ int pml_parsimony(pml_ctx* ctx, int32_t n_cols, int32_t k, const uint64_t* given
 int pml_parsimony_info(pml_ctx* ctx, int64_t* launches, double* passes_ms);
 
 /*
+ * Vertical collapse of the uploaded forest (pastml/visualisation/tree_compressor.py: collapse_vertically :251-298 with the
+ * lists compress_tree :87-96 starts from; what the Pajek map of pajek_timing = VERTICAL shows, :34-51): a node whose state sets
+ * equal its parent's in EVERY one of the n_cols columns belongs to its parent's vertex (roots never merge; an all-zero set
+ * is the empty set, equal to another empty set).  Needs pml_tree_upload only -- no pml_chars_alloc, no model; the scratch of the
+ * call (n_cols * n_nodes * W * 8 bytes for the sets -- the columns are walked in chunks if that does not fit,
+ * PASTML_HIP_COMPRESS_MAX_COLS bounds a chunk -- plus 23 bytes per node: five int32 and three byte arrays) is released before it returns.  Integer arithmetic
+ * only: results do not depend on launch geometry, chunking or the library's numbering.  Every array is in the CALLER's
+ * numbering, and so are the node ids that top_out and parent_vertex_out hold.
+ *   sets                 [n_cols][n_nodes][W]  state sets as masks (the layout of pml_parsimony; narrower columns zero-padded)
+ *   is_polytomy          [n_nodes] or NULL     non-zero: an internal node that internal_inside_out does not count (:94)
+ *   top_out              [n_nodes]  the first node (nearest to the root) of the node's vertex; top_out[n] == n starts a vertex
+ *   tips_inside_out      [n_nodes]  at a vertex's first node: the tips of the vertex (itself included); 0 elsewhere
+ *   internal_inside_out  [n_nodes]  the same for its internal nodes that are not flagged is_polytomy
+ *   parent_vertex_out    [n_nodes]  at a vertex's first node: the first node of the vertex above, -1 for a root; -1 elsewhere
+ * The first node of a vertex is found by pointer jumping, ceil(log2(deepest node)) rounds whatever the shape of the forest.
+ * pml_compress_vertical_info: HIP-event times of the last call's passes (equality with the parent over all columns, the
+ * pointer jumping, the counts; without transfers; taken only while pml_profile_enable is on, else 0) and its number of rounds.  PASTML_HIP_COMPRESS_PLAIN_ATOMICS: one atomic
+ * per node in the counts instead of one per run of neighbouring lanes with the same vertex (for measurements).
+ */
+int pml_compress_vertical(pml_ctx* ctx, int32_t n_cols, int32_t W, const uint64_t* sets, const uint8_t* is_polytomy,
+                          int32_t* top_out, int32_t* tips_inside_out, int32_t* internal_inside_out, int32_t* parent_vertex_out);
+int pml_compress_vertical_info(pml_ctx* ctx, double* merged_ms, double* jump_ms, double* counts_ms, int32_t* rounds);
+
+/*
  * n_repetitions scenarios of column col drawn forward from the roots (pastml/utilities/state_simulator.py:6-31):
  * roots ~ pi, child ~ row (parent state) of P_n(t).  Draws keyed by (seed, caller's node id, rep_offset + r):
  * results do not depend on launch geometry, chunking or the library's internal numbering.

@@ -1851,6 +1851,29 @@ int pml_parsimony_info(pml_ctx* ctx, int64_t* launches, double* passes_ms) {
     return PML_OK;
 }
 
+// Vertical collapse of the uploaded forest by equal state sets (pml_launch_compress.hip).  Needs the tree only; the scratch of
+// the call is freed before it returns.
+int pml_compress_vertical(pml_ctx* ctx, int32_t n_cols, int32_t W, const uint64_t* sets, const uint8_t* is_polytomy,
+                          int32_t* top_out, int32_t* tips_inside_out, int32_t* internal_inside_out, int32_t* parent_vertex_out) {
+    if (!ctx || ctx->N == 0) return fail(PML_ERR_INVALID, "upload the tree first");
+    if (n_cols <= 0) return fail(PML_ERR_INVALID, "n_cols must be positive");
+    if (W <= 0) return fail(PML_ERR_INVALID, "W must be positive");
+    if (W > PML_MAX_STATES / 64) return fail(PML_ERR_UNSUPPORTED, "W = %d words; at most %d are supported", W, PML_MAX_STATES / 64);
+    if (!sets || !top_out || !tips_inside_out || !internal_inside_out || !parent_vertex_out)
+        return fail(PML_ERR_INVALID, "NULL array");
+    return launch_compress(ctx, n_cols, W, (const u64*)sets, is_polytomy, top_out, tips_inside_out, internal_inside_out,
+                           parent_vertex_out);
+}
+
+int pml_compress_vertical_info(pml_ctx* ctx, double* merged_ms, double* jump_ms, double* counts_ms, int32_t* rounds) {
+    if (!ctx) return fail(PML_ERR_INVALID, "ctx is NULL");
+    if (merged_ms) *merged_ms = ctx->compress_ms[0];
+    if (jump_ms) *jump_ms = ctx->compress_ms[1];
+    if (counts_ms) *counts_ms = ctx->compress_ms[2];
+    if (rounds) *rounds = ctx->compress_rounds;
+    return PML_OK;
+}
+
 int pml_select_states(pml_ctx* ctx, int method, int force_joint, const uint64_t* lh_mask, uint64_t* masks_out,
                       int32_t* n_states_out) {
     PML_TRY(require_model(ctx));

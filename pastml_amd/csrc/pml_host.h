@@ -207,6 +207,10 @@ struct pml_ctx {
     // parsimony (pml_launch_parsimony.hip): kernel launches and event time of the passes of the last pml_parsimony
     long long pars_launches = 0;
     double pars_ms = 0;
+    // vertical collapse (pml_launch_compress.hip): event times of the merged pass, the pointer jumping and the counts of the
+    // last pml_compress_vertical (zero unless the context profiles), and its number of jumping rounds
+    double compress_ms[3] = {0, 0, 0};
+    int compress_rounds = 0;
 
     PmlComm* comm = nullptr;   // RCCL communicator attached by pml_comm_init (survives tree uploads)
 };

@@ -148,6 +148,10 @@ PML_INTERNAL int launch_simulate(pml_ctx* ctx, int col, int n_rep, int rep_offse
 // ---- pml_launch_parsimony.hip: the parsimony passes on packed state sets (pml_parsimony); host arrays in the caller's numbering
 PML_INTERNAL int launch_parsimony(pml_ctx* ctx, int n_cols, int k, const u64* given, int methods, u64* sets_out, i64* steps_out,
                                   i64* hist_out);
+// ---- pml_launch_compress.hip: vertical collapse of the forest by equal state sets (pml_compress_vertical); host arrays in the
+//      caller's numbering
+PML_INTERNAL int launch_compress(pml_ctx* ctx, int n_cols, int W, const u64* sets, const unsigned char* is_polytomy, int* top_out,
+                                 int* tips_out, int* internal_out, int* parent_vertex_out);
 
 // ---- pml_launch_expected.hip: exact expected transition counts of the columns [cb, ce) (pml_expected_counts); d_alt [N] in the
 //      library's numbering or null, d_out [cols][k][k], d_same [cols][N][k] in the caller's numbering (zeroed) or null

@@ -112,6 +112,9 @@ SIGNATURES = {
     'pml_parsimony': [_ctx_p, ctypes.c_int32, ctypes.c_int32, _c_uint64_p, ctypes.c_int, _c_uint64_p,
                       ctypes.POINTER(ctypes.c_int64), ctypes.POINTER(ctypes.c_int64)],
     'pml_parsimony_info': [_ctx_p, ctypes.POINTER(ctypes.c_int64), _c_double_p],
+    'pml_compress_vertical': [_ctx_p, ctypes.c_int32, ctypes.c_int32, _c_uint64_p, ctypes.POINTER(ctypes.c_uint8), _c_int32_p,
+                              _c_int32_p, _c_int32_p, _c_int32_p],
+    'pml_compress_vertical_info': [_ctx_p, _c_double_p, _c_double_p, _c_double_p, _c_int32_p],
     'pml_download': [_ctx_p, ctypes.c_int, ctypes.c_int32, ctypes.c_void_p],
     'pml_comm_unique_id': [ctypes.POINTER(ctypes.c_ubyte)],
     'pml_comm_init': [_ctx_p, ctypes.c_int, ctypes.c_int, ctypes.POINTER(ctypes.c_ubyte)],
@@ -830,6 +833,37 @@ class Engine(BareContext):
         launches, ms = ctypes.c_int64(0), ctypes.c_double(0)
         _check(self._lib.pml_parsimony_info(self._ctx, ctypes.byref(launches), ctypes.byref(ms)))
         return launches.value, ms.value
+
+    def compress_vertical(self, sets, is_polytomy=None):
+        """
+        Vertical collapse of the forest by equal state sets (pml_compress_vertical).  sets: uint64 [n, N, W] state sets of the
+        n columns (narrower columns zero-padded); is_polytomy: bool [N] or None, internal nodes that the counts leave out.
+        Returns (top, tips_inside, internal_inside, parent_vertex), int32 [N] each, node ids in the forest's own numbering:
+        top[i] is the first node of node i's vertex, the other three are filled at the first nodes (0 / -1 elsewhere).  Works
+        on any context with a tree, whatever its columns.
+        """
+        sets = _as(sets, np.uint64)
+        if sets.ndim == 2:
+            sets = sets[None]
+        if sets.ndim != 3 or sets.shape[1] != self.n_nodes or sets.shape[0] < 1 or sets.shape[2] < 1:
+            raise ValueError('sets must be [n, {}, W], got {}'.format(self.n_nodes, sets.shape))
+        flags = None
+        if is_polytomy is not None:
+            flags = _as(np.asarray(is_polytomy).astype(bool), np.uint8)
+            if flags.shape != (self.n_nodes,):
+                raise ValueError('is_polytomy must be [{}], got {}'.format(self.n_nodes, flags.shape))
+        out = [np.empty(self.n_nodes, dtype=np.int32) for _ in range(4)]
+        _check(self._lib.pml_compress_vertical(self._ctx, sets.shape[0], sets.shape[2], _ptr(sets, ctypes.c_uint64),
+                                               _ptr(flags, ctypes.c_uint8) if flags is not None else None,
+                                               *[_ptr(o, ctypes.c_int32) for o in out]))
+        return tuple(out)
+
+    def compress_vertical_info(self):
+        """(ms of the merged pass, of the pointer jumping, of the counts -- HIP events, taken after ``profile_enable()``, else
+        0 --, jumping rounds) of the last ``compress_vertical`` call."""
+        a, b, c, r = ctypes.c_double(0), ctypes.c_double(0), ctypes.c_double(0), ctypes.c_int32(0)
+        _check(self._lib.pml_compress_vertical_info(self._ctx, ctypes.byref(a), ctypes.byref(b), ctypes.byref(c), ctypes.byref(r)))
+        return a.value, b.value, c.value, r.value
 
     def download(self, what, col=0):
         N, k = self.n_nodes, self.k

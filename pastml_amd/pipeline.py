@@ -10,9 +10,15 @@ formats and under the reference's file names, so that the outputs are interchang
 * ``named.tree_<tree>.nwk``                                  the input tree(s) with every node named
 
 With ``resolve_polytomies`` acr() resolves polytomies from the predictions (pastml/acr.py:234-278): the new nodes
-``<parent>.polytomy_<states>`` are rows of the tables and nodes of the named tree.  HTML maps, iTOL upload, pajek and
-dates / timelines belong to PastML's visualisation layer (out of scope): asking for them raises
-NotImplementedError.  (The parsimony methods and COPY are host-side array passes of acr(); they run here too.)
+``<parent>.polytomy_<states>`` are rows of the tables and nodes of the named tree.  With ``pajek=<path>`` the compressed tree
+of the run -- every connected region of nodes with the same states in all result columns as one vertex, the vertical step
+of pastml/visualisation/tree_compressor.py, collapsed on the GPU (pastml_amd.visualisation.tree_compressor) -- is written as
+a Pajek network, the file of the reference's default ``pajek_timing='VERTICAL'``.  The reference only reaches its Pajek
+writer when ``html_compressed`` is asked for as well (cytoscape_manager.py:801-807); here ``pajek`` alone is enough.  The later
+timings (HORIZONTAL, TRIM: horizontal merging and trimming), HTML maps, focus / mixed mode, iTOL upload and dates / timelines
+belong to PastML's visualisation layer (out of scope): asking for them raises NotImplementedError, and
+so does ``pajek`` under a multi-process launch, where each rank has only its own columns.  (The parsimony methods and COPY
+are array passes of acr(); they run here too.)
 """
 import logging
 import os
@@ -326,19 +332,37 @@ def pastml_pipeline(tree, data=None, data_sep='\t', id_index=0, columns=None, pr
     """
     Reads tree(s) and annotations, reconstructs the ancestral states of all the characters in one batched ``acr()`` call
     on the GPU and writes the result tables into ``work_dir`` (default ``<tree>_pastml``).  Arguments as in
-    pastml/acr.py:316-327; those of the visualisation layer (html*, iTOL, colours, focus, timeline, pajek, root_date) are
-    not available here.  Returns the list of result dictionaries.
+    pastml/acr.py:316-327; those of the visualisation layer (html*, iTOL, colours, focus, timeline, root_date) are not
+    available here, except ``pajek`` with ``pajek_timing`` None or 'VERTICAL': the vertically compressed tree as a Pajek
+    network.  Returns the list of result dictionaries.
     """
     logger = logging.getLogger('pastml')
     if verbose:
         logging.basicConfig(level=logging.DEBUG, format='%(asctime)s: %(message)s', datefmt='%H:%M:%S')
         logger.setLevel(logging.DEBUG)
     asked = [name for name, value in (('html', html), ('html_compressed', html_compressed), ('html_mixed', html_mixed),
-                                       ('upload_to_itol', upload_to_itol), ('pajek', pajek), ('root_date', root_date))
+                                       ('upload_to_itol', upload_to_itol), ('root_date', root_date))
              if value]
     if asked:
         raise NotImplementedError('{}: visualisation and dating are PastML\'s own layers; this pipeline '
-                                  'covers tree + table -> reconstruction -> result tables'.format(', '.join(asked)))
+                                  'covers tree + table -> reconstruction -> result tables (and the Pajek network of the '
+                                  'vertically compressed tree: pajek=)'.format(', '.join(asked)))
+    if pajek:
+        from pastml_amd.visualisation.tree_compressor import VERTICAL, HORIZONTAL, TRIM
+        if pajek_timing is None:
+            pajek_timing = VERTICAL
+        if pajek_timing in (HORIZONTAL, TRIM):
+            raise NotImplementedError('pajek_timing={}: only the vertical collapse is implemented ({}); horizontal merging '
+                                      '({}) and trimming ({}) are not'.format(pajek_timing, VERTICAL, HORIZONTAL, TRIM))
+        if pajek_timing != VERTICAL:
+            raise ValueError('pajek_timing must be one of {}, {} or {}, not {!r}'.format(VERTICAL, HORIZONTAL, TRIM, pajek_timing))
+        from pastml_amd import sharding
+        comm = sharding.communicator()
+        if comm is not None and comm.world > 1:
+            # every rank holds only its own block of the characters, while a vertex is a region that agrees in all of them
+            raise NotImplementedError('pajek is not supported under a multi-process launch ({} ranks): the tree is '
+                                      'compressed over the predictions of all characters, and each rank has only its own; '
+                                      'run it in a single process'.format(comm.world))
     copy_only = COPY == prediction_method or (isinstance(prediction_method, list)
                                               and all(COPY == _ for _ in prediction_method))
     # the trees are this function's own from reading to writing (polytomy resolution edits them, and re-derives the
@@ -346,12 +370,12 @@ def pastml_pipeline(tree, data=None, data_sep='\t', id_index=0, columns=None, pr
     with trusted_flat_cache():
         return _pipeline(tree, data, data_sep, id_index, columns, prediction_method, model, parameters, rate_matrix,
                          out_data, work_dir, forced_joint, threads, reoptimise, smoothing, frequency_smoothing, copy_only,
-                         resolve_polytomies)
+                         resolve_polytomies, pajek)
 
 
 def _pipeline(tree, data, data_sep, id_index, columns, prediction_method, model, parameters, rate_matrix, out_data,
               work_dir, forced_joint, threads, reoptimise, smoothing, frequency_smoothing, copy_only,
-              resolve_polytomies=False):
+              resolve_polytomies=False, pajek=None):
     roots, columns, column2states, parameters, rates = \
         validate_input(tree, columns, data, data_sep, id_index, copy_only=copy_only, parameters=parameters,
                        rates=rate_matrix)
@@ -380,4 +404,12 @@ def _pipeline(tree, data, data_sep, id_index, columns, prediction_method, model,
             f.write('\n'.join(root.write() for root in roots))
     for r in results:
         _serialize_acr((r, work_dir))
+    if pajek:
+        # the compressed tree over ALL result columns, meta-method suffixes included (cytoscape_manager.py:801-807)
+        from pastml_amd.visualisation.tree_compressor import collapse_vertically, save_to_pajek
+        result_states = {r[CHARACTER]: r[STATES] for r in results}
+        compressed = collapse_vertically(roots, characters, result_states)
+        save_to_pajek(compressed, characters, pajek)
+        logging.getLogger('pastml').debug('Wrote the vertically compressed tree ({} vertices) to {}.'
+                                          .format(compressed.n_vertices, pajek))
     return results
