@@ -342,6 +342,38 @@ int pml_compress_vertical(pml_ctx* ctx, int32_t n_cols, int32_t W, const uint64_
 int pml_compress_vertical_info(pml_ctx* ctx, double* merged_ms, double* jump_ms, double* counts_ms, int32_t* rounds);
 
 /*
+ * One pass of the horizontal merging of a vertically compressed forest (pastml/visualisation/tree_compressor.py:
+ * collapse_horizontally :164-211): among the live children of every vertex, those of one configuration class collapse into the
+ * first of them in child order.  The class of a vertex is (bin, its state sets in all n_cols columns, the SET of (width, class)
+ * of its surviving children) -- its own width is no part of it -- and is labelled exactly, level by level from the deepest
+ * vertices up, by hash-consing integer pairs in a device table with 64-bit compare-and-swap: the hash chooses where to look,
+ * equality is that of the full pair.  The table is sized before the pass from the numbers of vertices, columns and words (twice
+ * the pairs a pass can make; 8 bytes a slot); a full table is an error, not a wait.  The ctx supplies the device and the stream;
+ * the uploaded forest is not used, and the scratch of the call is released before it returns.  Integer arithmetic only: the
+ * results do not depend on the launch geometry or on the order in which lanes reach the table.
+ *   parent     [n_vertices]  row of the vertex above, -1 for a root (roots never merge); the parent of a live vertex is live
+ *   rank       [n_vertices]  >= 0, child order among the siblings (any increasing key; distinct among siblings)
+ *   bin        [n_vertices]  >= 0
+ *   width_in   [n_vertices]  >= 1 where live
+ *   live_in    [n_vertices]  non-zero: the vertex takes part; the others are passed over (into = itself, live = 0, width = width_in)
+ *   sets       [n_cols][n_vertices][W]  state sets as masks, narrower columns zero-padded; W <= 8
+ *   into_out   [n_vertices]  the row the vertex merged into, itself if it stays
+ *   live_out   [n_vertices]  1 if the vertex is live afterwards: it did not merge into a sibling, nor did a vertex above it
+ *   width_out  [n_vertices]  the sum of the widths of its group at a group's first vertex, width_in elsewhere
+ *   groups_out               groups of two or more, or NULL
+ * The children of a vertex are put in order by (width, class): a lane's insertion sort up to 16 children, a workgroup's
+ * bitonic sort in LDS up to the tile that pml_compress_horizontal_info reports, in global scratch beyond it -- any arity.
+ * pml_compress_horizontal_info: HIP-event times of the last call (labelling of the states, the level loop, the pass that takes
+ * the vertices below a merged one out; without transfers; taken only while pml_profile_enable is on, else 0), its levels (depths
+ * of the vertex forest), kernel launches (at most two per level, plus 3 + ceil(log2(levels))), table slots, and the LDS tile.
+ */
+int pml_compress_horizontal(pml_ctx* ctx, int32_t n_vertices, int32_t n_cols, int32_t W, const int32_t* parent, const int32_t* rank,
+                            const int32_t* bin, const int32_t* width_in, const uint8_t* live_in, const uint64_t* sets,
+                            int32_t* into_out, uint8_t* live_out, int32_t* width_out, int32_t* groups_out);
+int pml_compress_horizontal_info(pml_ctx* ctx, double* states_ms, double* levels_ms, double* down_ms, int32_t* levels,
+                                 int64_t* launches, int64_t* table_slots, int32_t* sort_tile);
+
+/*
  * n_repetitions scenarios of column col drawn forward from the roots (pastml/utilities/state_simulator.py:6-31):
  * roots ~ pi, child ~ row (parent state) of P_n(t).  Draws keyed by (seed, caller's node id, rep_offset + r):
  * results do not depend on launch geometry, chunking or the library's internal numbering.

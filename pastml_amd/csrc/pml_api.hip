@@ -1874,6 +1874,35 @@ int pml_compress_vertical_info(pml_ctx* ctx, double* merged_ms, double* jump_ms,
     return PML_OK;
 }
 
+// One pass of the horizontal merging over a forest of vertices given as arrays (pml_launch_compress_horizontal.hip).  The
+// context supplies the device and the stream; the uploaded forest is not used.  The scratch of the call is freed before it returns.
+int pml_compress_horizontal(pml_ctx* ctx, int32_t n_vertices, int32_t n_cols, int32_t W, const int32_t* parent, const int32_t* rank,
+                            const int32_t* bin, const int32_t* width_in, const uint8_t* live_in, const uint64_t* sets,
+                            int32_t* into_out, uint8_t* live_out, int32_t* width_out, int32_t* groups_out) {
+    if (!ctx) return fail(PML_ERR_INVALID, "ctx is NULL");
+    if (n_vertices <= 0) return fail(PML_ERR_INVALID, "n_vertices must be positive");
+    if (n_cols <= 0) return fail(PML_ERR_INVALID, "n_cols must be positive");
+    if (W <= 0) return fail(PML_ERR_INVALID, "W must be positive");
+    if (W > PML_MAX_STATES / 64) return fail(PML_ERR_UNSUPPORTED, "W = %d words; at most %d are supported", W, PML_MAX_STATES / 64);
+    if (!parent || !rank || !bin || !width_in || !live_in || !sets || !into_out || !live_out || !width_out)
+        return fail(PML_ERR_INVALID, "NULL array");
+    return launch_compress_horizontal(ctx, n_vertices, n_cols, W, parent, rank, bin, width_in, live_in, (const u64*)sets, into_out,
+                                      live_out, width_out, groups_out);
+}
+
+int pml_compress_horizontal_info(pml_ctx* ctx, double* states_ms, double* levels_ms, double* down_ms, int32_t* levels,
+                                 int64_t* launches, int64_t* table_slots, int32_t* sort_tile) {
+    if (!ctx) return fail(PML_ERR_INVALID, "ctx is NULL");
+    if (states_ms) *states_ms = ctx->hz_ms[0];
+    if (levels_ms) *levels_ms = ctx->hz_ms[1];
+    if (down_ms) *down_ms = ctx->hz_ms[2];
+    if (levels) *levels = ctx->hz_levels;
+    if (launches) *launches = ctx->hz_launches;
+    if (table_slots) *table_slots = ctx->hz_slots;
+    if (sort_tile) *sort_tile = PML_HZ_SORT_TILE;
+    return PML_OK;
+}
+
 int pml_select_states(pml_ctx* ctx, int method, int force_joint, const uint64_t* lh_mask, uint64_t* masks_out,
                       int32_t* n_states_out) {
     PML_TRY(require_model(ctx));

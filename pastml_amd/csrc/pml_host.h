@@ -211,6 +211,11 @@ struct pml_ctx {
     // last pml_compress_vertical (zero unless the context profiles), and its number of jumping rounds
     double compress_ms[3] = {0, 0, 0};
     int compress_rounds = 0;
+    // horizontal merging (pml_launch_compress_horizontal.hip), last pml_compress_horizontal: event times of the labelling of the
+    // states, the level loop and the pass down (zero unless the context profiles), levels, kernel launches, slots of the table
+    double hz_ms[3] = {0, 0, 0};
+    int hz_levels = 0;
+    long long hz_launches = 0, hz_slots = 0;
 
     PmlComm* comm = nullptr;   // RCCL communicator attached by pml_comm_init (survives tree uploads)
 };

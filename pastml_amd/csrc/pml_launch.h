@@ -152,6 +152,12 @@ PML_INTERNAL int launch_parsimony(pml_ctx* ctx, int n_cols, int k, const u64* gi
 //      caller's numbering
 PML_INTERNAL int launch_compress(pml_ctx* ctx, int n_cols, int W, const u64* sets, const unsigned char* is_polytomy, int* top_out,
                                  int* tips_out, int* internal_out, int* parent_vertex_out);
+// ---- pml_launch_compress_horizontal.hip: one pass of the horizontal merging over a forest of V vertices
+//      (pml_compress_horizontal); host arrays, rows of the vertex forest
+#define PML_HZ_SORT_TILE 1024   // children of one vertex that a workgroup sorts in LDS (pml_compress_horizontal_info reports it)
+PML_INTERNAL int launch_compress_horizontal(pml_ctx* ctx, int V, int n_cols, int W, const int* parent, const int* rank, const int* bin,
+                                            const int* width_in, const unsigned char* live_in, const u64* sets, int* into_out,
+                                            unsigned char* live_out, int* width_out, int* groups_out);
 
 // ---- pml_launch_expected.hip: exact expected transition counts of the columns [cb, ce) (pml_expected_counts); d_alt [N] in the
 //      library's numbering or null, d_out [cols][k][k], d_same [cols][N][k] in the caller's numbering (zeroed) or null

@@ -115,6 +115,11 @@ SIGNATURES = {
     'pml_compress_vertical': [_ctx_p, ctypes.c_int32, ctypes.c_int32, _c_uint64_p, ctypes.POINTER(ctypes.c_uint8), _c_int32_p,
                               _c_int32_p, _c_int32_p, _c_int32_p],
     'pml_compress_vertical_info': [_ctx_p, _c_double_p, _c_double_p, _c_double_p, _c_int32_p],
+    'pml_compress_horizontal': [_ctx_p, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, _c_int32_p, _c_int32_p, _c_int32_p,
+                                _c_int32_p, ctypes.POINTER(ctypes.c_uint8), _c_uint64_p, _c_int32_p,
+                                ctypes.POINTER(ctypes.c_uint8), _c_int32_p, _c_int32_p],
+    'pml_compress_horizontal_info': [_ctx_p, _c_double_p, _c_double_p, _c_double_p, _c_int32_p, ctypes.POINTER(ctypes.c_int64),
+                                     ctypes.POINTER(ctypes.c_int64), _c_int32_p],
     'pml_download': [_ctx_p, ctypes.c_int, ctypes.c_int32, ctypes.c_void_p],
     'pml_comm_unique_id': [ctypes.POINTER(ctypes.c_ubyte)],
     'pml_comm_init': [_ctx_p, ctypes.c_int, ctypes.c_int, ctypes.POINTER(ctypes.c_ubyte)],
@@ -864,6 +869,52 @@ class Engine(BareContext):
         a, b, c, r = ctypes.c_double(0), ctypes.c_double(0), ctypes.c_double(0), ctypes.c_int32(0)
         _check(self._lib.pml_compress_vertical_info(self._ctx, ctypes.byref(a), ctypes.byref(b), ctypes.byref(c), ctypes.byref(r)))
         return a.value, b.value, c.value, r.value
+
+    def compress_horizontal(self, parent, rank, bins, width, live, sets):
+        """
+        One pass of the horizontal merging over a forest of V vertices given as arrays (pml_compress_horizontal; the forest this
+        context holds is not used).  parent, rank, bins, width: int32 [V] (row of the vertex above or -1, child order among the
+        siblings, the bin, the width in); live: bool [V]; sets: uint64 [n, V, W] state sets of the n columns, W <= 8.
+        Returns (into int32 [V], live bool [V], width int32 [V], groups merged): the row every vertex merged into (itself if it
+        stays), whether it is live afterwards, its width out.
+        """
+        parent = _as(parent, np.int32)
+        V = parent.shape[0] if parent.ndim == 1 else -1
+        if V < 1:
+            raise ValueError('parent must be [V] with V >= 1, got {}'.format(parent.shape))
+        rank, bins, width = _as(rank, np.int32), _as(bins, np.int32), _as(width, np.int32)
+        flags = _as(np.asarray(live).astype(bool), np.uint8)
+        for name, array in (('rank', rank), ('bins', bins), ('width', width), ('live', flags)):
+            if array.shape != (V,):
+                raise ValueError('{} must be [{}], got {}'.format(name, V, array.shape))
+        sets = _as(sets, np.uint64)
+        if sets.ndim == 2:
+            sets = sets[None]
+        if sets.ndim != 3 or sets.shape[1] != V or sets.shape[0] < 1 or sets.shape[2] < 1:
+            raise ValueError('sets must be [n, {}, W], got {}'.format(V, sets.shape))
+        into, width_out = np.empty(V, dtype=np.int32), np.empty(V, dtype=np.int32)
+        live_out = np.empty(V, dtype=np.uint8)
+        groups = ctypes.c_int32(0)
+        _check(self._lib.pml_compress_horizontal(self._ctx, V, sets.shape[0], sets.shape[2], _ptr(parent, ctypes.c_int32),
+                                                 _ptr(rank, ctypes.c_int32), _ptr(bins, ctypes.c_int32),
+                                                 _ptr(width, ctypes.c_int32), _ptr(flags, ctypes.c_uint8),
+                                                 _ptr(sets, ctypes.c_uint64), _ptr(into, ctypes.c_int32),
+                                                 _ptr(live_out, ctypes.c_uint8), _ptr(width_out, ctypes.c_int32),
+                                                 ctypes.byref(groups)))
+        return into, live_out.astype(bool), width_out, groups.value
+
+    def compress_horizontal_info(self):
+        """dict of the last ``compress_horizontal`` call: ``ms`` (labelling of the states, level loop, pass down -- HIP events,
+        taken after ``profile_enable()``, else 0), ``levels`` (depths of the vertex forest), ``launches``, ``table_slots`` and
+        ``sort_tile`` (children of one vertex that are sorted in LDS; more go through global scratch)."""
+        a, b, c = ctypes.c_double(0), ctypes.c_double(0), ctypes.c_double(0)
+        levels, tile = ctypes.c_int32(0), ctypes.c_int32(0)
+        launches, slots = ctypes.c_int64(0), ctypes.c_int64(0)
+        _check(self._lib.pml_compress_horizontal_info(self._ctx, ctypes.byref(a), ctypes.byref(b), ctypes.byref(c),
+                                                      ctypes.byref(levels), ctypes.byref(launches), ctypes.byref(slots),
+                                                      ctypes.byref(tile)))
+        return dict(ms=(a.value, b.value, c.value), levels=levels.value, launches=launches.value, table_slots=slots.value,
+                    sort_tile=tile.value)
 
     def download(self, what, col=0):
         N, k = self.n_nodes, self.k

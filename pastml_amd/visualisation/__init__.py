@@ -1,1 +1,1 @@
-"""What this project has of PastML's visualisation layer: the vertical step of the tree compressor and its Pajek network."""
+"""What this project has of PastML's visualisation layer: the vertical and horizontal steps of the tree compressor and their Pajek network."""

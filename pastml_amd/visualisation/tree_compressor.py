@@ -1,7 +1,8 @@
 """
-The compressed tree of a reconstruction, vertical step (pastml/visualisation/tree_compressor.py: ``collapse_vertically``
-:251-298 on the lists ``compress_tree`` :87-96 starts from), and its Pajek network (``_tree2pajek_vertices_arcs`` :34-51,
-``save_to_pajek`` :54-80) -- what the reference writes at its default ``pajek_timing='VERTICAL'``.
+The compressed tree of a reconstruction: the vertical step (pastml/visualisation/tree_compressor.py: ``collapse_vertically``
+:251-298 on the lists ``compress_tree`` :87-96 starts from), the horizontal step (``collapse_horizontally`` :164-211, the two
+calls of ``compress_tree`` :102-116) and the Pajek network (``_tree2pajek_vertices_arcs`` :34-51, ``save_to_pajek`` :54-80) --
+what the reference writes at ``pajek_timing='VERTICAL'`` (its default) and ``'HORIZONTAL'``.
 
 Every connected region of the forest whose nodes carry the same state sets in ALL columns becomes one vertex; the arcs
 between vertices are the state changes.  As arrays: node n is *merged* iff it has a parent and its sets equal the parent's
@@ -16,7 +17,17 @@ final children BEHIND the children that stay, so a vertex's children come in the
 pre-order and emitting each member's non-member children: vertex v sorts among its siblings by
 ``(pre[parent[top_v]], pre[top_v])``.
 
-Horizontal merging, trimming, focus / mixed mode (the rest of ``compress_tree``) are not implemented.
+Horizontal merging folds equal sibling configurations into one vertex with a width.  It is a bottom-up canonical labelling
+of subtrees: the class of a vertex is (bin, its states in all columns, the set of (width, class) of its surviving children),
+and among the children of a vertex those of one class collapse into the first.  One pass is one call into the HIP library
+(``Engine.compress_horizontal``: exact hash-consing in a device table, level by level); ``horizontal_pass_host`` restates it
+with ``np.unique`` / ``np.lexsort``.  The reference keys its cache of configurations by node NAME and so conflates vertices
+with duplicate or empty names; here the key is the vertex itself.
+
+Trimming (``pajek_timing='TRIM'``), focus / mixed mode (the rest of ``compress_tree``) are not implemented.
+
+    python -m pastml_amd.visualisation.tree_compressor --tree NAMED_TREE --states COMBINED_TABLE --pajek OUT
+           [--columns ...] [--pajek_timing VERTICAL|HORIZONTAL] [--tip_size_threshold N]
 """
 import logging
 
@@ -251,10 +262,14 @@ def _state_strings(states, words):
 
 def pajek_lines(compressed, columns=None):
     """
+    (vertex lines, arc lines) of a :class:`CompressedForest` (below) or a :class:`HorizontalForest` (``_horizontal_lines``).
+
     (vertex lines, arc lines) of the reference's ``_tree2pajek_vertices_arcs`` at vertical timing, the trees of the forest
     in turn with ids that continue.  ``<tips>`` joins the tips inside by ';': at this timing the reference's TIPS_INSIDE is
     still a flat list, so its outer ';'.join runs over single tips.
     """
+    if isinstance(compressed, HorizontalForest):
+        return _horizontal_lines(compressed, columns)
     columns = sorted(compressed.columns if columns is None else columns)
     V = compressed.n_vertices
     by_rank = np.empty(V, dtype=np.int64)
@@ -293,7 +308,7 @@ def save_to_pajek(compressed, columns, path):
     <id> "<vertex_name>" "<tips_inside>" "<column1>:<state(s)>" ["<column2>:<state(s)>" ...]
     ...
     *arcs
-    <source_id> <target_id> 1
+    <source_id> <target_id> <width of the target: 1 in a vertical map>
     ...
 
     (no newline after the last arc).  ``columns``: those to list, sorted by name; None for all of the collapse.
@@ -305,3 +320,279 @@ def save_to_pajek(compressed, columns, path):
         f.write('\n')
         f.write('*arcs\n')
         f.write('\n'.join(arcs))
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# horizontal merging
+# ---------------------------------------------------------------------------------------------------------------------
+REASONABLE_NUMBER_OF_TIPS = 15
+
+
+class HorizontalForest(object):
+    """
+    The horizontally merged forest, one entry per LIVE vertex in Pajek (pre-)order:
+
+        compressed         the :class:`CompressedForest` it was merged from
+        vertex             int64[L]      row of the live vertex in ``compressed`` (its name and states are the entry's)
+        width              int64[L]      configurations merged into it (the weight of the arc that enters it)
+        parent             int64[L]      entry of the vertex above, -1 for a root
+        n_tips_total       int64[L]      tips inside over all its configurations
+        members            int64[M]      rows of ``compressed``, the configurations of each entry in the reference's order
+        member_offsets     int64[L + 1]  where the members of each entry begin
+        merged_groups      [pass 1, pass 2]  groups of two or more that each pass merged
+        second_pass        bool[n_trees]     the trees that got the pass over decades of sizes
+    """
+
+    def __init__(self, **fields):
+        self.__dict__.update(fields)
+
+    @property
+    def n_vertices(self):
+        return len(self.vertex)
+
+
+def _rows_as_ids(rows):
+    """int64[n]: equal numbers for equal rows of an integer matrix [n, m], and only for those."""
+    if rows.shape[0] == 0:
+        return np.zeros(0, dtype=np.int64)
+    if rows.shape[1] == 0:
+        return np.zeros(rows.shape[0], dtype=np.int64)
+    return np.asarray(np.unique(rows, axis=0, return_inverse=True)[1]).reshape(-1).astype(np.int64)
+
+
+def vertex_depths(parent, live):
+    """int64[V]: branches between a live vertex and its root (0 for the others), by pointer jumping."""
+    depth = ((parent >= 0) & live).astype(np.int64)
+    above = np.where(live, parent, -1)
+    while (above >= 0).any():
+        on = np.flatnonzero(above >= 0)
+        depth[on] += depth[above[on]]
+        above[on] = above[above[on]]
+    return depth
+
+
+def horizontal_pass_host(parent, rank, bins, width, live, sets):
+    """
+    The numpy restatement of pml_compress_horizontal: one pass over a vertex forest, (into int32[V], live bool[V],
+    width int32[V], groups merged).  Level by level from the deepest vertices up; the classes of a level are rows made equal by
+    ``np.unique`` (the child lists of one length at a time, as one matrix), the sibling groups one ``np.lexsort``.  No bound on W.
+    """
+    parent = np.asarray(parent, dtype=np.int64)
+    rank = np.asarray(rank, dtype=np.int64)
+    bins = np.asarray(bins, dtype=np.int64)
+    live = np.asarray(live, dtype=bool)
+    V = len(parent)
+    w = np.asarray(width, dtype=np.int64).copy()
+    sets = np.asarray(sets, dtype=np.uint64)
+    depth = vertex_depths(parent, live)
+    sclass = np.zeros(V, dtype=np.int64)
+    sclass[live] = _rows_as_ids(np.moveaxis(sets, 0, 1).reshape(V, -1)[live].view(np.int64))
+    cls = np.zeros(V, dtype=np.int64)
+    stays = live.copy()               # not merged into a sibling
+    into = np.arange(V, dtype=np.int64)
+    groups = 0
+    ids = np.flatnonzero(live)
+    ids = ids[np.argsort(depth[ids], kind='stable')]
+    n_levels = int(depth[ids[-1]]) + 1 if len(ids) else 0
+    bounds = np.searchsorted(depth[ids], np.arange(n_levels + 1))
+    pos = np.full(V, -1, dtype=np.int64)
+    for d in range(n_levels - 1, -1, -1):
+        L = ids[bounds[d]:bounds[d + 1]]
+        below = ids[bounds[d + 1]:bounds[d + 2]] if d + 1 < n_levels else ids[:0]
+        C = below[stays[below]]
+        pos[L] = np.arange(len(L))
+        # the children of every vertex of the level in canonical order, as numbers of their (width, class)
+        o = np.lexsort((cls[C], w[C], pos[parent[C]]))
+        C = C[o]
+        item = _rows_as_ids(np.stack([w[C], cls[C]], axis=1))
+        arity = np.bincount(pos[parent[C]], minlength=len(L))
+        start = np.cumsum(arity) - arity
+        child_sig = np.zeros(len(L), dtype=np.int64)
+        for a in np.unique(arity):
+            if a:
+                sel = np.flatnonzero(arity == a)
+                child_sig[sel] = _rows_as_ids(item[start[sel][:, None] + np.arange(a)[None, :]])
+        cls[L] = _rows_as_ids(np.stack([bins[L], sclass[L], arity, child_sig], axis=1))
+        # siblings of one class: the first in child order takes them all
+        M = L[parent[L] >= 0]
+        if len(M):
+            M = M[np.lexsort((rank[M], cls[M], parent[M]))]
+            new = np.concatenate(([True], (parent[M][1:] != parent[M][:-1]) | (cls[M][1:] != cls[M][:-1])))
+            starts = np.flatnonzero(new)
+            first = M[starts][np.cumsum(new) - 1]
+            into[M] = first
+            stays[M] = M == first
+            w[M[starts]] = np.add.reduceat(w[M], starts)
+            groups += int((np.diff(np.concatenate((starts, [len(M)]))) > 1).sum())
+    gone = live & ~stays
+    for d in range(1, n_levels):
+        L = ids[bounds[d]:bounds[d + 1]]
+        gone[L] |= gone[parent[L]]
+    return into.astype(np.int32), live & ~gone, w.astype(np.int32), groups
+
+
+def _pass_runner(compressed, sets, device, engine):
+    """(function of (bins, width, live) that runs one pass, function that releases what it holds): device selection as in
+    ``collapse_arrays``."""
+    from pastml_amd import hip
+    parent = compressed.parent.astype(np.int32)
+    rank = compressed.order.astype(np.int32)
+    fits = sets.shape[2] <= MAX_DEVICE_WORDS
+    if device is None and engine is None:
+        device = fits and _device_ready()
+        if not fits:
+            logging.getLogger('pastml').debug('Horizontal merging on the host: sets of {} words, the device path takes at most {}.'
+                                              .format(sets.shape[2], MAX_DEVICE_WORDS))
+    if device is False and engine is None:
+        return (lambda bins, width, live: horizontal_pass_host(parent, rank, bins, width, live, sets)), (lambda: None)
+    if not fits:
+        raise ValueError('sets of {} words: the device path of the horizontal merging takes at most {} (512 states); '
+                         'device=False has no bound'.format(sets.shape[2], MAX_DEVICE_WORDS))
+    if engine is not None:
+        return (lambda bins, width, live: engine.compress_horizontal(parent, rank, bins, width, live, sets)), (lambda: None)
+    own = hip.Engine.tree_only(compressed.flat, device=None if device is True or device is None else int(device))
+    return (lambda bins, width, live: own.compress_horizontal(parent, rank, bins, width, live, sets)), own.close
+
+
+def collapse_horizontally(compressed, tip_size_threshold=REASONABLE_NUMBER_OF_TIPS, can_merge_diff_sizes=True, device=None,
+                          engine=None):
+    """
+    The horizontal merging of a :class:`CompressedForest` as ``compress_tree`` :102-116 does it, every tree on its own: a pass
+    with the number of tips inside as the bin, then -- for the trees that still have more than ``tip_size_threshold`` leaf
+    vertices, if ``can_merge_diff_sizes`` -- a pass with the decade of the mean number of tips per configuration.  Returns a
+    :class:`HorizontalForest`.  device / engine: as for ``collapse_vertically`` (the engine is used for its device and stream).
+    """
+    V = compressed.n_vertices
+    parent = compressed.parent
+    tree = compressed.tree
+    n_trees = int(tree.max()) + 1 if V else 0
+    sets = stacked_sets(compressed.words, V)
+    run, release = _pass_runner(compressed, sets, device, engine)
+    try:
+        tips = compressed.n_tips_inside.astype(np.int64)
+        into1, live, width, groups1 = run(tips.astype(np.int32), np.ones(V, dtype=np.int32), np.ones(V, dtype=bool))
+        width = width.astype(np.int64)
+        total = np.zeros(V, dtype=np.int64)
+        np.add.at(total, into1, tips)
+        has_live_child = np.zeros(V, dtype=bool)
+        has_live_child[parent[live & (parent >= 0)]] = True
+        second = np.zeros(n_trees, dtype=bool)
+        if can_merge_diff_sizes:
+            second = np.bincount(tree[live & ~has_live_child], minlength=n_trees) > tip_size_threshold
+        into2, groups2 = np.arange(V, dtype=np.int32), 0
+        live_in = live & second[tree]
+        if live_in.any():
+            logging.getLogger('pastml').debug('Allowed merging nodes of different sizes.')
+            bins = np.log10(np.maximum(1, total / width)).astype(np.int64)   # int(np.log10(max(1, NUM_TIPS_INSIDE))) :111
+            into2, live2, width2, groups2 = run(np.where(live_in, bins, 0).astype(np.int32), width.astype(np.int32), live_in)
+            live = np.where(second[tree], live2, live)
+            width = np.where(live_in, width2.astype(np.int64), width)
+    finally:
+        release()
+    for groups in (groups1, groups2):
+        if groups:
+            logging.getLogger('pastml').debug('Collapsed {} sets of equivalent configurations horizontally.'.format(groups))
+
+    # the configurations of a live vertex s: the vertices u under a live parent (or roots) with into2[into1[u]] == s, in the
+    # order of the reference's lists: the groups of pass 1 that pass 2 joined in child order, each in child order
+    order = compressed.order
+    final = into2[into1].astype(np.int64)
+    proper = (parent < 0) | live[np.maximum(parent, 0)]
+    members = np.flatnonzero(proper)
+    members = members[np.lexsort((order[members], order[into1[members]], order[final[members]]))]
+    vertex = np.flatnonzero(live)
+    vertex = vertex[np.argsort(order[vertex])]
+    entry = np.full(V, -1, dtype=np.int64)
+    entry[vertex] = np.arange(len(vertex))
+    counts = np.bincount(entry[final[members]], minlength=len(vertex))
+    n_tips_total = np.zeros(len(vertex), dtype=np.int64)
+    np.add.at(n_tips_total, entry[final[members]], compressed.n_tips_inside[members])
+    up = parent[vertex]
+    return HorizontalForest(compressed=compressed, vertex=vertex, width=width[vertex],
+                            parent=np.where(up >= 0, entry[np.maximum(up, 0)], -1), n_tips_total=n_tips_total, members=members,
+                            member_offsets=np.concatenate(([0], np.cumsum(counts))), merged_groups=[int(groups1), int(groups2)],
+                            second_pass=second)
+
+
+def _horizontal_lines(merged, columns=None):
+    """
+    (vertex lines, arc lines) at horizontal timing: the live vertices in pre-order; ``<tips>`` joins the configurations of a
+    vertex by ';', each the names of its tips joined by ',' in the order the vertical map lists them; an arc carries the
+    width of the vertex it enters.
+    """
+    compressed = merged.compressed
+    columns = sorted(compressed.columns if columns is None else columns)
+    L = merged.n_vertices
+    flat = compressed.flat
+    names = np.array([n.name for n in flat.nodes], dtype=object) if flat.nodes is not None else \
+        np.array(['n{}'.format(i) for i in range(flat.n_nodes)], dtype=object)
+    tip_names = [str(x) for x in names[compressed.tips].tolist()]
+    begins = compressed.tip_offsets[compressed.order[merged.members]].tolist()
+    ends = compressed.tip_offsets[compressed.order[merged.members] + 1].tolist()
+    configurations = [','.join(tip_names[a:b]) for a, b in zip(begins, ends)]
+    offsets = merged.member_offsets.tolist()
+    tip_text = np.array([';'.join(configurations[offsets[i]:offsets[i + 1]]) for i in range(L)] + [None], dtype=object)[:L]
+    ids = np.array([str(i) for i in range(1, L + 1)], dtype=object)
+    lines = ids + ' "' + np.array([str(x) for x in compressed.name[merged.vertex]] + [None], dtype=object)[:L] + '" "' + tip_text + '"'
+    for c in columns:
+        i = compressed.columns.index(c)
+        lines = lines + ' "' + '{}:'.format(c) + _state_strings(compressed.states[i], compressed.words[i][merged.vertex]) + '"'
+    child = np.flatnonzero(merged.parent >= 0)
+    arcs = ['{} {} {}'.format(a + 1, b + 1, w)
+            for a, b, w in zip(merged.parent[child].tolist(), child.tolist(), merged.width[child].tolist())]
+    return lines.tolist() if L else [], arcs
+
+
+def compress_forest(forest, columns, column2states=None, timing=VERTICAL, tip_size_threshold=REASONABLE_NUMBER_OF_TIPS,
+                    can_merge_diff_sizes=True, device=None, engine=None):
+    """
+    The compressed forest as ``compress_tree`` has it when it records the Pajek lines of ``timing``: a
+    :class:`CompressedForest` for VERTICAL, a :class:`HorizontalForest` for HORIZONTAL (``pajek_lines`` / ``save_to_pajek`` take
+    both).  TRIM is not implemented.
+    """
+    if timing == TRIM:
+        raise NotImplementedError('timing={}: trimming (remove_small_tips, remove_mediators) is not implemented; {} and {} are'
+                                  .format(TRIM, VERTICAL, HORIZONTAL))
+    if timing not in (VERTICAL, HORIZONTAL):
+        raise ValueError('timing must be one of {}, {} or {}, not {!r}'.format(VERTICAL, HORIZONTAL, TRIM, timing))
+    compressed = collapse_vertically(forest, columns, column2states, device=device, engine=engine)
+    if timing == VERTICAL:
+        return compressed
+    return collapse_horizontally(compressed, tip_size_threshold=tip_size_threshold, can_merge_diff_sizes=can_merge_diff_sizes,
+                                 device=device, engine=engine)
+
+
+def main(argv=None):
+    """The map of a finished run: the named tree and the combined ancestral-state table that the pipeline wrote -> Pajek."""
+    import argparse
+    import pandas as pd
+    from pastml_amd.annotation import preannotate_forest
+    from pastml_amd.tree import read_forest
+    parser = argparse.ArgumentParser(prog='python -m pastml_amd.visualisation.tree_compressor', description=main.__doc__)
+    parser.add_argument('--tree', required=True, help='the named tree of the run (newick, one tree per line)')
+    parser.add_argument('--states', required=True, help='its combined ancestral-state table (tab-separated, first column: node)')
+    parser.add_argument('--columns', nargs='*', default=None, help='the columns to compress over (default: all of the table)')
+    parser.add_argument('--pajek', required=True, help='the file to write')
+    parser.add_argument('--pajek_timing', default=VERTICAL, choices=[VERTICAL, HORIZONTAL, TRIM])
+    parser.add_argument('--tip_size_threshold', type=int, default=REASONABLE_NUMBER_OF_TIPS)
+    parser.add_argument('--host', action='store_true', help='numpy only, no GPU')
+    args = parser.parse_args(argv)
+    roots = read_forest(args.tree)
+    df = pd.read_csv(args.states, sep='\t', index_col=0, header=0, dtype=str, keep_default_na=False)
+    df.index = df.index.map(str)
+    columns = list(df.columns) if not args.columns else list(args.columns)
+    missing = [c for c in columns if c not in df.columns]
+    if missing:
+        raise ValueError('columns {} are not in {}'.format(', '.join(missing), args.states))
+    df = df[columns]
+    preannotate_forest(roots, df=df)
+    column2states = {c: np.array(sorted(set(df[c]) - {''})) for c in columns}
+    result = compress_forest(roots, columns, column2states, timing=args.pajek_timing, tip_size_threshold=args.tip_size_threshold,
+                             device=False if args.host else None)
+    save_to_pajek(result, columns, args.pajek)
+    return 0
+
+
+if __name__ == '__main__':
+    import sys
+    sys.exit(main())
