@@ -676,27 +676,15 @@ int pml_masks_from_tip_states(pml_ctx* ctx, int32_t col_begin, int32_t col_end, 
                        col_begin);
     HIP_TRY(hipGetLastError());
     if (n_tips > 0) {
-        int *d_ids = nullptr, *d_states = nullptr;
-        HIP_TRY(hipMalloc((void**)&d_ids, sizeof(int) * n_tips));
-        hipError_t e = hipMalloc((void**)&d_states, sizeof(int) * (size_t)nc * n_tips);
-        if (e != hipSuccess) {
-            (void)hipFree(d_ids);
-            return fail(PML_ERR_HIP, "hipMalloc failed: %s", hipGetErrorString(e));
-        }
-        e = hipMemcpyAsync(d_ids, tip_ids, sizeof(int) * n_tips, hipMemcpyHostToDevice, ctx->stream);
-        if (e == hipSuccess)
-            e = hipMemcpyAsync(d_states, states, sizeof(int) * (size_t)nc * n_tips, hipMemcpyHostToDevice, ctx->stream);
-        if (e == hipSuccess) {
-            dim3 g2(grid_for(ctx, n_tips, PML_BLOCK, nc), nc);
-            hipLaunchKernelGGL(masks_tips_kernel, g2, dim3(PML_BLOCK), 0, ctx->stream, ctx->N, ctx->W, ctx->k,
-                               ctx->d_masks, col_begin, n_tips, d_ids, d_states);
-            e = hipGetLastError();
-        }
-        hipError_t e2 = hipStreamSynchronize(ctx->stream);
-        (void)hipFree(d_ids);
-        (void)hipFree(d_states);
-        if (e != hipSuccess) return fail(PML_ERR_HIP, "tip mask upload failed: %s", hipGetErrorString(e));
-        if (e2 != hipSuccess) return fail(PML_ERR_HIP, "tip mask upload failed: %s", hipGetErrorString(e2));
+        CallScope mem(ctx->stream, false);   // (tip_ids may be own_ids, declared above)
+        int *d_ids, *d_states;
+        PML_TRY(mem.put(&d_ids, tip_ids, (size_t)n_tips));
+        PML_TRY(mem.put(&d_states, states, (size_t)nc * n_tips));
+        dim3 g2(grid_for(ctx, n_tips, PML_BLOCK, nc), nc);
+        hipLaunchKernelGGL(masks_tips_kernel, g2, dim3(PML_BLOCK), 0, ctx->stream, ctx->N, ctx->W, ctx->k,
+                           ctx->d_masks, col_begin, n_tips, d_ids, d_states);
+        HIP_TRY(hipGetLastError());
+        PML_TRY(mem.finish());
     }
     for (int col = col_begin; col < col_end; ++col) {
         bool all = n_tips == ctx->n_tips;   // (the ids are distinct tips or the masks would not be what the caller meant)
@@ -987,28 +975,17 @@ int pml_pij(pml_ctx* ctx, int32_t col, int32_t n_t, const double* ts, double* P_
     if (n_t <= 0 || !ts || !P_out) return fail(PML_ERR_INVALID, "bad t / output arrays");
     PML_TRY(params_push(ctx));
     const size_t kk = (size_t)ctx->k * ctx->k;
-    double *d_t = nullptr, *d_out = nullptr;
-    HIP_TRY(hipMalloc((void**)&d_t, sizeof(double) * n_t));
-    hipError_t e = hipMalloc((void**)&d_out, sizeof(double) * kk * n_t);
-    if (e != hipSuccess) {
-        (void)hipFree(d_t);
-        return fail(PML_ERR_HIP, "hipMalloc failed: %s", hipGetErrorString(e));
-    }
-    e = hipMemcpyAsync(d_t, ts, sizeof(double) * n_t, hipMemcpyHostToDevice, ctx->stream);
-    if (e == hipSuccess) {
-        const size_t total = kk * n_t;
-        dim3 grid((unsigned)std::min<size_t>((total + PML_BLOCK - 1) / PML_BLOCK, 65535));
-        hipLaunchKernelGGL(pij_explicit_kernel, grid, dim3(PML_BLOCK), 0, ctx->stream, cols_of(ctx), model_of(ctx), col,
-                           n_t, d_t, d_out);
-        e = hipGetLastError();
-    }
-    if (e == hipSuccess) e = hipMemcpyAsync(P_out, d_out, sizeof(double) * kk * n_t, hipMemcpyDeviceToHost, ctx->stream);
-    hipError_t e2 = hipStreamSynchronize(ctx->stream);
-    (void)hipFree(d_t);
-    (void)hipFree(d_out);
-    if (e != hipSuccess) return fail(PML_ERR_HIP, "pml_pij failed: %s", hipGetErrorString(e));
-    if (e2 != hipSuccess) return fail(PML_ERR_HIP, "pml_pij failed: %s", hipGetErrorString(e2));
-    return PML_OK;
+    CallScope mem(ctx->stream, false);
+    double *d_t, *d_out;
+    PML_TRY(mem.put(&d_t, ts, (size_t)n_t));
+    PML_TRY(mem.get(&d_out, kk * n_t));
+    const size_t total = kk * n_t;
+    dim3 grid((unsigned)std::min<size_t>((total + PML_BLOCK - 1) / PML_BLOCK, 65535));
+    hipLaunchKernelGGL(pij_explicit_kernel, grid, dim3(PML_BLOCK), 0, ctx->stream, cols_of(ctx), model_of(ctx), col,
+                       n_t, d_t, d_out);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemcpyAsync(P_out, d_out, sizeof(double) * kk * n_t, hipMemcpyDeviceToHost, ctx->stream));
+    return mem.finish();
 }
 
 int pml_pij_batch(pml_ctx* ctx, double* P_out) {
@@ -1016,39 +993,34 @@ int pml_pij_batch(pml_ctx* ctx, double* P_out) {
     PML_TRY(run_prep(ctx));
     if (P_out) {
         const size_t kk = (size_t)ctx->k * ctx->k;
-        double* d_out = nullptr;
-        HIP_TRY(hipMalloc((void**)&d_out, sizeof(double) * kk * ctx->N));
-        hipError_t e = hipSuccess;
-        for (int col = 0; col < ctx->C && e == hipSuccess; ++col) {
+        std::vector<double> tmp;   // (matrix models: a column's matrices as the sweeps keep them)
+        CallScope mem(ctx->stream, false);
+        double* d_out;
+        PML_TRY(mem.get(&d_out, kk * ctx->N));
+        for (int col = 0; col < ctx->C; ++col) {
             if (ctx->kind == PML_MODEL_F81) {
                 // expand the stored e per branch: same arithmetic as the explicit kernel
                 const size_t total = kk * ctx->N;
                 dim3 grid((unsigned)std::min<size_t>((total + PML_BLOCK - 1) / PML_BLOCK, 65535));
                 hipLaunchKernelGGL(pij_explicit_kernel, grid, dim3(PML_BLOCK), 0, ctx->stream, cols_of(ctx),
                                    model_of(ctx), col, ctx->N, ctx->d_dist, d_out);
-                e = hipGetLastError();
-                if (e == hipSuccess)
-                    e = hipMemcpyAsync(P_out + (size_t)col * ctx->N * kk, d_out, sizeof(double) * kk * ctx->N,
-                                       hipMemcpyDeviceToHost, ctx->stream);
+                HIP_TRY(hipGetLastError());
+                HIP_TRY(hipMemcpyAsync(P_out + (size_t)col * ctx->N * kk, d_out, sizeof(double) * kk * ctx->N,
+                                       hipMemcpyDeviceToHost, ctx->stream));
             } else {
                 // the matrices the sweeps use, transposed back on the host
-                std::vector<double> tmp((size_t)ctx->N * ctx->k * ctx->ks);
-                e = hipMemcpyAsync(tmp.data(), ctx->d_P + (size_t)col * ctx->N * ctx->k * ctx->ks,
-                                   tmp.size() * sizeof(double), hipMemcpyDeviceToHost, ctx->stream);
-                if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
-                if (e == hipSuccess) {
-                    double* out = P_out + (size_t)col * ctx->N * kk;
-                    for (int n = 0; n < ctx->N; ++n)
-                        for (int i = 0; i < ctx->k; ++i)
-                            for (int j = 0; j < ctx->k; ++j)
-                                out[(size_t)n * kk + (size_t)i * ctx->k + j] =
-                                    tmp[((size_t)n * ctx->k + j) * ctx->ks + i];
-                }
+                tmp.resize((size_t)ctx->N * ctx->k * ctx->ks);
+                HIP_TRY(hipMemcpyAsync(tmp.data(), ctx->d_P + (size_t)col * ctx->N * ctx->k * ctx->ks,
+                                       tmp.size() * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+                HIP_TRY(hipStreamSynchronize(ctx->stream));
+                double* out = P_out + (size_t)col * ctx->N * kk;
+                for (int n = 0; n < ctx->N; ++n)
+                    for (int i = 0; i < ctx->k; ++i)
+                        for (int j = 0; j < ctx->k; ++j)
+                            out[(size_t)n * kk + (size_t)i * ctx->k + j] = tmp[((size_t)n * ctx->k + j) * ctx->ks + i];
             }
-            if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
+            PML_TRY(mem.finish());
         }
-        (void)hipFree(d_out);
-        if (e != hipSuccess) return fail(PML_ERR_HIP, "pml_pij_batch failed: %s", hipGetErrorString(e));
         rows_to_api_inplace(ctx, P_out, kk, (size_t)ctx->C);
     }
     return PML_OK;
@@ -1693,55 +1665,43 @@ static int marginal_counts_impl(pml_ctx* ctx, int32_t col, int32_t n_repetitions
     PML_TRY(materialize_tip_posteriors(ctx));
     PML_TRY(run_prep(ctx));  // P(t) of every branch (the fused eigen sweeps never materialise it) / exp(-mu t')
     const size_t k = ctx->k, N = (size_t)ctx->N;
-    int *d_counts = nullptr, *d_same = nullptr;
-    long long* d_result = nullptr;
-    unsigned char* d_alt = nullptr;
-    hipError_t e = hipMalloc((void**)&d_counts, N * k * sizeof(int));
-    if (e == hipSuccess) e = hipMalloc((void**)&d_result, k * k * sizeof(long long));
-    if (e == hipSuccess) e = hipMemsetAsync(d_result, 0, k * k * sizeof(long long), ctx->stream);
     std::vector<unsigned char> alt;
-    if (e == hipSuccess && altered != nullptr) {
-        alt.assign(N, 0);
-        for (size_t i = 0; i < N; ++i) alt[(size_t)internal_id(ctx, (int)i)] = altered[i] ? 1 : 0;
-        e = hipMalloc((void**)&d_alt, N);
-        if (e == hipSuccess) e = hipMalloc((void**)&d_same, N * k * sizeof(int));
-        if (e == hipSuccess) e = hipMemcpyAsync(d_alt, alt.data(), N, hipMemcpyHostToDevice, ctx->stream);
-        if (e == hipSuccess) e = hipMemsetAsync(d_same, 0, N * k * sizeof(int), ctx->stream);
-    }
-    if (e == hipSuccess) {
-        const PmlTree t = tree_of(ctx);
-        const PmlCols c = cols_of(ctx);
-        const PmlState st = state_of(ctx);
-        const PmlModel m = model_of(ctx);
-        const double* P = ctx->kind == PML_MODEL_F81 ? nullptr : ctx->d_P;
-        // (the draws are keyed by the CALLER's node ids: the library's internal numbering must not show in the result)
-        hipLaunchKernelGGL(counts_roots_kernel, dim3(std::min(ctx->n_roots, 1024)), dim3(64), 0, ctx->stream, t, c, st, col,
-                           n_repetitions, seed, d_counts, ctx->d_old_of_new);
-        for (int l = 0; l < ctx->n_td_levels; ++l) {
-            const int a = ctx->forest.td_parent_offsets[l], b = ctx->forest.td_parent_offsets[l + 1];
-            if (b <= a) continue;
-            hipLaunchKernelGGL(counts_level_kernel, dim3(std::min(b - a, 65536)), dim3(64), 0, ctx->stream, t, c, st, m, P,
-                               col, n_repetitions, seed, ctx->d_td_parents + a, b - a, d_counts, d_result, ctx->d_old_of_new,
-                               d_alt, d_same);
-        }
-        e = hipGetLastError();
-    }
     std::vector<long long> h(k * k);
-    if (e == hipSuccess) e = hipMemcpyAsync(h.data(), d_result, k * k * sizeof(long long), hipMemcpyDeviceToHost, ctx->stream);
-    int fetched = PML_OK;
-    if (e == hipSuccess && altered != nullptr) {
-        // (tips' rows of d_counts are written by their parents' passes: every node has its row)
-        if (state_counts_out) fetched = fetch_rows(ctx, d_counts, k, k, 1, state_counts_out);
-        if (fetched == PML_OK && same_out) fetched = fetch_rows(ctx, d_same, k, k, 1, same_out);
+    CallScope mem(ctx->stream, false);
+    int *d_counts, *d_same = nullptr;
+    long long* d_result;
+    unsigned char* d_alt = nullptr;
+    PML_TRY(mem.get(&d_counts, N * k));
+    PML_TRY(mem.get(&d_result, k * k));
+    HIP_TRY(hipMemsetAsync(d_result, 0, k * k * sizeof(long long), ctx->stream));
+    if (altered != nullptr) {
+        PML_TRY(upload_altered(ctx, mem, altered, alt, &d_alt));
+        PML_TRY(mem.get(&d_same, N * k));
+        HIP_TRY(hipMemsetAsync(d_same, 0, N * k * sizeof(int), ctx->stream));
     }
-    const hipError_t e2 = hipStreamSynchronize(ctx->stream);
-    (void)hipFree(d_counts);
-    if (d_result) (void)hipFree(d_result);
-    if (d_alt) (void)hipFree(d_alt);
-    if (d_same) (void)hipFree(d_same);
-    if (e != hipSuccess) return fail(PML_ERR_HIP, "pml_marginal_counts failed: %s", hipGetErrorString(e));
-    if (e2 != hipSuccess) return fail(PML_ERR_HIP, "pml_marginal_counts failed: %s", hipGetErrorString(e2));
-    PML_TRY(fetched);
+    const PmlTree t = tree_of(ctx);
+    const PmlCols c = cols_of(ctx);
+    const PmlState st = state_of(ctx);
+    const PmlModel m = model_of(ctx);
+    const double* P = ctx->kind == PML_MODEL_F81 ? nullptr : ctx->d_P;
+    // (the draws are keyed by the CALLER's node ids: the library's internal numbering must not show in the result)
+    hipLaunchKernelGGL(counts_roots_kernel, dim3(std::min(ctx->n_roots, 1024)), dim3(64), 0, ctx->stream, t, c, st, col,
+                       n_repetitions, seed, d_counts, ctx->d_old_of_new);
+    for (int l = 0; l < ctx->n_td_levels; ++l) {
+        const int a = ctx->forest.td_parent_offsets[l], b = ctx->forest.td_parent_offsets[l + 1];
+        if (b <= a) continue;
+        hipLaunchKernelGGL(counts_level_kernel, dim3(std::min(b - a, 65536)), dim3(64), 0, ctx->stream, t, c, st, m, P,
+                           col, n_repetitions, seed, ctx->d_td_parents + a, b - a, d_counts, d_result, ctx->d_old_of_new,
+                           d_alt, d_same);
+    }
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemcpyAsync(h.data(), d_result, k * k * sizeof(long long), hipMemcpyDeviceToHost, ctx->stream));
+    if (altered != nullptr) {
+        // (tips' rows of d_counts are written by their parents' passes: every node has its row)
+        PML_TRY(fetch_rows(ctx, d_counts, k, k, 1, state_counts_out));
+        PML_TRY(fetch_rows(ctx, d_same, k, k, 1, same_out));
+    }
+    PML_TRY(mem.finish());
     for (size_t i = 0; i < k * k; ++i) result_out[i] = altered != nullptr ? (double)h[i] : (double)h[i] / (double)n_repetitions;
     return PML_OK;
 }
@@ -1774,34 +1734,20 @@ int pml_expected_counts(pml_ctx* ctx, int32_t col_begin, int32_t col_end, const 
     PML_TRY(run_prep(ctx));  // P(t) of every branch (the fused sweeps never materialise it) / exp(-mu t')
     const size_t k = ctx->k, N = (size_t)ctx->N, cols = (size_t)(col_end - col_begin);
     const bool with_same = altered != nullptr && same_out != nullptr;
-    double *d_out = nullptr, *d_same = nullptr;
-    unsigned char* d_alt = nullptr;
     std::vector<unsigned char> alt;
-    hipError_t e = hipMalloc((void**)&d_out, cols * k * k * sizeof(double));
-    if (e == hipSuccess && altered != nullptr) {
-        alt.assign(N, 0);
-        for (size_t i = 0; i < N; ++i) alt[(size_t)internal_id(ctx, (int)i)] = altered[i] ? 1 : 0;
-        e = hipMalloc((void**)&d_alt, N);
-        if (e == hipSuccess) e = hipMemcpyAsync(d_alt, alt.data(), N, hipMemcpyHostToDevice, ctx->stream);
+    CallScope mem(ctx->stream, false);
+    double *d_out, *d_same = nullptr;
+    unsigned char* d_alt = nullptr;
+    PML_TRY(mem.get(&d_out, cols * k * k));
+    if (altered != nullptr) PML_TRY(upload_altered(ctx, mem, altered, alt, &d_alt));
+    if (with_same) {
+        PML_TRY(mem.get(&d_same, cols * N * k));
+        HIP_TRY(hipMemsetAsync(d_same, 0, cols * N * k * sizeof(double), ctx->stream));
     }
-    if (e == hipSuccess && with_same) {
-        e = hipMalloc((void**)&d_same, cols * N * k * sizeof(double));
-        if (e == hipSuccess) e = hipMemsetAsync(d_same, 0, cols * N * k * sizeof(double), ctx->stream);
-    }
-    int status = PML_OK;
-    if (e == hipSuccess) status = launch_expected(ctx, col_begin, col_end, d_alt, d_out, d_same);
-    if (e == hipSuccess && status == PML_OK)
-        e = hipMemcpyAsync(counts_out, d_out, cols * k * k * sizeof(double), hipMemcpyDeviceToHost, ctx->stream);
-    if (e == hipSuccess && status == PML_OK && with_same)
-        e = hipMemcpyAsync(same_out, d_same, cols * N * k * sizeof(double), hipMemcpyDeviceToHost, ctx->stream);
-    const hipError_t e2 = hipStreamSynchronize(ctx->stream);
-    if (d_out) (void)hipFree(d_out);
-    if (d_alt) (void)hipFree(d_alt);
-    if (d_same) (void)hipFree(d_same);
-    PML_TRY(status);
-    if (e != hipSuccess) return fail(PML_ERR_HIP, "pml_expected_counts failed: %s", hipGetErrorString(e));
-    if (e2 != hipSuccess) return fail(PML_ERR_HIP, "pml_expected_counts failed: %s", hipGetErrorString(e2));
-    return PML_OK;
+    PML_TRY(launch_expected(ctx, col_begin, col_end, d_alt, d_out, d_same));
+    HIP_TRY(hipMemcpyAsync(counts_out, d_out, cols * k * k * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+    if (with_same) HIP_TRY(hipMemcpyAsync(same_out, d_same, cols * N * k * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+    return mem.finish();
 }
 
 // n_repetitions scenarios of column col drawn forward from the roots (pml_launch_simulate.hip).  Needs a model, no sweep: the
@@ -1816,19 +1762,13 @@ int pml_simulate_states(pml_ctx* ctx, int32_t col, int32_t n_repetitions, int32_
     PML_TRY(run_prep(ctx, true));
     const size_t es = ctx->k > 256 ? 2 : 1;
     const size_t rs = ((size_t)n_repetitions + 3) / 4 * 4;
-    void* d_states = nullptr;
-    HIP_TRY(hipMalloc(&d_states, (size_t)ctx->N * rs * es));
-    int status = launch_simulate(ctx, col, n_repetitions, rep_offset, seed, d_states, rs);
-    hipError_t e = hipSuccess;
-    if (status == PML_OK)
-        e = hipMemcpy2DAsync(states_out, (size_t)n_repetitions * es, d_states, rs * es, (size_t)n_repetitions * es, (size_t)ctx->N,
-                             hipMemcpyDeviceToHost, ctx->stream);
-    const hipError_t e2 = hipStreamSynchronize(ctx->stream);
-    (void)hipFree(d_states);
-    PML_TRY(status);
-    if (e != hipSuccess) return fail(PML_ERR_HIP, "pml_simulate_states failed: %s", hipGetErrorString(e));
-    if (e2 != hipSuccess) return fail(PML_ERR_HIP, "pml_simulate_states failed: %s", hipGetErrorString(e2));
-    return PML_OK;
+    CallScope mem(ctx->stream, false);
+    unsigned char* d_states;
+    PML_TRY(mem.get(&d_states, (size_t)ctx->N * rs * es));
+    PML_TRY(launch_simulate(ctx, col, rep_offset, seed, d_states, rs));
+    HIP_TRY(hipMemcpy2DAsync(states_out, (size_t)n_repetitions * es, d_states, rs * es, (size_t)n_repetitions * es, (size_t)ctx->N,
+                             hipMemcpyDeviceToHost, ctx->stream));
+    return mem.finish();
 }
 
 // Maximum parsimony of n_cols characters on the uploaded forest (pml_launch_parsimony.hip).  Needs the tree only: no columns,
@@ -1914,39 +1854,28 @@ int pml_select_states(pml_ctx* ctx, int method, int force_joint, const uint64_t*
     note_tips_observed(ctx, 0, ctx->C, false);  // (masks from now on: whatever was selected)
     const size_t CN = (size_t)ctx->C * ctx->N;
     if (!ctx->d_nsel) PML_TRY(dev_alloc(ctx, &ctx->d_nsel, CN));
+    if (lh_mask && ctx->k % 64) {
+        const u64 valid = (1ull << (ctx->k % 64)) - 1ull;
+        for (size_t i = ctx->W - 1; i < CN * ctx->W; i += ctx->W)
+            if (lh_mask[i] & ~valid) return fail(PML_ERR_INVALID, "lh_mask word %zu has bits beyond k", i);
+    }
+    std::vector<u64> lh_mask_own;   // (the caller's rows in the library's numbering)
+    CallScope mem(ctx->stream, false);
     u64* d_lh_mask = nullptr;
-    std::vector<u64> lh_mask_own;   // (the caller's rows in the library's numbering, alive until the call has waited for its copies)
     if (lh_mask) {
-        if (ctx->k % 64) {
-            const u64 valid = (1ull << (ctx->k % 64)) - 1ull;
-            for (size_t i = ctx->W - 1; i < CN * ctx->W; i += ctx->W)
-                if (lh_mask[i] & ~valid) return fail(PML_ERR_INVALID, "lh_mask word %zu has bits beyond k", i);
-        }
-        HIP_TRY(hipMalloc((void**)&d_lh_mask, CN * ctx->W * sizeof(u64)));
+        const u64* src = (const u64*)lh_mask;
         if (permuted(ctx)) {
             lh_mask_own.resize(CN * ctx->W);
-            rows_to_internal(ctx, (const u64*)lh_mask, lh_mask_own.data(), (size_t)ctx->W, (size_t)ctx->C);
-            lh_mask = (const uint64_t*)lh_mask_own.data();
+            rows_to_internal(ctx, src, lh_mask_own.data(), (size_t)ctx->W, (size_t)ctx->C);
+            src = lh_mask_own.data();
         }
-        hipError_t e = hipMemcpyAsync(d_lh_mask, lh_mask, CN * ctx->W * sizeof(u64), hipMemcpyHostToDevice, ctx->stream);
-        if (e != hipSuccess) {
-            (void)hipFree(d_lh_mask);
-            return fail(PML_ERR_HIP, "lh_mask upload failed: %s", hipGetErrorString(e));
-        }
+        PML_TRY(mem.put(&d_lh_mask, src, CN * ctx->W));
     }
-    const int status = dispatch_select(ctx, method, force_joint, d_lh_mask);   // pml_launch_matrix.hip
-    hipError_t e = hipGetLastError();
-    int fetched = PML_OK;
-    if (e == hipSuccess && status == PML_OK) {
-        fetched = fetch_rows(ctx, (const u64*)ctx->d_masks, (size_t)ctx->W, (size_t)ctx->W, (size_t)ctx->C, (u64*)masks_out);
-        if (fetched == PML_OK) fetched = fetch_rows(ctx, ctx->d_nsel, 1, 1, (size_t)ctx->C, n_states_out);
-    }
-    hipError_t e2 = hipStreamSynchronize(ctx->stream);
-    if (d_lh_mask) (void)hipFree(d_lh_mask);
-    if (status != PML_OK) return status;
-    if (e != hipSuccess) return fail(PML_ERR_HIP, "pml_select_states failed: %s", hipGetErrorString(e));
-    if (fetched != PML_OK) return fetched;
-    if (e2 != hipSuccess) return fail(PML_ERR_HIP, "pml_select_states failed: %s", hipGetErrorString(e2));
+    PML_TRY(dispatch_select(ctx, method, force_joint, d_lh_mask));   // pml_launch_matrix.hip
+    HIP_TRY(hipGetLastError());
+    PML_TRY(fetch_rows(ctx, (const u64*)ctx->d_masks, (size_t)ctx->W, (size_t)ctx->W, (size_t)ctx->C, (u64*)masks_out));
+    PML_TRY(fetch_rows(ctx, ctx->d_nsel, 1, 1, (size_t)ctx->C, n_states_out));
+    PML_TRY(mem.finish());
     // the columns' masks changed: sweeps must be redone, the posteriors themselves stay valid for inspection
     ctx->prep_dirty = true;
     ctx->bu_mode = -1;

@@ -220,6 +220,8 @@ struct pml_ctx {
     PmlComm* comm = nullptr;   // RCCL communicator attached by pml_comm_init (survives tree uploads)
 };
 
+#include "pml_call_scope.h"   // the scratch and events of ONE call (what the context itself holds: dev_alloc below)
+
 // ---------------------------------------------------------------------------------------------------------------------
 template <typename T>
 static int dev_alloc(pml_ctx* ctx, T** p, size_t count) {

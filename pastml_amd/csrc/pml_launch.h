@@ -144,7 +144,7 @@ PML_INTERNAL int launch_eigen_joint_tips(pml_ctx* ctx);
 PML_INTERNAL int launch_pij_valu(pml_ctx* ctx);
 // ---- pml_launch_simulate.hip: forward simulation of a column along the forest (pml_simulate_states); d_states [N][rs] in the
 //      caller's numbering, uint8 for k <= 256, else uint16
-PML_INTERNAL int launch_simulate(pml_ctx* ctx, int col, int n_rep, int rep_offset, u64 seed, void* d_states, size_t rs);
+PML_INTERNAL int launch_simulate(pml_ctx* ctx, int col, int rep_offset, u64 seed, void* d_states, size_t rs);
 // ---- pml_launch_parsimony.hip: the parsimony passes on packed state sets (pml_parsimony); host arrays in the caller's numbering
 PML_INTERNAL int launch_parsimony(pml_ctx* ctx, int n_cols, int k, const u64* given, int methods, u64* sets_out, i64* steps_out,
                                   i64* hist_out);

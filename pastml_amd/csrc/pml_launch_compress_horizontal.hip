@@ -5,55 +5,6 @@
 #include "pml_launch.h"
 #include "pml_kernels_compress_horizontal.h"
 
-namespace {
-
-struct Scratch {
-    std::vector<void*> p;
-    ~Scratch() {
-        for (void* q : p) (void)hipFree(q);
-    }
-    template <typename T>
-    int get(T** out, size_t count) {
-        void* q = nullptr;
-        const hipError_t e = hipMalloc(&q, std::max<size_t>(1, count) * sizeof(T));
-        if (e != hipSuccess) return fail(PML_ERR_HIP, "hipMalloc of %zu bytes failed: %s", count * sizeof(T), hipGetErrorString(e));
-        p.push_back(q);
-        *out = (T*)q;
-        return PML_OK;
-    }
-    template <typename T>
-    int put(T** out, const T* host, size_t count, hipStream_t s) {
-        PML_TRY(get(out, count));
-        if (count) HIP_TRY(hipMemcpyAsync(*out, host, count * sizeof(T), hipMemcpyHostToDevice, s));
-        return PML_OK;
-    }
-};
-
-struct Events {
-    bool on;
-    std::vector<hipEvent_t> ev;
-    explicit Events(bool on_) : on(on_) {}
-    ~Events() {
-        for (hipEvent_t e : ev) (void)hipEventDestroy(e);
-    }
-    int mark(hipStream_t s) {
-        if (!on) return PML_OK;
-        hipEvent_t e;
-        HIP_TRY(hipEventCreate(&e));
-        ev.push_back(e);
-        HIP_TRY(hipEventRecord(e, s));
-        return PML_OK;
-    }
-};
-
-size_t pow2_from(size_t n) {
-    size_t p = 1;
-    while (p < n) p <<= 1;
-    return p;
-}
-
-}  // namespace
-
 PML_INTERNAL int launch_compress_horizontal(pml_ctx* ctx, int V, int n_cols, int W, const int* parent, const int* rank, const int* bin,
                                             const int* width_in, const unsigned char* live_in, const u64* sets, int* into_out,
                                             unsigned char* live_out, int* width_out, int* groups_out) {
@@ -139,7 +90,8 @@ PML_INTERNAL int launch_compress_horizontal(pml_ctx* ctx, int V, int n_cols, int
     // ---- device ---------------------------------------------------------------------------------------------------------
     HIP_TRY(hipSetDevice(ctx->device));
     hipStream_t s = ctx->stream;
-    Scratch mem;
+    int flags[2] = {0, 0};   // [0] a table was full, [1] groups of two or more: copied back at the end
+    CallScope mem(s, ctx->profile);   // (events for pml_compress_horizontal_info only while the context profiles)
     HzTables t;
     int *d_parent, *d_rank, *d_bin, *d_width_in, *d_child_off, *d_child_idx, *d_small, *d_block, *d_width, *d_into, *d_flags;
     int *d_up[2];
@@ -148,17 +100,17 @@ PML_INTERNAL int launch_compress_horizontal(pml_ctx* ctx, int V, int n_cols, int
     u32 *d_sclass, *d_cls, *d_slot_of;
     u64 *d_sets, *d_sort;
     const size_t n_words = (size_t)n_cols * V * W;
-    PML_TRY(mem.put(&d_parent, parent, (size_t)V, s));
-    PML_TRY(mem.put(&d_rank, rank, (size_t)V, s));
-    PML_TRY(mem.put(&d_bin, bin, (size_t)V, s));
-    PML_TRY(mem.put(&d_width_in, width_in, (size_t)V, s));
-    PML_TRY(mem.put(&d_live_in, live_in, (size_t)V, s));
-    PML_TRY(mem.put(&d_sets, sets, n_words, s));
-    PML_TRY(mem.put(&d_child_off, child_off.data(), (size_t)V + 1, s));
-    PML_TRY(mem.put(&d_child_idx, child_idx.data(), (size_t)E, s));
-    PML_TRY(mem.put(&d_small, small_list.data(), (size_t)small_off[n_levels], s));
-    PML_TRY(mem.put(&d_block, block_list.data(), (size_t)block_off[n_levels], s));
-    PML_TRY(mem.put(&d_block_scratch, block_scratch.data(), (size_t)block_off[n_levels], s));
+    PML_TRY(mem.put(&d_parent, parent, (size_t)V));
+    PML_TRY(mem.put(&d_rank, rank, (size_t)V));
+    PML_TRY(mem.put(&d_bin, bin, (size_t)V));
+    PML_TRY(mem.put(&d_width_in, width_in, (size_t)V));
+    PML_TRY(mem.put(&d_live_in, live_in, (size_t)V));
+    PML_TRY(mem.put(&d_sets, sets, n_words));
+    PML_TRY(mem.put(&d_child_off, child_off.data(), (size_t)V + 1));
+    PML_TRY(mem.put(&d_child_idx, child_idx.data(), (size_t)E));
+    PML_TRY(mem.put(&d_small, small_list.data(), (size_t)small_off[n_levels]));
+    PML_TRY(mem.put(&d_block, block_list.data(), (size_t)block_off[n_levels]));
+    PML_TRY(mem.put(&d_block_scratch, block_scratch.data(), (size_t)block_off[n_levels]));
     PML_TRY(mem.get(&d_width, (size_t)V));
     PML_TRY(mem.get(&d_live, (size_t)V));
     PML_TRY(mem.get(&d_into, (size_t)V));
@@ -166,7 +118,7 @@ PML_INTERNAL int launch_compress_horizontal(pml_ctx* ctx, int V, int n_cols, int
     PML_TRY(mem.get(&d_cls, (size_t)V));
     PML_TRY(mem.get(&d_slot_of, (size_t)V));
     PML_TRY(mem.get(&d_sort, scratch_words));
-    PML_TRY(mem.get(&d_flags, 2));   // [0] a table was full, [1] groups of two or more
+    PML_TRY(mem.get(&d_flags, 2));
     for (int i = 0; i < 2; ++i) {
         PML_TRY(mem.get(&d_up[i], (size_t)V));
         PML_TRY(mem.get(&d_gone[i], (size_t)V));
@@ -209,16 +161,15 @@ PML_INTERNAL int launch_compress_horizontal(pml_ctx* ctx, int V, int n_cols, int
     a.into = d_into;
     a.groups = d_flags + 1;
 
-    Events ev(ctx->profile);
     long long launches = 0;
     const int vertex_blocks = (V + PML_HZ_THREADS - 1) / PML_HZ_THREADS;
-    PML_TRY(ev.mark(s));
+    PML_TRY(mem.mark());
     if (n_live > 0) {
         hipLaunchKernelGGL(hz_states_kernel, dim3(vertex_blocks), dim3(PML_HZ_THREADS), 0, s, t, d_sets, d_live_in, d_sclass, V, W, n_cols);
         HIP_TRY(hipGetLastError());
         ++launches;
     }
-    PML_TRY(ev.mark(s));
+    PML_TRY(mem.mark());
     for (int d = n_levels - 1; d >= 0; --d) {
         const int ns = small_off[d + 1] - small_off[d], nb = block_off[d + 1] - block_off[d];
         if (ns > 0) {
@@ -234,7 +185,7 @@ PML_INTERNAL int launch_compress_horizontal(pml_ctx* ctx, int V, int n_cols, int
             ++launches;
         }
     }
-    PML_TRY(ev.mark(s));
+    PML_TRY(mem.mark());
     // vertices under one that left leave too: 2^rounds > the deepest level
     int cur = 0;
     if (n_live > 0) {
@@ -253,17 +204,17 @@ PML_INTERNAL int launch_compress_horizontal(pml_ctx* ctx, int V, int n_cols, int
         HIP_TRY(hipGetLastError());
         ++launches;
     }
-    PML_TRY(ev.mark(s));
-    int flags[2] = {0, 0};
+    PML_TRY(mem.mark());
     HIP_TRY(hipMemcpyAsync(into_out, d_into, (size_t)V * sizeof(int), hipMemcpyDeviceToHost, s));
     HIP_TRY(hipMemcpyAsync(live_out, d_live, (size_t)V, hipMemcpyDeviceToHost, s));
     HIP_TRY(hipMemcpyAsync(width_out, d_width, (size_t)V * sizeof(int), hipMemcpyDeviceToHost, s));
     HIP_TRY(hipMemcpyAsync(flags, d_flags, sizeof(flags), hipMemcpyDeviceToHost, s));
-    HIP_TRY(hipStreamSynchronize(s));
-    float ms[3] = {0.f, 0.f, 0.f};
-    if (ev.on)
-        for (int i = 0; i < 3; ++i) HIP_TRY(hipEventElapsedTime(&ms[i], ev.ev[i], ev.ev[i + 1]));
-    for (int i = 0; i < 3; ++i) ctx->hz_ms[i] = ms[i];
+    PML_TRY(mem.finish());
+    for (int i = 0; i < 3; ++i) {
+        float ms = 0.f;
+        PML_TRY(mem.elapsed(i, i + 1, &ms));
+        ctx->hz_ms[i] = ms;
+    }
     ctx->hz_levels = n_levels;
     ctx->hz_launches = launches;
     ctx->hz_slots = (long long)slots;

@@ -43,12 +43,12 @@ PML_INTERNAL int launch_expected(pml_ctx* ctx, int cb, int ce, const unsigned ch
     a.partial = a.corr = a.rowsum = a.dterm = nullptr;
     const size_t n_partial = (size_t)cols * a.n_pieces * k * k, n_corr = (size_t)cols * a.n_ppieces * k;
     const size_t n_branch = f81 ? (size_t)cols * N : (size_t)cols * N * k;
-    double* scratch = nullptr;
-    HIP_TRY(hipMalloc((void**)&scratch, (n_partial + n_corr + n_branch) * sizeof(double)));
+    CallScope mem(ctx->stream, false);
+    double* scratch;   // one allocation: the partials, the parents' corrections, the per-branch terms
+    PML_TRY(mem.get(&scratch, n_partial + n_corr + n_branch));
     a.partial = scratch;
     a.corr = scratch + n_partial;
     (f81 ? a.rowsum : a.dterm) = scratch + n_partial + n_corr;
-    int status = PML_OK;
     if (f81) {
         const int T = (k + 15) / 16, TG = (T + 3) / 4;
         if (TG == 1) {
@@ -64,17 +64,10 @@ PML_INTERNAL int launch_expected(pml_ctx* ctx, int cb, int ce, const unsigned ch
     } else if (k <= 256) {
         hipLaunchKernelGGL(expected_matrix_kernel<4>, dim3(a.n_pieces, (k + 31) / 32, cols), dim3(256), 0, ctx->stream, a);
     } else {
-        status = fail(PML_ERR_UNSUPPORTED, "k = %d: the matrix models hold at most 256 states", k);
+        return fail(PML_ERR_UNSUPPORTED, "k = %d: the matrix models hold at most 256 states", k);
     }
-    if (status == PML_OK) {
-        hipLaunchKernelGGL(expected_parents_kernel, dim3(a.n_ppieces, cols), dim3(256), 0, ctx->stream, a);
-        hipLaunchKernelGGL(expected_reduce_kernel, dim3((k * k + 255) / 256, cols), dim3(256), 0, ctx->stream, a);
-    }
-    const hipError_t e = hipGetLastError();
-    const hipError_t e2 = hipStreamSynchronize(ctx->stream);   // (the scratch goes)
-    (void)hipFree(scratch);
-    PML_TRY(status);
-    HIP_TRY(e);
-    HIP_TRY(e2);
-    return PML_OK;
+    hipLaunchKernelGGL(expected_parents_kernel, dim3(a.n_ppieces, cols), dim3(256), 0, ctx->stream, a);
+    hipLaunchKernelGGL(expected_reduce_kernel, dim3((k * k + 255) / 256, cols), dim3(256), 0, ctx->stream, a);
+    HIP_TRY(hipGetLastError());
+    return mem.finish();   // (the scratch goes)
 }

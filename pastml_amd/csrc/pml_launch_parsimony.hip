@@ -1,5 +1,5 @@
-// Launches of the parsimony passes (pml_kernels_parsimony.h): scratch, chunking over the columns, the level schedule of every
-// pass.  pml_parsimony (pml_api.hip) checks the arguments.
+// Launches of the parsimony passes (pml_kernels_parsimony.h): the chunks of columns, the level schedule of every pass; the
+// scratch and the event brackets live in a CallScope (pml_call_scope.h).  pml_parsimony (pml_api.hip) checks the arguments.
 #include "pml_launch.h"
 #include "pml_kernels_parsimony.h"
 
@@ -60,44 +60,13 @@ static int run_pass(ParsRun& r, const PmlParsArgs& a, const std::vector<int>& of
     return PML_OK;
 }
 
-struct Scratch {
-    std::vector<void*> p;
-    ~Scratch() {
-        for (void* q : p) (void)hipFree(q);
-    }
-    template <typename T>
-    int get(T** out, size_t count) {
-        void* q = nullptr;
-        const hipError_t e = hipMalloc(&q, std::max<size_t>(1, count) * sizeof(T));
-        if (e != hipSuccess) return fail(PML_ERR_HIP, "hipMalloc of %zu bytes failed: %s", count * sizeof(T), hipGetErrorString(e));
-        p.push_back(q);
-        *out = (T*)q;
-        return PML_OK;
-    }
-};
-
-struct Events {
-    std::vector<hipEvent_t> ev;
-    ~Events() {
-        for (hipEvent_t e : ev) (void)hipEventDestroy(e);
-    }
-    int mark(hipStream_t s) {
-        hipEvent_t e;
-        HIP_TRY(hipEventCreate(&e));
-        ev.push_back(e);
-        HIP_TRY(hipEventRecord(e, s));
-        return PML_OK;
-    }
-};
-
 }  // namespace
 
 PML_INTERNAL int launch_parsimony(pml_ctx* ctx, int n_cols, int k, const u64* given, int methods, u64* sets_out, i64* steps_out,
                                   i64* hist_out) {
     const PmlForest& f = ctx->forest;
     const int N = ctx->N, W = (k + 63) / 64;
-    int WG = 1;
-    while (WG < W) WG <<= 1;
+    const int WG = (int)pow2_from((size_t)W);
     int maxc = 0;
     for (int i = 0; i < N; ++i) maxc = std::max(maxc, f.n_children[i]);
     int planes = 2;
@@ -107,16 +76,12 @@ PML_INTERNAL int launch_parsimony(pml_ctx* ctx, int n_cols, int k, const u64* gi
     const size_t col_words = (size_t)N * W, hist_len = (size_t)k + 1;
 
     // columns per chunk: what the scratch allows (half of the free memory at most)
-    HIP_TRY(hipSetDevice(ctx->device));
-    size_t free_b = 0, total_b = 0;
-    HIP_TRY(hipMemGetInfo(&free_b, &total_b));
     const size_t per_col = col_words * 8 * PML_PARS_SETS_PER_COLUMN + (size_t)N * 8 + 3 * (hist_len + 1) * 8;
-    long long chunk = (long long)std::min<size_t>(free_b / 2 / per_col, 65535);
-    if (ctx->tune.on(T_PARS_MAX_COLS)) chunk = std::min(chunk, std::max(1ll, ctx->tune.get(T_PARS_MAX_COLS, 1)));
-    if (chunk < 1) return fail(PML_ERR_HIP, "pml_parsimony: %zu bytes of scratch per column do not fit the device", per_col);
-    chunk = std::min<long long>(chunk, n_cols);
+    long long chunk;
+    PML_TRY(columns_per_chunk(ctx, per_col, 65535, T_PARS_MAX_COLS, n_cols, "pml_parsimony", &chunk));
 
-    Scratch mem;
+    hipStream_t s = ctx->stream;
+    CallScope mem(s, true);   // (events always: pml_parsimony_info reports the passes' time whether or not the context profiles)
     u64 *d_stage, *d_init, *d_bu, *d_up, *d_out, *d_z, *d_steps, *d_hist;
     i64* d_m;
     int* d_tdp_offsets;
@@ -129,9 +94,7 @@ PML_INTERNAL int launch_parsimony(pml_ctx* ctx, int n_cols, int k, const u64* gi
     PML_TRY(mem.get(&d_m, (size_t)chunk * N));
     PML_TRY(mem.get(&d_steps, (size_t)3 * chunk));
     PML_TRY(mem.get(&d_hist, (size_t)3 * chunk * hist_len));
-    PML_TRY(mem.get(&d_tdp_offsets, f.td_parent_offsets.size()));
-    HIP_TRY(hipMemcpyAsync(d_tdp_offsets, f.td_parent_offsets.data(), f.td_parent_offsets.size() * sizeof(int), hipMemcpyHostToDevice,
-                           ctx->stream));
+    PML_TRY(mem.put(&d_tdp_offsets, f.td_parent_offsets.data(), f.td_parent_offsets.size()));
 
     ParsRun r;
     r.ctx = ctx;
@@ -154,7 +117,6 @@ PML_INTERNAL int launch_parsimony(pml_ctx* ctx, int n_cols, int k, const u64* gi
     base.m = d_m;
     const bool perm = !ctx->old_of_new.empty();
     const int first_root = f.td_offsets[0], n_roots = f.td_offsets[1] - f.td_offsets[0];
-    hipStream_t s = ctx->stream;
     double pass_ms = 0;
 
     for (int c0 = 0; c0 < n_cols; c0 += (int)chunk) {
@@ -162,13 +124,12 @@ PML_INTERNAL int launch_parsimony(pml_ctx* ctx, int n_cols, int k, const u64* gi
         const size_t words = (size_t)cc * col_words;
         const int flat_blocks = (int)std::min<size_t>(((size_t)cc * N + 255) / 256, 16384);
         r.cols = cc;
-        Events ev;
-        std::vector<int> pass_seg;   // indices i of the event pairs (i, i + 1) that bracket passes
+        std::vector<size_t> pass_seg;   // indices i of the event pairs (i, i + 1) that bracket passes
         HIP_TRY(hipMemcpyAsync(d_stage, given + (size_t)c0 * col_words, words * 8, hipMemcpyHostToDevice, s));
         HIP_TRY(hipMemsetAsync(d_steps, 0, (size_t)3 * cc * 8, s));
         HIP_TRY(hipMemsetAsync(d_hist, 0, (size_t)3 * cc * hist_len * 8, s));
-        PML_TRY(ev.mark(s));
-        pass_seg.push_back(0);
+        PML_TRY(mem.mark());
+        pass_seg.push_back(mem.n_marks() - 1);
         hipLaunchKernelGGL(pars_init_kernel, dim3(flat_blocks), dim3(256), 0, s, d_stage, d_init, perm ? ctx->d_old_of_new : nullptr, N, W,
                            base.last_word, cc);
         HIP_TRY(hipGetLastError());
@@ -200,14 +161,14 @@ PML_INTERNAL int launch_parsimony(pml_ctx* ctx, int n_cols, int k, const u64* gi
                                d_steps + (size_t)slot * cc, N, first_root, n_roots);
             HIP_TRY(hipGetLastError());
             ++r.launches;
-            PML_TRY(ev.mark(s));
+            PML_TRY(mem.mark());
             hipLaunchKernelGGL(pars_gather_kernel, dim3(flat_blocks), dim3(256), 0, s, d_out, d_stage, perm ? ctx->d_new_of_old : nullptr,
                                N, W, cc);
             HIP_TRY(hipGetLastError());
             ++r.launches;
             HIP_TRY(hipMemcpyAsync(sets_out + ((size_t)slot * n_cols + c0) * col_words, d_stage, words * 8, hipMemcpyDeviceToHost, s));
-            PML_TRY(ev.mark(s));
-            pass_seg.push_back((int)ev.ev.size() - 1);
+            PML_TRY(mem.mark());
+            pass_seg.push_back(mem.n_marks() - 1);
             ++slot;
             return PML_OK;
         };
@@ -237,16 +198,16 @@ PML_INTERNAL int launch_parsimony(pml_ctx* ctx, int n_cols, int k, const u64* gi
                 PML_TRY(finish());
             }
         }
-        PML_TRY(ev.mark(s));
+        PML_TRY(mem.mark());
         for (int m = 0; m < n_methods; ++m) {
             HIP_TRY(hipMemcpyAsync(steps_out + (size_t)m * n_cols + c0, d_steps + (size_t)m * cc, (size_t)cc * 8, hipMemcpyDeviceToHost, s));
             HIP_TRY(hipMemcpyAsync(hist_out + ((size_t)m * n_cols + c0) * hist_len, d_hist + (size_t)m * cc * hist_len,
                                    (size_t)cc * hist_len * 8, hipMemcpyDeviceToHost, s));
         }
-        HIP_TRY(hipStreamSynchronize(s));
-        for (int i : pass_seg) {
+        PML_TRY(mem.finish());
+        for (size_t i : pass_seg) {
             float ms = 0.f;
-            HIP_TRY(hipEventElapsedTime(&ms, ev.ev[i], ev.ev[i + 1]));
+            PML_TRY(mem.elapsed(i, i + 1, &ms));
             pass_ms += ms;
         }
     }

@@ -86,14 +86,13 @@ static int sim_run(pml_ctx* ctx, PmlSimArgs a, int threads, int D, size_t lds, l
     return PML_OK;
 }
 
-PML_INTERNAL int launch_simulate(pml_ctx* ctx, int col, int n_rep, int rep_offset, u64 seed, void* d_states, size_t rs) {
+PML_INTERNAL int launch_simulate(pml_ctx* ctx, int col, int rep_offset, u64 seed, void* d_states, size_t rs) {
     const int k = ctx->k;
     const int n_tuples = (int)(rs / 4);
     const int threads = std::min(PML_SIM_THREADS, 64 * ((n_tuples + 63) / 64));
     const int n_tiles = (n_tuples + threads - 1) / threads;
     const int D = frontier_depth(ctx, n_tiles);
     if (D < ctx->n_td_levels) PML_TRY(subtree_lists(ctx, D));
-    (void)n_rep;
     PmlSimArgs a;
     a.parent = ctx->d_parent;
     a.api_id = ctx->d_old_of_new;   // (null when the library works in the caller's numbering)
@@ -124,11 +123,8 @@ PML_INTERNAL int launch_simulate(pml_ctx* ctx, int col, int n_rep, int rep_offse
     // wide matrix models: a slice of k x k doubles per workgroup, the grid bounded by PML_SIM_SCRATCH_BYTES
     const size_t slice = (size_t)k * k * sizeof(double);
     const long long blocks = std::max<long long>(1, (long long)(PML_SIM_SCRATCH_BYTES / slice));
-    HIP_TRY(hipMalloc((void**)&a.scratch, (size_t)blocks * slice));
-    const int status = sim_run<unsigned char, PML_SIM_MATRIX_SCRATCH>(ctx, a, threads, D, (size_t)k * sizeof(double), blocks);
-    const hipError_t e = hipStreamSynchronize(ctx->stream);
-    (void)hipFree(a.scratch);
-    PML_TRY(status);
-    HIP_TRY(e);
-    return PML_OK;
+    CallScope mem(ctx->stream, false);
+    PML_TRY(mem.get(&a.scratch, (size_t)blocks * k * k));
+    PML_TRY((sim_run<unsigned char, PML_SIM_MATRIX_SCRATCH>(ctx, a, threads, D, (size_t)k * sizeof(double), blocks)));
+    return mem.finish();   // (the scratch goes)
 }
