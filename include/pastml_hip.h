@@ -374,6 +374,41 @@ int pml_compress_horizontal_info(pml_ctx* ctx, double* states_ms, double* levels
                                  int64_t* launches, int64_t* table_slots, int32_t* sort_tile);
 
 /*
+ * The trimming of a horizontally merged forest (pastml/visualisation/tree_compressor.py: compress_tree :118-159,
+ * remove_small_tips :214-248, remove_mediators :301-340) over its live vertices, entries in Pajek pre-order; the trees of the
+ * forest side by side, each with a threshold of its own.  The ctx supplies the device and the stream; the uploaded forest is
+ * not used, and the scratch of the call is released before it returns.  Integer and exactly rounded float64 work only: the
+ * results do not depend on the launch geometry.
+ *   parent        [n_vertices]  entry above, -1 for a root; parent[i] < i, and every subtree is a run of consecutive entries
+ *   tree          [n_vertices]  in [0, n_trees), that of the parent
+ *   n_tips_total  [n_vertices]  >= 0, tips inside over all configurations of the vertex
+ *   width         [n_vertices]  >= 1, configurations merged into the vertex
+ *   sets          [n_cols][n_vertices][W]  state sets as masks, narrower columns zero-padded; W <= 8
+ *   trim_tree     [n_trees]     non-zero: the tree is over the gate (more than tip_size_threshold leaf vertices)
+ *   tsize_out     [n_vertices]  (n_tips_total / width) * the product of the widths from the root down; 0 outside trim_tree.  A
+ *                               product or a size of 2^53 or more fails the call (PML_ERR_UNSUPPORTED)
+ *   threshold_out [n_trees]     the tip_size_threshold-th largest tsize among the non-root vertices with tsize > that of all
+ *                               their children; NaN where nothing happens to the tree (not in trim_tree, or no candidate is smaller)
+ *   keep_out      [n_vertices]  1: a root, or some vertex of its subtree has tsize >= threshold (1 outside the trimmed trees)
+ *   spliced_out   [n_vertices]  1: a mediator that is spliced out -- kept, no root, width 1, no tips, one kept child, and in every
+ *                               column at least two states that are exactly those of its parent and of its child after the
+ *                               splices below it
+ *   new_parent_out[n_vertices]  the nearest entry above that is not spliced out; -1 for a root and for a vertex that is gone
+ *   moved_out     [n_vertices]  1: new_parent is not parent (the vertex goes behind the children that stayed)
+ * The k-th largest candidate of every tree is taken on the host inside the call, from one download of the candidate values.
+ * pml_compress_trim_info: HIP-event times of the last call (sizes and candidates, removal, mediators and parents; without
+ * transfers; taken only while pml_profile_enable is on, else 0), the levels of the vertex forest, the rounds of the multiplier
+ * (ceil(log2(levels))), kernel launches (0 where no tree is in trim_tree, 3 + rounds where none gets a threshold, else
+ * 9 + rounds), and the entries of one workgroup of the prefix count.
+ */
+int pml_compress_trim(pml_ctx* ctx, int32_t n_vertices, int32_t n_cols, int32_t W, const int32_t* parent, const int32_t* tree,
+                      const int32_t* n_tips_total, const int32_t* width, const uint64_t* sets, int32_t tip_size_threshold,
+                      int32_t n_trees, const uint8_t* trim_tree, double* tsize_out, uint8_t* keep_out, uint8_t* spliced_out,
+                      int32_t* new_parent_out, uint8_t* moved_out, double* threshold_out);
+int pml_compress_trim_info(pml_ctx* ctx, double* sizes_ms, double* removal_ms, double* mediators_ms, int32_t* levels, int32_t* rounds,
+                           int64_t* launches, int32_t* scan_tile);
+
+/*
  * n_repetitions scenarios of column col drawn forward from the roots (pastml/utilities/state_simulator.py:6-31):
  * roots ~ pi, child ~ row (parent state) of P_n(t).  Draws keyed by (seed, caller's node id, rep_offset + r):
  * results do not depend on launch geometry, chunking or the library's internal numbering.

@@ -1843,6 +1843,39 @@ int pml_compress_horizontal_info(pml_ctx* ctx, double* states_ms, double* levels
     return PML_OK;
 }
 
+// The trimming of a horizontally merged forest given as arrays (pml_launch_compress_trim.hip).  The context supplies the device
+// and the stream; the uploaded forest is not used.  The scratch of the call is freed before it returns.
+int pml_compress_trim(pml_ctx* ctx, int32_t n_vertices, int32_t n_cols, int32_t W, const int32_t* parent, const int32_t* tree,
+                      const int32_t* n_tips_total, const int32_t* width, const uint64_t* sets, int32_t tip_size_threshold,
+                      int32_t n_trees, const uint8_t* trim_tree, double* tsize_out, uint8_t* keep_out, uint8_t* spliced_out,
+                      int32_t* new_parent_out, uint8_t* moved_out, double* threshold_out) {
+    if (!ctx) return fail(PML_ERR_INVALID, "ctx is NULL");
+    if (n_vertices <= 0) return fail(PML_ERR_INVALID, "n_vertices must be positive");
+    if (n_cols <= 0) return fail(PML_ERR_INVALID, "n_cols must be positive");
+    if (n_trees <= 0) return fail(PML_ERR_INVALID, "n_trees must be positive");
+    if (W <= 0) return fail(PML_ERR_INVALID, "W must be positive");
+    if (W > PML_MAX_STATES / 64) return fail(PML_ERR_UNSUPPORTED, "W = %d words; at most %d are supported", W, PML_MAX_STATES / 64);
+    if (tip_size_threshold < 0) return fail(PML_ERR_INVALID, "tip_size_threshold must not be negative");
+    if (!parent || !tree || !n_tips_total || !width || !sets || !trim_tree || !tsize_out || !keep_out || !spliced_out ||
+        !new_parent_out || !moved_out || !threshold_out)
+        return fail(PML_ERR_INVALID, "NULL array");
+    return launch_compress_trim(ctx, n_vertices, n_cols, W, parent, tree, n_tips_total, width, (const u64*)sets, tip_size_threshold,
+                                n_trees, trim_tree, tsize_out, keep_out, spliced_out, new_parent_out, moved_out, threshold_out);
+}
+
+int pml_compress_trim_info(pml_ctx* ctx, double* sizes_ms, double* removal_ms, double* mediators_ms, int32_t* levels, int32_t* rounds,
+                           int64_t* launches, int32_t* scan_tile) {
+    if (!ctx) return fail(PML_ERR_INVALID, "ctx is NULL");
+    if (sizes_ms) *sizes_ms = ctx->trim_ms[0];
+    if (removal_ms) *removal_ms = ctx->trim_ms[1];
+    if (mediators_ms) *mediators_ms = ctx->trim_ms[2];
+    if (levels) *levels = ctx->trim_levels;
+    if (rounds) *rounds = ctx->trim_rounds;
+    if (launches) *launches = ctx->trim_launches;
+    if (scan_tile) *scan_tile = PML_TRIM_SCAN_TILE;
+    return PML_OK;
+}
+
 int pml_select_states(pml_ctx* ctx, int method, int force_joint, const uint64_t* lh_mask, uint64_t* masks_out,
                       int32_t* n_states_out) {
     PML_TRY(require_model(ctx));

@@ -216,6 +216,11 @@ struct pml_ctx {
     double hz_ms[3] = {0, 0, 0};
     int hz_levels = 0;
     long long hz_launches = 0, hz_slots = 0;
+    // trimming (pml_launch_compress_trim.hip), last pml_compress_trim: event times of the sizes, the removal and the mediators
+    // (zero unless the context profiles), levels of the vertex forest, rounds of the multiplier, kernel launches
+    double trim_ms[3] = {0, 0, 0};
+    int trim_levels = 0, trim_rounds = 0;
+    long long trim_launches = 0;
 
     PmlComm* comm = nullptr;   // RCCL communicator attached by pml_comm_init (survives tree uploads)
 };

@@ -158,6 +158,13 @@ PML_INTERNAL int launch_compress(pml_ctx* ctx, int n_cols, int W, const u64* set
 PML_INTERNAL int launch_compress_horizontal(pml_ctx* ctx, int V, int n_cols, int W, const int* parent, const int* rank, const int* bin,
                                             const int* width_in, const unsigned char* live_in, const u64* sets, int* into_out,
                                             unsigned char* live_out, int* width_out, int* groups_out);
+// ---- pml_launch_compress_trim.hip: the trimming of a horizontally merged forest of L live vertices in pre-order
+//      (pml_compress_trim); host arrays, entries of the vertex forest
+#define PML_TRIM_SCAN_TILE 1024   // entries of one workgroup of the prefix count (pml_compress_trim_info reports it)
+PML_INTERNAL int launch_compress_trim(pml_ctx* ctx, int L, int n_cols, int W, const int* parent, const int* tree, const int* T,
+                                      const int* w, const u64* sets, int tip_size_threshold, int n_trees,
+                                      const unsigned char* trim_tree, double* tsize_out, unsigned char* keep_out,
+                                      unsigned char* spliced_out, int* new_parent_out, unsigned char* moved_out, double* threshold_out);
 
 // ---- pml_launch_expected.hip: exact expected transition counts of the columns [cb, ce) (pml_expected_counts); d_alt [N] in the
 //      library's numbering or null, d_out [cols][k][k], d_same [cols][N][k] in the caller's numbering (zeroed) or null

@@ -120,6 +120,12 @@ SIGNATURES = {
                                 ctypes.POINTER(ctypes.c_uint8), _c_int32_p, _c_int32_p],
     'pml_compress_horizontal_info': [_ctx_p, _c_double_p, _c_double_p, _c_double_p, _c_int32_p, ctypes.POINTER(ctypes.c_int64),
                                      ctypes.POINTER(ctypes.c_int64), _c_int32_p],
+    'pml_compress_trim': [_ctx_p, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, _c_int32_p, _c_int32_p, _c_int32_p, _c_int32_p,
+                          _c_uint64_p, ctypes.c_int32, ctypes.c_int32, ctypes.POINTER(ctypes.c_uint8), _c_double_p,
+                          ctypes.POINTER(ctypes.c_uint8), ctypes.POINTER(ctypes.c_uint8), _c_int32_p,
+                          ctypes.POINTER(ctypes.c_uint8), _c_double_p],
+    'pml_compress_trim_info': [_ctx_p, _c_double_p, _c_double_p, _c_double_p, _c_int32_p, _c_int32_p,
+                               ctypes.POINTER(ctypes.c_int64), _c_int32_p],
     'pml_download': [_ctx_p, ctypes.c_int, ctypes.c_int32, ctypes.c_void_p],
     'pml_comm_unique_id': [ctypes.POINTER(ctypes.c_ubyte)],
     'pml_comm_init': [_ctx_p, ctypes.c_int, ctypes.c_int, ctypes.POINTER(ctypes.c_ubyte)],
@@ -915,6 +921,52 @@ class Engine(BareContext):
                                                       ctypes.byref(tile)))
         return dict(ms=(a.value, b.value, c.value), levels=levels.value, launches=launches.value, table_slots=slots.value,
                     sort_tile=tile.value)
+
+    def compress_trim(self, parent, tree, n_tips_total, width, sets, tip_size_threshold, trim_tree):
+        """
+        The trimming of a horizontally merged forest of L live vertices in pre-order (pml_compress_trim; the forest this context
+        holds is not used).  parent, tree, n_tips_total, width: int32 [L]; sets: uint64 [n, L, W] state sets of the n columns,
+        W <= 8; trim_tree: bool [n_trees], the trees over the gate.  Returns (tsize float64 [L], keep bool [L], spliced bool [L],
+        new_parent int32 [L], moved bool [L], threshold float64 [n_trees]) as ``tree_compressor.trim_host`` does.
+        """
+        parent = _as(parent, np.int32)
+        L = parent.shape[0] if parent.ndim == 1 else -1
+        if L < 1:
+            raise ValueError('parent must be [L] with L >= 1, got {}'.format(parent.shape))
+        tree, tips, width = _as(tree, np.int32), _as(n_tips_total, np.int32), _as(width, np.int32)
+        for name, array in (('tree', tree), ('n_tips_total', tips), ('width', width)):
+            if array.shape != (L,):
+                raise ValueError('{} must be [{}], got {}'.format(name, L, array.shape))
+        flags = _as(np.asarray(trim_tree).astype(bool), np.uint8)
+        if flags.ndim != 1 or flags.shape[0] < 1:
+            raise ValueError('trim_tree must be [n_trees] with n_trees >= 1, got {}'.format(flags.shape))
+        sets = _as(sets, np.uint64)
+        if sets.ndim == 2:
+            sets = sets[None]
+        if sets.ndim != 3 or sets.shape[1] != L or sets.shape[0] < 1 or sets.shape[2] < 1:
+            raise ValueError('sets must be [n, {}, W], got {}'.format(L, sets.shape))
+        tsize, threshold = np.empty(L, dtype=np.float64), np.empty(flags.shape[0], dtype=np.float64)
+        keep, spliced, moved = (np.empty(L, dtype=np.uint8) for _ in range(3))
+        new_parent = np.empty(L, dtype=np.int32)
+        _check(self._lib.pml_compress_trim(self._ctx, L, sets.shape[0], sets.shape[2], _ptr(parent, ctypes.c_int32),
+                                           _ptr(tree, ctypes.c_int32), _ptr(tips, ctypes.c_int32), _ptr(width, ctypes.c_int32),
+                                           _ptr(sets, ctypes.c_uint64), int(tip_size_threshold), flags.shape[0],
+                                           _ptr(flags, ctypes.c_uint8), _ptr(tsize, ctypes.c_double), _ptr(keep, ctypes.c_uint8),
+                                           _ptr(spliced, ctypes.c_uint8), _ptr(new_parent, ctypes.c_int32),
+                                           _ptr(moved, ctypes.c_uint8), _ptr(threshold, ctypes.c_double)))
+        return tsize, keep.astype(bool), spliced.astype(bool), new_parent, moved.astype(bool), threshold
+
+    def compress_trim_info(self):
+        """dict of the last ``compress_trim`` call: ``ms`` (sizes and candidates, removal, mediators and parents -- HIP events,
+        taken after ``profile_enable()``, else 0), ``levels`` (depths of the vertex forest), ``rounds`` (of the multiplier),
+        ``launches`` and ``scan_tile`` (entries of one workgroup of the prefix count)."""
+        a, b, c = ctypes.c_double(0), ctypes.c_double(0), ctypes.c_double(0)
+        levels, rounds, tile = ctypes.c_int32(0), ctypes.c_int32(0), ctypes.c_int32(0)
+        launches = ctypes.c_int64(0)
+        _check(self._lib.pml_compress_trim_info(self._ctx, ctypes.byref(a), ctypes.byref(b), ctypes.byref(c), ctypes.byref(levels),
+                                                ctypes.byref(rounds), ctypes.byref(launches), ctypes.byref(tile)))
+        return dict(ms=(a.value, b.value, c.value), levels=levels.value, rounds=rounds.value, launches=launches.value,
+                    scan_tile=tile.value)
 
     def download(self, what, col=0):
         N, k = self.n_nodes, self.k

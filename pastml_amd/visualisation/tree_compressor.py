@@ -2,7 +2,7 @@
 The compressed tree of a reconstruction: the vertical step (pastml/visualisation/tree_compressor.py: ``collapse_vertically``
 :251-298 on the lists ``compress_tree`` :87-96 starts from), the horizontal step (``collapse_horizontally`` :164-211, the two
 calls of ``compress_tree`` :102-116) and the Pajek network (``_tree2pajek_vertices_arcs`` :34-51, ``save_to_pajek`` :54-80) --
-what the reference writes at ``pajek_timing='VERTICAL'`` (its default) and ``'HORIZONTAL'``.
+what the reference writes at ``pajek_timing='VERTICAL'`` (its default), ``'HORIZONTAL'`` and ``'TRIM'``.
 
 Every connected region of the forest whose nodes carry the same state sets in ALL columns becomes one vertex; the arcs
 between vertices are the state changes.  As arrays: node n is *merged* iff it has a parent and its sets equal the parent's
@@ -24,10 +24,22 @@ and among the children of a vertex those of one class collapse into the first.  
 with ``np.unique`` / ``np.lexsort``.  The reference keys its cache of configurations by node NAME and so conflates vertices
 with duplicate or empty names; here the key is the vertex itself.
 
-Trimming (``pajek_timing='TRIM'``), focus / mixed mode (the rest of ``compress_tree``) are not implemented.
+Trimming (``compress_tree`` :118-159, ``remove_small_tips`` :214-248, ``remove_mediators`` :301-340) works on the live
+vertices of the merged forest in Pajek pre-order.  The size of a vertex is its mean number of tips per configuration times the
+product of the widths from the root down (float64, the reference's operations in its order); the threshold of a tree is the
+``tip_size_threshold``-th largest size among the vertices larger than all their children.  The repeated removal of small leaves
+is a closed form -- a vertex survives iff it is a root or its subtree, a run of the pre-order, holds a vertex of the size: a
+prefix count -- and the mediators form chains that are decided from the bottom upwards.  Sizes, flags and new parents are one
+call into the HIP library (``Engine.compress_trim``), restated by ``trim_host``; the child order after splicing (the children
+that stayed, then the replacements), the new pre-order and the member lists are array passes on the host, and the pass after
+the trimming is ``Engine.compress_horizontal`` as it is.  ``compress_tree`` is the whole compressor for all three timings.
+``compress_forest(timing='TRIM')`` and ``--pajek_timing TRIM`` still raise NotImplementedError (they point to ``compress_tree``
+and ``--trim``).  Sizes of 2^53 and more are an error on both paths: Python's unbounded integers are not reproduced.
+
+Focus / mixed mode (the rest of ``compress_tree``) is not implemented.
 
     python -m pastml_amd.visualisation.tree_compressor --tree NAMED_TREE --states COMBINED_TABLE --pajek OUT
-           [--columns ...] [--pajek_timing VERTICAL|HORIZONTAL] [--tip_size_threshold N]
+           [--columns ...] [--pajek_timing VERTICAL|HORIZONTAL | --trim] [--tip_size_threshold N]
 """
 import logging
 
@@ -514,6 +526,282 @@ def collapse_horizontally(compressed, tip_size_threshold=REASONABLE_NUMBER_OF_TI
                             second_pass=second)
 
 
+# ---------------------------------------------------------------------------------------------------------------------
+# trimming
+# ---------------------------------------------------------------------------------------------------------------------
+MAX_EXACT = float(2 ** 53)   # multipliers and sizes from here on are refused: float64 no longer holds every integer
+
+
+class TrimmedForest(HorizontalForest):
+    """
+    The trimmed forest: a :class:`HorizontalForest` (``merged_groups`` has a third entry, the groups of the pass after the
+    trimming) and
+
+        threshold          float64[n_trees]  the size threshold of each tree, NaN where the tree was not trimmed
+        removed            int64[]           rows of ``compressed``: the vertices that the removal of small tips took out
+        mediators          int64[]           rows of ``compressed``: the mediators spliced out
+        horizontal         the :class:`HorizontalForest` it was trimmed from
+    """
+
+
+def _check_vertex_forest(parent, tree, n_tips_total, width, n_trees):
+    """(depth int64[L], subtree size int64[L]) of a vertex forest in pre-order, or a ValueError that says what is wrong."""
+    L = len(parent)
+    ids = np.arange(L, dtype=np.int64)
+    if ((parent < -1) | (parent >= ids)).any():
+        bad = int(np.flatnonzero((parent < -1) | (parent >= ids))[0])
+        raise ValueError('parent[{}] = {}: the entries are in pre-order, a parent comes before its children'.format(bad, parent[bad]))
+    if (width < 1).any():
+        raise ValueError('width[{}] < 1'.format(int(np.flatnonzero(width < 1)[0])))
+    if (n_tips_total < 0).any():
+        raise ValueError('n_tips_total[{}] < 0'.format(int(np.flatnonzero(n_tips_total < 0)[0])))
+    if ((tree < 0) | (tree >= n_trees)).any():
+        raise ValueError('tree ids must lie in [0, {})'.format(n_trees))
+    child = parent >= 0
+    if (tree[child] != tree[parent[child]]).any():
+        raise ValueError('a vertex and its parent are in different trees')
+    depth = vertex_depths(parent, np.ones(L, dtype=bool))
+    size = np.ones(L, dtype=np.int64)
+    by_depth = np.argsort(depth, kind='stable')
+    bounds = np.searchsorted(depth[by_depth], np.arange(int(depth.max()) + 2 if L else 1))
+    for d in range(len(bounds) - 2, 0, -1):
+        level = by_depth[bounds[d]:bounds[d + 1]]
+        np.add.at(size, parent[level], size[level])
+    if (ids[child] + size[child] > parent[child] + size[parent[child]]).any():
+        raise ValueError('the entries are not in pre-order: a subtree is no run of consecutive entries')
+    return depth, size
+
+
+def trim_host(parent, tree, n_tips_total, width, sets, tip_size_threshold, trim_tree):
+    """
+    The numpy restatement of pml_compress_trim over the live vertices of a horizontally merged forest, entries in pre-order:
+    parent int[L] (-1: a root, else < the entry), tree int[L], n_tips_total int[L], width int[L], sets uint64[n_cols, L, W] (no
+    bound on W), trim_tree bool[n_trees] (the trees over the gate).  Returns
+
+        tsize       float64[L]  (n_tips_total / width) * the product of the widths from the root down, 0 outside the trees to trim
+        keep        bool[L]     survives the removal of small tips (True outside the trimmed trees)
+        spliced     bool[L]     a mediator that is spliced out
+        new_parent  int32[L]    the entry above afterwards (-1: a root, or a vertex that is gone)
+        moved       bool[L]     re-attached behind the children that stayed (its parent of before was spliced out)
+        threshold   float64[n_trees]  NaN where nothing happens to the tree
+    """
+    parent = np.asarray(parent, dtype=np.int64)
+    tree = np.asarray(tree, dtype=np.int64)
+    T = np.asarray(n_tips_total, dtype=np.int64)
+    w = np.asarray(width, dtype=np.int64)
+    sets = np.asarray(sets, dtype=np.uint64)
+    trim_tree = np.asarray(trim_tree, dtype=bool)
+    k = int(tip_size_threshold)
+    if k < 0:
+        raise ValueError('tip_size_threshold must not be negative, got {}'.format(k))
+    L, n_trees = len(parent), len(trim_tree)
+    depth, size = _check_vertex_forest(parent, tree, T, w, n_trees)
+    ids = np.arange(L, dtype=np.int64)
+    tsize = np.zeros(L, dtype=np.float64)
+    keep = np.ones(L, dtype=bool)
+    spliced = np.zeros(L, dtype=bool)
+    moved = np.zeros(L, dtype=bool)
+    new_parent = parent.astype(np.int32)
+    threshold = np.full(n_trees, np.nan)
+    if not trim_tree.any():
+        return tsize, keep, spliced, new_parent, moved, threshold
+    on = trim_tree[tree]
+
+    # sizes: the multiplier by pointer jumping with products (exact below 2^53, whatever the order of the factors)
+    mult = w.astype(np.float64)
+    up = parent.copy()
+    for _ in range(jump_rounds(int(depth.max()) + 1)):
+        has = np.flatnonzero(up >= 0)
+        mult[has], up[has] = mult[has] * mult[up[has]], up[up[has]]
+    tsize = np.where(on, (T.astype(np.float64) / w.astype(np.float64)) * mult, 0.)
+    if ((mult >= MAX_EXACT) & on).any() or (tsize >= MAX_EXACT).any():
+        raise ValueError('the widths along a path multiply to 2^53 or more: sizes beyond the exact range of float64 are not supported')
+
+    # threshold: the k-th largest among the non-root vertices that are larger than all their children
+    child = parent >= 0
+    child_max = np.zeros(L, dtype=np.float64)
+    np.maximum.at(child_max, parent[child], tsize[child])
+    candidate = child & on & (tsize > child_max)
+    for t in np.flatnonzero(trim_tree):
+        values = np.sort(tsize[candidate & (tree == t)])
+        if len(values) == 0:
+            continue
+        chosen = values[-k] if 0 < k <= len(values) else values[0]
+        if values[0] < chosen:
+            threshold[t] = chosen
+    trimmed = ~np.isnan(threshold)
+    if not trimmed.any():
+        return tsize, keep, spliced, new_parent, moved, threshold
+    on = trimmed[tree]
+
+    # removal: a vertex survives iff it is a root or its subtree -- a run of the pre-order -- holds a vertex of the size
+    big = on & (tsize >= np.where(on, threshold[tree], 0.))
+    before = np.concatenate(([0], np.cumsum(big)))
+    keep = ~on | ~child | (before[ids + size] - before[ids] > 0)
+
+    # mediators: chains of candidates, each the only surviving child of the one above, decided from the bottom upwards
+    kept_child = np.flatnonzero(child & keep)
+    n_kept = np.bincount(parent[kept_child], minlength=L)
+    only = np.zeros(L, dtype=np.int64)
+    only[parent[kept_child]] = kept_child
+    structural = on & keep & child & (w == 1) & (T == 0) & (n_kept == 1)
+    bits = np.unpackbits(np.ascontiguousarray(sets).view(np.uint8), axis=2).sum(axis=2) if sets.size else np.zeros(sets.shape[:2], int)
+    front = np.flatnonzero(structural & ~structural[only])
+    below = only[front]
+    while len(front):
+        fits = ((sets[:, front] == (sets[:, below] | sets[:, parent[front]])).all(axis=2) & (bits[:, front] >= 2)).all(axis=0)
+        spliced[front] = fits
+        below = np.where(fits, below, front)
+        go = structural[parent[front]]
+        front, below = parent[front][go], below[go]
+    above = parent.copy()
+    while True:
+        jump = np.flatnonzero((above >= 0) & spliced[np.maximum(above, 0)])
+        if not len(jump):
+            break
+        above[jump] = parent[above[jump]]
+    stays = keep & ~spliced
+    new_parent = np.where(stays, above, -1).astype(np.int32)
+    moved = stays & (above != parent)
+    return tsize, keep, spliced, new_parent, moved, threshold
+
+
+def _engine_for(flat, n_words_wide, device, engine, what):
+    """(the engine to call or None for numpy, function that releases it): device selection as in ``collapse_arrays``."""
+    from pastml_amd import hip
+    fits = n_words_wide <= MAX_DEVICE_WORDS
+    if device is None and engine is None:
+        device = fits and _device_ready()
+        if not fits:
+            logging.getLogger('pastml').debug('{} on the host: sets of {} words, the device path takes at most {}.'
+                                              .format(what, n_words_wide, MAX_DEVICE_WORDS))
+    if device is False and engine is None:
+        return None, (lambda: None)
+    if not fits:
+        raise ValueError('sets of {} words: the device path of the {} takes at most {} (512 states); '
+                         'device=False has no bound'.format(n_words_wide, what.lower(), MAX_DEVICE_WORDS))
+    if engine is not None:
+        return engine, (lambda: None)
+    own = hip.Engine.tree_only(flat, device=None if device is True or device is None else int(device))
+    return own, own.close
+
+
+def _preorder_ranks(parent, size, key):
+    """int64[V]: rank in the pre-order of a forest whose siblings (and roots) come in ascending ``key``; size: subtree sizes."""
+    V = len(parent)
+    if V == 0:
+        return np.zeros(0, dtype=np.int64)
+    sib = np.lexsort((key, parent))
+    sorted_parent = parent[sib]
+    before = np.cumsum(size[sib]) - size[sib]
+    new_group = np.concatenate(([True], sorted_parent[1:] != sorted_parent[:-1]))
+    step = np.empty(V, dtype=np.int64)
+    step[sib] = before - before[np.flatnonzero(new_group)][np.cumsum(new_group) - 1] + (sorted_parent >= 0)
+    order = step.copy()
+    above = parent.copy()
+    while (above >= 0).any():
+        on = np.flatnonzero(above >= 0)
+        order[on] += order[above[on]]
+        above[on] = above[above[on]]
+    return order
+
+
+def trim(merged, tip_size_threshold=REASONABLE_NUMBER_OF_TIPS, can_merge_diff_sizes=True, device=None, engine=None):
+    """
+    The trimming of a :class:`HorizontalForest` as ``compress_tree`` :118-156 does it, every tree on its own: a tree with more
+    than ``tip_size_threshold`` leaf vertices loses the vertices whose subtrees hold nothing of the size of its
+    ``tip_size_threshold``-th largest tip (``remove_small_tips``), then the mediators (``remove_mediators``), then gets one more
+    horizontal pass.  The sizes, the flags and the new parents are one call into the HIP library (``Engine.compress_trim``) or
+    ``trim_host``; the new child order, the pre-order and the member lists are array passes on the host; the pass is
+    ``Engine.compress_horizontal`` / ``horizontal_pass_host``.  Returns a :class:`TrimmedForest`.
+    """
+    k = int(tip_size_threshold)
+    if k < 0:
+        raise ValueError('tip_size_threshold must not be negative, got {}'.format(k))
+    compressed = merged.compressed
+    L = merged.n_vertices
+    parent = merged.parent.astype(np.int64)
+    tree = compressed.tree[merged.vertex]
+    n_trees = len(merged.second_pass)
+    has_child = np.zeros(L, dtype=bool)
+    has_child[parent[parent >= 0]] = True
+    over_gate = np.bincount(tree[~has_child], minlength=n_trees) > k
+    sets = stacked_sets([w[merged.vertex] for w in compressed.words], L)
+    if L and max(int(merged.n_tips_total.max()), int(merged.width.max())) > np.iinfo(np.int32).max:
+        raise ValueError('tips or widths beyond 32 bits')
+    eng, release = _engine_for(compressed.flat, sets.shape[2], device, engine, 'Trimming')
+    try:
+        arrays = (parent.astype(np.int32), tree.astype(np.int32), merged.n_tips_total.astype(np.int32), merged.width.astype(np.int32),
+                  sets, k, over_gate)
+        if not L:
+            tsize, keep, spliced, new_parent, moved, threshold = (np.zeros(0), np.zeros(0, bool), np.zeros(0, bool),
+                                                                  np.zeros(0, np.int32), np.zeros(0, bool), np.full(n_trees, np.nan))
+        else:
+            tsize, keep, spliced, new_parent, moved, threshold = (trim_host if eng is None else eng.compress_trim)(*arrays)
+        trimmed = ~np.isnan(threshold)
+        log = logging.getLogger('pastml')
+        for t in np.flatnonzero(trimmed):
+            log.debug('Set tip size threshold to {} (the size of the {}-th largest tip).'.format(threshold[t], k))
+
+        # the forest that is left, children in the order of the reference: those that stayed, then those re-attached, each in
+        # the old order (entries are in pre-order, so the order of the chain tops is the order of what replaces them)
+        stays = np.flatnonzero(keep & ~spliced)
+        n = len(stays)
+        entry = np.full(L, -1, dtype=np.int64)
+        entry[stays] = np.arange(n)
+        up = new_parent[stays].astype(np.int64)
+        up = np.where(up >= 0, entry[np.maximum(up, 0)], -1)
+        depth, old_size = _check_vertex_forest(parent, tree.astype(np.int64), merged.n_tips_total.astype(np.int64),
+                                               merged.width.astype(np.int64), n_trees) if L else (np.zeros(0, np.int64),) * 2
+        stays_before = np.concatenate(([0], np.cumsum(keep & ~spliced)))
+        size = stays_before[stays + old_size[stays]] - stays_before[stays]
+        order = _preorder_ranks(up, size, moved[stays].astype(np.int64) * L + stays)
+        by_rank = np.empty(n, dtype=np.int64)
+        by_rank[order] = np.arange(n)
+        old = stays[by_rank]                         # old entry of every new one, new pre-order
+        up = np.where(up[by_rank] >= 0, order[np.maximum(up[by_rank], 0)], -1)
+        width = merged.width[old].astype(np.int64)
+        total = merged.n_tips_total[old].astype(np.int64)
+
+        # the pass after the trimming, over the trimmed trees: the bin that was bound last
+        into, live, groups = np.arange(n, dtype=np.int64), np.ones(n, dtype=bool), 0
+        in_pass = trimmed[tree[old]]
+        if in_pass.any():
+            num = total / width
+            decade = (np.asarray(merged.second_pass, dtype=bool) & bool(can_merge_diff_sizes))[tree[old]]
+            bins = np.where(decade, np.log10(np.maximum(1, num)).astype(np.int64), np.unique(num, return_inverse=True)[1].reshape(-1))
+            args = (up.astype(np.int32), np.arange(n, dtype=np.int32), np.where(in_pass, bins, 0).astype(np.int32),
+                    width.astype(np.int32), in_pass, sets[:, old])
+            into, live2, width2, groups = (horizontal_pass_host if eng is None else eng.compress_horizontal)(*args)
+            into = into.astype(np.int64)
+            live = np.where(in_pass, live2, True)
+            width = np.where(in_pass, width2.astype(np.int64), width)
+    finally:
+        release()
+    if groups:
+        logging.getLogger('pastml').debug('Collapsed {} sets of equivalent configurations horizontally.'.format(groups))
+
+    # members: a survivor takes the configurations of the siblings merged into it, in the new child order
+    final = np.flatnonzero(live)
+    row = np.full(n, -1, dtype=np.int64)
+    row[final] = np.arange(len(final))
+    proper = np.flatnonzero((up < 0) | live[np.maximum(up, 0)])
+    proper = proper[np.lexsort((proper, row[into[proper]]))]
+    begin, count = merged.member_offsets[:-1][old[proper]], np.diff(merged.member_offsets)[old[proper]]
+    ends = np.cumsum(count)
+    members = merged.members[np.repeat(begin - (ends - count), count) + np.arange(int(ends[-1]) if len(ends) else 0)]
+    counts = np.zeros(len(final), dtype=np.int64)
+    np.add.at(counts, row[into[proper]], count)
+    offsets = np.concatenate(([0], np.cumsum(counts)))
+    n_tips_total = np.zeros(len(final), dtype=np.int64)
+    np.add.at(n_tips_total, np.repeat(np.arange(len(final)), counts), compressed.n_tips_inside[members])
+    return TrimmedForest(compressed=compressed, vertex=merged.vertex[old[final]], width=width[final],
+                         parent=np.where(up[final] >= 0, row[np.maximum(up[final], 0)], -1), n_tips_total=n_tips_total,
+                         members=members, member_offsets=offsets, merged_groups=list(merged.merged_groups) + [int(groups)],
+                         second_pass=merged.second_pass, threshold=threshold, removed=merged.vertex[~keep],
+                         mediators=merged.vertex[spliced], horizontal=merged, tsize=tsize)
+
+
 def _horizontal_lines(merged, columns=None):
     """
     (vertex lines, arc lines) at horizontal timing: the live vertices in pre-order; ``<tips>`` joins the configurations of a
@@ -548,11 +836,11 @@ def compress_forest(forest, columns, column2states=None, timing=VERTICAL, tip_si
     """
     The compressed forest as ``compress_tree`` has it when it records the Pajek lines of ``timing``: a
     :class:`CompressedForest` for VERTICAL, a :class:`HorizontalForest` for HORIZONTAL (``pajek_lines`` / ``save_to_pajek`` take
-    both).  TRIM is not implemented.
+    both).  TRIM is refused here: the trimmed forest is ``compress_tree`` (``--trim`` on the command line).
     """
     if timing == TRIM:
-        raise NotImplementedError('timing={}: trimming (remove_small_tips, remove_mediators) is not implemented; {} and {} are'
-                                  .format(TRIM, VERTICAL, HORIZONTAL))
+        raise NotImplementedError('timing={}: compress_forest stops at {} and {}; the trimmed forest is compress_tree(..., '
+                                  'pajek_timing={}), --trim on the command line'.format(TRIM, VERTICAL, HORIZONTAL, TRIM))
     if timing not in (VERTICAL, HORIZONTAL):
         raise ValueError('timing must be one of {}, {} or {}, not {!r}'.format(VERTICAL, HORIZONTAL, TRIM, timing))
     compressed = collapse_vertically(forest, columns, column2states, device=device, engine=engine)
@@ -560,6 +848,26 @@ def compress_forest(forest, columns, column2states=None, timing=VERTICAL, tip_si
         return compressed
     return collapse_horizontally(compressed, tip_size_threshold=tip_size_threshold, can_merge_diff_sizes=can_merge_diff_sizes,
                                  device=device, engine=engine)
+
+
+def compress_tree(forest, columns, column2states=None, tip_size_threshold=REASONABLE_NUMBER_OF_TIPS, can_merge_diff_sizes=True,
+                  pajek_timing=TRIM, device=None, engine=None):
+    """
+    The whole compressor under the reference's name: the forest as ``compress_tree`` has it when it records the Pajek lines of
+    ``pajek_timing`` -- a :class:`CompressedForest` for VERTICAL, a :class:`HorizontalForest` for HORIZONTAL, a
+    :class:`TrimmedForest` for TRIM (``pajek_lines`` / ``save_to_pajek`` take them all).
+    """
+    if pajek_timing not in (VERTICAL, HORIZONTAL, TRIM):
+        raise ValueError('pajek_timing must be one of {}, {} or {}, not {!r}'.format(VERTICAL, HORIZONTAL, TRIM, pajek_timing))
+    if int(tip_size_threshold) < 0:
+        raise ValueError('tip_size_threshold must not be negative, got {}'.format(tip_size_threshold))
+    if pajek_timing != TRIM:
+        return compress_forest(forest, columns, column2states, timing=pajek_timing, tip_size_threshold=tip_size_threshold,
+                               can_merge_diff_sizes=can_merge_diff_sizes, device=device, engine=engine)
+    merged = compress_forest(forest, columns, column2states, timing=HORIZONTAL, tip_size_threshold=tip_size_threshold,
+                             can_merge_diff_sizes=can_merge_diff_sizes, device=device, engine=engine)
+    return trim(merged, tip_size_threshold=tip_size_threshold, can_merge_diff_sizes=can_merge_diff_sizes, device=device,
+                engine=engine)
 
 
 def main(argv=None):
@@ -574,6 +882,7 @@ def main(argv=None):
     parser.add_argument('--columns', nargs='*', default=None, help='the columns to compress over (default: all of the table)')
     parser.add_argument('--pajek', required=True, help='the file to write')
     parser.add_argument('--pajek_timing', default=VERTICAL, choices=[VERTICAL, HORIZONTAL, TRIM])
+    parser.add_argument('--trim', action='store_true', help='the map after trimming (with --pajek_timing left at its default)')
     parser.add_argument('--tip_size_threshold', type=int, default=REASONABLE_NUMBER_OF_TIPS)
     parser.add_argument('--host', action='store_true', help='numpy only, no GPU')
     args = parser.parse_args(argv)
@@ -587,8 +896,14 @@ def main(argv=None):
     df = df[columns]
     preannotate_forest(roots, df=df)
     column2states = {c: np.array(sorted(set(df[c]) - {''})) for c in columns}
-    result = compress_forest(roots, columns, column2states, timing=args.pajek_timing, tip_size_threshold=args.tip_size_threshold,
-                             device=False if args.host else None)
+    if args.trim and args.pajek_timing != VERTICAL:
+        parser.error('--trim goes with --pajek_timing left at its default')
+    if args.trim:
+        result = compress_tree(roots, columns, column2states, tip_size_threshold=args.tip_size_threshold, pajek_timing=TRIM,
+                               device=False if args.host else None)
+    else:
+        result = compress_forest(roots, columns, column2states, timing=args.pajek_timing,
+                                 tip_size_threshold=args.tip_size_threshold, device=False if args.host else None)
     save_to_pajek(result, columns, args.pajek)
     return 0
 
