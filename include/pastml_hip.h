@@ -418,6 +418,24 @@ int pml_compress_trim_info(pml_ctx* ctx, double* sizes_ms, double* removal_ms, d
 int pml_simulate_states(pml_ctx* ctx, int32_t col, int32_t n_repetitions, int32_t rep_offset, uint64_t seed,
                         void* states_out);
 
+/*
+ * n_repetitions scenarios of column col drawn from the joint posterior given the tips: complete, internally consistent
+ * histories, one state per node and repetition.  The law is the one pml_marginal_counts samples (pastml/ml.py:786-824), applied
+ * per repetition: a root draws from its marginal posterior row; a child n of a parent in state a draws b with probability
+ * proportional to w_n[b] max(P_n[b][a], 0),  w_n[b] = BU_n[b] pi_b mask_n[b]  (BU = 1 at tips).  The masks are the ones the
+ * marginal pass ran with: with tau == 0 those altered by the zero-branch handling (ml.py:352-387) -- the scenarios follow that
+ * pass's law; the reference's fractional counts for altered pairs belong to the count table and have no part here.
+ * Needs pml_bottom_up (marginal) and pml_top_down_marginals first, PML_ERR_INVALID otherwise.  F81 family: k <= 512, one
+ * cumulative table per node; HKY / eigen models: k <= 256, cumulative rows per branch from the P(t) batch; PML_ERR_UNSUPPORTED
+ * beyond.  Draws keyed by (seed, caller's node id, rep_offset + r) with a counter tag of their own: results do not depend on
+ * launch geometry, chunking or the library's internal numbering, and calls with consecutive rep_offsets make up one larger call.
+ * states_out[n_nodes][n_repetitions], caller's numbering; uint8 for k <= 256, else uint16.
+ * n_fallback_out: the draws whose weights summed to zero and were taken from the node's own posterior row instead (with the
+ * same uniform); 0 after a consistent pass.
+ */
+int pml_sample_scenarios(pml_ctx* ctx, int32_t col, int32_t n_repetitions, int32_t rep_offset, uint64_t seed,
+                         void* states_out, int64_t* n_fallback_out);
+
 /* ---- multi-GPU (one process per GPU) ----------------------------------------------------------------------------------- */
 /*
  * The characters of a run are independent (pastml/acr.py:213-231 hands them to a pool one by one, each with its own

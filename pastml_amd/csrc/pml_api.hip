@@ -1771,6 +1771,40 @@ int pml_simulate_states(pml_ctx* ctx, int32_t col, int32_t n_repetitions, int32_
     return mem.finish();
 }
 
+// n_repetitions scenarios of column col drawn from the joint posterior (pml_launch_scenarios.hip), from the vectors the marginal
+// pass left on the device.  Rows and copy-out as in pml_simulate_states; n_fallback_out: the draws that found no weight.
+int pml_sample_scenarios(pml_ctx* ctx, int32_t col, int32_t n_repetitions, int32_t rep_offset, uint64_t seed, void* states_out,
+                         int64_t* n_fallback_out) {
+    PML_TRY(require_model(ctx));
+    if (col < 0 || col >= ctx->C || !states_out || !n_fallback_out) return fail(PML_ERR_INVALID, "bad column / output");
+    if (n_repetitions <= 0) return fail(PML_ERR_INVALID, "n_repetitions must be positive");
+    if (rep_offset < 0) return fail(PML_ERR_INVALID, "rep_offset must not be negative");
+    if (ctx->bu_mode != 1 || !ctx->td_valid)
+        return fail(PML_ERR_INVALID, "pml_sample_scenarios needs a marginal pml_bottom_up and pml_top_down_marginals first");
+    const int most = ctx->kind == PML_MODEL_F81 ? 512 : 256;
+    if (ctx->k > most) return fail(PML_ERR_UNSUPPORTED, "k = %d: pml_sample_scenarios holds at most %d states for this model", ctx->k, most);
+    PML_TRY(wait_pending(ctx, true));   // (a pass that ended in a spin on the completion word may have left the stream busy)
+    PML_TRY(materialize_cherries(ctx));  // the conditional probabilities need every bottom-up vector
+    PML_TRY(materialize_tip_posteriors(ctx));   // (a single-tip tree's root; the rows of the fallback)
+    PML_TRY(run_prep(ctx));  // P(t) of every branch (the fused sweeps never materialise it) / exp(-mu t')
+    const size_t es = ctx->k > 256 ? 2 : 1;
+    const size_t rs = ((size_t)n_repetitions + 3) / 4 * 4;
+    unsigned long long fallen = 0;
+    CallScope mem(ctx->stream, false);
+    unsigned char* d_states;
+    unsigned long long* d_fallen;
+    PML_TRY(mem.get(&d_states, (size_t)ctx->N * rs * es));
+    PML_TRY(mem.get(&d_fallen, 1));
+    HIP_TRY(hipMemsetAsync(d_fallen, 0, sizeof(unsigned long long), ctx->stream));
+    PML_TRY(launch_scenarios(ctx, col, n_repetitions, rep_offset, seed, d_states, rs, d_fallen));
+    HIP_TRY(hipMemcpy2DAsync(states_out, (size_t)n_repetitions * es, d_states, rs * es, (size_t)n_repetitions * es, (size_t)ctx->N,
+                             hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(hipMemcpyAsync(&fallen, d_fallen, sizeof(unsigned long long), hipMemcpyDeviceToHost, ctx->stream));
+    PML_TRY(mem.finish());
+    *n_fallback_out = (int64_t)fallen;
+    return PML_OK;
+}
+
 // Maximum parsimony of n_cols characters on the uploaded forest (pml_launch_parsimony.hip).  Needs the tree only: no columns,
 // no model, no likelihood vectors -- the scratch of the call is freed before it returns.
 int pml_parsimony(pml_ctx* ctx, int32_t n_cols, int32_t k, const uint64_t* given, int methods, uint64_t* sets_out,

@@ -145,6 +145,14 @@ PML_INTERNAL int launch_pij_valu(pml_ctx* ctx);
 // ---- pml_launch_simulate.hip: forward simulation of a column along the forest (pml_simulate_states); d_states [N][rs] in the
 //      caller's numbering, uint8 for k <= 256, else uint16
 PML_INTERNAL int launch_simulate(pml_ctx* ctx, int col, int rep_offset, u64 seed, void* d_states, size_t rs);
+//      its schedule, which the scenario sampler shares: the frontier depth D for n_tiles repetition tiles per node, and the preorder
+//      lists of the subtrees rooted at depth D (ctx->d_sim_lists / d_sim_off / sim_n_lists)
+PML_INTERNAL int sim_frontier_depth(const pml_ctx* ctx, int n_tiles);
+PML_INTERNAL int sim_subtree_lists(pml_ctx* ctx, int D);
+// ---- pml_launch_scenarios.hip: scenarios of a column from the joint posterior after a marginal pass (pml_sample_scenarios);
+//      d_states as for launch_simulate, d_fallback: one counter (zeroed)
+PML_INTERNAL int launch_scenarios(pml_ctx* ctx, int col, int n_rep, int rep_offset, u64 seed, void* d_states, size_t rs,
+                                  unsigned long long* d_fallback);
 // ---- pml_launch_parsimony.hip: the parsimony passes on packed state sets (pml_parsimony); host arrays in the caller's numbering
 PML_INTERNAL int launch_parsimony(pml_ctx* ctx, int n_cols, int k, const u64* given, int methods, u64* sets_out, i64* steps_out,
                                   i64* hist_out);

@@ -11,7 +11,7 @@
 #define PML_SIM_MAX_TOP 16
 #define PML_SIM_SCRATCH_BYTES (256ull << 20)   // bound of the cumulative rows of wide matrix models (PML_SIM_MATRIX_SCRATCH)
 
-static int frontier_depth(const pml_ctx* ctx, int n_tiles) {
+PML_INTERNAL int sim_frontier_depth(const pml_ctx* ctx, int n_tiles) {
     const int L = ctx->n_td_levels;
     for (int d = 0; d < L; ++d) {
         const long long cnt = ctx->forest.td_offsets[d + 1] - ctx->forest.td_offsets[d];
@@ -21,7 +21,7 @@ static int frontier_depth(const pml_ctx* ctx, int n_tiles) {
 }
 
 // preorder lists of the subtrees rooted at depth D (entries: PmlSimArgs::lists), uploaded once per (tree, D)
-static int subtree_lists(pml_ctx* ctx, int D) {
+PML_INTERNAL int sim_subtree_lists(pml_ctx* ctx, int D) {
     if (ctx->sim_depth == D) return PML_OK;
     const int r0 = ctx->forest.td_offsets[D], r1 = ctx->forest.td_offsets[D + 1];
     const int* fc = ctx->forest.first_child.data();   // (the library's numbering: a node's children are fc[n] .. fc[n] + nc - 1)
@@ -91,8 +91,8 @@ PML_INTERNAL int launch_simulate(pml_ctx* ctx, int col, int rep_offset, u64 seed
     const int n_tuples = (int)(rs / 4);
     const int threads = std::min(PML_SIM_THREADS, 64 * ((n_tuples + 63) / 64));
     const int n_tiles = (n_tuples + threads - 1) / threads;
-    const int D = frontier_depth(ctx, n_tiles);
-    if (D < ctx->n_td_levels) PML_TRY(subtree_lists(ctx, D));
+    const int D = sim_frontier_depth(ctx, n_tiles);
+    if (D < ctx->n_td_levels) PML_TRY(sim_subtree_lists(ctx, D));
     PmlSimArgs a;
     a.parent = ctx->d_parent;
     a.api_id = ctx->d_old_of_new;   // (null when the library works in the caller's numbering)

@@ -109,6 +109,8 @@ SIGNATURES = {
                                     _c_double_p, _c_int32_p, _c_int32_p],
     'pml_expected_counts': [_ctx_p, ctypes.c_int32, ctypes.c_int32, ctypes.POINTER(ctypes.c_uint8), _c_double_p, _c_double_p],
     'pml_simulate_states': [_ctx_p, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_uint64, ctypes.c_void_p],
+    'pml_sample_scenarios': [_ctx_p, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_uint64, ctypes.c_void_p,
+                             ctypes.POINTER(ctypes.c_int64)],
     'pml_parsimony': [_ctx_p, ctypes.c_int32, ctypes.c_int32, _c_uint64_p, ctypes.c_int, _c_uint64_p,
                       ctypes.POINTER(ctypes.c_int64), ctypes.POINTER(ctypes.c_int64)],
     'pml_parsimony_info': [_ctx_p, ctypes.POINTER(ctypes.c_int64), _c_double_p],
@@ -811,6 +813,21 @@ class Engine(BareContext):
         _check(self._lib.pml_simulate_states(self._ctx, col, int(n_repetitions), int(rep_offset), ctypes.c_uint64(int(seed)),
                                              out.ctypes.data_as(ctypes.c_void_p)))
         return out
+
+    def sample_scenarios(self, count, seed, rep_offset=0, col=0):
+        """
+        count scenarios of column col drawn from the joint posterior after a marginal pass (pml_sample_scenarios): a root from
+        its marginal posterior, a child from BU_n[b] pi_b mask_n[b] P_n[b][a] given its parent's state a in the same repetition.
+        Returns (states [n_nodes, count] in this engine's node numbering, uint8 for k <= 256, else uint16; the number of draws
+        that found no weight and fell back on the node's posterior -- 0 after a consistent pass).  Repetition r is drawn with
+        the generator keyed by (seed, node, rep_offset + r): consecutive calls with consecutive rep_offsets make up one larger call.
+        """
+        dtype = np.uint8 if self.k <= 256 else np.uint16
+        out = np.empty((self.n_nodes, int(count)), dtype=dtype)
+        fallen = ctypes.c_int64(0)
+        _check(self._lib.pml_sample_scenarios(self._ctx, col, int(count), int(rep_offset), ctypes.c_uint64(int(seed)),
+                                              out.ctypes.data_as(ctypes.c_void_p), ctypes.byref(fallen)))
+        return out, fallen.value
 
     @classmethod
     def tree_only(cls, flat, device=None, tune=None):
