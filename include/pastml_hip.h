@@ -191,6 +191,24 @@ int pml_pij(pml_ctx* ctx, int32_t col, int32_t n_t, const double* t, double* P_o
  * the tree changed.  If P_out != NULL, additionally copies out P for every branch: P_out[n_cols][n_nodes][k][k].
  */
 int pml_pij_batch(pml_ctx* ctx, double* P_out);
+/*
+ * Eigen models with 33 .. 256 states: the sweeps that read P(t) -- the joint sweep beyond 64 states, every sweep beyond 128 and
+ * wherever the fused sweeps are switched off -- build it in a window of `branches` matrices per column instead of keeping
+ * n_nodes of them: a level is cut into runs of parents whose children fit the window, and each run's launch follows one that
+ * builds exactly those branches' matrices (pml_pij_window.h).  This is the reference's way -- a branch's matrix is built where
+ * it is needed and dropped, pastml/models/CustomRatesModel.py:70-79, generator.py:54-65 --; every matrix is computed by the
+ * instructions that compute it for the batch, so the sweeps leave the same bits.  branches = 0: off, the batch as before.
+ * Allocates n_cols x branches x k x ks doubles (branches capped at n_nodes) and frees the batch if there is one.
+ * PML_ERR_UNSUPPORTED for F81 / HKY contexts, for k <= 32 and under PASTML_HIP_NO_MFMA / _NO_PIJ_WIDE (the batch is then built by
+ * another kernel, whose bits a window would not leave; set after the window, they take it away at the next sweep); PML_ERR_INVALID below the largest fan-out of the forest (the message
+ * names it) and before the first model is set.  pml_pij_batch, pml_marginal_counts, pml_expected_counts, pml_simulate_states,
+ * pml_sample_scenarios and the download of the top-down vectors still read P(t) of the whole tree: on a windowed context they
+ * allocate the batch as they do on any other, and it stays until the window is set again.
+ * PASTML_HIP_PIJ_WINDOW=<branches> does the same for every context it fits (raised to the fan-out, capped at n_nodes).
+ */
+int pml_pij_window_set(pml_ctx* ctx, long long branches);
+/* What is allocated now: the window's branches (0: off) and bytes, and the bytes of the whole-tree batch (0: never allocated or freed). */
+int pml_pij_window_info(pml_ctx* ctx, long long* branches, long long* window_bytes, long long* batch_bytes);
 
 /* ---- sweeps --------------------------------------------------------------------------------------------------------- */
 /*

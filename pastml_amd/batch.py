@@ -201,6 +201,7 @@ class CharacterBatch(object):
         self._uploaded = None
         self._uploaded_models = None
         self.n_sweeps = 0
+        self.pij_window = 0   # branches of the P(t) window of this batch's contexts (run_tasks; 0: the whole-tree batch)
 
     # ------------------------------------------------------------------------------------------------ resources
     @property
@@ -285,6 +286,15 @@ class CharacterBatch(object):
         if getattr(self, cache_attr) != keys:
             engine.set_models(models, col_begin=col_begin)
             setattr(self, cache_attr, keys)
+        self._apply_window(engine)
+
+    def _apply_window(self, engine, optimiser=False):
+        """The P(t) window run_tasks planned for this batch (0: none), on a context whose models are set; a pooled engine may
+        come with another batch's.  The optimiser's context runs sum sweeps only, which are fused up to 128 states and never
+        read P(t): it gets a window beyond 128 states only (_window_bytes_per_branch charges accordingly)."""
+        want = self.pij_window if (not optimiser or self.k > 128) else 0
+        if getattr(engine, '_pij_window', 0) != want:
+            engine.pij_window_set(want)
 
     def _upload_masks(self):
         eng = self.engine
@@ -499,6 +509,7 @@ class CharacterBatch(object):
                     eng.set_mask_words(self.masks[c], col_begin=i)
                     opt['variant'][i] = 0
             eng.set_models(models)
+            self._apply_window(eng, optimiser=True)
             opt['all_set'] = True
             opt['staged'] = eng.kind == hip.KIND_F81   # (every column's parameters are in the engine's staging arrays now)
         else:
@@ -1367,14 +1378,68 @@ def reconstruct(batch, tasks, lnl, force_joint=True):
 # states read P(t) of every branch from HBM, k x k doubles per node and column (Limits): the joint sweep of the
 # character's own column always (65 - 128 states: the sum sweeps are fused, so the optimiser's columns need none), every column
 # beyond 128 states.
-def _column_bytes(flat, k, widths, kind=hip.KIND_F81):
+# windowed: the contexts build P(t) in a window (pml_pij_window_set) -- no term in n_nodes x k x k; the windows themselves are
+# charged by _window_bytes_per_branch.
+def _column_bytes(flat, k, widths, kind=hip.KIND_F81, windowed=False):
     ks = k + (k & 1)
     own, point = 17 * ks + 96, 8 * ks + 64
-    if kind == hip.KIND_EIGEN and k > 64:
+    if kind == hip.KIND_EIGEN and k > 64 and not windowed:
         own += 8 * k * ks
         if k > 128:
             point += 8 * k * ks
     return flat.n_nodes * (own + sum(widths) / max(1, len(widths)) * point)
+
+
+def _window_bytes_per_branch(k, widths):
+    """Bytes one branch of the P(t) window costs per character: a k x ks matrix in the character's own context (its joint sweep
+    reads P(t)) and, beyond 128 states, one per column of its optimiser block (up to 128 the sum sweeps are fused and the
+    optimiser's context gets no window: the same split as _column_bytes makes for the whole-tree batch)."""
+    lane = 2 if k <= 128 else 4   # states per lane of the matrix sweeps: a row of P(t) is padded to a multiple of it
+    ks = -(-k // lane) * lane
+    return 8.0 * k * ks * (1 + (sum(widths) / max(1, len(widths)) if k > 128 else 0))
+
+
+# Branches a window should hold, where the budget allows, before more characters share a context.  Measured at k = 128 on a
+# 65 536-tip tree x 4 characters (profiles/pij_window.txt, rows "window 4096" / "window 512" / "window 128"): the joint sweep
+# costs 1.10 x the materialised one with 4 096 branches, 1.21 x with 512, 4.2 x with 128 (launch-bound); larger is better still,
+# and the planner takes the largest window that fits once the characters per context are chosen.  Other k: not measured.
+PIJ_WINDOW_PREFERRED = 4096
+
+
+def plan_pij_window(flat, k, widths, kind, n_members, free, character='?', setting=None):
+    """
+    Materialised or windowed P(t) for a group of n_members characters: (characters per context, branches of the window -- 0:
+    the whole-tree batch).  Materialised whenever at least one column fits the 0.6 x free budget, so no run that fitted before
+    changes; windowed otherwise (eigen models beyond 64 states, whose sweeps read P(t)): as many characters per context as
+    leave a window of PIJ_WINDOW_PREFERRED branches, then the largest window that fits, never above the number of nodes and
+    never below the largest fan-out.  MemoryError if not even the largest fan-out fits.
+    setting: PASTML_AMD_PIJ_WINDOW -- 'auto' (None), '0' (always materialised: the numbers of before), or the branches to use.
+    """
+    setting = 'auto' if setting in (None, '') else str(setting).strip().lower()
+    budget = 0.6 * free
+    per_char = _column_bytes(flat, k, widths, kind=kind)
+    chunk = max(1, min(n_members, 4096, int(budget / max(1.0, per_char))))
+    eligible = kind == hip.KIND_EIGEN and 64 < k <= 256
+    if setting == '0' or not eligible or (setting == 'auto' and int(budget / max(1.0, per_char)) >= 1):
+        return chunk, 0
+    n, fan = int(flat.n_nodes), int(np.max(flat.n_children))
+    lean = _column_bytes(flat, k, widths, kind=kind, windowed=True)
+    per_branch = _window_bytes_per_branch(k, widths)
+    if lean + fan * per_branch > budget:
+        raise MemoryError('character {} (k = {}): {:.3g} bytes of device memory are planned for it, and its columns with a '
+                          'window of P(t) for the {} branches of the largest polytomy need {:.3g}'
+                          .format(character, k, budget, fan, lean + fan * per_branch))
+    if setting != 'auto':
+        branches = max(fan, min(n, int(setting)))
+        if lean + branches * per_branch > budget:
+            raise MemoryError('character {} (k = {}): a window of {} branches (PASTML_AMD_PIJ_WINDOW; largest polytomy: {}) '
+                              'needs {:.3g} bytes, {:.3g} are planned'.format(character, k, branches, fan,
+                                                                               lean + branches * per_branch, budget))
+        return max(1, min(n_members, 4096, int(budget / (lean + branches * per_branch)))), branches
+    prefer = min(n, max(fan, PIJ_WINDOW_PREFERRED))
+    chunk = max(1, min(n_members, 4096, int(budget / (lean + prefer * per_branch))))
+    branches = int((budget / chunk - lean) / per_branch)
+    return chunk, max(fan, min(n, branches))
 
 
 def visible_devices(device=None):
@@ -1423,14 +1488,22 @@ def run_tasks(forest, tasks, force_joint=True, device=None, flat=None, seeds=Non
     # by the host loop, which does not get shorter)
     split_min = float(os.environ.get('PASTML_AMD_SPLIT_MIN_WORK', 2e5))
     jobs, job_bytes = [], []
+    stats['pij_window'] = []   # per group: where its sweeps find P(t) (plan_pij_window)
     for key, members in groups.items():
         k = key[0]
-        per_char = _column_bytes(flat, k, [block_width(tasks[i].model) for i in members], kind=key[1])
-        chunk = max(1, min(len(members), 4096, int(0.6 * free / max(1.0, per_char))))
+        widths = [block_width(tasks[i].model) for i in members]
+        chunk, window = plan_pij_window(flat, k, widths, key[1], len(members), free, character=tasks[members[0]].character,
+                                        setting=os.environ.get('PASTML_AMD_PIJ_WINDOW'))
+        per_char = _column_bytes(flat, k, widths, kind=key[1], windowed=window > 0) + window * _window_bytes_per_branch(k, widths)
+        stats['pij_window'].append(dict(k=k, characters=len(members), mode='windowed' if window else 'materialised',
+                                        branches=window, characters_per_context=chunk))
+        logging.getLogger('pastml').debug('P(t) of the {} character(s) with {} states: {}'.format(
+            len(members), k, 'a window of {} branches, {} character(s) per context'.format(window, chunk) if window
+            else 'materialised for the whole tree'))
         if len(devices) > 1 and len(members) >= 2 and flat.n_nodes * len(members) >= split_min:
             chunk = min(chunk, -(-len(members) // len(devices)))
         for a in range(0, len(members), chunk):
-            jobs.append((k, members[a:a + chunk]))
+            jobs.append((k, members[a:a + chunk], window))
             job_bytes.append(per_char * len(members[a:a + chunk]))
     # placement: largest job first, each on the device that holds the least so far (deterministic)
     load = [0.0] * len(devices)
@@ -1439,7 +1512,7 @@ def run_tasks(forest, tasks, force_joint=True, device=None, flat=None, seeds=Non
         d = min(range(len(devices)), key=lambda q: (load[q], q))
         job_device[j] = devices[d]
         load[d] += job_bytes[j]
-    jobs = [(k, part, job_device[j]) for j, (k, part) in enumerate(jobs)]
+    jobs = [(k, part, job_device[j], window) for j, (k, part, window) in enumerate(jobs)]
     total_bytes = max(load) if load else 0.0
     stats['devices'] = sorted(set(job_device)) if jobs else []
 
@@ -1454,9 +1527,10 @@ def run_tasks(forest, tasks, force_joint=True, device=None, flat=None, seeds=Non
     import time
 
     def prepare(job):
-        k, part, dev = job
+        k, part, dev, window = job
         group = [tasks[i] for i in part]
         batch = CharacterBatch(flat, k, len(group), device=dev)
+        batch.pij_window = window
         for c, t in enumerate(group):
             batch.set_annotation(c, *annotation_words(flat, t.character, t.model.states))
         batch.initialize_allowed_states()

@@ -5,6 +5,7 @@
 #include "pml_kernels_counts.h"
 #include "pml_kernels_eigen_gemm.h"   // (eig_sym_kernel)
 #include "pml_comm.h"
+#include "pml_pij_window.h"
 
 // sha256 (first 16 hex digits) over the sources this library was compiled from, handed in by pastml_amd/build.py; the
 // marker in front lets build.py read it out of the file without loading it
@@ -324,6 +325,8 @@ int pml_tree_upload(pml_ctx* ctx, int32_t n_nodes, int32_t n_roots, const int32_
     PML_TRY(put(ctx, &ctx->d_dist, t.dist, n_nodes));
     PML_TRY(put(ctx, &ctx->d_bu_order, t.bu_order, n_internal));
     PML_TRY(put(ctx, &ctx->d_td_parents, t.td_parents, n_internal));
+    ctx->bu_order.assign(t.bu_order, t.bu_order + n_internal);   // (host copies: the window planner cuts these lists into runs)
+    ctx->td_parents.assign(t.td_parents, t.td_parents + n_internal);
     if (permuted(ctx)) {
         PML_TRY(put(ctx, &ctx->d_new_of_old, ctx->new_of_old));
         PML_TRY(put(ctx, &ctx->d_old_of_new, ctx->old_of_new));
@@ -912,6 +915,107 @@ static int require_model(pml_ctx* ctx) {
     return PML_OK;
 }
 
+// ---------------------------------------------------------------------------------------------------------------------
+// P(t) in a window (pml_pij_window.h).  The plans the branch lists are cut from are those of the sweeps that read P(t): the
+// plain level launches, whatever the switches of the fused sweeps say -- a sweep's own plan, cut again when it is enqueued
+// (run_plan), must list the same branches.
+static PmlSweepTraits sweep_traits(const pml_ctx* ctx);
+static PmlSchedules schedules_of(const pml_ctx* ctx);
+
+static void window_drop(pml_ctx* ctx) {
+    const size_t kk = (size_t)ctx->k * ctx->ks;
+    dev_release(ctx, &ctx->d_pij_window, (size_t)ctx->C * (size_t)ctx->pij_window * kk);
+    for (int i = 0; i < 2; ++i) {
+        dev_release(ctx, &ctx->d_win_branches[i], ctx->win_branches[i].size());
+        dev_release(ctx, &ctx->d_win_slot[i], (size_t)ctx->N);
+        ctx->win_branches[i].clear();
+    }
+    ctx->win_cuts.clear();
+    ctx->pij_window = 0;
+}
+
+static int window_set(pml_ctx* ctx, long long branches) {
+    HIP_TRY(hipSetDevice(ctx->device));
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    ctx->pending.spin = false;
+    // a captured launch sequence was made for the other source of P(t)
+    drop_sweep_graphs(ctx);
+    ctx->prep_dirty = true;
+    window_drop(ctx);
+    if (branches == 0) return PML_OK;
+    const long long B = std::min<long long>(branches, ctx->N);
+    PmlSweepTraits t = sweep_traits(ctx);
+    t.eigen_fused = t.eigen_gemm = t.eigen_joint_valu = t.hky_fused = false;
+    PmlWindowPlan W[2];
+    const std::vector<PmlLaunch> plans[2] = {pml_plan_bottom_up(ctx->forest, schedules_of(ctx), t, false),
+                                             pml_plan_top_down(ctx->forest, schedules_of(ctx), t, false)};
+    for (int i = 0; i < 2; ++i) {
+        const std::string bad = pml_plan_pij_window(plans[i], ctx->forest, ctx->bu_order, ctx->td_parents, B, W[i]);
+        if (!bad.empty()) return fail(PML_ERR_INVALID, "%s", bad.c_str());
+    }
+    const size_t kk = (size_t)ctx->k * ctx->ks;
+    dev_release(ctx, &ctx->d_P, (size_t)ctx->C * ctx->N * kk);   // the batch goes: the sweeps no longer read it
+    PML_TRY(arm_pij_wide_list(ctx));   // (the LDS attribute of the build kernel: not inside a stream capture)
+    int status = dev_alloc(ctx, &ctx->d_pij_window, (size_t)ctx->C * (size_t)B * kk);
+    for (int i = 0; i < 2 && status == PML_OK; ++i) {
+        status = put(ctx, &ctx->d_win_branches[i], W[i].branches);
+        if (status == PML_OK) status = put(ctx, &ctx->d_win_slot[i], W[i].slot);
+        ctx->win_branches[i].swap(W[i].branches);
+    }
+    ctx->pij_window = B;
+    const hipError_t e = hipStreamSynchronize(ctx->stream);   // (the host tables go out of scope)
+    if (status != PML_OK || e != hipSuccess) {
+        window_drop(ctx);
+        return status != PML_OK ? status : fail(PML_ERR_HIP, "upload of the window's tables failed: %s", hipGetErrorString(e));
+    }
+    return PML_OK;
+}
+
+// (NO_MFMA / NO_PIJ_WIDE: the batch is then built by the one-thread-per-entry kernel, whose sums associate differently from the
+// matrix-core kernel the window is built with -- a window would not leave the batch's bits, so there is none under them)
+static bool window_eligible(const pml_ctx* ctx) {
+    return ctx->kind == PML_MODEL_EIGEN && ctx->k > 32 && ctx->k <= PML_MAX_STATES_MATRIX && !ctx->tune.on(T_NO_MFMA) &&
+           !ctx->tune.on(T_NO_PIJ_WIDE);
+}
+
+// PASTML_HIP_PIJ_WINDOW (branches; 0: the batch): applied where a sweep is submitted, once per value -- the model kind and the
+// columns are known there.  It is raised to the largest fan-out and capped at the number of nodes; contexts the window is not
+// for (F81, HKY, k <= 32) ignore it.  Not set: what pml_pij_window_set said stands.
+static int window_from_tunable(pml_ctx* ctx) {
+    // (a switch set after the window took away what the window is built with: back to the batch)
+    if (ctx->pij_window > 0 && !window_eligible(ctx)) PML_TRY(window_set(ctx, 0));
+    if (!ctx->tune.on(T_PIJ_WINDOW)) return PML_OK;
+    const long long want = ctx->tune.get(T_PIJ_WINDOW, 0);
+    if (want == ctx->pij_window_tuned) return PML_OK;
+    ctx->pij_window_tuned = want;
+    if (!window_eligible(ctx) || want < 0) return PML_OK;
+    return window_set(ctx, want == 0 ? 0 : std::max<long long>(want, pml_window_max_fanout(ctx->forest)));
+}
+
+int pml_pij_window_set(pml_ctx* ctx, long long branches) {
+    if (!ctx || ctx->C == 0) return fail(PML_ERR_INVALID, "allocate the columns first");
+    if (branches < 0) return fail(PML_ERR_INVALID, "a window of %lld branches", branches);
+    if (branches == 0) return window_set(ctx, 0);
+    if (ctx->kind < 0) return fail(PML_ERR_INVALID, "set the model first: the window is for eigen models");
+    if (!window_eligible(ctx))
+        return fail(PML_ERR_UNSUPPORTED, "the P(t) window is for eigen models with 33 .. %d states whose P(t) is built on the matrix "
+                    "cores (this context: model kind %d, k = %d, NO_MFMA %d, NO_PIJ_WIDE %d)", PML_MAX_STATES_MATRIX, ctx->kind, ctx->k,
+                    (int)ctx->tune.on(T_NO_MFMA), (int)ctx->tune.on(T_NO_PIJ_WIDE));
+    const int fan = pml_window_max_fanout(ctx->forest);
+    if (branches < fan)
+        return fail(PML_ERR_INVALID, "a window of %lld branches is below the largest fan-out of the forest, %d", branches, fan);
+    return window_set(ctx, branches);
+}
+
+int pml_pij_window_info(pml_ctx* ctx, long long* branches, long long* window_bytes, long long* batch_bytes) {
+    if (!ctx) return fail(PML_ERR_INVALID, "ctx is NULL");
+    const long long kk = (long long)ctx->k * ctx->ks * (long long)sizeof(double);
+    if (branches) *branches = ctx->pij_window;
+    if (window_bytes) *window_bytes = ctx->d_pij_window ? (long long)ctx->C * ctx->pij_window * kk : 0;
+    if (batch_bytes) *batch_bytes = ctx->d_P ? (long long)ctx->C * ctx->N * kk : 0;
+    return PML_OK;
+}
+
 static int ensure_transition_storage(pml_ctx* ctx) {
     if (ctx->kind != PML_MODEL_F81 && !ctx->d_P)
         PML_TRY(dev_alloc(ctx, &ctx->d_P, (size_t)ctx->C * ctx->N * ctx->k * ctx->ks));
@@ -1073,7 +1177,37 @@ static PmlSchedules schedules_of(const pml_ctx* ctx) {
 // one call of a launcher per record.  bottom_up: they are a bottom-up sweep's, which looks at the flags of the active
 // columns.  The profile brackets open and close where a record's bracket differs from the one before it, and a bracket's
 // launches are its records.  (What the launches leave behind: pml_plan_outcome.)
-static int run_plan(pml_ctx* ctx, const std::vector<PmlLaunch>& plan, bool bottom_up, int is_marginal, bool force_prep) {
+// A context with a window (pml_pij_window.h) issues the windowed sequence: the plan's plain level records cut into runs, each run's
+// launch behind the one that builds its branches' matrices into the window; the per-branch pass builds nothing.
+static int run_plan(pml_ctx* ctx, const std::vector<PmlLaunch>& whole_plan, bool bottom_up, int is_marginal, bool force_prep) {
+    const bool windowed = ctx->pij_window > 0 && ctx->kind == PML_MODEL_EIGEN;
+    const int wtab = bottom_up ? 0 : 1;
+    const std::vector<PmlWindowStep>* cached = nullptr;
+    std::vector<PmlLaunch> cut;
+    if (windowed) {
+        auto same = [](const PmlLaunch& a, const PmlLaunch& b) {
+            return a.op == b.op && a.list == b.list && a.kind == b.kind && a.bracket == b.bracket && a.branch == b.branch &&
+                   a.signal == b.signal && a.cherries == b.cherries && a.first == b.first && a.count == b.count && a.arg == b.arg;
+        };
+        for (const pml_ctx::WindowCut& c : ctx->win_cuts)
+            if (c.plan.size() == whole_plan.size() && std::equal(c.plan.begin(), c.plan.end(), whole_plan.begin(), same)) cached = &c.steps;
+        if (cached == nullptr) {
+            PmlWindowPlan W;
+            const std::string bad = pml_plan_pij_window(whole_plan, ctx->forest, ctx->bu_order, ctx->td_parents, ctx->pij_window, W);
+            if (!bad.empty()) return fail(PML_ERR_INVALID, "%s", bad.c_str());
+            if (!W.branches.empty() && W.branches != ctx->win_branches[wtab])
+                return fail(PML_ERR_INVALID, "the sweep's runs are not the ones the window's branch lists were uploaded for");
+            if (ctx->win_cuts.size() >= 16) ctx->win_cuts.clear();   // (a handful of plans per context: two sweeps, signalling or not)
+            ctx->win_cuts.push_back(pml_ctx::WindowCut{whole_plan, std::move(W.steps)});
+            cached = &ctx->win_cuts.back().steps;
+        }
+        cut.reserve(cached->size());
+        for (const PmlWindowStep& w : *cached) cut.push_back(w.launch);
+    }
+    static const std::vector<PmlWindowStep> no_steps;
+    const std::vector<PmlWindowStep>& steps = windowed ? *cached : no_steps;
+    const std::vector<PmlLaunch>& plan = windowed ? cut : whole_plan;
+    size_t at = 0;
     const pml_ctx::EigenTiers& E = ctx->eig_tiers;
     const pml_ctx::BacktraceTiers& B = ctx->bt_tiers;
     const int* order = bottom_up ? ctx->d_bu_order : nullptr;   // (top-down: the nodes of a depth are a contiguous id range)
@@ -1093,6 +1227,13 @@ static int run_plan(pml_ctx* ctx, const std::vector<PmlLaunch>& plan, bool botto
             launches = 0;
         }
         ++launches;
+        const PmlWindowStep* run = windowed ? &steps[at] : nullptr;
+        ++at;
+        if (run != nullptr && run->build_count > 0) {
+            PML_TRY(launch_pij_wide_list(ctx, ctx->d_pij_window, ctx->pij_window, ctx->d_win_branches[wtab] + run->build_first,
+                                         run->build_count));
+            ++launches;
+        }
         const bool joint = r.kind == EIG_JOINT, gemm = r.kind == EIG_GEMM;   // (of the eigen ops; else the fused matrix-core kernels)
         switch (r.op) {
             case OP_RESET_ERR:
@@ -1101,7 +1242,7 @@ static int run_plan(pml_ctx* ctx, const std::vector<PmlLaunch>& plan, bool botto
                 HIP_TRY(hipGetLastError());
                 break;
             case OP_PREP:   // (brackets itself: other callers run it outside a sweep)
-                PML_TRY(run_prep(ctx, force_prep, true));
+                if (!windowed) PML_TRY(run_prep(ctx, force_prep, true));
                 break;
             case OP_LOGLIK:
                 // ln L and the error words are written straight into pinned host memory by the last kernel
@@ -1111,7 +1252,8 @@ static int run_plan(pml_ctx* ctx, const std::vector<PmlLaunch>& plan, bool botto
                 HIP_TRY(hipGetLastError());
                 break;
             case OP_LEVEL:
-                PML_TRY(dispatch_sweep(ctx, (SweepKind)r.kind, r.list, r.first, r.count, r.cherries, bottom_up));
+                PML_TRY(dispatch_sweep(ctx, (SweepKind)r.kind, r.list, r.first, r.count, r.cherries, bottom_up,
+                                       windowed && (r.list == L_BU_PLAIN || r.list == L_TD_PLAIN) ? wtab : -1));
                 break;
             case OP_ROOTS:
                 PML_TRY(dispatch_sweep(ctx, SW_ROOTS, L_NONE, 0, r.count));
@@ -1263,7 +1405,7 @@ static void note_bottom_up(pml_ctx* ctx, int is_marginal, const PmlSweepOutcome&
     const bool f81_marginal = is_marginal && ctx->kind == PML_MODEL_F81;
     ctx->js_valid = false;
     ctx->bu_fused_joint = outcome.fused_joint;
-    if (!sweep_without_p(ctx, is_marginal)) ctx->prep_dirty = false;   // (else no batch ran)
+    if (!sweep_without_p(ctx, is_marginal) && ctx->pij_window == 0) ctx->prep_dirty = false;   // (else no batch ran)
     ctx->bu_fused = (f81_marginal && ctx->n_cherries > 0) || ctx->bu_fused_joint;
     // (a sweep of some of the columns says nothing about the others: where an earlier sweep of the level schedule left the
     // children of their two-level units out of memory they still are -- rebuilding rows that are in memory is harmless)
@@ -1310,6 +1452,7 @@ static int generation_before(pml_ctx* ctx, u64* generation) {
 static int submit_bottom_up(pml_ctx* ctx, int is_marginal, const uint8_t* active, bool may_spin, PmlCapture capture,
                             PmlSweepOutcome* outcome) {
     set_active_columns(ctx, active);
+    if (capture == CAP_NONE) PML_TRY(window_from_tunable(ctx));
     u64 generation = 0;
     PML_TRY(generation_before(ctx, &generation));
     // A sweep of a few columns of a context of many is scheduled as a context of few would be (the workgroups of the
@@ -1340,7 +1483,7 @@ static int submit_bottom_up(pml_ctx* ctx, int is_marginal, const uint8_t* active
         PML_TRY(dev_alloc(ctx, &ctx->d_tip_rest, (size_t)ctx->C * std::max(1, ctx->n_tips)));
         PML_TRY(dev_alloc(ctx, &ctx->d_tip_rest_count, (size_t)ctx->C));
     }
-    if (!sweep_without_p(ctx, is_marginal)) PML_TRY(ensure_transition_storage(ctx));
+    if (!sweep_without_p(ctx, is_marginal) && ctx->pij_window == 0) PML_TRY(ensure_transition_storage(ctx));
     ctx->bu_mode = -1;
     ctx->td_valid = ctx->js_valid = false;
     // mid-size forests: the level launches are latency-bound, replay them as one hipGraph

@@ -22,6 +22,7 @@
 
 #include "pml_model.h"   // PmlTree, PmlCols, PmlState, PmlUnit, PmlModel (and the F81 / miscellaneous kernels' headers below it)
 #include "pml_schedule.h" // PmlTune, the schedules' host side, PmlForest
+#include "pml_pij_window.h" // PmlWindowStep
 
 struct PmlComm;  // pml_comm.h (pml_api.hip only)
 
@@ -147,6 +148,21 @@ struct pml_ctx {
     std::vector<char> model_set;  // per column
     std::vector<char> tips_observed;  // per column: every tip has exactly one allowed state (known from pml_masks_from_tip_states)
     bool prep_dirty = true;
+    // P(t) in a window instead of the batch (pml_pij_window.h; eigen models beyond 32 states, pml_pij_window_set): B branches per
+    // column; the branch lists of the bottom-up [0] and the top-down [1] level lists in run order, and the per-node slot tables
+    long long pij_window = 0;            // B; 0 = the batch of the whole tree (d_P)
+    long long pij_window_tuned = -1;     // the value of PASTML_HIP_PIJ_WINDOW that was applied last (window_from_tunable)
+    double* d_pij_window = nullptr;      // [C][B][k][ks]
+    int *d_win_branches[2] = {nullptr, nullptr}, *d_win_slot[2] = {nullptr, nullptr};
+    std::vector<int> win_branches[2];    // host copies: a sweep's windowed plan must list what was uploaded
+    std::vector<int> bu_order, td_parents;   // the plain level lists on the host (library's numbering), for the window planner
+    // the windowed sequences already cut for this window, by the plan they were cut from (a sweep's plan is a few records per
+    // level; cutting it is O(N)): an uncaptured sweep plans its runs once, not per likelihood evaluation.  Dropped with the window.
+    struct WindowCut {
+        std::vector<PmlLaunch> plan;
+        std::vector<PmlWindowStep> steps;
+    };
+    std::vector<WindowCut> win_cuts;
 
     // state
     double *d_E = nullptr, *d_P = nullptr, *d_bu = nullptr, *d_S = nullptr, *d_td = nullptr, *d_post = nullptr,
@@ -240,6 +256,21 @@ static int dev_alloc(pml_ctx* ctx, T** p, size_t count) {
     ctx->held += count * sizeof(T);
     *p = (T*)q;
     return PML_OK;
+}
+
+// gives back one of the context's own allocations before the context goes
+template <typename T>
+static void dev_release(pml_ctx* ctx, T** p, size_t count) {
+    if (!*p) return;
+    for (size_t i = 0; i < ctx->allocs.size(); ++i)
+        if (ctx->allocs[i] == (void*)*p) {
+            ctx->allocs.erase(ctx->allocs.begin() + (long)i);
+            break;
+        }
+    (void)hipFree((void*)*p);
+    const size_t bytes = (count ? count : 1) * sizeof(T);
+    ctx->held -= std::min(ctx->held, bytes);
+    *p = nullptr;
 }
 
 static void drop_graph(pml_ctx::GraphSlot& g) {

@@ -49,7 +49,18 @@ __device__ __forceinline__ void matvec_prow(const PRow4& r, const double* __rest
 
 #define PML_P_MATERIALISED 0
 #define PML_P_HKY 1
+#define PML_P_WINDOW 2
 
+// Where a sweep finds P(t) of a child's branch.  PML_P_MATERIALISED: the batch of the whole tree, P + (col N + ch) k ks
+// (PML_P_HKY: nowhere, the pointer is null).  PML_P_WINDOW (pml_pij_window.h): the launch's parents are one run, the matrices
+// of their children were built into the column's window of B slots right before it, and child ch lies in slot[ch].
+struct PmlPWindow {
+    const double* base;   // [C][B][k][ks]
+    const int* slot;      // per node: the slot of its branch in the run that reads it
+    long long B;
+};
+template <int SRC> struct PmlPSource { typedef const double* __restrict__ type; };
+template <> struct PmlPSource<PML_P_WINDOW> { typedef PmlPWindow type; };
 // out[i] = sum_j P[i][j] v[j]  (rows i = s0 .. s0+R-1 of this lane), v staged in LDS
 template <int R>
 __device__ __forceinline__ void matvec_rows(const double* __restrict__ Pt, int k, int ks, int s0, bool lane_valid,
@@ -77,11 +88,12 @@ __device__ __forceinline__ void matvec_rows(const double* __restrict__ Pt, int k
 
 // replaces calc_node_bu_likelihood (pastml/ml.py:124-148) for materialised P
 // SRC = PML_P_HKY (only G = 4, R = 1, k = 4): P(t) of a child's branch from the closed form, in registers.
+// SRC = PML_P_WINDOW: the matrices of this launch's children from the window (PmlPWindow); the arithmetic is untouched.
 template <int G, int R, bool JOINT, int SRC = PML_P_MATERIALISED>
 __global__ void __launch_bounds__(PML_BLOCK)
-bu_matrix_kernel(PmlTree t, PmlCols c, PmlState st, const double* __restrict__ P, PmlModel m,
+bu_matrix_kernel(PmlTree t, PmlCols c, PmlState st, typename PmlPSource<SRC>::type P, PmlModel m,
                  const int* __restrict__ level_nodes, int n_level) {
-    static_assert(SRC == PML_P_MATERIALISED || (G == 4 && R == 1), "the HKY source is for one state per lane, k = 4");
+    static_assert(SRC != PML_P_HKY || (G == 4 && R == 1), "the HKY source is for one state per lane, k = 4");
     constexpr int UW = 64 / G;
     __shared__ double lds[PML_WAVES_PER_BLOCK * UW][G * R];
     const int lane = threadIdx.x & 63;
@@ -130,7 +142,9 @@ bu_matrix_kernel(PmlTree t, PmlCols c, PmlState st, const double* __restrict__ P
             if (observed >= 0) {
                 // v is a unit vector: sum_j P[i][j] v[j] is P[i][s] exactly (the other terms are zeros), and the
                 // arg-max scan has a closed form, so one 8k-byte row of Pt is read instead of the whole matrix
-                const double* Pt = P + (colN + ch) * pstride;
+                const double* Pt;
+                if constexpr (SRC == PML_P_WINDOW) Pt = P.base + ((size_t)col * (size_t)P.B + (size_t)P.slot[ch]) * pstride;
+                else Pt = P + (colN + ch) * pstride;
                 double msg[R];
                 if (SRC == PML_P_HKY) {
                     msg[0] = prow_pick(prow, observed);
@@ -203,7 +217,9 @@ bu_matrix_kernel(PmlTree t, PmlCols c, PmlState st, const double* __restrict__ P
                 esum += st.be[colN + ch];
             }
             stage_vec<R>(slot, s0, v);
-            const double* Pt = P + (colN + ch) * pstride;
+            const double* Pt;
+            if constexpr (SRC == PML_P_WINDOW) Pt = P.base + ((size_t)col * (size_t)P.B + (size_t)P.slot[ch]) * pstride;
+            else Pt = P + (colN + ch) * pstride;
             double msg[R];
             if (!JOINT) {
                 if (SRC == PML_P_HKY) {
@@ -297,9 +313,9 @@ bu_matrix_kernel(PmlTree t, PmlCols c, PmlState st, const double* __restrict__ P
 // replaces calc_node_td_likelihood (ml.py:273-290) + marginals (:454-460, :498-500) for materialised P
 template <int G, int R, int SRC = PML_P_MATERIALISED>
 __global__ void __launch_bounds__(PML_BLOCK)
-td_matrix_kernel(PmlTree t, PmlCols c, PmlState st, const double* __restrict__ P, PmlModel m,
+td_matrix_kernel(PmlTree t, PmlCols c, PmlState st, typename PmlPSource<SRC>::type P, PmlModel m,
                  const int* __restrict__ level_parents, int n_level) {
-    static_assert(SRC == PML_P_MATERIALISED || (G == 4 && R == 1), "the HKY source is for one state per lane, k = 4");
+    static_assert(SRC != PML_P_HKY || (G == 4 && R == 1), "the HKY source is for one state per lane, k = 4");
     constexpr int UW = 64 / G;
     __shared__ double lds[PML_WAVES_PER_BLOCK * UW][G * R];
     const int lane = threadIdx.x & 63;
@@ -358,7 +374,9 @@ td_matrix_kernel(PmlTree t, PmlCols c, PmlState st, const double* __restrict__ P
                 }
                 bec = st.be[colN + ch];
             }
-            const double* Pt = P + (colN + ch) * pstride;
+            const double* Pt;
+            if constexpr (SRC == PML_P_WINDOW) Pt = P.base + ((size_t)col * (size_t)P.B + (size_t)P.slot[ch]) * pstride;
+            else Pt = P + (colN + ch) * pstride;
             PRow4 prow;
             if (SRC == PML_P_HKY)
                 prow = hky_row(c.pi + (size_t)col * c.ks, m.kappa[col],

@@ -38,13 +38,28 @@ static inline size_t pijw_lds_bytes(int k, int ntc) {
     return ((size_t)KP * 16 * ntc + (size_t)PML_PIJW_WAVES * KP) * sizeof(double);
 }
 
-template <int NTC>
+// The list form (LIST = true; pml_pij_window.h): the workgroups share out the `count` entries of a run's branch list instead of
+// the node ids, entry i is branch branches[i], and its matrix goes to slot i of the column's window of B slots,
+// base + (col B + i) k ks, instead of P + (col N + b) k ks.  count <= B (the host checks it: pml_plan_pij_window,
+// launch_pij_wide_list).  Everything per branch is the same code, so a matrix has the same bits wherever it is written.
+struct PijwList {
+    double* base;          // [C][B][k][ks]
+    const int* branches;   // node ids of the run
+    int count;
+    long long B;
+};
+template <bool LIST> struct PijwOut { typedef double* __restrict__ type; };
+template <> struct PijwOut<true> { typedef PijwList type; };
+
+template <int NTC, bool LIST = false>
 __global__ void __launch_bounds__(PML_PIJW_BLOCK)
-pij_eigen_wide_kernel(PmlTree t, PmlCols c, PmlModel m, double* __restrict__ P, int branches_per_block) {
+pij_eigen_wide_kernel(PmlTree t, PmlCols c, PmlModel m, typename PijwOut<LIST>::type P, int branches_per_block) {
     extern __shared__ double pijw_smem[];
     const int k = c.k, ks = c.ks;
     const int col = blockIdx.y;
-    const size_t colN = (size_t)col * t.N;
+    size_t colN;
+    if constexpr (LIST) colN = (size_t)col * (size_t)P.B;
+    else colN = (size_t)col * t.N;
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int lo = lane & 15, hi = lane >> 4;
     const int KP = (k + 3) & ~3, KS = KP >> 2;
@@ -57,7 +72,10 @@ pij_eigen_wide_kernel(PmlTree t, PmlCols c, PmlModel m, double* __restrict__ P, 
     const double sfc = m.sf[col], tau = m.tau[col], tf = m.tauf[col];
     const int NT = (ks + 15) >> 4, JT = (k + 15) >> 4;
     const int b_lo = blockIdx.x * branches_per_block;
-    const int b_hi = min(t.N, b_lo + branches_per_block);
+    int b_end;
+    if constexpr (LIST) b_end = P.count;
+    else b_end = t.N;
+    const int b_hi = min(b_end, b_lo + branches_per_block);
     for (int nt0 = 0; nt0 < NT; nt0 += NTC) {
         const int i_base = 16 * nt0;
         __syncthreads();   // the previous slice has been consumed
@@ -69,10 +87,15 @@ pij_eigen_wide_kernel(PmlTree t, PmlCols c, PmlModel m, double* __restrict__ P, 
         }
         __syncthreads();
         for (int b = b_lo + wave; b < b_hi; b += PML_PIJW_WAVES) {
-            const double tq = (t.dist[b] + tau) * tf * sfc;
+            double tb;
+            if constexpr (LIST) tb = t.dist[P.branches[b]];
+            else tb = t.dist[b];
+            const double tq = (tb + tau) * tf * sfc;
             for (int mm = lane; mm < KP; mm += 64) sE[mm] = mm < k ? exp(gd[mm] * tq) : 0.0;
             wave_lds_sync();
-            double* const out_b = P + (colN + b) * (size_t)k * ks;
+            double* out_b;
+            if constexpr (LIST) out_b = P.base + (colN + b) * (size_t)k * ks;
+            else out_b = P + (colN + b) * (size_t)k * ks;
             for (int jt = 0; jt < JT; ++jt) {
                 // rows j of this tile; rows beyond k (the last tile) are computed from row k - 1 and never written
                 const int jc = min(16 * jt + lo, k - 1);

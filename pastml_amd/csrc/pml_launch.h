@@ -108,7 +108,9 @@ static bool eigen_joint_valu(const pml_ctx* c) {
 
 
 // ---- pml_launch_matrix.hip: sweeps of the models with a materialised (or closed-form 4 x 4) P(t), state selection
-PML_INTERNAL int dispatch_sweep_matrix(pml_ctx* ctx, SweepKind what, const int* level, int n_level);
+//      window: -1, or which of the context's slot tables (0 bottom-up, 1 top-down) locates P(t) of the launch's children in the
+//      window (pml_pij_window.h)
+PML_INTERNAL int dispatch_sweep_matrix(pml_ctx* ctx, SweepKind what, const int* level, int n_level, int window = -1);
 PML_INTERNAL int dispatch_select(pml_ctx* ctx, int method, int force_joint, const u64* d_lh_mask);
 // ---- pml_launch_f81_level.hip: F81-family level launches over n_level units.  cherries: the top-down staging hint (some unit
 //      has a cherry among its first two children); bu_sweep: part of a bottom-up sweep, which looks at the active-column flags
@@ -129,6 +131,10 @@ PML_INTERNAL int launch_eigen_narrow(pml_ctx* ctx, int mode, const int* nodes, c
 PML_INTERNAL int launch_eigen_tips(pml_ctx* ctx, int joint);
 PML_INTERNAL int launch_pij_mfma(pml_ctx* ctx);
 PML_INTERNAL int launch_pij_wide(pml_ctx* ctx);
+//      the list form: P(t) of `count` branches of a device list into the slots 0 .. count - 1 of the window of B slots per column;
+//      arm_pij_wide_list asks for the kernel's LDS once, outside any stream capture (pml_pij_window_set)
+PML_INTERNAL int launch_pij_wide_list(pml_ctx* ctx, double* window, long long B, const int* d_branches, int count);
+PML_INTERNAL int arm_pij_wide_list(pml_ctx* ctx);
 // ---- pml_launch_eigen_gemm.hip: sum sweeps as two small GEMMs per 16 nodes
 PML_INTERNAL int launch_eigen_gemm(pml_ctx* ctx, int mode, const int* nodes, int first, int n);
 PML_INTERNAL int launch_eigen_gemm_narrow(pml_ctx* ctx, int mode, const int* nodes, const int* d_offsets, int first_level,
@@ -203,9 +209,9 @@ static inline int with_lds(const pml_ctx* ctx, K kernel, size_t bytes) {
 
 // a level launch over the entries first .. first + n_level of a list: its unit descriptors (F81 family) or its node ids
 static inline int dispatch_sweep(pml_ctx* ctx, SweepKind what, int list, int first, int n_level, bool cherries = true,
-                                 bool bu_sweep = false) {
+                                 bool bu_sweep = false, int window = -1) {
     if (n_level <= 0) return PML_OK;
     if (ctx->kind == PML_MODEL_F81) return dispatch_sweep_f81(ctx, what, ctx->d_unit_lists[list] + first, n_level, cherries, bu_sweep);
     const int* nodes = list == L_BU_PLAIN ? ctx->d_bu_order : (list == L_TD_PLAIN ? ctx->d_td_parents : nullptr);
-    return dispatch_sweep_matrix(ctx, what, nodes ? nodes + first : nullptr, n_level);
+    return dispatch_sweep_matrix(ctx, what, nodes ? nodes + first : nullptr, n_level, window);
 }

@@ -4,13 +4,37 @@
 
 // matrix-model sweeps: contiguous state ownership (state = g * R + r)
 template <int G, int R>
-static void launch_sweep(pml_ctx* ctx, SweepKind what, const int* level, int n_level) {
+static void launch_sweep(pml_ctx* ctx, SweepKind what, const int* level, int n_level, int window) {
     const PmlTree t = tree_of(ctx, false);
     const PmlCols c = cols_of(ctx);
     const PmlState st = state_of(ctx);
     const int upb = PML_WAVES_PER_BLOCK * (64 / G);
     dim3 grid(grid_for(ctx, n_level, upb, ctx->C), ctx->C), block(PML_BLOCK);
     const PmlModel m = model_of(ctx);
+    if (window >= 0) {
+        // P(t) of this launch's children from the window (pml_pij_window.h): eigen models beyond 32 states, whose lane shapes
+        // are 32 x 2, 64 x 2 and 64 x 4 (pick_group)
+        constexpr bool wide = G * R > 32 && R >= 2;
+        constexpr int GG = wide ? G : 64, RR = wide ? R : 2;   // (keeps the other shapes from instantiating it)
+        const PmlPWindow w = {ctx->d_pij_window, ctx->d_win_slot[window], ctx->pij_window};
+        switch (what) {
+            case SW_BU_MARG:
+                hipLaunchKernelGGL((bu_matrix_kernel<GG, RR, false, PML_P_WINDOW>), grid, block, 0, ctx->stream, t, c, st, w, m, level,
+                                   n_level);
+                break;
+            case SW_BU_JOINT:
+                hipLaunchKernelGGL((bu_matrix_kernel<GG, RR, true, PML_P_WINDOW>), grid, block, 0, ctx->stream, t, c, st, w, m, level,
+                                   n_level);
+                break;
+            case SW_TD:
+                hipLaunchKernelGGL((td_matrix_kernel<GG, RR, PML_P_WINDOW>), grid, block, 0, ctx->stream, t, c, st, w, m, level,
+                                   n_level);
+                break;
+            default:
+                break;
+        }
+        return;
+    }
     if (G == 4 && R == 1 && hky_fused(ctx)) {  // HKY: P(t) from the closed form, in registers (no batch in HBM)
         constexpr int GG = G == 4 ? 4 : 4, RR = R == 1 ? 1 : 1;  // (keeps the other shapes from instantiating it)
         switch (what) {
@@ -61,11 +85,16 @@ static void launch_select(pml_ctx* ctx, int method, int force_joint, const u64* 
 }
 
 
-int dispatch_sweep_matrix(pml_ctx* ctx, SweepKind what, const int* level, int n_level) {
+int dispatch_sweep_matrix(pml_ctx* ctx, SweepKind what, const int* level, int n_level, int window) {
     if (n_level <= 0) return PML_OK;
+    if (window >= 0) {
+        const bool sweep = what == SW_BU_MARG || what == SW_BU_JOINT || what == SW_TD;
+        if (!sweep || ctx->pij_window <= 0 || !ctx->d_pij_window || !ctx->d_win_slot[window] || (long long)ctx->G * ctx->R <= 32 || ctx->R < 2)
+            return fail(PML_ERR_INVALID, "no P(t) window for sweep kind %d of a context with G=%d R=%d", (int)what, ctx->G, ctx->R);
+    }
 #define X(G_, R_)                                             \
     if (ctx->G == G_ && ctx->R == R_) {                       \
-        launch_sweep<G_, R_>(ctx, what, level, n_level);      \
+        launch_sweep<G_, R_>(ctx, what, level, n_level, window); \
         HIP_TRY(hipGetLastError());                           \
         return PML_OK;                                        \
     }

@@ -93,6 +93,8 @@ SIGNATURES = {
                             _c_double_p, _c_double_p, _c_double_p, _c_double_p],
     'pml_pij': [_ctx_p, ctypes.c_int32, ctypes.c_int32, _c_double_p, _c_double_p],
     'pml_pij_batch': [_ctx_p, _c_double_p],
+    'pml_pij_window_set': [_ctx_p, ctypes.c_longlong],
+    'pml_pij_window_info': [_ctx_p] + [ctypes.POINTER(ctypes.c_longlong)] * 3,
     'pml_bottom_up': [_ctx_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p],
     'pml_bottom_up_submit': [_ctx_p, ctypes.c_int],
     'pml_bottom_up_submit_columns': [_ctx_p, ctypes.c_int, ctypes.c_void_p],
@@ -658,6 +660,18 @@ class Engine(BareContext):
             out = np.empty((self.n_cols, self.n_nodes, self.k, self.k), dtype=np.float64)
         _check(self._lib.pml_pij_batch(self._ctx, None if out is None else _ptr(out, ctypes.c_double)))
         return out
+
+    def pij_window_set(self, branches):
+        """Eigen models with 33 .. 256 states: the sweeps build P(t) in a window of ``branches`` matrices per column instead of
+        keeping one per node (pml_pij_window_set; 0: off).  Needs the models to be set.  Same bits as the batch."""
+        _check(self._lib.pml_pij_window_set(self._ctx, int(branches)))
+        self._pij_window = int(branches)
+
+    def pij_window_info(self):
+        """(branches of the window -- 0: off --, bytes of the window, bytes of the whole-tree batch of P(t)) as allocated now."""
+        v = [ctypes.c_longlong(0) for _ in range(3)]
+        _check(self._lib.pml_pij_window_info(self._ctx, *[ctypes.byref(x) for x in v]))
+        return v[0].value, v[1].value, v[2].value
 
     def _sweep_results(self, status):
         # copies of the engine's own result buffers (callers keep what they get)
