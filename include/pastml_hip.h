@@ -189,6 +189,9 @@ int pml_pij(pml_ctx* ctx, int32_t col, int32_t n_t, const double* t, double* P_o
  * Materialises the per-branch transition data of every column on the device (F81 family: e = exp(-mu t') per
  * branch; HKY / eigen models: the full k x k matrix per branch).  The sweeps call it implicitly when the model or
  * the tree changed.  If P_out != NULL, additionally copies out P for every branch: P_out[n_cols][n_nodes][k][k].
+ * It hands out per-branch data by definition: on a context with a window (pml_pij_window_set) it still allocates and fills the
+ * batch of the whole tree, which then stays until the window is set again; so does pml_download of PML_BUF_TD / PML_BUF_TD_SF,
+ * which fills in the top-down vectors of the nodes no sweep stores from P(t) of every branch.  Nothing else does.
  */
 int pml_pij_batch(pml_ctx* ctx, double* P_out);
 /*
@@ -201,9 +204,16 @@ int pml_pij_batch(pml_ctx* ctx, double* P_out);
  * Allocates n_cols x branches x k x ks doubles (branches capped at n_nodes) and frees the batch if there is one.
  * PML_ERR_UNSUPPORTED for F81 / HKY contexts, for k <= 32 and under PASTML_HIP_NO_MFMA / _NO_PIJ_WIDE (the batch is then built by
  * another kernel, whose bits a window would not leave; set after the window, they take it away at the next sweep); PML_ERR_INVALID below the largest fan-out of the forest (the message
- * names it) and before the first model is set.  pml_pij_batch, pml_marginal_counts, pml_expected_counts, pml_simulate_states,
- * pml_sample_scenarios and the download of the top-down vectors still read P(t) of the whole tree: on a windowed context they
- * allocate the batch as they do on any other, and it stays until the window is set again.
+ * names it) and before the first model is set.
+ * The entries that read P(t) outside the sweeps -- pml_marginal_counts(_altered), pml_expected_counts, pml_simulate_states,
+ * pml_sample_scenarios -- read the window too, in runs: one launch builds exactly the branches the next launch of the entry reads,
+ * for the columns of the call only (the sampled counts: the runs of the top-down sweep; the exact counts: whole pieces of 128 ids,
+ * in a window of one piece per column of their own where the context's is smaller; the simulator and the sampler: runs of nodes of
+ * a depth level, then groups of whole frontier subtrees, the frontier moving down where a subtree exceeds the window).  They leave
+ * what they leave on a context without a window, allocate no term in n_nodes x k x k, and the context holds after the call what
+ * it held before.  Only pml_pij_batch and the download of the top-down vectors (PML_BUF_TD / _SF) still materialise the whole
+ * tree: they hand out per-branch data by definition, allocate the batch as on any other context, and it stays until the window is
+ * set again -- pml_pij_window_info reports batch_bytes == 0 until one of the two is called.
  * PASTML_HIP_PIJ_WINDOW=<branches> does the same for every context it fits (raised to the fan-out, capped at n_nodes).
  */
 int pml_pij_window_set(pml_ctx* ctx, long long branches);
@@ -280,6 +290,8 @@ int pml_select_states(pml_ctx* ctx, int method, int force_joint, const uint64_t*
  * without nodes altered by the zero-branch handling (ml.py:352-387; with them: pml_marginal_counts_altered), with a counter-based
  * generator (Philox-4x32-10 keyed by seed): statistical, not bitwise, parity with the reference's numpy draws.
  * Needs pml_bottom_up (marginal) and pml_top_down_marginals first.  counts_out[k][k].
+ * On a context with a P(t) window (pml_pij_window_set) the level launches are cut into the runs of the top-down sweep and read
+ * the window, built for this column only: the same draws, no batch of the whole tree.
  */
 int pml_marginal_counts(pml_ctx* ctx, int32_t col, int32_t n_repetitions, uint64_t seed, double* counts_out);
 /*
@@ -289,7 +301,7 @@ int pml_marginal_counts(pml_ctx* ctx, int32_t col, int32_t n_repetitions, uint64
  * (ml.py:806-812, 840-853, 857-858), which the caller forms from what comes back -- sums_out[k][k]: the sums of the draws of all
  * other pairs, diagonal corrected for all other parents, NOT divided by n_repetitions; state_counts_out[n_nodes][k]: how often
  * each node was in each state; same_out[n_nodes][k]: for a parent of such a pair, its same-state draws over its other children
- * (rows of other nodes are zero).  pastml_amd.ml.marginal_counts is that caller.
+ * (rows of other nodes are zero).  pastml_amd.ml.marginal_counts is that caller.  Windowed contexts: as pml_marginal_counts.
  */
 int pml_marginal_counts_altered(pml_ctx* ctx, int32_t col, int32_t n_repetitions, uint64_t seed, const uint8_t* altered,
                                 double* sums_out, int32_t* state_counts_out, int32_t* same_out);
@@ -310,7 +322,10 @@ int pml_marginal_counts_altered(pml_ctx* ctx, int32_t col, int32_t n_repetitions
  * norm ps[i], same_p[i] += norm[i] ps[i]) left to the caller: pastml_amd.ml.expected_counts.
  * counts_out[n_cols][k][k]; same_out[n_cols][n_nodes][k] or NULL.  F81 family: k <= 512, the sum over the branches runs on the FP64
  * matrix cores; HKY / eigen models: k <= 256.  No atomics: the result does not depend on launch geometry, on the schedule
- * switches, on the library's numbering or on the column a character sits in.
+ * switches, on the library's numbering or on the column a character sits in -- nor on a P(t) window (pml_pij_window_set): the
+ * branch pass then runs in runs of whole pieces of 128 ids behind the build of their matrices for the columns of the call (in a
+ * window of one piece per column of the call's own where the context's holds fewer than 128 branches), pieces, partials and the
+ * order of every sum untouched, and the batch of the whole tree is not allocated.
  */
 int pml_expected_counts(pml_ctx* ctx, int32_t col_begin, int32_t col_end, const uint8_t* altered, double* counts_out,
                         double* same_out);
@@ -432,6 +447,10 @@ int pml_compress_trim_info(pml_ctx* ctx, double* sizes_ms, double* removal_ms, d
  * results do not depend on launch geometry, chunking or the library's internal numbering.
  * states_out[n_nodes][n_repetitions], caller's numbering; uint8 for k <= 256, else uint16.
  * Needs a model (pml_model_set_*), no sweep.
+ * On a context with a P(t) window (pml_pij_window_set) the depth levels above the frontier run in runs of at most `branches`
+ * nodes and the frontier's subtrees in groups of whole subtrees of at most `branches` nodes together, each behind the build of
+ * its matrices for this column; a frontier subtree larger than the window moves the frontier down for the call.  The same
+ * states, more launches, no batch of the whole tree.
  */
 int pml_simulate_states(pml_ctx* ctx, int32_t col, int32_t n_repetitions, int32_t rep_offset, uint64_t seed,
                         void* states_out);
@@ -450,6 +469,7 @@ int pml_simulate_states(pml_ctx* ctx, int32_t col, int32_t n_repetitions, int32_
  * states_out[n_nodes][n_repetitions], caller's numbering; uint8 for k <= 256, else uint16.
  * n_fallback_out: the draws whose weights summed to zero and were taken from the node's own posterior row instead (with the
  * same uniform); 0 after a consistent pass.
+ * On a context with a P(t) window: the windowed schedule of pml_simulate_states, the same states and the same count.
  */
 int pml_sample_scenarios(pml_ctx* ctx, int32_t col, int32_t n_repetitions, int32_t rep_offset, uint64_t seed,
                          void* states_out, int64_t* n_fallback_out);

@@ -1442,6 +1442,61 @@ def plan_pij_window(flat, k, widths, kind, n_members, free, character='?', setti
     return chunk, max(fan, min(n, branches))
 
 
+def plan_consumer_window(flat, k, kind, n_cols, free, character='?', setting=None):
+    """
+    Materialised or windowed P(t) for the entries that read it outside the sweeps -- expected_counts, marginal_counts,
+    sample_scenarios, simulate_states -- on a context of n_cols characters: the branches of the window, or 0
+    for the whole-tree batch.  The rules and the setting are plan_pij_window's: materialised whenever one column's batch fits
+    the 0.6 x free budget, so nothing that ran before changes; else (eigen models with 33 .. 256 states, for which the library
+    has a window) the largest window that fits beside the columns' vectors, never above the number of nodes and never below
+    the largest fan-out.  MemoryError if not even the largest fan-out fits.
+    setting: PASTML_AMD_PIJ_WINDOW -- 'auto' (None), '0' (always materialised), or the branches to use.
+    """
+    setting = 'auto' if setting in (None, '') else str(setting).strip().lower()
+    budget = 0.6 * free
+    n, fan = int(flat.n_nodes), int(np.max(flat.n_children))
+    lean_one = _column_bytes(flat, k, [0], kind=kind, windowed=True)
+    per_branch_one = _window_bytes_per_branch(k, [0])
+    eligible = kind == hip.KIND_EIGEN and 32 < k <= 256
+    if setting == '0' or not eligible or (setting == 'auto' and lean_one + n * per_branch_one <= budget):
+        return 0
+    lean, per_branch = n_cols * lean_one, n_cols * per_branch_one
+    if lean + fan * per_branch > budget:
+        raise MemoryError('character {} (k = {}): {:.3g} bytes of device memory are planned for it, and its columns with a '
+                          'window of P(t) for the {} branches of the largest polytomy need {:.3g}'
+                          .format(character, k, budget, fan, lean + fan * per_branch))
+    if setting != 'auto':
+        branches = max(fan, min(n, int(setting)))
+        if lean + branches * per_branch > budget:
+            raise MemoryError('character {} (k = {}): a window of {} branches (PASTML_AMD_PIJ_WINDOW; largest polytomy: {}) '
+                              'needs {:.3g} bytes, {:.3g} are planned'.format(character, k, branches, fan,
+                                                                               lean + branches * per_branch, budget))
+        return branches
+    return max(fan, min(n, int((budget - lean) / per_branch)))
+
+
+def planned_free_bytes(device=None):
+    """Free memory of the device a front end plans with: what the device reports, capped by PASTML_AMD_DEVICE_BYTES (tests)."""
+    with hip.BareContext(device) as probe:
+        _, free = probe.memory()
+    if os.environ.get('PASTML_AMD_DEVICE_BYTES'):
+        free = min(free, int(float(os.environ['PASTML_AMD_DEVICE_BYTES'])))
+    return free
+
+
+def consumer_window(flat, k, kind, n_cols, character, what, device=None):
+    """plan_consumer_window for the front end ``what`` (its name), from the device's free memory and PASTML_AMD_PIJ_WINDOW:
+    (branches -- 0: materialised --, the record the front end keeps as ``<function>.last_stats['pij_window']``, like
+    run_tasks.last_stats).  The choice goes to the ``pastml`` logger as well."""
+    window = 0
+    if kind == hip.KIND_EIGEN and 32 < k <= 256:   # (else there is nothing to plan, and no device is asked)
+        window = plan_consumer_window(flat, k, kind, n_cols, planned_free_bytes(device), character=character,
+                                      setting=os.environ.get('PASTML_AMD_PIJ_WINDOW'))
+    logging.getLogger('pastml').debug('{}: P(t) of character {} ({} states): {}'.format(
+        what, character, k, 'a window of {} branches'.format(window) if window else 'materialised for the whole tree'))
+    return window, dict(k=k, characters=n_cols, character=character, mode='windowed' if window else 'materialised', branches=window)
+
+
 def visible_devices(device=None):
     """
     The GPUs one process spreads its groups of characters over.  A process that is one rank of a multi-process launch

@@ -931,6 +931,7 @@ static void window_drop(pml_ctx* ctx) {
         ctx->win_branches[i].clear();
     }
     ctx->win_cuts.clear();
+    ctx->win_td_runs.clear();
     ctx->pij_window = 0;
 }
 
@@ -962,6 +963,8 @@ static int window_set(pml_ctx* ctx, long long branches) {
         if (status == PML_OK) status = put(ctx, &ctx->d_win_slot[i], W[i].slot);
         ctx->win_branches[i].swap(W[i].branches);
     }
+    for (const PmlWindowStep& w : W[1].steps)
+        if (w.launch.op == OP_LEVEL && w.launch.list == L_TD_PLAIN && w.launch.count > 0) ctx->win_td_runs.push_back(w);
     ctx->pij_window = B;
     const hipError_t e = hipStreamSynchronize(ctx->stream);   // (the host tables go out of scope)
     if (status != PML_OK || e != hipSuccess) {
@@ -1020,6 +1023,14 @@ static int ensure_transition_storage(pml_ctx* ctx) {
     if (ctx->kind != PML_MODEL_F81 && !ctx->d_P)
         PML_TRY(dev_alloc(ctx, &ctx->d_P, (size_t)ctx->C * ctx->N * ctx->k * ctx->ks));
     return PML_OK;
+}
+
+// What the entries that read P(t) outside a sweep prepare: the batch of the whole tree -- or, on a context with a window
+// (pml_pij_window.h), only the parameters the list build reads: they build their matrices run by run, and no batch is allocated.
+static int run_prep(pml_ctx* ctx, bool force, bool bu_sweep);
+static int consumer_prep(pml_ctx* ctx, bool force = false) {
+    if (!pij_windowed(ctx)) return run_prep(ctx, force, false);
+    return params_push(ctx);
 }
 
 static int run_prep(pml_ctx* ctx, bool force = false, bool bu_sweep = false) {
@@ -1806,7 +1817,7 @@ static int marginal_counts_impl(pml_ctx* ctx, int32_t col, int32_t n_repetitions
     if (ctx->k > PML_COUNTS_MAX_K) return fail(PML_ERR_UNSUPPORTED, "k = %d: at most %d states", ctx->k, PML_COUNTS_MAX_K);
     PML_TRY(materialize_cherries(ctx));  // the conditional probabilities need every bottom-up vector
     PML_TRY(materialize_tip_posteriors(ctx));
-    PML_TRY(run_prep(ctx));  // P(t) of every branch (the fused eigen sweeps never materialise it) / exp(-mu t')
+    PML_TRY(consumer_prep(ctx));  // P(t) of every branch (the fused eigen sweeps never materialise it) / exp(-mu t'); or the window
     const size_t k = ctx->k, N = (size_t)ctx->N;
     std::vector<unsigned char> alt;
     std::vector<long long> h(k * k);
@@ -1830,10 +1841,27 @@ static int marginal_counts_impl(pml_ctx* ctx, int32_t col, int32_t n_repetitions
     // (the draws are keyed by the CALLER's node ids: the library's internal numbering must not show in the result)
     hipLaunchKernelGGL(counts_roots_kernel, dim3(std::min(ctx->n_roots, 1024)), dim3(64), 0, ctx->stream, t, c, st, col,
                        n_repetitions, seed, d_counts, ctx->d_old_of_new);
+    if (pij_windowed(ctx)) {
+        // the runs of the top-down sweep (parents of one level whose children fit the window), each behind the build of its
+        // children's matrices for this column: the draws are keyed by the node, so the cuts do not show
+        const PmlPWindow w = {ctx->d_pij_window, ctx->d_win_slot[1], ctx->pij_window};
+        size_t covered = 0;
+        for (const PmlWindowStep& r : ctx->win_td_runs) covered += (size_t)r.launch.count;
+        if (covered != ctx->td_parents.size())
+            return fail(PML_ERR_INVALID, "the window's top-down runs cover %zu of %zu parents", covered, ctx->td_parents.size());
+        for (const PmlWindowStep& r : ctx->win_td_runs) {
+            if (r.build_count > 0)
+                PML_TRY(launch_pij_wide_list(ctx, ctx->d_pij_window, ctx->pij_window, ctx->d_win_branches[1] + r.build_first,
+                                             r.build_count, col, col + 1));
+            hipLaunchKernelGGL(counts_level_kernel<PML_P_WINDOW>, dim3(std::min(r.launch.count, 65536)), dim3(64), 0, ctx->stream,
+                               t, c, st, m, w, col, n_repetitions, seed, ctx->d_td_parents + r.launch.first, r.launch.count, d_counts,
+                               d_result, ctx->d_old_of_new, d_alt, d_same);
+        }
+    } else
     for (int l = 0; l < ctx->n_td_levels; ++l) {
         const int a = ctx->forest.td_parent_offsets[l], b = ctx->forest.td_parent_offsets[l + 1];
         if (b <= a) continue;
-        hipLaunchKernelGGL(counts_level_kernel, dim3(std::min(b - a, 65536)), dim3(64), 0, ctx->stream, t, c, st, m, P,
+        hipLaunchKernelGGL(counts_level_kernel<>, dim3(std::min(b - a, 65536)), dim3(64), 0, ctx->stream, t, c, st, m, P,
                            col, n_repetitions, seed, ctx->d_td_parents + a, b - a, d_counts, d_result, ctx->d_old_of_new,
                            d_alt, d_same);
     }
@@ -1874,7 +1902,7 @@ int pml_expected_counts(pml_ctx* ctx, int32_t col_begin, int32_t col_end, const 
     PML_TRY(wait_pending(ctx, true));   // (a pass that ended in a spin on the completion word may have left the stream busy)
     PML_TRY(materialize_cherries(ctx));  // the conditional probabilities need every bottom-up vector
     PML_TRY(materialize_tip_posteriors(ctx));
-    PML_TRY(run_prep(ctx));  // P(t) of every branch (the fused sweeps never materialise it) / exp(-mu t')
+    PML_TRY(consumer_prep(ctx));  // P(t) of every branch (the fused sweeps never materialise it) / exp(-mu t'); or the window
     const size_t k = ctx->k, N = (size_t)ctx->N, cols = (size_t)(col_end - col_begin);
     const bool with_same = altered != nullptr && same_out != nullptr;
     std::vector<unsigned char> alt;
@@ -1901,8 +1929,10 @@ int pml_simulate_states(pml_ctx* ctx, int32_t col, int32_t n_repetitions, int32_
     if (col < 0 || col >= ctx->C || !states_out) return fail(PML_ERR_INVALID, "bad column / output");
     if (n_repetitions <= 0) return fail(PML_ERR_INVALID, "n_repetitions must be positive");
     if (rep_offset < 0) return fail(PML_ERR_INVALID, "rep_offset must not be negative");
-    // (the sweeps may have left E / P(t) in registers only, or for other parameters: prepared afresh)
-    PML_TRY(run_prep(ctx, true));
+    // (the sweeps may have left E / P(t) in registers only, or for other parameters: prepared afresh; a context with a window
+    // pushes the parameters and builds its matrices run by run)
+    PML_TRY(window_from_tunable(ctx));
+    PML_TRY(consumer_prep(ctx, true));
     const size_t es = ctx->k > 256 ? 2 : 1;
     const size_t rs = ((size_t)n_repetitions + 3) / 4 * 4;
     CallScope mem(ctx->stream, false);
@@ -1929,7 +1959,7 @@ int pml_sample_scenarios(pml_ctx* ctx, int32_t col, int32_t n_repetitions, int32
     PML_TRY(wait_pending(ctx, true));   // (a pass that ended in a spin on the completion word may have left the stream busy)
     PML_TRY(materialize_cherries(ctx));  // the conditional probabilities need every bottom-up vector
     PML_TRY(materialize_tip_posteriors(ctx));   // (a single-tip tree's root; the rows of the fallback)
-    PML_TRY(run_prep(ctx));  // P(t) of every branch (the fused sweeps never materialise it) / exp(-mu t')
+    PML_TRY(consumer_prep(ctx));  // P(t) of every branch (the fused sweeps never materialise it) / exp(-mu t'); or the window
     const size_t es = ctx->k > 256 ? 2 : 1;
     const size_t rs = ((size_t)n_repetitions + 3) / 4 * 4;
     unsigned long long fallen = 0;

@@ -163,6 +163,8 @@ struct pml_ctx {
         std::vector<PmlWindowStep> steps;
     };
     std::vector<WindowCut> win_cuts;
+    // the runs of the plain top-down level list the slot table [1] was made for: pml_marginal_counts walks them (window_set)
+    std::vector<PmlWindowStep> win_td_runs;
 
     // state
     double *d_E = nullptr, *d_P = nullptr, *d_bu = nullptr, *d_S = nullptr, *d_td = nullptr, *d_post = nullptr,

@@ -80,9 +80,12 @@ counts_roots_kernel(PmlTree t, PmlCols c, PmlState st, int col, int n_rep, u64 s
 #endif
 
 // one depth level: parents[0 .. n_parents), one wavefront (= one 64-thread block) per parent
+// SRC = PML_P_WINDOW (pml_pij_window.h): the parents are one run of the top-down sweep's window plan and the matrices of their
+// children were built into the column's window right before (PmlPWindow: base is the column's, slot the top-down table).
 #ifdef PML_PLAIN_KERNELS   // (launched by pml_api.hip only: the other translation units leave it out)
+template <int SRC = PML_P_MATERIALISED>
 PML_GLOBAL void __launch_bounds__(64)
-counts_level_kernel(PmlTree t, PmlCols c, PmlState st, PmlModel m, const double* __restrict__ P, int col, int n_rep,
+counts_level_kernel(PmlTree t, PmlCols c, PmlState st, PmlModel m, typename PmlPSource<SRC>::type P, int col, int n_rep,
                     u64 seed, const int* __restrict__ parents, int n_parents, int* __restrict__ counts,
                     long long* __restrict__ result, const int* __restrict__ api_id,
                     const unsigned char* __restrict__ altered, int* __restrict__ same_out) {
@@ -124,7 +127,9 @@ counts_level_kernel(PmlTree t, PmlCols c, PmlState st, PmlModel m, const double*
             __syncthreads();
             double e = 0.0;
             if (m.kind == PML_MODEL_F81) e = st.E[colN + n];
-            const double* Pt = P != nullptr ? P + (colN + n) * (size_t)k * ks : nullptr;
+            const double* Pt;
+            if constexpr (SRC == PML_P_WINDOW) Pt = P.base + (size_t)P.slot[n] * (size_t)k * ks;
+            else Pt = P != nullptr ? P + (colN + n) * (size_t)k * ks : nullptr;
             for (int a = 0; a < k; ++a) {
                 const int ca = pc[a];
                 if (ca == 0) continue;  // block-uniform

@@ -19,7 +19,7 @@
 // unaltered part is  sum_n u_n (x) w_n + diag(sum_n q_p[a] e w_n[a] / den_n[a]),  u_n[a] = q_p[a] (1 - e) pi_a / den_n[a]:
 // U^T W on the FP64 matrix cores (expected_f81_kernel), the diagonal terms in the pass over the parents.
 // Matrix models (HKY, eigen): the per-branch term is the elementwise product of P_n^T, w_n and q_p / den_n, read from the
-// materialised P(t) (expected_matrix_kernel) -- k^2 doubles per branch, memory-bound.
+// materialised P(t), or from its window (expected_matrix_kernel) -- k^2 doubles per branch, memory-bound.
 //
 // Bits.  No floating-point atomics.  The nodes are walked in the CALLER's numbering and cut into pieces of a fixed number of
 // ids (a function of k and the model kind only); a workgroup owns one piece's partial k x k (or one piece of parents' partial
@@ -50,6 +50,10 @@ struct PmlExpArgs {
     double* dterm;                  // [cols][N][k] matrix models: q_p[a] M_n[a][a] per branch, written by the branch pass
     double* same;                   // [cols][N][k] caller's numbering, or null: same_p of the parents of a pair with an altered end
     double* out;                    // [cols][k][k]
+    // P(t) in a window (pml_pij_window.h; expected_matrix_kernel<CK, true>): this launch is the run of the pieces piece0 ..
+    // piece0 + gridDim.x, P is the window [cols of the call][win_B][k][ks] and the branch of id i lies in slot i - piece0 piece
+    int piece0;
+    long long win_B;
 };
 
 // w_n[b] = BU_n[b] pi_b mask_n[b]; row = col * N + n.  Every load is issued whatever the mask, the tip flag or b say (a clamped
@@ -163,7 +167,8 @@ __global__ void __launch_bounds__(256) expected_f81_kernel(PmlExpArgs A) {
 // round robin (32 / CK rows each), the lanes hold the columns b = lane + 64 c.  Per branch and row a: den = sum_b w[b] Pt[a][b]
 // over the wavefront (fixed order), then acc += q_p[a] / den * w[b] Pt[a][b].  The diagonal entry goes to dterm for the pass
 // over the parents.
-template <int CK>
+// WIN: the pieces of one run, P(t) from the window (PmlExpArgs::piece0); a piece's partial, its ids and their order are the same.
+template <int CK, bool WIN = false>
 __global__ void __launch_bounds__(256) expected_matrix_kernel(PmlExpArgs A) {
     constexpr int RW = 32 / CK;
     const int k = A.k, ks = A.ks;
@@ -176,7 +181,8 @@ __global__ void __launch_bounds__(256) expected_matrix_kernel(PmlExpArgs A) {
     for (int r = 0; r < RW; ++r)
 #pragma unroll
         for (int c = 0; c < CK; ++c) acc[r][c] = 0.0;
-    const int i0 = blockIdx.x * A.piece, i1 = min(A.N, i0 + A.piece);
+    const int piece_x = WIN ? A.piece0 + (int)blockIdx.x : (int)blockIdx.x;
+    const int i0 = piece_x * A.piece, i1 = min(A.N, i0 + A.piece);
     for (int i = i0; i < i1; ++i) {
         const int n = A.new_of_old ? A.new_of_old[i] : i;
         const int p = A.parent[n];
@@ -187,7 +193,9 @@ __global__ void __launch_bounds__(256) expected_matrix_kernel(PmlExpArgs A) {
         double w[CK];
 #pragma unroll
         for (int c = 0; c < CK; ++c) w[c] = exp_weight(A, col, row, tip, lane + 64 * c);
-        const double* Pt = A.P + row * (size_t)k * ks;
+        const double* Pt;
+        if constexpr (WIN) Pt = A.P + ((size_t)blockIdx.z * (size_t)A.win_B + (size_t)(i - A.piece0 * A.piece)) * (size_t)k * ks;
+        else Pt = A.P + row * (size_t)k * ks;
 #pragma unroll
         for (int r = 0; r < RW; ++r) {
             const int a = a_base + 4 * r;
@@ -211,7 +219,7 @@ __global__ void __launch_bounds__(256) expected_matrix_kernel(PmlExpArgs A) {
             }
         }
     }
-    double* out = A.partial + ((size_t)blockIdx.z * A.n_pieces + blockIdx.x) * k * k;
+    double* out = A.partial + ((size_t)blockIdx.z * A.n_pieces + piece_x) * k * k;
 #pragma unroll
     for (int r = 0; r < RW; ++r) {
         const int a = a_base + 4 * r;

@@ -42,11 +42,14 @@ static inline size_t pijw_lds_bytes(int k, int ntc) {
 // the node ids, entry i is branch branches[i], and its matrix goes to slot i of the column's window of B slots,
 // base + (col B + i) k ks, instead of P + (col N + b) k ks.  count <= B (the host checks it: pml_plan_pij_window,
 // launch_pij_wide_list).  Everything per branch is the same code, so a matrix has the same bits wherever it is written.
+// The grid's y range are the columns col0 .. of the context (a sweep: all of them; a call for some columns builds those only),
+// and column col0 + y owns the y-th window of the buffer.
 struct PijwList {
-    double* base;          // [C][B][k][ks]
+    double* base;          // [columns of the launch][B][k][ks]
     const int* branches;   // node ids of the run
     int count;
     long long B;
+    int col0;
 };
 template <bool LIST> struct PijwOut { typedef double* __restrict__ type; };
 template <> struct PijwOut<true> { typedef PijwList type; };
@@ -56,10 +59,14 @@ __global__ void __launch_bounds__(PML_PIJW_BLOCK)
 pij_eigen_wide_kernel(PmlTree t, PmlCols c, PmlModel m, typename PijwOut<LIST>::type P, int branches_per_block) {
     extern __shared__ double pijw_smem[];
     const int k = c.k, ks = c.ks;
-    const int col = blockIdx.y;
+    int col = blockIdx.y;
     size_t colN;
-    if constexpr (LIST) colN = (size_t)col * (size_t)P.B;
-    else colN = (size_t)col * t.N;
+    if constexpr (LIST) {
+        colN = (size_t)blockIdx.y * (size_t)P.B;
+        col += P.col0;
+    } else {
+        colN = (size_t)col * t.N;
+    }
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int lo = lane & 15, hi = lane >> 4;
     const int KP = (k + 3) & ~3, KS = KP >> 2;

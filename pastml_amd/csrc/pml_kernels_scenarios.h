@@ -51,7 +51,7 @@ struct PmlScenArgs {
     const double* bu;         // [N][ks] (tips: not stored)
     const double* post;       // [N][ks]
     const double* E;          // [N] (F81)
-    const double* P;          // [N][k][ks] (matrix models): P^T per branch
+    const double* P;          // [N][k][ks] (matrix models): P^T per branch; WIN: the column's window [B][k][ks] (PmlSimArgs::P)
     double* scratch;          // [gridDim.x][k][k] (PML_SIM_MATRIX_SCRATCH)
     unsigned long long* n_fallback;
 };
@@ -105,8 +105,10 @@ __device__ __forceinline__ int scen_fallback(const double* post, int k, double u
 // Items (list, tile) in a grid-stride loop over blockIdx.x; all threads of a workgroup take the same item and build the
 // node's table together.  Dynamic LDS, F81: pi [k], w_n [k], the cumulative table [k]; matrix models: w_n [k] (a root: its
 // cumulative posterior), then (MATRIX_LDS) the rows [k][k].
-template <typename T, int MODE>
+// WIN: P(t) of a node from its slot of the window (the fourth field of a list entry; entry i of a level launch: i).
+template <typename T, int MODE, bool WIN = false>
 __global__ void __launch_bounds__(PML_SIM_THREADS) scenarios_kernel(PmlScenArgs a) {
+    static_assert(!WIN || MODE != PML_SIM_F81, "the window holds matrices");
     typedef SimWord<T> SW;
     typedef typename SW::W Word;
     extern __shared__ double scen_lds[];
@@ -138,7 +140,7 @@ __global__ void __launch_bounds__(PML_SIM_THREADS) scenarios_kernel(PmlScenArgs 
         }
         int4 next = a.lists != nullptr ? a.lists[q0] : make_int4(0, 0, 0, 0);   // (loaded a step ahead, as in the simulator)
         for (int q = q0; q < q1; ++q) {
-            int n, p;
+            int n, p, slot;
             unsigned key, prow;
             if (a.lists != nullptr) {
                 const int4 cur = next;
@@ -147,11 +149,13 @@ __global__ void __launch_bounds__(PML_SIM_THREADS) scenarios_kernel(PmlScenArgs 
                 key = (unsigned)cur.y;
                 p = cur.z;
                 prow = (unsigned)cur.z;
+                slot = cur.w;
             } else {
                 n = q;
                 p = a.parent[n];
                 key = (unsigned)(a.api_id ? a.api_id[n] : n);
                 prow = p < 0 ? 0u : (unsigned)(a.api_id ? a.api_id[p] : p);
+                slot = li;
             }
             const double* post = a.post + (size_t)n * a.ks;
             // the node's table (p and n are the same in every thread of the workgroup)
@@ -178,7 +182,7 @@ __global__ void __launch_bounds__(PML_SIM_THREADS) scenarios_kernel(PmlScenArgs 
                 for (int b = tid; b < k; b += blockDim.x) wv[b] = scen_weight(a, (size_t)n, tip, b);
                 __syncthreads();
                 // row a (parent state) of the branch: P_n[b][a] is entry b of row a of the stored transpose
-                const double* Pt = a.P + (size_t)n * k * a.ks;
+                const double* Pt = a.P + (size_t)(WIN ? slot : n) * k * a.ks;
                 for (int r = tid; r < k; r += blockDim.x) {
                     double run = 0.0;
                     for (int b = 0; b < k; ++b) {

@@ -35,8 +35,9 @@
 struct PmlSimArgs {
     const int* parent;        // internal ids
     const int* api_id;        // caller's id of an internal node (null: the same)
-    const int4* lists;        // node lists, entries (internal id, caller's id, caller's id of the parent or -1, 0)
-                              // (null: list i is the single node first_node + i)
+    const int4* lists;        // node lists, entries (internal id, caller's id, caller's id of the parent or -1, slot of the
+                              // branch's matrix in the P(t) window: 0 where there is none)
+                              // (null: list i is the single node first_node + i, and its slot is i)
     const int* list_off;      // [n_lists + 1]
     int first_node, n_lists;
     int n_tiles;              // repetition tiles per list (blockDim.x tuples each)
@@ -48,7 +49,8 @@ struct PmlSimArgs {
     int k, ks;
     const double* pi;         // [ks] of the column
     const double* E;          // [N] of the column (F81)
-    const double* P;          // [N][k][ks] of the column (matrix models)
+    const double* P;          // [N][k][ks] of the column (matrix models); WIN: the column's window [B][k][ks], whose slots hold
+                              // the matrices of this launch's nodes (pml_pij_window.h: built right before it)
     double* scratch;          // [gridDim.x][k][k] (PML_SIM_MATRIX_SCRATCH)
 };
 
@@ -130,8 +132,10 @@ __device__ __forceinline__ double sim_wave_scan(double v, int lane) {
 // models share the branch's cumulative rows).  Dynamic LDS: cumulative pi [k], then (MATRIX_LDS) the rows [k][k].
 // 8 waves per SIMD: at the compiler's own choice (101 SGPRs, 7 waves) a subtree walk of 2048 workgroups ran in more than one
 // round (profiles/simulate_scale.txt); the SGPRs beyond spill into VGPR lanes, not scratch.
-template <typename T, int MODE>
+// WIN: P(t) of a node from its slot of the window instead of the batch; nothing else differs.
+template <typename T, int MODE, bool WIN = false>
 __global__ void __launch_bounds__(PML_SIM_THREADS) __attribute__((amdgpu_waves_per_eu(8, 8))) simulate_kernel(PmlSimArgs a) {
+    static_assert(!WIN || MODE != PML_SIM_F81, "the window holds matrices");
     typedef SimWord<T> SW;
     typedef typename SW::W Word;
     extern __shared__ double sim_lds[];
@@ -172,7 +176,7 @@ __global__ void __launch_bounds__(PML_SIM_THREADS) __attribute__((amdgpu_waves_p
         // one load per node (the parent's states), not three (list -> parent -> states)
         int4 next = a.lists != nullptr ? a.lists[q0] : make_int4(0, 0, 0, 0);
         for (int q = q0; q < q1; ++q) {
-            int n, p;
+            int n, p, slot;
             unsigned key, prow;
             if (a.lists != nullptr) {
                 const int4 cur = next;
@@ -181,16 +185,18 @@ __global__ void __launch_bounds__(PML_SIM_THREADS) __attribute__((amdgpu_waves_p
                 key = (unsigned)cur.y;
                 p = cur.z;
                 prow = (unsigned)cur.z;
+                slot = cur.w;
             } else {
                 n = q;
                 p = a.parent[n];
                 key = (unsigned)(a.api_id ? a.api_id[n] : n);
                 prow = p < 0 ? 0u : (unsigned)(a.api_id ? a.api_id[p] : p);
+                slot = li;
             }
             if (MODE != PML_SIM_F81 && p >= 0) {
                 // the branch's cumulative rows: row a (parent state) of P is column a of the stored transpose
                 __syncthreads();   // (the previous node's draws are done with the table)
-                const double* Pt = a.P + (size_t)n * k * a.ks;
+                const double* Pt = a.P + (size_t)(WIN ? slot : n) * k * a.ks;
                 for (int r = tid; r < k; r += blockDim.x) {
                     double run = 0.0;
                     for (int b = 0; b < k; ++b) {

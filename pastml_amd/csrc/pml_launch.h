@@ -133,7 +133,10 @@ PML_INTERNAL int launch_pij_mfma(pml_ctx* ctx);
 PML_INTERNAL int launch_pij_wide(pml_ctx* ctx);
 //      the list form: P(t) of `count` branches of a device list into the slots 0 .. count - 1 of the window of B slots per column;
 //      arm_pij_wide_list asks for the kernel's LDS once, outside any stream capture (pml_pij_window_set)
-PML_INTERNAL int launch_pij_wide_list(pml_ctx* ctx, double* window, long long B, const int* d_branches, int count);
+//      for the columns [col_begin, col_end) of the context only (col_end < 0: all of them), whose windows are the first
+//      col_end - col_begin of the buffer: a call for one column does not pay for the others
+PML_INTERNAL int launch_pij_wide_list(pml_ctx* ctx, double* window, long long B, const int* d_branches, int count, int col_begin = 0,
+                                      int col_end = -1);
 PML_INTERNAL int arm_pij_wide_list(pml_ctx* ctx);
 // ---- pml_launch_eigen_gemm.hip: sum sweeps as two small GEMMs per 16 nodes
 PML_INTERNAL int launch_eigen_gemm(pml_ctx* ctx, int mode, const int* nodes, int first, int n);
@@ -155,6 +158,35 @@ PML_INTERNAL int launch_simulate(pml_ctx* ctx, int col, int rep_offset, u64 seed
 //      lists of the subtrees rooted at depth D (ctx->d_sim_lists / d_sim_off / sim_n_lists)
 PML_INTERNAL int sim_frontier_depth(const pml_ctx* ctx, int n_tiles);
 PML_INTERNAL int sim_subtree_lists(pml_ctx* ctx, int D);
+//      On a context with a P(t) window (pml_pij_window.h) the two run the windowed form of that schedule: the levels above the
+//      frontier and the frontier's subtrees cut into runs of at most B branches (pml_plan_sim_window), each behind the launch that
+//      builds the run's matrices for the call's column.  sim_window_prepare plans and uploads it into the call's scope -- `w` is
+//      declared before the scope, whose copies read its host tables --, sim_window_run issues it (launch(args): one launch).
+static inline bool pij_windowed(const pml_ctx* ctx) {
+    return ctx->pij_window > 0 && ctx->kind == PML_MODEL_EIGEN && ctx->d_pij_window != nullptr;
+}
+struct SimWindowDevice {
+    PmlSimWindowPlan plan;
+    std::vector<int4> lists;   // entries of the frontier subtrees (PmlSimArgs::lists), the slot in the fourth field
+    int* d_order = nullptr;    // plan.order
+    int4* d_lists = nullptr;
+    int* d_off = nullptr;      // plan.sub_off
+};
+PML_INTERNAL int sim_window_prepare(pml_ctx* ctx, int D, CallScope& mem, SimWindowDevice& w);
+template <class Args, class Launch>
+static inline int sim_window_run(pml_ctx* ctx, Args a, const SimWindowDevice& w, int col, const Launch& launch) {
+    for (int part = 0; part < 2; ++part)
+        for (const PmlSimWindowRun& r : part == 0 ? w.plan.levels : w.plan.groups) {
+            if (r.build_count > 0)
+                PML_TRY(launch_pij_wide_list(ctx, ctx->d_pij_window, ctx->pij_window, w.d_order + r.build_first, r.build_count, col, col + 1));
+            a.lists = part == 0 ? nullptr : w.d_lists;
+            a.list_off = part == 0 ? nullptr : w.d_off + r.first;
+            a.first_node = part == 0 ? r.first : 0;
+            a.n_lists = r.count;
+            PML_TRY(launch(a));
+        }
+    return PML_OK;
+}
 // ---- pml_launch_scenarios.hip: scenarios of a column from the joint posterior after a marginal pass (pml_sample_scenarios);
 //      d_states as for launch_simulate, d_fallback: one counter (zeroed)
 PML_INTERNAL int launch_scenarios(pml_ctx* ctx, int col, int n_rep, int rep_offset, u64 seed, void* d_states, size_t rs,

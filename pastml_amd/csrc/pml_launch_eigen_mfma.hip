@@ -135,26 +135,28 @@ int launch_pij_wide(pml_ctx* ctx) {
 }
 
 // ... of the branches of one run of a windowed sweep (pml_pij_window.h): the same tiles and LDS, the grid sized by the run
-static int pij_wide_list(pml_ctx* ctx, bool arm_only, double* window, long long B, const int* d_branches, int count) {
+static int pij_wide_list(pml_ctx* ctx, bool arm_only, double* window, long long B, const int* d_branches, int count, int cb, int ce) {
     const int k = ctx->k;
     if (k <= 32 || k > PML_MAX_STATES_MATRIX) return fail(PML_ERR_UNSUPPORTED, "the P(t) window is for 33 .. %d states, not %d", PML_MAX_STATES_MATRIX, k);
     const int ntc = pijw_tiles(k, ctx->ks);
     const size_t lds = pijw_lds_bytes(k, ntc);
-    if (!arm_only && (count <= 0 || (long long)count > B || !window || !d_branches))
-        return fail(PML_ERR_INVALID, "a run of %d branches for a window of %lld", count, B);
+    if (ce < 0) ce = ctx->C;
+    if (!arm_only && (count <= 0 || (long long)count > B || !window || !d_branches || cb < 0 || ce > ctx->C || cb >= ce))
+        return fail(PML_ERR_INVALID, "a run of %d branches for a window of %lld, columns %d .. %d", count, B, cb, ce);
+    const int cols = arm_only ? ctx->C : ce - cb;
     const PmlTree t = tree_of(ctx);
     const PmlCols c = cols_of(ctx);
     const PmlModel m = model_of(ctx);
-    int blocks = std::max(1, (int)ctx->tune.get(T_PIJ_BLOCKS, 1024) / std::max(1, ctx->C));
+    int blocks = std::max(1, (int)ctx->tune.get(T_PIJ_BLOCKS, 1024) / std::max(1, cols));
     blocks = std::max(1, std::min(blocks, (count + PML_PIJW_WAVES - 1) / PML_PIJW_WAVES));
     const int bpb = std::max(1, (count + blocks - 1) / blocks);
-    dim3 grid((std::max(1, count) + bpb - 1) / bpb, ctx->C);
+    dim3 grid((std::max(1, count) + bpb - 1) / bpb, cols);
 #define PML_PIJW_CASE(NTC_)                                                                                          \
     if (ntc == NTC_) {                                                                                               \
         PML_TRY(with_lds(ctx, pij_eigen_wide_kernel<NTC_, true>, lds));                                              \
         if (!arm_only)                                                                                               \
             hipLaunchKernelGGL((pij_eigen_wide_kernel<NTC_, true>), grid, dim3(PML_PIJW_BLOCK), lds, ctx->stream, t, c, m, \
-                               (PijwList{window, d_branches, count, B}), bpb);                                       \
+                               (PijwList{window, d_branches, count, B, cb}), bpb);                                    \
     }
     PML_PIJW_CASE(1) PML_PIJW_CASE(2) PML_PIJW_CASE(3) PML_PIJW_CASE(4)
     PML_PIJW_CASE(5) PML_PIJW_CASE(6) PML_PIJW_CASE(7) PML_PIJW_CASE(8)
@@ -162,10 +164,10 @@ static int pij_wide_list(pml_ctx* ctx, bool arm_only, double* window, long long 
     if (!arm_only) HIP_TRY(hipGetLastError());
     return PML_OK;
 }
-int launch_pij_wide_list(pml_ctx* ctx, double* window, long long B, const int* d_branches, int count) {
-    return pij_wide_list(ctx, false, window, B, d_branches, count);
+int launch_pij_wide_list(pml_ctx* ctx, double* window, long long B, const int* d_branches, int count, int col_begin, int col_end) {
+    return pij_wide_list(ctx, false, window, B, d_branches, count, col_begin, col_end);
 }
-int arm_pij_wide_list(pml_ctx* ctx) { return pij_wide_list(ctx, true, nullptr, 0, nullptr, 0); }
+int arm_pij_wide_list(pml_ctx* ctx) { return pij_wide_list(ctx, true, nullptr, 0, nullptr, 0, 0, -1); }
 
 
 // P(t) of every branch on the FP64 matrix cores, 16 <= k <= 32 (run_prep)

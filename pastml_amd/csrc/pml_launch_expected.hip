@@ -17,6 +17,8 @@ static int expected_piece(const pml_ctx* ctx) {
 PML_INTERNAL int launch_expected(pml_ctx* ctx, int cb, int ce, const unsigned char* d_alt, double* d_out, double* d_same) {
     const int k = ctx->k, N = ctx->N, cols = ce - cb;
     const bool f81 = ctx->kind == PML_MODEL_F81;
+    const bool windowed = pij_windowed(ctx);
+    std::vector<int> ids;   // (windowed: the branch list of the call; before the scope, whose copy reads it)
     PmlExpArgs a;
     a.parent = ctx->d_parent;
     a.first_child = ctx->d_first_child;
@@ -41,6 +43,8 @@ PML_INTERNAL int launch_expected(pml_ctx* ctx, int cb, int ce, const unsigned ch
     a.same = d_same;
     a.out = d_out;
     a.partial = a.corr = a.rowsum = a.dterm = nullptr;
+    a.piece0 = 0;
+    a.win_B = 0;
     const size_t n_partial = (size_t)cols * a.n_pieces * k * k, n_corr = (size_t)cols * a.n_ppieces * k;
     const size_t n_branch = f81 ? (size_t)cols * N : (size_t)cols * N * k;
     CallScope mem(ctx->stream, false);
@@ -57,6 +61,36 @@ PML_INTERNAL int launch_expected(pml_ctx* ctx, int cb, int ce, const unsigned ch
             hipLaunchKernelGGL(expected_rowsum_kernel, dim3((N + 15) / 16, cols), dim3(256), 0, ctx->stream, a);
             hipLaunchKernelGGL(expected_f81_kernel<1>, dim3(a.n_pieces, TG * TG, cols), dim3(256), 0, ctx->stream, a);
         }
+    } else if (windowed) {
+        // P(t) in a window: runs of whole pieces, each behind the build of its ids' branches for the columns of the call (the x
+        // range of the grid starts at the run's first piece: partials, per-branch terms and the reduce do not notice).  A window
+        // below one piece: the call takes one of a piece per column of its own, gone with the scope.
+        if (k > 256) return fail(PML_ERR_UNSUPPORTED, "k = %d: the matrix models hold at most 256 states", k);
+        double* window = ctx->d_pij_window;
+        a.win_B = ctx->pij_window;
+        if (a.win_B < a.piece) {
+            a.win_B = a.piece;
+            PML_TRY(mem.get(&window, (size_t)cols * a.piece * k * ctx->ks));
+        }
+        a.P = window;
+        std::vector<PmlPieceRun> runs;
+        const std::string bad = pml_window_piece_runs(N, a.piece, a.win_B, runs);
+        if (!bad.empty()) return fail(PML_ERR_INVALID, "%s", bad.c_str());
+        ids.resize((size_t)N);
+        for (int i = 0; i < N; ++i) ids[(size_t)i] = ctx->new_of_old.empty() ? i : ctx->new_of_old[(size_t)i];
+        int* d_ids;
+        PML_TRY(mem.put(&d_ids, (const int*)ids.data(), ids.size()));
+        const int rows = k <= 64 ? 1 : (k <= 128 ? (k + 63) / 64 : (k + 31) / 32);
+        for (const PmlPieceRun& r : runs) {
+            const int i0 = r.p0 * a.piece, i1 = std::min(N, r.p1 * a.piece);
+            PML_TRY(launch_pij_wide_list(ctx, window, a.win_B, d_ids + i0, i1 - i0, cb, ce));   // (a root among them: built, never read)
+            a.piece0 = r.p0;
+            const dim3 grid(r.p1 - r.p0, rows, cols);
+            if (k <= 64) hipLaunchKernelGGL((expected_matrix_kernel<1, true>), grid, dim3(256), 0, ctx->stream, a);
+            else if (k <= 128) hipLaunchKernelGGL((expected_matrix_kernel<2, true>), grid, dim3(256), 0, ctx->stream, a);
+            else hipLaunchKernelGGL((expected_matrix_kernel<4, true>), grid, dim3(256), 0, ctx->stream, a);
+        }
+        a.piece0 = 0;
     } else if (k <= 64) {
         hipLaunchKernelGGL(expected_matrix_kernel<1>, dim3(a.n_pieces, 1, cols), dim3(256), 0, ctx->stream, a);
     } else if (k <= 128) {

@@ -6,13 +6,13 @@
 
 #define PML_SCEN_SCRATCH_BYTES (256ull << 20)   // bound of the cumulative rows of wide matrix models (PML_SIM_MATRIX_SCRATCH)
 
-template <typename T, int MODE>
+template <typename T, int MODE, bool WIN = false>
 static int scen_launch(pml_ctx* ctx, PmlScenArgs a, int threads, size_t lds, long long max_blocks) {
     const long long items = (long long)a.n_lists * a.n_tiles;
     if (items <= 0) return PML_OK;
     const int blocks = (int)std::min<long long>(items, max_blocks);
-    if (lds > 64 * 1024) PML_TRY(with_lds(ctx, scenarios_kernel<T, MODE>, lds));
-    hipLaunchKernelGGL((scenarios_kernel<T, MODE>), dim3(blocks), dim3(threads), lds, ctx->stream, a);
+    if (lds > 64 * 1024) PML_TRY(with_lds(ctx, scenarios_kernel<T, MODE, WIN>, lds));
+    hipLaunchKernelGGL((scenarios_kernel<T, MODE, WIN>), dim3(blocks), dim3(threads), lds, ctx->stream, a);
     HIP_TRY(hipGetLastError());
     return PML_OK;
 }
@@ -46,7 +46,8 @@ PML_INTERNAL int launch_scenarios(pml_ctx* ctx, int col, int n_rep, int rep_offs
     const int threads = std::min(PML_SIM_THREADS, 64 * ((n_tuples + 63) / 64));
     const int n_tiles = (n_tuples + threads - 1) / threads;
     const int D = sim_frontier_depth(ctx, n_tiles);
-    if (D < ctx->n_td_levels) PML_TRY(sim_subtree_lists(ctx, D));
+    const bool windowed = pij_windowed(ctx);
+    if (D < ctx->n_td_levels && !windowed) PML_TRY(sim_subtree_lists(ctx, D));
     const size_t colN = (size_t)col * ctx->N;
     PmlScenArgs a;
     a.parent = ctx->d_parent;
@@ -75,6 +76,26 @@ PML_INTERNAL int launch_scenarios(pml_ctx* ctx, int col, int n_rep, int rep_offs
     a.scratch = nullptr;
     a.n_fallback = d_fallback;
     const long long cap = 1 << 20;
+    if (windowed) {
+        // P(t) from the context's window, built run by run for this column (its window is the first of the buffer)
+        SimWindowDevice w;
+        CallScope mem(ctx->stream, false);
+        PML_TRY(sim_window_prepare(ctx, D, mem, w));
+        a.P = ctx->d_pij_window;
+        if (k <= PML_SIM_LDS_K) {
+            const size_t lds = (size_t)(k + k * k) * sizeof(double);
+            PML_TRY(sim_window_run(ctx, a, w, col, [&](const PmlScenArgs& x) {
+                return scen_launch<unsigned char, PML_SIM_MATRIX_LDS, true>(ctx, x, threads, lds, cap);
+            }));
+        } else {
+            const long long blocks = std::max<long long>(1, (long long)(PML_SCEN_SCRATCH_BYTES / ((size_t)k * k * sizeof(double))));
+            PML_TRY(mem.get(&a.scratch, (size_t)blocks * k * k));
+            PML_TRY(sim_window_run(ctx, a, w, col, [&](const PmlScenArgs& x) {
+                return scen_launch<unsigned char, PML_SIM_MATRIX_SCRATCH, true>(ctx, x, threads, (size_t)k * sizeof(double), blocks);
+            }));
+        }
+        return mem.finish();
+    }
     if (f81) {
         const size_t lds = (size_t)3 * k * sizeof(double);
         if (k > 256) return scen_run<unsigned short, PML_SIM_F81>(ctx, a, threads, D, lds, cap);

@@ -56,13 +56,35 @@ PML_INTERNAL int sim_subtree_lists(pml_ctx* ctx, int D) {
     return PML_OK;
 }
 
-template <typename T, int MODE>
+// The windowed form of the schedule (pml_pij_window.h: pml_plan_sim_window), uploaded for one call: the branch lists of the runs
+// and the preorder lists of the frontier subtrees, whose entries carry their slot in the group's window.  The context's own
+// lists (sim_subtree_lists) are left alone: the frontier of a windowed call may lie deeper.
+PML_INTERNAL int sim_window_prepare(pml_ctx* ctx, int D, CallScope& mem, SimWindowDevice& w) {
+    const std::string bad = pml_plan_sim_window(ctx->forest, D, ctx->pij_window, w.plan);
+    if (!bad.empty()) return fail(PML_ERR_INVALID, "%s", bad.c_str());
+    const bool perm = !ctx->old_of_new.empty();
+    auto api = [&](int n) { return perm ? ctx->old_of_new[n] : n; };
+    const PmlSimWindowPlan& P = w.plan;
+    w.lists.resize(P.order.size() - (size_t)P.list_base);
+    for (const PmlSimWindowRun& g : P.groups)
+        for (int i = 0; i < g.build_count; ++i) {
+            const int n = P.order[(size_t)(g.build_first + i)];
+            const int p = ctx->forest.parent[n];
+            w.lists[(size_t)(g.build_first - P.list_base + i)] = make_int4(n, api(n), p < 0 ? -1 : api(p), i);
+        }
+    PML_TRY(mem.put(&w.d_order, (const int*)P.order.data(), P.order.size()));
+    PML_TRY(mem.put(&w.d_lists, (const int4*)w.lists.data(), w.lists.size()));
+    PML_TRY(mem.put(&w.d_off, (const int*)P.sub_off.data(), P.sub_off.size()));
+    return PML_OK;
+}
+
+template <typename T, int MODE, bool WIN = false>
 static int sim_launch(pml_ctx* ctx, PmlSimArgs a, int threads, size_t lds, long long max_blocks) {
     const long long items = (long long)a.n_lists * a.n_tiles;
     if (items <= 0) return PML_OK;
     const int blocks = (int)std::min<long long>(items, max_blocks);
-    if (lds > 64 * 1024) PML_TRY(with_lds(ctx, simulate_kernel<T, MODE>, lds));
-    hipLaunchKernelGGL((simulate_kernel<T, MODE>), dim3(blocks), dim3(threads), lds, ctx->stream, a);
+    if (lds > 64 * 1024) PML_TRY(with_lds(ctx, simulate_kernel<T, MODE, WIN>, lds));
+    hipLaunchKernelGGL((simulate_kernel<T, MODE, WIN>), dim3(blocks), dim3(threads), lds, ctx->stream, a);
     HIP_TRY(hipGetLastError());
     return PML_OK;
 }
@@ -92,7 +114,8 @@ PML_INTERNAL int launch_simulate(pml_ctx* ctx, int col, int rep_offset, u64 seed
     const int threads = std::min(PML_SIM_THREADS, 64 * ((n_tuples + 63) / 64));
     const int n_tiles = (n_tuples + threads - 1) / threads;
     const int D = sim_frontier_depth(ctx, n_tiles);
-    if (D < ctx->n_td_levels) PML_TRY(sim_subtree_lists(ctx, D));
+    const bool windowed = pij_windowed(ctx);
+    if (D < ctx->n_td_levels && !windowed) PML_TRY(sim_subtree_lists(ctx, D));
     PmlSimArgs a;
     a.parent = ctx->d_parent;
     a.api_id = ctx->d_old_of_new;   // (null when the library works in the caller's numbering)
@@ -113,6 +136,26 @@ PML_INTERNAL int launch_simulate(pml_ctx* ctx, int col, int rep_offset, u64 seed
     a.P = ctx->kind == PML_MODEL_F81 ? nullptr : ctx->d_P + (size_t)col * ctx->N * k * ctx->ks;
     a.scratch = nullptr;
     const long long cap = 1 << 20;
+    if (windowed) {
+        // P(t) from the context's window, built run by run for this column (its window is the first of the buffer)
+        SimWindowDevice w;
+        CallScope mem(ctx->stream, false);
+        PML_TRY(sim_window_prepare(ctx, D, mem, w));
+        a.P = ctx->d_pij_window;
+        if (k <= PML_SIM_LDS_K) {
+            const size_t lds = (size_t)(k + k * k) * sizeof(double);
+            PML_TRY(sim_window_run(ctx, a, w, col, [&](const PmlSimArgs& x) {
+                return sim_launch<unsigned char, PML_SIM_MATRIX_LDS, true>(ctx, x, threads, lds, cap);
+            }));
+        } else {
+            const long long blocks = std::max<long long>(1, (long long)(PML_SIM_SCRATCH_BYTES / ((size_t)k * k * sizeof(double))));
+            PML_TRY(mem.get(&a.scratch, (size_t)blocks * k * k));
+            PML_TRY(sim_window_run(ctx, a, w, col, [&](const PmlSimArgs& x) {
+                return sim_launch<unsigned char, PML_SIM_MATRIX_SCRATCH, true>(ctx, x, threads, (size_t)k * sizeof(double), blocks);
+            }));
+        }
+        return mem.finish();
+    }
     if (ctx->kind == PML_MODEL_F81) {
         const size_t lds = (size_t)k * sizeof(double);
         if (k > 256) return sim_run<unsigned short, PML_SIM_F81>(ctx, a, threads, D, lds, cap);

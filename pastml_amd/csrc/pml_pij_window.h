@@ -32,3 +32,36 @@ PML_PLAN int pml_window_max_fanout(const PmlForest& f);
 // its list).
 PML_PLAN std::string pml_plan_pij_window(const std::vector<PmlLaunch>& plan, const PmlForest& f, const std::vector<int>& bu_order,
                                          const std::vector<int>& td_parents, long long B, PmlWindowPlan& out);
+
+// ---- the consumers of P(t) outside the sweeps: the exact and the sampled counts, the simulator, the scenario sampler ----------
+// They run in runs as well: one launch of the list build for exactly the branches the next consumer launch reads (for the
+// columns of the call only), then that launch, which finds branch i of the run's list in slot i.  The sampled counts walk the
+// top-down level list and take the runs of the top-down sweep (PmlWindowPlan above, kept on the context); the cuts of the other
+// three are below.  None of them moves a floating-point sum or a draw: a run only says where a matrix lies.
+
+// Exact counts: the branch pass walks the caller's ids in pieces of `piece`, one workgroup per piece; a run is the whole pieces
+// [p0, p1), its branch list the ids [piece p0, min(n_ids, piece p1)) in order (slot = id - piece p0).  B < piece: refused -- the
+// call then takes a window of one piece of its own.
+struct PmlPieceRun {
+    int p0, p1;
+};
+PML_PLAN std::string pml_window_piece_runs(int n_ids, int piece, long long B, std::vector<PmlPieceRun>& out);
+
+// Simulator and scenario sampler (pml_launch_simulate.hip): the depth levels above the frontier one launch per run of at most B
+// consecutive nodes (slot = node - first node of the run; depth 0 are the roots and builds nothing), the subtrees rooted at the
+// frontier depth in groups of consecutive subtrees whose preorder lists hold at most B entries together (slot = position in the
+// group; a root among them is built harmlessly and never read).  A subtree is never split: where one at the asked depth holds
+// more than B nodes the frontier moves down for this call -- in the limit to the number of levels, level launches only.  The
+// results cannot tell: a node's draw is a function of (seed, node, repetition).
+struct PmlSimWindowRun {
+    int first, count;               // a level run: nodes; a group: frontier subtrees (indices into sub_off)
+    int build_first, build_count;   // entries of `order` built into slots 0 .. build_count - 1 (0: nothing)
+};
+struct PmlSimWindowPlan {
+    int depth = 0;                  // the frontier depth used (>= the one asked for)
+    std::vector<PmlSimWindowRun> levels, groups;
+    std::vector<int> order;         // the branch lists of the runs one after the other, then the subtrees in preorder
+    int list_base = 0;              // where the subtrees begin in `order`
+    std::vector<int> sub_off;       // [subtrees + 1]: a subtree's entries, counted from list_base
+};
+PML_PLAN std::string pml_plan_sim_window(const PmlForest& f, int depth, long long B, PmlSimWindowPlan& out);

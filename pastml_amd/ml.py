@@ -114,6 +114,8 @@ class ForestProblem(object):
         self.nodes = self.flat.nodes
         self.N = self.flat.n_nodes
         self.batch = CharacterBatch(self.flat, self.k, 1, device=device)
+        self._device = device
+        self.pij_window_stats = None   # where the context finds P(t): planned before the first sweep (batch.consumer_window)
 
     # the reference's 0/1 arrays, converted on access
     @property
@@ -171,7 +173,12 @@ class ForestProblem(object):
     # ------------------------------------------------------------------------------------------------ device
     def bottom_up_loglikelihood(self, model, is_marginal=True, alter=True):
         """Sum over the trees of the forest of get_bottom_up_loglikelihood (ml.py:82-121)."""
-        from pastml_amd.batch import LikelihoodError, likelihood_error
+        from pastml_amd.batch import LikelihoodError, consumer_window, likelihood_error
+        if self.pij_window_stats is None:
+            # a character whose whole-tree batch of P(t) does not fit the device runs with a window of it: the sweeps and what
+            # marginal_counts / sample_scenarios do after them (MemoryError if not even the smallest window fits)
+            self.batch.pij_window, self.pij_window_stats = consumer_window(
+                self.flat, self.k, model.kernel_spec()['kind'], 1, self.character, 'ForestProblem', device=self._device)
         try:
             return float(self.batch.bottom_up([model], is_marginal=is_marginal, alter=alter)[0])
         except LikelihoodError as e:
@@ -520,6 +527,7 @@ def marginal_counts(forest, character, model, n_repetitions=1_000, device_sampli
         problem.initialize_allowed_states()
         altered = problem.alter_zero_node_allowed_states() if 0 == model.tau else np.zeros(0, dtype=np.int64)
         problem.bottom_up_loglikelihood(model, is_marginal=True, alter=False)
+        marginal_counts.last_stats = dict(pij_window=[problem.pij_window_stats])
         posterior, _, _ = problem.top_down_marginals()
         if device_sampling and not len(altered) and k <= 256:   # (the device sampler's tables hold 256 states)
             # no node altered by the zero-branch handling: the scenarios are drawn on the device (same scheme, a
@@ -684,9 +692,10 @@ def expected_counts(forest, characters, models):
     :param characters: a character (feature name) or a list of them; models: a model or a list, one per character
     :return: a k x k array, entry [i, j] = expected number of i -> j changes per scenario -- or a list of them
     """
-    from pastml_amd.batch import CharacterBatch, LikelihoodError, annotation_words, likelihood_error
+    from pastml_amd.batch import CharacterBatch, LikelihoodError, annotation_words, consumer_window, likelihood_error
     if isinstance(forest, TreeNode):
         forest = [forest]
+    expected_counts.last_stats = dict(pij_window=[])   # per group: where its context finds P(t) (batch.consumer_window)
     single = isinstance(characters, str)
     if single:
         characters, models = [characters], [models]
@@ -698,9 +707,12 @@ def expected_counts(forest, characters, models):
     for i, model in enumerate(models):
         groups.setdefault((len(model.states), model.kernel_spec()['kind']), []).append(i)
     results = [None] * len(characters)
-    for (k, _), members in groups.items():
+    for (k, kind), members in groups.items():
         group_models = [models[i] for i in members]
+        window, record = consumer_window(flat, k, kind, len(members), characters[members[0]], 'expected_counts')
+        expected_counts.last_stats['pij_window'].append(record)
         with CharacterBatch(flat, k, len(members)) as batch:
+            batch.pij_window = window
             for c, i in enumerate(members):
                 batch.set_annotation(c, *annotation_words(flat, characters[i], models[i].states))
             batch.initialize_allowed_states()

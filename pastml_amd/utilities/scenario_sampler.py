@@ -14,7 +14,7 @@ from pastml_amd import hip, sharding
 from pastml_amd.ml import ForestProblem
 from pastml_amd.models._closed_form import EFT, F81, JC
 from pastml_amd.tree import ArrayColumn, TreeNode
-from pastml_amd.utilities.state_simulator import _chunk, _reserved_bytes
+from pastml_amd.utilities.state_simulator import _window_and_chunk
 
 
 def sample_scenarios(forest, character, model, n_repetitions=1_000):
@@ -63,8 +63,15 @@ def sample_scenarios(forest, character, model, n_repetitions=1_000):
         _, free = engine.memory()
         if os.environ.get('PASTML_AMD_DEVICE_BYTES'):   # plan as if the device had this much free memory (tests)
             free = min(free, int(float(os.environ['PASTML_AMD_DEVICE_BYTES'])))
-        free -= _reserved_bytes(flat.n_nodes, k, matrix)   # (the fused sweeps leave P(t) to the first call)
-        chunk = _chunk(flat.n_nodes, n_repetitions, np.dtype(dtype).itemsize, free)
+        # (the fused sweeps leave the batch of P(t) to the first call; a window is the context's already and is charged instead:
+        # ForestProblem planned it before the first sweep)
+        record = dict(problem.pij_window_stats)
+        window, chunk = _window_and_chunk(flat, k, matrix, record['branches'], n_repetitions, np.dtype(dtype).itemsize,
+                                          free + record['branches'] * k * ((k + 7) // 8 * 8) * 8)
+        if window != record['branches']:
+            engine.pij_window_set(window)   # (a smaller window for fewer chunks of repetitions: the pass's results stay)
+        record.update(branches=window, repetitions_per_call=chunk)
+        sample_scenarios.last_stats = dict(pij_window=[record])
         n_fallback = 0
         for offset in range(0, n_repetitions, chunk):
             count = min(chunk, n_repetitions - offset)
