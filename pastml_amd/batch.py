@@ -413,7 +413,7 @@ class CharacterBatch(object):
         return nsel.astype(np.int64)
 
     # ------------------------------------------------------------------------------------------------ optimiser columns
-    def open_optimiser(self, widths):
+    def open_optimiser(self, widths, tune=None):
         """
         A second context whose columns are blocks, one block of widths[c] columns per character: the points of one
         finite-difference gradient of character c go into block c.  All columns of a block carry the character's masks
@@ -421,10 +421,15 @@ class CharacterBatch(object):
         alteration depends on the masks only, not on the parameters, so it is computed once per character, when its
         first point with tau == 0 comes, for the hundreds of evaluations of an optimisation; the saved '.initial'
         masks stay, as after a sequence of single evaluations.
+        tune: schedule switches for the context (hip.Engine; tests take the blocks through every schedule) -- such a context is
+        built for this batch and not pooled.
         """
         offsets = np.concatenate(([0], np.cumsum(widths))).astype(np.int64)
         total = int(offsets[-1])
-        eng = hip.acquire_engine(self.flat, total, self.k, device=self._device)
+        if tune:
+            eng = hip.Engine(self.flat, total, self.k, device=self._device, tune=tune)
+        else:
+            eng = hip.acquire_engine(self.flat, total, self.k, device=self._device)
         self._opt = dict(engine=eng, offsets=offsets, total=total, variant=np.full(total, -1, dtype=np.int64),
                          altered={}, models=[None] * total, all_set=False)
         return self._opt

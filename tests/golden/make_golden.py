@@ -1198,6 +1198,118 @@ CASES['hiv1c_year_trace'] = case_hiv1c_year_trace
 # input moves by a rounding error (the fixture keeps the run summaries and the final values)
 CASES['hiv1c_year_trace_perturbed'] = lambda: case_hiv1c_year_trace(1e-12)
 
+
+def albania_derived_columns(df):
+    """Country and two columns derived from it (three regions; Albania against the rest), missing values kept."""
+    region = {'Africa': 'Africa', 'Albania': 'Balkans', 'Greece': 'Balkans', 'EastEurope': 'Europe', 'WestEurope': 'Europe'}
+    out = df[['Country']].copy()
+    out['Region'] = [region.get(v, v) for v in df['Country']]
+    out['IsAlbania'] = [v if pd.isna(v) else ('yes' if v == 'Albania' else 'no') for v in df['Country']]
+    return out
+
+
+def case_albania_free_params():
+    """
+    The two acr() arguments that change the optimiser's parameter vector, on Albania / Country, MPPA: tau=None (the pipeline's
+    smoothing=True: tau is optimised) and frequency_smoothing=True, for F81 / JC / EFT, and F81 with the observed frequencies given
+    in column2parameters (then the reference keeps the smoothing and drops the frequency optimisation, models/__init__.py:409).
+    Every run is repeated with every L-BFGS-B start multiplied by (1 + 1e-12) and (1 - 1e-12) -- the reference's own spread under a
+    rounding error of its input -- through the wrapped `minimize` of case_hiv1c_year_trace.  The unperturbed F81 run with tau=None
+    also records every vector its objective was asked at and the value it returned, in order.  Then one call with three
+    characters and tau=None: only the first optimises tau (acr.py:185-187).
+    """
+    import scipy.optimize
+    from pastml.annotation import preannotate_forest
+    from pastml.acr import calculate_observed_freqs
+    real = scipy.optimize.minimize
+    tree0, df0 = albania_inputs()
+    preannotate_forest([tree0], df=df0)
+    states = np.array(sorted(v for v in df0['Country'].unique() if not pd.isna(v) and '' != v))
+    _, observed, _ = calculate_observed_freqs('Country', [tree0], states)
+    given = {'Country': {s: float(f) for s, f in zip(states, observed)}}
+    runs = [('F81_tau', dict(model='F81', tau=None)),
+            ('JC_tau', dict(model='JC', tau=None)),
+            ('EFT_tau', dict(model='EFT', tau=None)),
+            ('F81_fs', dict(model='F81', frequency_smoothing=True)),
+            ('F81_given_fs', dict(model='F81', frequency_smoothing=True, column2parameters=given)),
+            ('F81_given_fs_tau', dict(model='F81', frequency_smoothing=True, column2parameters=given, tau=None))]
+    out = dict(states=np.array(states, dtype=str), observed_frequencies=observed, run_names=np.array([r[0] for r in runs], dtype=str),
+               start_points_moved_by=1e-12)
+
+    def run(kwargs, perturb, trace=None, df=None):
+        count = [0]
+
+        def wrapped(fun, x0, **kw):
+            count[0] += 1
+            x0 = np.array(x0, dtype=np.float64) * (1.0 + perturb)
+            if trace is None:
+                return real(fun, x0=x0, **kw)
+
+            def recording(ps):
+                value = fun(ps)
+                trace.append((np.array(ps, dtype=np.float64), float(value)))
+                return value
+            return real(recording, x0=x0, **kw)
+
+        tree, dfc = albania_inputs()
+        rml.minimize = wrapped
+        try:
+            np.random.seed(239)
+            res = racr(tree, dfc if df is None else df(dfc), prediction_method='MPPA', threads=1, **kwargs)
+        finally:
+            rml.minimize = real
+        return tree, res, count[0]
+
+    def arrays(tree, res, column):
+        model = res['model']
+        nodes = our_tree.FlatForest.from_trees([tree]).nodes
+        s2i = {s: i for i, s in enumerate(model.states)}
+        sel = np.zeros((len(nodes), len(s2i)), dtype=np.int8)
+        for i, n in enumerate(nodes):
+            for s in getattr(n, column):
+                sel[i, s2i[s]] = 1
+        return dict(loglik=res['log_likelihood'], sf=float(model.sf), tau=float(model.tau),
+                    frequencies=np.array(model.frequencies, dtype=np.float64),
+                    posterior=res['marginal_probabilities'].loc[[n.name for n in nodes]].values, selected_mppa=sel,
+                    loglik_restricted_MPPA=res['log_likelihood_restricted_MPPA'],
+                    loglik_restricted_MAP=res['log_likelihood_restricted_MAP'],
+                    loglik_restricted_JOINT=res['log_likelihood_restricted_JOINT'],
+                    states=np.array(model.states, dtype=str))
+
+    for name, kwargs in runs:
+        for label, perturb in (('', 0.0), ('plus_', 1e-12), ('minus_', -1e-12)):
+            trace = [] if (name == 'F81_tau' and not perturb) else None
+            tree, res, n_runs = run(kwargs, perturb, trace)
+            pre = '{}_{}'.format(name, label)
+            for key, v in arrays(tree, res[0], 'Country').items():
+                out[pre + key] = v
+            out[pre + 'n_minimize'] = n_runs
+            if trace is not None:
+                # the searches of one run differ in length (sf and tau alone, then everything): padded with NaN
+                width = max(len(x) for x, _ in trace)
+                xs = np.full((len(trace), width), np.nan)
+                for i, (x, _) in enumerate(trace):
+                    xs[i, :len(x)] = x
+                out[pre + 'trace_x'] = xs
+                out[pre + 'trace_n'] = np.array([len(x) for x, _ in trace], dtype=np.int32)
+                out[pre + 'trace_value'] = np.array([v for _, v in trace])
+            print(pre, out[pre + 'loglik'], out[pre + 'sf'], out[pre + 'tau'], n_runs, flush=True)
+
+    tree, results, n_runs = run(dict(model='F81', tau=None), 0.0, df=albania_derived_columns)
+    _, df3 = albania_inputs()
+    df3 = albania_derived_columns(df3)
+    out['three_columns'] = np.array(df3.columns, dtype=str)
+    out['three_index'] = np.array(df3.index.map(str), dtype=str)
+    out['three_values'] = np.array(df3.fillna('').values, dtype=str)
+    out['three_n_minimize'] = n_runs
+    for res in results:
+        for key, v in arrays(tree, res, res['character']).items():
+            out['three_{}_{}'.format(res['character'], key)] = v
+    save('albania_free_params', **out)
+
+
+CASES['albania_free_params'] = case_albania_free_params
+
 if __name__ == '__main__':
     np.random.seed(239)
     todo = sys.argv[1:] or list(CASES)

@@ -3,6 +3,7 @@ CPU-only tests of the host-side logic of the boundary (no sweep is computed here
 frequencies, masks and their zero-branch alteration, MAP / MPPA selection including the reference's stateful
 '.initial' behaviour -- all against golden vectors produced by the real reference.
 """
+import itertools
 import os
 
 import numpy as np
@@ -391,24 +392,24 @@ def test_kernel_points_decodes_a_batch_like_one_vector_at_a_time():
     fs = ForestStats([read_tree(os.path.join(GOLDEN, 'data', 'Albanian.tree.152tax.tre'))])
     rng = np.random.default_rng(0)
     for k in (2, 3, 5, 12, 36, 67):
-        for optimise_tau in (False, True):
-            for fixed in (False, True):
-                states = ['s%02d' % i for i in range(k)]
-                freqs = np.random.default_rng(k).dirichlet(np.ones(k))
-                a, b = (F81Model(states=states, forest_stats=fs, optimise_tau=optimise_tau, frequencies=freqs.copy())
-                        for _ in range(2))
-                if fixed:
-                    a.fix_extra_params()
-                    b.fix_extra_params()
-                bounds = a.get_bounds()
-                lo, up = bounds[:, 0], bounds[:, 1]
-                vectors = [lo + (up - lo) * rng.uniform(0, 1, len(lo)) ** 3 for _ in range(k + 2)]
-                if optimise_tau:
-                    vectors[1][1] = 0.0
-                pa, pb = a.kernel_points(vectors), ModelWithFrequencies.kernel_points(b, vectors)
-                for (sa, ra), (sb, rb) in zip(pa, pb):
-                    assert np.array_equal(sa['pi'], sb['pi']) and ra == rb
-                assert np.array_equal(a.frequencies, b.frequencies) and (a.sf, a.tau, a._tau_factor) == (b.sf, b.tau, b._tau_factor)
+        # (smoothing: one pseudo-count parameter instead of k - 1 ratios, applied to the CURRENT frequencies)
+        for optimise_tau, fixed, smoothing in itertools.product((False, True), repeat=3):
+            states = ['s%02d' % i for i in range(k)]
+            freqs = np.random.default_rng(k).dirichlet(np.ones(k))
+            a, b = (F81Model(states=states, forest_stats=fs, optimise_tau=optimise_tau, frequencies=freqs.copy(),
+                             frequency_smoothing=smoothing) for _ in range(2))
+            if fixed:
+                a.fix_extra_params()
+                b.fix_extra_params()
+            bounds = a.get_bounds()
+            lo, up = bounds[:, 0], bounds[:, 1]
+            vectors = [lo + (up - lo) * rng.uniform(0, 1, len(lo)) ** 3 for _ in range(k + 2)]
+            if optimise_tau:
+                vectors[1][1] = 0.0
+            pa, pb = a.kernel_points(vectors), ModelWithFrequencies.kernel_points(b, vectors)
+            for (sa, ra), (sb, rb) in zip(pa, pb):
+                assert np.array_equal(sa['pi'], sb['pi']) and ra == rb
+            assert np.array_equal(a.frequencies, b.frequencies) and (a.sf, a.tau, a._tau_factor) == (b.sf, b.tau, b._tau_factor)
     jc = JCModel(states=['a', 'b', 'c'], forest_stats=fs)
     assert [p[1][0] for p in jc.kernel_points([np.array([v]) for v in (1., 2., 3.)])] == [1., 2., 3.] and jc.sf == 3.
 
