@@ -442,6 +442,73 @@ int pml_compress_trim_info(pml_ctx* ctx, double* sizes_ms, double* removal_ms, d
                            int64_t* launches, int32_t* scan_tile);
 
 /*
+ * The timeline of the compressed map (pastml/tree.py: annotate_dates :51-65; pastml/visualisation/cytoscape_manager.py: the
+ * get_date of visualize :751-762 and the milestone loop of _forest2json_compressed :219-268) over a forest given as arrays.
+ * The ctx supplies the device and the stream; the uploaded forest is not used, and the scratch of the call is released before
+ * it returns.  One addition per date in the order of the reference, minima and integer work: the results do not depend on the
+ * launch geometry.  Node ids are breadth-first over the forest: level d is the run [level_offsets[d], level_offsets[d + 1]),
+ * level 0 the roots, and the parent of a node of level d lies in level d - 1.
+ *   level_offsets [n_levels + 1]  ascending from 0 to n_nodes
+ *   parent        [n_nodes]   -1 for the roots
+ *   dist          [n_nodes]   branch length above the node
+ *   given         [n_nodes]   the date given for the node, NaN for none
+ *   root_dates    [roots]     the date of a root without a given date
+ *   alive         [n_nodes]   non-zero: the node is in the full tree after the trimming
+ *   up            [n_nodes]   its nearest alive ancestor, -1 for a root; up[n] < n
+ *   config        [n_nodes]   the configuration the node is inside, -1 for none
+ *   is_tip, is_polytomy [n_nodes]   the original tips; the nodes that are counted in no configuration
+ *   top           [n_configs] the first node of every configuration
+ *   below_lo, below_hi [n_configs]  the tips below top are tip_order[below_lo : below_hi]
+ *   tip_order     [n_tips]    the tips in left-to-right leaf order
+ *   member_offsets[n_vertices + 1]  the configurations of vertex v are the run [member_offsets[v], member_offsets[v + 1])
+ *   timeline_type 0 SAMPLED, 1 NODES, 2 LTT
+ *   milestones    [n_milestones]  strictly ascending, at most 64
+ *   dates_only    non-zero: return after the dates (date_out is filled, nothing else is read or written but the first five
+ *                 node arrays), so that the caller can choose the milestones
+ * Results: date_out, get_date_out [n_nodes]; n_roots .. below_max [n_vertices][n_milestones] -- the configurations of the vertex
+ * whose top has get_date <= milestone i, and the minimum and maximum over them of the tips inside, the internal nodes inside and
+ * the tips below at that milestone (0 where there is none); first_milestone [n_vertices], n_milestones for never.
+ * pml_timeline_info: HIP-event times of the last call (dates, get_date, bins, role counts, tips below, vertices; without
+ * transfers; taken only while pml_profile_enable is on, else 0), the levels, the kernel launches, the launches of the date sweep
+ * (a level of more than fuse_width nodes is a launch of its own, a run of consecutive smaller levels is one launch of one
+ * workgroup) and fuse_width.
+ */
+typedef struct pml_timeline_in {
+    int32_t n_nodes, n_levels, n_configs, n_tips, n_vertices, timeline_type, n_milestones, dates_only;
+    const int32_t* level_offsets;
+    const int32_t* parent;
+    const double* dist;
+    const double* given;
+    const double* root_dates;
+    const uint8_t* alive;
+    const int32_t* up;
+    const int32_t* config;
+    const uint8_t* is_tip;
+    const uint8_t* is_polytomy;
+    const int32_t* top;
+    const int32_t* below_lo;
+    const int32_t* below_hi;
+    const int32_t* tip_order;
+    const int32_t* member_offsets;
+    const double* milestones;
+} pml_timeline_in;
+typedef struct pml_timeline_out {
+    double* date;
+    double* get_date;
+    int32_t* n_roots;
+    int32_t* tips_min;
+    int32_t* tips_max;
+    int32_t* internal_min;
+    int32_t* internal_max;
+    int32_t* below_min;
+    int32_t* below_max;
+    int32_t* first_milestone;
+} pml_timeline_out;
+int pml_timeline(pml_ctx* ctx, const pml_timeline_in* in, const pml_timeline_out* out);
+int pml_timeline_info(pml_ctx* ctx, double* stage_ms /* [6] */, int32_t* levels, int64_t* launches, int64_t* date_launches,
+                      int32_t* fuse_width);
+
+/*
  * n_repetitions scenarios of column col drawn forward from the roots (pastml/utilities/state_simulator.py:6-31):
  * roots ~ pi, child ~ row (parent state) of P_n(t).  Draws keyed by (seed, caller's node id, rep_offset + r):
  * results do not depend on launch geometry, chunking or the library's internal numbering.

@@ -2083,6 +2083,40 @@ int pml_compress_trim_info(pml_ctx* ctx, double* sizes_ms, double* removal_ms, d
     return PML_OK;
 }
 
+// The timeline of a compressed forest given as arrays (pml_launch_timeline.hip).  The context supplies the device and the stream;
+// the uploaded forest is not used.  The scratch of the call is freed before it returns.
+int pml_timeline(pml_ctx* ctx, const pml_timeline_in* in, const pml_timeline_out* out) {
+    if (!ctx) return fail(PML_ERR_INVALID, "ctx is NULL");
+    if (!in || !out) return fail(PML_ERR_INVALID, "NULL argument");
+    if (in->n_nodes <= 0) return fail(PML_ERR_INVALID, "n_nodes must be positive");
+    if (in->n_levels <= 0 || in->n_levels > in->n_nodes) return fail(PML_ERR_INVALID, "n_levels must lie in [1, n_nodes]");
+    if (!in->level_offsets || !in->parent || !in->dist || !in->given || !in->root_dates || !out->date)
+        return fail(PML_ERR_INVALID, "NULL array");
+    if (!in->dates_only) {
+        if (in->n_configs <= 0 || in->n_tips <= 0 || in->n_vertices <= 0)
+            return fail(PML_ERR_INVALID, "n_configs, n_tips and n_vertices must be positive");
+        if (in->n_milestones <= 0) return fail(PML_ERR_INVALID, "n_milestones must be positive");
+        if (in->n_milestones > 64) return fail(PML_ERR_UNSUPPORTED, "%d milestones; at most 64 are supported", in->n_milestones);
+        if (in->timeline_type < 0 || in->timeline_type > 2) return fail(PML_ERR_INVALID, "timeline_type must be 0 (SAMPLED), 1 (NODES) or 2 (LTT)");
+        if (!in->alive || !in->up || !in->config || !in->is_tip || !in->is_polytomy || !in->top || !in->below_lo || !in->below_hi ||
+            !in->tip_order || !in->member_offsets || !in->milestones || !out->get_date || !out->n_roots || !out->tips_min ||
+            !out->tips_max || !out->internal_min || !out->internal_max || !out->below_min || !out->below_max || !out->first_milestone)
+            return fail(PML_ERR_INVALID, "NULL array");
+    }
+    return launch_timeline(ctx, *in, *out);
+}
+
+int pml_timeline_info(pml_ctx* ctx, double* stage_ms, int32_t* levels, int64_t* launches, int64_t* date_launches, int32_t* fuse_width) {
+    if (!ctx) return fail(PML_ERR_INVALID, "ctx is NULL");
+    if (stage_ms)
+        for (int i = 0; i < 6; ++i) stage_ms[i] = ctx->tl_ms[i];
+    if (levels) *levels = ctx->tl_levels;
+    if (launches) *launches = ctx->tl_launches;
+    if (date_launches) *date_launches = ctx->tl_date_launches;
+    if (fuse_width) *fuse_width = PML_TL_FUSE_WIDTH;
+    return PML_OK;
+}
+
 int pml_select_states(pml_ctx* ctx, int method, int force_joint, const uint64_t* lh_mask, uint64_t* masks_out,
                       int32_t* n_states_out) {
     PML_TRY(require_model(ctx));

@@ -239,6 +239,11 @@ struct pml_ctx {
     double trim_ms[3] = {0, 0, 0};
     int trim_levels = 0, trim_rounds = 0;
     long long trim_launches = 0;
+    // timeline (pml_launch_timeline.hip), last pml_timeline: event times of the dates, get_date, the bins, the role counts, the
+    // tips below and the vertices (zero unless the context profiles), levels, kernel launches, those of the date sweep
+    double tl_ms[6] = {0, 0, 0, 0, 0, 0};
+    int tl_levels = 0;
+    long long tl_launches = 0, tl_date_launches = 0;
 
     PmlComm* comm = nullptr;   // RCCL communicator attached by pml_comm_init (survives tree uploads)
 };

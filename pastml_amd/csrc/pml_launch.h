@@ -211,6 +211,9 @@ PML_INTERNAL int launch_compress_trim(pml_ctx* ctx, int L, int n_cols, int W, co
                                       const int* w, const u64* sets, int tip_size_threshold, int n_trees,
                                       const unsigned char* trim_tree, double* tsize_out, unsigned char* keep_out,
                                       unsigned char* spliced_out, int* new_parent_out, unsigned char* moved_out, double* threshold_out);
+// ---- pml_launch_timeline.hip: dates, get_date and the per-milestone counts of the compressed map (pml_timeline); host arrays
+#define PML_TL_FUSE_WIDTH 512   // levels of at most this many nodes may share a launch of one workgroup (pml_timeline_info reports it)
+PML_INTERNAL int launch_timeline(pml_ctx* ctx, const pml_timeline_in& in, const pml_timeline_out& out);
 
 // ---- pml_launch_expected.hip: exact expected transition counts of the columns [cb, ce) (pml_expected_counts); d_alt [N] in the
 //      library's numbering or null, d_out [cols][k][k], d_same [cols][N][k] in the caller's numbering (zeroed) or null

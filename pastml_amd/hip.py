@@ -130,6 +130,8 @@ SIGNATURES = {
                           ctypes.POINTER(ctypes.c_uint8), _c_double_p],
     'pml_compress_trim_info': [_ctx_p, _c_double_p, _c_double_p, _c_double_p, _c_int32_p, _c_int32_p,
                                ctypes.POINTER(ctypes.c_int64), _c_int32_p],
+    'pml_timeline': [_ctx_p, ctypes.c_void_p, ctypes.c_void_p],
+    'pml_timeline_info': [_ctx_p, _c_double_p, _c_int32_p, ctypes.POINTER(ctypes.c_int64), ctypes.POINTER(ctypes.c_int64), _c_int32_p],
     'pml_download': [_ctx_p, ctypes.c_int, ctypes.c_int32, ctypes.c_void_p],
     'pml_comm_unique_id': [ctypes.POINTER(ctypes.c_ubyte)],
     'pml_comm_init': [_ctx_p, ctypes.c_int, ctypes.c_int, ctypes.POINTER(ctypes.c_ubyte)],
@@ -149,6 +151,25 @@ SIGNATURES = {
     'pml_profile_enable': [_ctx_p, ctypes.c_int],
     'pml_profile_read': [_ctx_p, ctypes.c_int, _c_double_p, ctypes.POINTER(ctypes.c_int64), ctypes.c_int],
 }
+TIMELINE_TYPES = {'SAMPLED': 0, 'NODES': 1, 'LTT': 2}   # timeline_type of pml_timeline
+TIMELINE_MAX_MILESTONES = 64
+
+
+class _TimelineIn(ctypes.Structure):
+    """pml_timeline_in (include/pastml_hip.h)."""
+    _fields_ = [(name, ctypes.c_int32) for name in ('n_nodes', 'n_levels', 'n_configs', 'n_tips', 'n_vertices', 'timeline_type',
+                                                    'n_milestones', 'dates_only')] + \
+               [(name, ctypes.c_void_p) for name in ('level_offsets', 'parent', 'dist', 'given', 'root_dates', 'alive', 'up', 'config',
+                                                     'is_tip', 'is_polytomy', 'top', 'below_lo', 'below_hi', 'tip_order',
+                                                     'member_offsets', 'milestones')]
+
+
+class _TimelineOut(ctypes.Structure):
+    """pml_timeline_out (include/pastml_hip.h)."""
+    _fields_ = [(name, ctypes.c_void_p) for name in ('date', 'get_date', 'n_roots', 'tips_min', 'tips_max', 'internal_min',
+                                                     'internal_max', 'below_min', 'below_max', 'first_milestone')]
+
+
 _RESTYPES = {'pml_last_error': ctypes.c_char_p, 'pml_build_digest': ctypes.c_char_p}
 
 _lib = None
@@ -998,6 +1019,84 @@ class Engine(BareContext):
                                                 ctypes.byref(rounds), ctypes.byref(launches), ctypes.byref(tile)))
         return dict(ms=(a.value, b.value, c.value), levels=levels.value, rounds=rounds.value, launches=launches.value,
                     scan_tile=tile.value)
+
+    def timeline(self, level_offsets, parent, dist, given, root_dates, alive=None, up=None, config=None, is_tip=None,
+                 is_polytomy=None, top=None, below_lo=None, below_hi=None, tip_order=None, member_offsets=None,
+                 timeline_type='SAMPLED', milestones=None):
+        """
+        Dates, get_date and the per-milestone counts of a compressed forest given as arrays (pml_timeline; the forest this
+        context holds is not used).  Node arrays [N] in breadth-first ids with ``level_offsets`` [levels + 1]; configuration
+        arrays [C]; ``tip_order`` [T]; ``member_offsets`` [L + 1]; ``milestones`` float64 [M], M <= 64, ascending.  With
+        ``milestones=None`` only the dates are computed (the other arrays may be left out) and ``date`` float64 [N] is returned;
+        else a dict of ``date``, ``get_date`` float64 [N], ``n_roots``, ``tips_min``, ``tips_max``, ``internal_min``,
+        ``internal_max``, ``below_min``, ``below_max`` int32 [L, M] and ``first_milestone`` int32 [L], as
+        ``visualisation.timeline.timeline_host`` gives them.
+        """
+        keep = []   # the arrays the structures point to
+
+        def held(array, dtype, shape, name):
+            array = _as(array, dtype)
+            if array.shape != shape:
+                raise ValueError('{} must be {}, got {}'.format(name, list(shape), array.shape))
+            keep.append(array)
+            return array.ctypes.data
+
+        level_offsets = _as(level_offsets, np.int32)
+        parent = _as(parent, np.int32)
+        if parent.ndim != 1 or level_offsets.ndim != 1 or len(parent) < 1 or len(level_offsets) < 2:
+            raise ValueError('parent must be [N] with N >= 1 and level_offsets [levels + 1]')
+        N, D = len(parent), len(level_offsets) - 1
+        n_roots = int(level_offsets[1])
+        a = _TimelineIn(n_nodes=N, n_levels=D, dates_only=1 if milestones is None else 0)
+        a.level_offsets = held(level_offsets, np.int32, (D + 1,), 'level_offsets')
+        a.parent = held(parent, np.int32, (N,), 'parent')
+        a.dist = held(dist, np.float64, (N,), 'dist')
+        a.given = held(given, np.float64, (N,), 'given')
+        a.root_dates = held(root_dates, np.float64, (n_roots,), 'root_dates')
+        date = np.empty(N, dtype=np.float64)
+        o = _TimelineOut(date=date.ctypes.data)
+        if milestones is None:
+            _check(self._lib.pml_timeline(self._ctx, ctypes.addressof(a), ctypes.addressof(o)))
+            return date
+        if timeline_type not in TIMELINE_TYPES:
+            raise ValueError('timeline_type must be one of {}, not {!r}'.format(', '.join(TIMELINE_TYPES), timeline_type))
+        milestones = _as(milestones, np.float64)
+        top = _as(top, np.int32)
+        tip_order = _as(tip_order, np.int32)
+        member_offsets = _as(member_offsets, np.int32)
+        if milestones.ndim != 1 or top.ndim != 1 or tip_order.ndim != 1 or member_offsets.ndim != 1 or len(member_offsets) < 2:
+            raise ValueError('milestones, top, tip_order and member_offsets must be one-dimensional')
+        M, C, T, L = len(milestones), len(top), len(tip_order), len(member_offsets) - 1
+        if M > TIMELINE_MAX_MILESTONES:
+            raise ValueError('{} milestones: the device path takes at most {}'.format(M, TIMELINE_MAX_MILESTONES))
+        a.n_configs, a.n_tips, a.n_vertices, a.n_milestones, a.timeline_type = C, T, L, M, TIMELINE_TYPES[timeline_type]
+        for name, array, dtype in (('alive', alive, np.uint8), ('up', up, np.int32), ('config', config, np.int32),
+                                   ('is_tip', is_tip, np.uint8), ('is_polytomy', is_polytomy, np.uint8)):
+            setattr(a, name, held(np.asarray(array).astype(dtype), dtype, (N,), name))
+        a.top = held(top, np.int32, (C,), 'top')
+        a.below_lo = held(below_lo, np.int32, (C,), 'below_lo')
+        a.below_hi = held(below_hi, np.int32, (C,), 'below_hi')
+        a.tip_order = held(tip_order, np.int32, (T,), 'tip_order')
+        a.member_offsets = held(member_offsets, np.int32, (L + 1,), 'member_offsets')
+        a.milestones = held(milestones, np.float64, (M,), 'milestones')
+        result = dict(date=date, get_date=np.empty(N, dtype=np.float64), first_milestone=np.empty(L, dtype=np.int32))
+        for name in ('n_roots', 'tips_min', 'tips_max', 'internal_min', 'internal_max', 'below_min', 'below_max'):
+            result[name] = np.empty((L, M), dtype=np.int32)
+        for name, array in result.items():
+            setattr(o, name, array.ctypes.data)
+        _check(self._lib.pml_timeline(self._ctx, ctypes.addressof(a), ctypes.addressof(o)))
+        return result
+
+    def timeline_info(self):
+        """dict of the last ``timeline`` call: ``ms`` (dates, get_date, bins, role counts, tips below, vertices -- HIP events, taken
+        after ``profile_enable()``, else 0), ``levels``, ``launches``, ``date_launches`` (those of the date sweep: a run of
+        consecutive levels of at most ``fuse_width`` nodes is one) and ``fuse_width``."""
+        ms = (ctypes.c_double * 6)()
+        levels, launches, date_launches, fuse = ctypes.c_int32(0), ctypes.c_int64(0), ctypes.c_int64(0), ctypes.c_int32(0)
+        _check(self._lib.pml_timeline_info(self._ctx, ms, ctypes.byref(levels), ctypes.byref(launches), ctypes.byref(date_launches),
+                                           ctypes.byref(fuse)))
+        return dict(ms=tuple(ms), levels=levels.value, launches=launches.value, date_launches=date_launches.value,
+                    fuse_width=fuse.value)
 
     def download(self, what, col=0):
         N, k = self.n_nodes, self.k

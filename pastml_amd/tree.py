@@ -8,8 +8,9 @@ Two representations live here:
   ``is_root``, ``is_leaf``, ``add_feature(s)``, ``del_feature``, ``features``, leaf iteration).  ete3 itself is not
   installed on our boxes, so callers build trees with :func:`read_tree` / :func:`read_forest`
   (reference: ``pastml/tree.py:176-222``).  Newick reading/naming and the polytomy resolution of ``acr()``
-  (:func:`resolve_trees` / :func:`unresolve_trees`, ``pastml/tree.py:344-492``) are provided; dates and nexus
-  (``pastml/tree.py`` rest) are out of scope.
+  (:func:`resolve_trees` / :func:`unresolve_trees`, ``pastml/tree.py:344-492``) are provided, and the dates of the nodes
+  as an array (:func:`annotate_dates`, ``pastml/tree.py:51-65``; :func:`parse_date`); dates read from newick comments and
+  nexus (``pastml/tree.py`` rest) are out of scope.
 
 * :class:`FlatForest` -- the structure-of-arrays form that is uploaded to the GPU: nodes are renumbered in
   breadth-first (level) order over the whole forest so that (i) the children of a node are contiguous,
@@ -1097,3 +1098,81 @@ def unresolve_trees(column2states, forest):
     elif num_polytomies - num_removed_nodes + num_new_nodes:
         logging.getLogger('pastml').debug('All the polytomy resolutions are consistent with model parameters.')
     return num_removed_nodes
+
+
+# =====================================================================================================================
+# Dates
+# =====================================================================================================================
+
+def datetime2numeric(d):
+    """A datetime as a number of years (pastml/__init__.py:18-31): 2016-12-31 -> 2016.9972677595629, 2016-1-1 -> 2016.0."""
+    from datetime import datetime
+    first_jan_this_year = datetime(year=d.year, month=1, day=1)
+    first_jan_next_year = datetime(year=d.year + 1, month=1, day=1)
+    return d.year + (d - first_jan_this_year) / (first_jan_next_year - first_jan_this_year)
+
+
+def numeric2datetime(d):
+    """A number of years as a datetime (pastml/__init__.py:34-53): 2016.9972677595629 -> 2016-12-31."""
+    from datetime import datetime
+    year = int(d)
+    days_in_this_year = datetime(year=year + 1, month=1, day=1) - datetime(year=year, month=1, day=1)
+    day_of_this_year = int(round(days_in_this_year.days * (d % 1), 6)) + 1
+    for m in range(1, 13):
+        days_in_m = (datetime(year=year if m < 12 else (year + 1), month=m % 12 + 1, day=1) - datetime(year=year, month=m, day=1)).days
+        if days_in_m >= day_of_this_year:
+            return datetime(year=year, month=m, day=day_of_this_year)
+        day_of_this_year -= days_in_m
+
+
+def parse_date(d):
+    """A root date as a number (pastml/tree.py:32-39): a float as it is, else a calendar date (pandas reads it where it is
+    installed, else ``datetime.fromisoformat``) through :func:`datetime2numeric`."""
+    try:
+        return float(d)
+    except ValueError:
+        try:
+            try:
+                import pandas as pd
+                when = pd.to_datetime(d)
+            except ImportError:
+                from datetime import datetime
+                when = datetime.fromisoformat(str(d).strip())
+            return datetime2numeric(when)
+        except ValueError:
+            raise ValueError('Could not infer the date format for root date "{}", please check it.'.format(d))
+
+
+def root_date_array(flat, root_dates=None):
+    """float64[R]: the date of every root that has no given date -- ``root_dates`` (one for all or one per tree), 0 for none."""
+    R = len(flat.roots)
+    if root_dates is None:
+        return np.zeros(R, dtype=np.float64)
+    values = [root_dates] if np.isscalar(root_dates) else list(root_dates)
+    if len(values) == 1:
+        values = values * R
+    if len(values) != R:
+        raise ValueError('{} root dates for {} trees'.format(len(values), R))
+    return np.array([float(v) if v else 0. for v in values], dtype=np.float64)   # (``root_date if root_date else 0``)
+
+
+def annotate_dates(flat, root_dates=None, given=None):
+    """
+    float64[N]: the date of every node of a :class:`FlatForest`, as the reference's ``annotate_dates`` sets them
+    (pastml/tree.py:51-65).  ``given``: float64[N], NaN where no date is given.  A root without a given date gets its
+    ``root_dates`` entry, or 0; any other node its given date, else ``date[parent] + dist``: one addition per node, level by level
+    from the roots, so the dates carry the bits of the reference's sequential ``parent_date + node.dist``.
+    """
+    N = flat.n_nodes
+    given = np.full(N, np.nan) if given is None else np.asarray(given, dtype=np.float64)
+    if given.shape != (N,):
+        raise ValueError('given must be [{}], got {}'.format(N, given.shape))
+    roots = root_date_array(flat, root_dates)
+    date = np.empty(N, dtype=np.float64)
+    offsets = flat.td_offsets
+    R = int(offsets[1])
+    date[:R] = np.where(np.isnan(given[:R]), roots, given[:R])
+    for d in range(1, len(offsets) - 1):
+        a, b = int(offsets[d]), int(offsets[d + 1])
+        date[a:b] = np.where(np.isnan(given[a:b]), date[flat.parent[a:b]] + flat.dist[a:b], given[a:b])
+    return date

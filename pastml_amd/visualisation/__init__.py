@@ -1,1 +1,2 @@
-"""What this project has of PastML's visualisation layer: the vertical and horizontal steps of the tree compressor and their Pajek network."""
+"""What this project has of PastML's visualisation layer: the tree compressor (vertical and horizontal steps, trimming) with its
+Pajek network, and the timeline of the compressed map."""

@@ -40,6 +40,9 @@ Focus / mixed mode (the rest of ``compress_tree``) is not implemented.
 
     python -m pastml_amd.visualisation.tree_compressor --tree NAMED_TREE --states COMBINED_TABLE --pajek OUT
            [--columns ...] [--pajek_timing VERTICAL|HORIZONTAL | --trim] [--tip_size_threshold N]
+           [--timeline OUT [--root_date D [D ...]] [--timeline_type SAMPLED|NODES|LTT]]
+
+The timeline of the map -- dates, milestones and what every vertex holds at each of them -- is ``visualisation/timeline.py``.
 """
 import logging
 
@@ -885,7 +888,18 @@ def main(argv=None):
     parser.add_argument('--trim', action='store_true', help='the map after trimming (with --pajek_timing left at its default)')
     parser.add_argument('--tip_size_threshold', type=int, default=REASONABLE_NUMBER_OF_TIPS)
     parser.add_argument('--host', action='store_true', help='numpy only, no GPU')
+    parser.add_argument('--timeline', default=None, metavar='OUT',
+                        help='also write the timeline of the map as a table (pastml_amd.visualisation.timeline)')
+    parser.add_argument('--root_date', nargs='+', default=None, metavar='D',
+                        help='date of the root(s), for --timeline: one for all trees or one per tree; a number or a calendar date')
+    parser.add_argument('--timeline_type', default='SAMPLED', choices=['SAMPLED', 'NODES', 'LTT'])
     args = parser.parse_args(argv)
+    if args.timeline:
+        from pastml_amd import sharding
+        world = sharding.rank_world()[1]
+        if world > 1:
+            raise NotImplementedError('--timeline is not supported under a multi-process launch ({} ranks): run it in a single '
+                                      'process'.format(world))
     roots = read_forest(args.tree)
     df = pd.read_csv(args.states, sep='\t', index_col=0, header=0, dtype=str, keep_default_na=False)
     df.index = df.index.map(str)
@@ -905,6 +919,12 @@ def main(argv=None):
         result = compress_forest(roots, columns, column2states, timing=args.pajek_timing,
                                  tip_size_threshold=args.tip_size_threshold, device=False if args.host else None)
     save_to_pajek(result, columns, args.pajek)
+    if args.timeline:
+        from pastml_amd.tree import parse_date
+        from pastml_amd.visualisation.timeline import timeline, write_timeline
+        root_dates = [parse_date(d) for d in args.root_date] if args.root_date else None
+        write_timeline(timeline(result, root_dates=root_dates, timeline_type=args.timeline_type, device=False if args.host else None),
+                       result, args.timeline)
     return 0
 
 
