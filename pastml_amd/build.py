@@ -20,7 +20,7 @@ SOURCES = ['pml_launch_f81_level.hip', 'pml_launch_f81_wide.hip', 'pml_launch_f8
            'pml_schedule.cpp', 'pml_pij_window.cpp', 'pml_api.hip']
 HEADERS = ['pml_device.h', 'pml_kernels_f81.h', 'pml_kernels_misc.h', 'pml_model.h', 'pml_kernels_matrix.h', 'pml_kernels_pij.h', 'pml_kernels_pij_wide.h',
            'pml_kernels_counts.h', 'pml_philox.h', 'pml_kernels_simulate.h', 'pml_kernels_scenarios.h', 'pml_kernels_parsimony.h', 'pml_kernels_expected.h', 'pml_kernels_compress.h', 'pml_kernels_compress_horizontal.h', 'pml_kernels_compress_trim.h', 'pml_kernels_timeline.h',
-           'pml_kernels_eigen_mfma.h', 'pml_kernels_eigen_gemm.h', 'pml_kernels_eigen_joint.h', 'pml_comm.h', 'pml_schedule.h', 'pml_pij_window.h', 'pml_host.h', 'pml_call_scope.h',
+           'pml_kernels_eigen_mfma.h', 'pml_kernels_eigen_gemm.h', 'pml_kernels_eigen_joint.h', 'pml_comm.h', 'pml_schedule.h', 'pml_pij_window.h', 'pml_host.h', 'pml_call_scope.h', 'pml_results.h',
            'pml_launch.h', 'pml_launch_f81_level.h',
            os.path.join('..', '..', 'include', 'pastml_hip.h')]
 CFLAGS = ['-O3', '--offload-arch=gfx950', '-std=c++17', '-ffp-contract=on', '-fPIC']

@@ -186,9 +186,7 @@ int pml_ctx_set_option(pml_ctx* ctx, int option, int value) {
     if (option == PML_OPT_EIGEN_FUSED) {
         if ((value != 0) != ctx->eig_fused_opt) {
             drop_sweep_graphs(ctx);
-            ctx->prep_dirty = true;
-            ctx->bu_mode = -1;
-            ctx->td_valid = ctx->js_valid = false;
+            ctx->results.inputs_changed();
         }
         ctx->eig_fused_opt = value != 0;
         return PML_OK;
@@ -196,9 +194,7 @@ int pml_ctx_set_option(pml_ctx* ctx, int option, int value) {
     if (option == PML_OPT_EIGEN_JOINT_VALU) {
         if ((value != 0) != ctx->eigj_valu_opt) {
             drop_graph(ctx->bu_graph[0]);
-            ctx->prep_dirty = true;
-            ctx->bu_mode = -1;
-            ctx->td_valid = ctx->js_valid = false;
+            ctx->results.inputs_changed();
         }
         ctx->eigj_valu_opt = value != 0;
         return PML_OK;
@@ -227,9 +223,7 @@ int pml_ctx_set_tunable(pml_ctx* ctx, const char* name, int64_t value, int is_se
         // a captured launch sequence was made under the old setting
         drop_sweep_graphs(ctx);
         drop_graph(ctx->bt_graph);
-        ctx->prep_dirty = true;
-        ctx->bu_mode = -1;
-        ctx->td_valid = ctx->js_valid = false;
+        ctx->results.inputs_changed();
         return PML_OK;
     }
     return fail(PML_ERR_INVALID, "unknown tunable %s", name);
@@ -585,9 +579,7 @@ int pml_chars_alloc(pml_ctx* ctx, int32_t n_cols, int32_t k) {
     ctx->eig_sym.assign(n_cols, 0);
     ctx->eig_sym_all = false;
     ctx->tips_observed.assign(n_cols, 0);
-    ctx->prep_dirty = true;
-    ctx->bu_mode = -1;
-    ctx->td_valid = ctx->js_valid = false;
+    ctx->results.inputs_changed();
     // Thin ends of a large forest.  A level is thin while a launch of its own is mostly latency: up to 4 096 units, and up to
     // THIN_BYTES (20 MB) of state vectors over all columns -- beyond, the level kernels stream it faster than workgroups
     // that walk subtrees.  Measured (profiles/r05u_thin_ends.txt, THIN_UNITS sweeps): k = 4 x 32 columns 4 096 (16 384 loses
@@ -610,12 +602,15 @@ static int check_cols(pml_ctx* ctx, int cb, int ce) {
     return PML_OK;
 }
 
-static int materialize_tip_posteriors(pml_ctx* ctx);
-
-static void invalidate(pml_ctx* ctx) {
-    ctx->prep_dirty = true;
-    ctx->bu_mode = -1;
-    ctx->td_valid = ctx->js_valid = false;
+// PML_OPT_IMPLICIT_TIP_POSTERIORS: whoever reads the posterior table gets the rows the sweep left implicit first
+static int materialize_tip_posteriors(pml_ctx* ctx) {
+    if (!ctx->results.tip_posteriors_missing() || !ctx->d_post || ctx->n_tips == 0) return PML_OK;
+    dim3 grid(grid_for(ctx, ctx->n_tips, PML_BLOCK, ctx->C), ctx->C);
+    hipLaunchKernelGGL(tip_posteriors_kernel, grid, dim3(PML_BLOCK), 0, ctx->stream, cols_of(ctx), state_of(ctx), ctx->N,
+                       ctx->d_tips, ctx->n_tips);
+    HIP_TRY(hipGetLastError());
+    ctx->results.tip_posteriors_written();
+    return PML_OK;
 }
 
 // what is known about the tips of columns [col_begin, col_end); the captured launch sequence of the joint sweep depends
@@ -653,7 +648,7 @@ int pml_masks_upload(pml_ctx* ctx, int32_t col_begin, int32_t col_end, const uin
     PML_TRY(upload(ctx, ctx->d_masks + col_begin * per_col, src, per_col * (col_end - col_begin)));
     HIP_TRY(hipStreamSynchronize(ctx->stream));
     note_tips_observed(ctx, col_begin, col_end, false);
-    invalidate(ctx);
+    ctx->results.inputs_changed();
     return PML_OK;
 }
 
@@ -694,7 +689,7 @@ int pml_masks_from_tip_states(pml_ctx* ctx, int32_t col_begin, int32_t col_end, 
         for (int j = 0; all && j < n_tips; ++j) all = states[(size_t)(col - col_begin) * n_tips + j] >= 0;
         note_tips_observed(ctx, col, col + 1, all);
     }
-    invalidate(ctx);
+    ctx->results.inputs_changed();
     return PML_OK;
 }
 
@@ -727,7 +722,7 @@ int pml_masks_initial_upload(pml_ctx* ctx, int32_t col_begin, int32_t col_end, c
     PML_TRY(upload(ctx, ctx->d_masks_init + col_begin * per_col, src, per_col * (col_end - col_begin)));
     HIP_TRY(hipStreamSynchronize(ctx->stream));
     ctx->has_init = true;
-    ctx->bu_mode = -1;
+    ctx->results.initial_masks_changed();
     return PML_OK;
 }
 
@@ -759,7 +754,7 @@ static int set_common(pml_ctx* ctx, int kind, int cb, int ce, const double* pi, 
     memcpy(h + C * ks + C + cb, tau, nc * sizeof(double));
     memcpy(h + C * ks + 2 * C + cb, tauf, nc * sizeof(double));
     for (int i = cb; i < ce; ++i) ctx->model_set[i] = 1;
-    invalidate(ctx);
+    ctx->results.inputs_changed();
     return PML_OK;
 }
 
@@ -941,7 +936,7 @@ static int window_set(pml_ctx* ctx, long long branches) {
     ctx->pending.spin = false;
     // a captured launch sequence was made for the other source of P(t)
     drop_sweep_graphs(ctx);
-    ctx->prep_dirty = true;
+    ctx->results.pij_source_changed();
     window_drop(ctx);
     if (branches == 0) return PML_OK;
     const long long B = std::min<long long>(branches, ctx->N);
@@ -1037,7 +1032,7 @@ static int run_prep(pml_ctx* ctx, bool force = false, bool bu_sweep = false) {
     // (callers outside a sweep: pml_pij_batch, pml_marginal_counts, downloads; a sweep's own copy went out, or into the
     // capture, before its first launch: enqueue_bottom_up)
     if (!bu_sweep) PML_TRY(params_push(ctx));
-    if (!ctx->prep_dirty && !force) return PML_OK;
+    if (!ctx->results.pij_stale() && !force) return PML_OK;
     const PmlTree t = tree_of(ctx);
     const PmlCols c = cols_of(ctx, bu_sweep);
     const PmlModel m = model_of(ctx);
@@ -1080,7 +1075,7 @@ static int run_prep(pml_ctx* ctx, bool force = false, bool bu_sweep = false) {
         HIP_TRY(hipGetLastError());
     }
     PML_TRY(prof_end(ctx, 2, 1));
-    ctx->prep_dirty = false;
+    ctx->results.pij_built();
     return PML_OK;
 }
 
@@ -1272,7 +1267,7 @@ static int run_plan(pml_ctx* ctx, const std::vector<PmlLaunch>& whole_plan, bool
             case OP_LEVELS: {
                 // (the fused lists of the whole forest are the launcher's default: it picks the sorted ones where they pay)
                 const bool whole = r.list == L_BU_FUSED || r.list == L_TD_FUSED;
-                const int do_prep = (bottom_up && r.arg && (ctx->prep_dirty || force_prep)) ? 1 : 0;
+                const int do_prep = (bottom_up && r.arg && (ctx->results.pij_stale() || force_prep)) ? 1 : 0;
                 PML_TRY(dispatch_small_f81(ctx, bottom_up, r.signal, do_prep, whole ? r.first : 0, r.count,
                                            whole ? nullptr : ctx->d_unit_lists[r.list], whole ? nullptr : ctx->d_list_offsets[r.list] + r.first,
                                            bottom_up ? 0 : r.arg));
@@ -1413,14 +1408,9 @@ static bool sweep_without_p(const pml_ctx* ctx, int is_marginal) {
 
 // what a bottom-up sweep leaves behind (a replayed pml_marginal_pass runs no submit_bottom_up)
 static void note_bottom_up(pml_ctx* ctx, int is_marginal, const PmlSweepOutcome& outcome) {
-    const bool f81_marginal = is_marginal && ctx->kind == PML_MODEL_F81;
-    ctx->js_valid = false;
-    ctx->bu_fused_joint = outcome.fused_joint;
-    if (!sweep_without_p(ctx, is_marginal) && ctx->pij_window == 0) ctx->prep_dirty = false;   // (else no batch ran)
-    ctx->bu_fused = (f81_marginal && ctx->n_cherries > 0) || ctx->bu_fused_joint;
-    // (a sweep of some of the columns says nothing about the others: where an earlier sweep of the level schedule left the
-    // children of their two-level units out of memory they still are -- rebuilding rows that are in memory is harmless)
-    ctx->bu_absorbed = (f81_marginal && super_sweeps(ctx)) || (ctx->active_partial && ctx->bu_absorbed);
+    const bool ran_batch = !sweep_without_p(ctx, is_marginal) && ctx->pij_window == 0;
+    ctx->results.bottom_up_submitted(is_marginal != 0, ctx->kind == PML_MODEL_F81, ctx->n_cherries > 0, super_sweeps(ctx), ran_batch,
+                                     ctx->active_partial, outcome.fused_joint);
 }
 
 // Waits for what was submitted last (a bottom-up sweep, a marginal pass).  Where its last launch raises the pinned word
@@ -1495,8 +1485,7 @@ static int submit_bottom_up(pml_ctx* ctx, int is_marginal, const uint8_t* active
         PML_TRY(dev_alloc(ctx, &ctx->d_tip_rest_count, (size_t)ctx->C));
     }
     if (!sweep_without_p(ctx, is_marginal) && ctx->pij_window == 0) PML_TRY(ensure_transition_storage(ctx));
-    ctx->bu_mode = -1;
-    ctx->td_valid = ctx->js_valid = false;
+    ctx->results.no_results();   // (from here on the buffers are being overwritten, whether every launch goes through or not)
     // mid-size forests: the level launches are latency-bound, replay them as one hipGraph
     const int n_launches = small_path ? 1 : (is_marginal && ctx->kind == PML_MODEL_F81 ? (int)ctx->forest.bu_offsets_f.size() - 1
                                                                                           : ctx->n_bu_levels);
@@ -1536,7 +1525,7 @@ static int collect_bottom_up(pml_ctx* ctx, int is_marginal, double* loglik_out, 
         if (err_parent) err_parent[c] = ep;
         if (err_child) err_child[c] = ec;
     }
-    if (status == PML_OK) ctx->bu_mode = is_marginal ? 1 : 0;
+    if (status == PML_OK) ctx->results.bottom_up_collected(is_marginal != 0);
     return status;
 }
 
@@ -1569,11 +1558,7 @@ int pml_bottom_up_collect(pml_ctx* ctx, int is_marginal, double* loglik_out, int
 
 // what a top-down sweep leaves behind (a replayed pml_marginal_pass runs no run_top_down)
 static void note_top_down(pml_ctx* ctx) {
-    ctx->td_valid = true;
-    ctx->td_vec_valid = ctx->kind != PML_MODEL_F81 || ctx->keep_td;
-    ctx->td_filled = false;
-    ctx->post_ever = true;
-    ctx->tip_post_missing = state_of(ctx).implicit_tips;
+    ctx->results.top_down_submitted(ctx->kind != PML_MODEL_F81 || ctx->keep_td, state_of(ctx).implicit_tips);
 }
 
 // the top-down launches (shared by pml_top_down_marginals and the lazy TD materialisation of pml_download), as
@@ -1607,24 +1592,13 @@ static int run_top_down(pml_ctx* ctx, bool wants_signal = false, PmlCapture capt
     return PML_OK;
 }
 
-// PML_OPT_IMPLICIT_TIP_POSTERIORS: whoever reads the posterior table gets the rows the sweep left implicit first
-static int materialize_tip_posteriors(pml_ctx* ctx) {
-    if (!ctx->tip_post_missing || !ctx->d_post || ctx->n_tips == 0) return PML_OK;
-    dim3 grid(grid_for(ctx, ctx->n_tips, PML_BLOCK, ctx->C), ctx->C);
-    hipLaunchKernelGGL(tip_posteriors_kernel, grid, dim3(PML_BLOCK), 0, ctx->stream, cols_of(ctx), state_of(ctx), ctx->N,
-                       ctx->d_tips, ctx->n_tips);
-    HIP_TRY(hipGetLastError());
-    ctx->tip_post_missing = false;
-    return PML_OK;
-}
-
 static int materialize_cherries(pml_ctx* ctx);
 
 // For inspection (pml_download of the TD buffers): every non-root node gets its top-down vector.  F81 family: the
 // sweep did not write its TD vectors, it is repeated with the stores switched on (same arithmetic); then the vectors of
 // the nodes no sweep stores (tips; fused cherries) are filled in level by level (td_fill_kernel).
 static int materialize_td(pml_ctx* ctx) {
-    if (!ctx->td_vec_valid) {
+    if (ctx->results.td_vectors_missing()) {
         // one sweep with the stores on; the option itself stays as the caller set it (a pooled ctx must not keep
         // paying for TD stores because somebody once looked at them)
         const bool was = ctx->keep_td;
@@ -1640,7 +1614,7 @@ static int materialize_td(pml_ctx* ctx) {
         PML_TRY(status);
         HIP_TRY(hipStreamSynchronize(ctx->stream));
     }
-    if (!ctx->td_filled) {
+    if (ctx->results.td_fill_missing()) {
         const bool f81 = ctx->kind == PML_MODEL_F81;
         if (f81) {
             PML_TRY(materialize_cherries(ctx));  // the cherries' bottom-up vectors
@@ -1659,7 +1633,7 @@ static int materialize_td(pml_ctx* ctx) {
             HIP_TRY(hipGetLastError());
         }
         HIP_TRY(hipStreamSynchronize(ctx->stream));
-        ctx->td_filled = true;
+        ctx->results.td_fill_written();
     }
     return PML_OK;
 }
@@ -1685,7 +1659,7 @@ static int fetch_marginals(pml_ctx* ctx, double* posterior_out, double* lh_sum_o
 
 int pml_top_down_marginals(pml_ctx* ctx, double* posterior_out, double* lh_sum_out, double* lh_sf_out) {
     PML_TRY(require_model(ctx));
-    if (ctx->bu_mode != 1) return fail(PML_ERR_INVALID, "pml_top_down_marginals needs a successful marginal pml_bottom_up first");
+    if (!ctx->results.has_marginal()) return fail(PML_ERR_INVALID, "pml_top_down_marginals needs a successful marginal pml_bottom_up first");
     PML_TRY(run_top_down(ctx));
     return fetch_marginals(ctx, posterior_out, lh_sum_out, lh_sf_out);
 }
@@ -1714,7 +1688,6 @@ int pml_marginal_pass(pml_ctx* ctx, double* loglik_out, int32_t* err_parent, int
         PML_TRY(run_captured(ctx, ctx->mp_graph, CAP_NONE, [&](PmlCapture, PmlSweepOutcome* o) -> int {
             PmlSweepOutcome td;
             PML_TRY(submit_bottom_up(ctx, 1, nullptr, false, CAP_PASS, o));
-            ctx->bu_mode = 1;
             PML_TRY(run_top_down(ctx, true, CAP_PASS, &td));
             o->then(td);
             return PML_OK;
@@ -1725,7 +1698,6 @@ int pml_marginal_pass(pml_ctx* ctx, double* loglik_out, int32_t* err_parent, int
     } else {
         PmlSweepOutcome td;
         PML_TRY(submit_bottom_up(ctx, 1, nullptr, false, CAP_NONE, &pass));  // (this call waits for the whole pass)
-        ctx->bu_mode = 1;  // provisional, for run_top_down's bookkeeping; collect_bottom_up has the last word
         PML_TRY(run_top_down(ctx, td_small, CAP_NONE, &td));  // (the single launch is enqueued afresh every time; level sweeps may replay a graph)
         pass.then(td);
     }
@@ -1752,10 +1724,9 @@ int pml_marginal_pass(pml_ctx* ctx, double* loglik_out, int32_t* err_parent, int
     } else {
         fetched = fetch_marginals(ctx, posterior_out, lh_sum_out, lh_sf_out);  // synchronises
     }
-    ctx->bu_mode = -1;
     const int status = collect_bottom_up(ctx, 1, loglik_out, err_parent, err_child);
     if (status != PML_OK) {
-        ctx->td_valid = false;  // a column without likelihood: its top-down results mean nothing
+        ctx->results.no_results();  // a column without likelihood: its top-down results mean nothing
         return status;
     }
     return fetched;
@@ -1775,8 +1746,7 @@ static int submit_joint_backtrace(pml_ctx* ctx) {
 }
 
 static int fetch_joint_states(pml_ctx* ctx, int32_t* joint_state_out) {
-    ctx->js_valid = true;
-    ctx->js_ever = true;
+    ctx->results.joint_states_fetched();
     PML_TRY(fetch_rows(ctx, ctx->d_js, 1, 1, (size_t)ctx->C, joint_state_out));
     HIP_TRY(hipStreamSynchronize(ctx->stream));
     return PML_OK;
@@ -1784,7 +1754,7 @@ static int fetch_joint_states(pml_ctx* ctx, int32_t* joint_state_out) {
 
 int pml_joint_backtrace(pml_ctx* ctx, int32_t* joint_state_out) {
     PML_TRY(require_model(ctx));
-    if (ctx->bu_mode != 0) return fail(PML_ERR_INVALID, "pml_joint_backtrace needs a successful joint pml_bottom_up first");
+    if (!ctx->results.has_joint()) return fail(PML_ERR_INVALID, "pml_joint_backtrace needs a successful joint pml_bottom_up first");
     PML_TRY(submit_joint_backtrace(ctx));
     return fetch_joint_states(ctx, joint_state_out);
 }
@@ -1799,10 +1769,24 @@ int pml_joint_pass(pml_ctx* ctx, double* loglik_out, int32_t* err_parent, int32_
     const int fetched = fetch_joint_states(ctx, joint_state_out);  // synchronises
     const int status = collect_bottom_up(ctx, 0, loglik_out, err_parent, err_child);
     if (status != PML_OK) {
-        ctx->js_valid = false;
+        ctx->results.no_results();
         return status;
     }
     return fetched;
+}
+
+// What pml_marginal_counts, pml_expected_counts and pml_sample_scenarios read: the results of a marginal bottom-up and a top-down
+// sweep (entry: who asks) ...
+static int need_marginal_pass(pml_ctx* ctx, const char* entry) {
+    if (!ctx->results.has_marginal() || !ctx->results.has_top_down())
+        return fail(PML_ERR_INVALID, "%s needs a marginal pml_bottom_up and pml_top_down_marginals first", entry);
+    return PML_OK;
+}
+// ... with every row of them in memory (once the entry knows that it holds this many states: the batch is allocated here)
+static int write_marginal_pass(pml_ctx* ctx) {
+    PML_TRY(materialize_cherries(ctx));  // the conditional probabilities need every bottom-up vector
+    PML_TRY(materialize_tip_posteriors(ctx));   // (a single-tip tree's root; the rows of the scenario sampler's fallback)
+    return consumer_prep(ctx);  // P(t) of every branch (the fused sweeps never materialise it) / exp(-mu t'); or the window
 }
 
 // altered (caller's ids, or null): see counts_level_kernel.  result_out: the k x k sums of the draws (not divided by
@@ -1812,12 +1796,9 @@ static int marginal_counts_impl(pml_ctx* ctx, int32_t col, int32_t n_repetitions
     PML_TRY(require_model(ctx));
     if (col < 0 || col >= ctx->C || !result_out) return fail(PML_ERR_INVALID, "bad column / output");
     if (n_repetitions <= 0) return fail(PML_ERR_INVALID, "n_repetitions must be positive");
-    if (ctx->bu_mode != 1 || !ctx->td_valid)
-        return fail(PML_ERR_INVALID, "pml_marginal_counts needs a marginal pml_bottom_up and pml_top_down_marginals first");
+    PML_TRY(need_marginal_pass(ctx, "pml_marginal_counts"));
     if (ctx->k > PML_COUNTS_MAX_K) return fail(PML_ERR_UNSUPPORTED, "k = %d: at most %d states", ctx->k, PML_COUNTS_MAX_K);
-    PML_TRY(materialize_cherries(ctx));  // the conditional probabilities need every bottom-up vector
-    PML_TRY(materialize_tip_posteriors(ctx));
-    PML_TRY(consumer_prep(ctx));  // P(t) of every branch (the fused eigen sweeps never materialise it) / exp(-mu t'); or the window
+    PML_TRY(write_marginal_pass(ctx));
     const size_t k = ctx->k, N = (size_t)ctx->N;
     std::vector<unsigned char> alt;
     std::vector<long long> h(k * k);
@@ -1895,14 +1876,11 @@ int pml_expected_counts(pml_ctx* ctx, int32_t col_begin, int32_t col_end, const 
     PML_TRY(require_model(ctx));
     PML_TRY(check_cols(ctx, col_begin, col_end));
     if (!counts_out) return fail(PML_ERR_INVALID, "counts_out is NULL");
-    if (ctx->bu_mode != 1 || !ctx->td_valid)
-        return fail(PML_ERR_INVALID, "pml_expected_counts needs a marginal pml_bottom_up and pml_top_down_marginals first");
+    PML_TRY(need_marginal_pass(ctx, "pml_expected_counts"));
     if (ctx->kind != PML_MODEL_F81 && ctx->k > 256)
         return fail(PML_ERR_UNSUPPORTED, "k = %d: the matrix models hold at most 256 states", ctx->k);
     PML_TRY(wait_pending(ctx, true));   // (a pass that ended in a spin on the completion word may have left the stream busy)
-    PML_TRY(materialize_cherries(ctx));  // the conditional probabilities need every bottom-up vector
-    PML_TRY(materialize_tip_posteriors(ctx));
-    PML_TRY(consumer_prep(ctx));  // P(t) of every branch (the fused sweeps never materialise it) / exp(-mu t'); or the window
+    PML_TRY(write_marginal_pass(ctx));
     const size_t k = ctx->k, N = (size_t)ctx->N, cols = (size_t)(col_end - col_begin);
     const bool with_same = altered != nullptr && same_out != nullptr;
     std::vector<unsigned char> alt;
@@ -1952,14 +1930,11 @@ int pml_sample_scenarios(pml_ctx* ctx, int32_t col, int32_t n_repetitions, int32
     if (col < 0 || col >= ctx->C || !states_out || !n_fallback_out) return fail(PML_ERR_INVALID, "bad column / output");
     if (n_repetitions <= 0) return fail(PML_ERR_INVALID, "n_repetitions must be positive");
     if (rep_offset < 0) return fail(PML_ERR_INVALID, "rep_offset must not be negative");
-    if (ctx->bu_mode != 1 || !ctx->td_valid)
-        return fail(PML_ERR_INVALID, "pml_sample_scenarios needs a marginal pml_bottom_up and pml_top_down_marginals first");
+    PML_TRY(need_marginal_pass(ctx, "pml_sample_scenarios"));
     const int most = ctx->kind == PML_MODEL_F81 ? 512 : 256;
     if (ctx->k > most) return fail(PML_ERR_UNSUPPORTED, "k = %d: pml_sample_scenarios holds at most %d states for this model", ctx->k, most);
     PML_TRY(wait_pending(ctx, true));   // (a pass that ended in a spin on the completion word may have left the stream busy)
-    PML_TRY(materialize_cherries(ctx));  // the conditional probabilities need every bottom-up vector
-    PML_TRY(materialize_tip_posteriors(ctx));   // (a single-tip tree's root; the rows of the fallback)
-    PML_TRY(consumer_prep(ctx));  // P(t) of every branch (the fused sweeps never materialise it) / exp(-mu t'); or the window
+    PML_TRY(write_marginal_pass(ctx));
     const size_t es = ctx->k > 256 ? 2 : 1;
     const size_t rs = ((size_t)n_repetitions + 3) / 4 * 4;
     unsigned long long fallen = 0;
@@ -2120,9 +2095,9 @@ int pml_timeline_info(pml_ctx* ctx, double* stage_ms, int32_t* levels, int64_t* 
 int pml_select_states(pml_ctx* ctx, int method, int force_joint, const uint64_t* lh_mask, uint64_t* masks_out,
                       int32_t* n_states_out) {
     PML_TRY(require_model(ctx));
-    if (!ctx->post_ever) return fail(PML_ERR_INVALID, "pml_select_states needs pml_top_down_marginals first");
+    if (!ctx->results.posteriors_exist()) return fail(PML_ERR_INVALID, "pml_select_states needs pml_top_down_marginals first");
     if (method != 0 && method != 1) return fail(PML_ERR_INVALID, "method must be 0 (MAP) or 1 (MPPA)");
-    if (method == 1 && force_joint && !ctx->js_ever)
+    if (method == 1 && force_joint && !ctx->results.joint_states_exist())
         return fail(PML_ERR_INVALID, "force_joint needs the joint states of a pml_joint_backtrace");
     PML_TRY(materialize_tip_posteriors(ctx));  // the selection reads every row, and rewrites the masks
     note_tips_observed(ctx, 0, ctx->C, false);  // (masks from now on: whatever was selected)
@@ -2151,8 +2126,7 @@ int pml_select_states(pml_ctx* ctx, int method, int force_joint, const uint64_t*
     PML_TRY(fetch_rows(ctx, ctx->d_nsel, 1, 1, (size_t)ctx->C, n_states_out));
     PML_TRY(mem.finish());
     // the columns' masks changed: sweeps must be redone, the posteriors themselves stay valid for inspection
-    ctx->prep_dirty = true;
-    ctx->bu_mode = -1;
+    ctx->results.masks_selected();
     return PML_OK;
 }
 
@@ -2181,7 +2155,7 @@ static int fetch_exponents(pml_ctx* ctx, const i64* src, int col, double* out) {
 
 // after a fused sweep the cherries' bottom-up vectors only ever existed in registers: compute them for inspection
 static int materialize_cherries(pml_ctx* ctx) {
-    if (ctx->bu_absorbed) {
+    if (ctx->results.children_missing()) {
         // the children of the two-level units: their own units (two cherries of two tips), from the tips
         PML_TRY(dispatch_sweep(ctx, SW_BU_MARG_FUSED_NOVEC, L_CHILD_UNITS, 0, ctx->sup.n_child_units));  // (nothing if 0)
         // ... and the children of the stacked units (two stored children each; in chunks of at most 65 536 units: the
@@ -2189,13 +2163,20 @@ static int materialize_cherries(pml_ctx* ctx) {
         for (int a = 0; a < 2 * ctx->sup.n_stack; a += 65536)
             PML_TRY(dispatch_sweep(ctx, SW_BU_MARG_FUSED, L_STACK_CHILDREN, a, std::min(65536, 2 * ctx->sup.n_stack - a)));
         HIP_TRY(hipStreamSynchronize(ctx->stream));
-        ctx->bu_absorbed = false;
+        ctx->results.children_written();
     }
-    if (!ctx->bu_fused) return PML_OK;
-    PML_TRY(dispatch_sweep(ctx, ctx->bu_fused_joint ? SW_BU_CHERRIES_JOINT : SW_BU_CHERRIES, L_CHERRIES, 0, ctx->n_cherries));
+    if (!ctx->results.cherries_missing()) return PML_OK;
+    PML_TRY(dispatch_sweep(ctx, ctx->results.cherries_joint() ? SW_BU_CHERRIES_JOINT : SW_BU_CHERRIES, L_CHERRIES, 0, ctx->n_cherries));
     HIP_TRY(hipStreamSynchronize(ctx->stream));
-    ctx->bu_fused = false;
+    ctx->results.cherries_written();
     return PML_OK;
+}
+
+static int need_top_down(pml_ctx* ctx) {
+    return ctx->results.has_top_down() ? PML_OK : fail(PML_ERR_INVALID, "no valid top-down sweep");
+}
+static int need_joint_states(pml_ctx* ctx) {
+    return ctx->results.has_joint_states() ? PML_OK : fail(PML_ERR_INVALID, "no valid joint back-trace");
 }
 
 static int download_internal(pml_ctx* ctx, int what, int32_t col, void* out);
@@ -2234,7 +2215,7 @@ static int download_internal(pml_ctx* ctx, int what, int32_t col, void* out) {
     const double nan = std::numeric_limits<double>::quiet_NaN();
     switch (what) {
         case PML_BUF_BU: {
-            if (ctx->bu_mode < 0) return fail(PML_ERR_INVALID, "no valid bottom-up sweep");
+            if (!ctx->results.has_bottom_up()) return fail(PML_ERR_INVALID, "no valid bottom-up sweep");
             double* o = (double*)out;
             PML_TRY(fetch_vectors(ctx, ctx->d_bu, col, o));
             std::vector<u64> m(N * ctx->W);
@@ -2245,33 +2226,33 @@ static int download_internal(pml_ctx* ctx, int what, int32_t col, void* out) {
             return PML_OK;
         }
         case PML_BUF_BU_SF: {
-            if (ctx->bu_mode < 0) return fail(PML_ERR_INVALID, "no valid bottom-up sweep");
+            if (!ctx->results.has_bottom_up()) return fail(PML_ERR_INVALID, "no valid bottom-up sweep");
             PML_TRY(fetch_exponents(ctx, ctx->d_be, col, (double*)out));
             for (size_t n = 0; n < N; ++n)
                 if (ctx->forest.n_children[n] == 0) ((double*)out)[n] = 0.0;
             return PML_OK;
         }
         case PML_BUF_TD:
-            if (!ctx->td_valid) return fail(PML_ERR_INVALID, "no valid top-down sweep");
+            PML_TRY(need_top_down(ctx));
             PML_TRY(materialize_td(ctx));
             return fetch_vectors(ctx, ctx->d_td, col, (double*)out);
         case PML_BUF_TD_SF:
-            if (!ctx->td_valid) return fail(PML_ERR_INVALID, "no valid top-down sweep");
+            PML_TRY(need_top_down(ctx));
             PML_TRY(materialize_td(ctx));
             return fetch_exponents(ctx, ctx->d_te, col, (double*)out);
         case PML_BUF_POSTERIOR:
-            if (!ctx->td_valid) return fail(PML_ERR_INVALID, "no valid top-down sweep");
+            PML_TRY(need_top_down(ctx));
             PML_TRY(materialize_tip_posteriors(ctx));
             return fetch_vectors(ctx, ctx->d_post, col, (double*)out);
         case PML_BUF_LH_SUM:
-            if (!ctx->td_valid) return fail(PML_ERR_INVALID, "no valid top-down sweep");
+            PML_TRY(need_top_down(ctx));
             HIP_TRY(hipMemcpy(out, ctx->d_lhsum + (size_t)col * N, N * sizeof(double), hipMemcpyDeviceToHost));
             return PML_OK;
         case PML_BUF_LH_SF:
-            if (!ctx->td_valid) return fail(PML_ERR_INVALID, "no valid top-down sweep");
+            PML_TRY(need_top_down(ctx));
             return fetch_exponents(ctx, ctx->d_lhe, col, (double*)out);
         case PML_BUF_JOINT_TABLE: {
-            if (ctx->bu_mode != 0) return fail(PML_ERR_INVALID, "no valid joint sweep");
+            if (!ctx->results.has_joint()) return fail(PML_ERR_INVALID, "no valid joint sweep");
             // the tables hold one byte per entry on the device (two beyond 256 states); the interface hands out int32
             const size_t width = ctx->k > 256 ? 2 : 1;
             std::vector<pml_jt> tmp(N * ctx->ks * width);
@@ -2283,7 +2264,7 @@ static int download_internal(pml_ctx* ctx, int what, int32_t col, void* out) {
             return PML_OK;
         }
         case PML_BUF_JOINT_STATE:
-            if (!ctx->js_valid) return fail(PML_ERR_INVALID, "no valid joint back-trace");
+            PML_TRY(need_joint_states(ctx));
             HIP_TRY(hipMemcpy(out, ctx->d_js + (size_t)col * N, N * sizeof(int), hipMemcpyDeviceToHost));
             return PML_OK;
         case PML_BUF_BRANCH_EXP:
@@ -2530,24 +2511,24 @@ int pml_download_strided(pml_ctx* ctx, int what, int32_t col, int32_t first, int
     size_t row_bytes = 0, src_row_bytes = 0;
     switch (what) {
         case PML_BUF_POSTERIOR:
-            if (!ctx->td_valid) return fail(PML_ERR_INVALID, "no valid top-down sweep");
+            PML_TRY(need_top_down(ctx));
             PML_TRY(materialize_tip_posteriors(ctx));
             src = ctx->d_post + ((size_t)col * N + first) * ctx->ks;
             row_bytes = ctx->k * sizeof(double);
             src_row_bytes = ctx->ks * sizeof(double);
             break;
         case PML_BUF_LH_SUM:
-            if (!ctx->td_valid) return fail(PML_ERR_INVALID, "no valid top-down sweep");
+            PML_TRY(need_top_down(ctx));
             src = ctx->d_lhsum + (size_t)col * N + first;
             row_bytes = src_row_bytes = sizeof(double);
             break;
         case PML_BUF_LH_SF:
-            if (!ctx->td_valid) return fail(PML_ERR_INVALID, "no valid top-down sweep");
+            PML_TRY(need_top_down(ctx));
             src = ctx->d_lhe + (size_t)col * N + first;
             row_bytes = src_row_bytes = sizeof(i64);
             break;
         case PML_BUF_JOINT_STATE:
-            if (!ctx->js_valid) return fail(PML_ERR_INVALID, "no valid joint back-trace");
+            PML_TRY(need_joint_states(ctx));
             src = ctx->d_js + (size_t)col * N + first;
             row_bytes = src_row_bytes = sizeof(int);
             break;

@@ -23,6 +23,7 @@
 #include "pml_model.h"   // PmlTree, PmlCols, PmlState, PmlUnit, PmlModel (and the F81 / miscellaneous kernels' headers below it)
 #include "pml_schedule.h" // PmlTune, the schedules' host side, PmlForest
 #include "pml_pij_window.h" // PmlWindowStep
+#include "pml_results.h"   // PmlResults: what the result buffers hold
 
 struct PmlComm;  // pml_comm.h (pml_api.hip only)
 
@@ -119,9 +120,6 @@ struct pml_ctx {
     std::vector<int> td_cherry_prefix; // over the fused top-down units: how many before it have a cherry as child 0 or 1
     std::vector<char> bu_level_vec;    // the same for the plain levels (joint sweep: every internal node is stored)
     int n_cherries = 0;
-    bool bu_fused = false;  // the last bottom-up sweep left the cherries unmaterialised
-    bool bu_absorbed = false;  // ... and the children of the two-level units
-    bool bu_fused_joint = false;  // ... and it was a joint sweep (note_bottom_up, from the sweep's outcome)
 
     // columns
     int C = 0, k = 0, ks = 0, W = 0, G = 0, R = 0;
@@ -147,7 +145,6 @@ struct pml_ctx {
     double *d_sf = nullptr, *d_tau = nullptr, *d_tauf = nullptr;
     std::vector<char> model_set;  // per column
     std::vector<char> tips_observed;  // per column: every tip has exactly one allowed state (known from pml_masks_from_tip_states)
-    bool prep_dirty = true;
     // P(t) in a window instead of the batch (pml_pij_window.h; eigen models beyond 32 states, pml_pij_window_set): B branches per
     // column; the branch lists of the bottom-up [0] and the top-down [1] level lists in run order, and the per-node slot tables
     long long pij_window = 0;            // B; 0 = the batch of the whole tree (d_P)
@@ -173,9 +170,7 @@ struct pml_ctx {
     pml_jt* d_J = nullptr;  // arg-max tables, one byte per entry (two beyond 256 states)
     int* d_js = nullptr;
     u64* d_err = nullptr;
-    int bu_mode = -1;  // -1 invalid, 1 marginal, 0 joint
-    bool js_ever = false;  // joint states of some earlier joint sweep are still in d_js
-    bool post_ever = false;  // posteriors of some earlier top-down sweep are still in d_post
+    PmlResults results;  // which of these hold a valid sweep's results, and which rows the sweeps left out of memory
     int* d_nsel = nullptr;
     // hipGraph replay of the launch sequence of a sweep (level kernels are launch-bound on mid-size trees)
     struct GraphSlot {
@@ -205,14 +200,10 @@ struct pml_ctx {
         u64 expect = 0;     // what *h_done shows when what was submitted last has finished
         bool spin = false;  // its end raises the word and nobody has waited for it yet: wait_pending spins
     } pending;
-    bool td_valid = false, js_valid = false;
     bool keep_td = false;      // PML_OPT_KEEP_TD (or a pml_download of the TD vectors asked for them)
-    bool td_vec_valid = false; // the TD vectors of the last top-down sweep are in d_td
-    bool td_filled = false;    // ... including those of the nodes the sweeps do not store (td_fill_kernel)
     bool eig_fused_opt = true; // PML_OPT_EIGEN_FUSED
     bool eigj_valu_opt = true; // PML_OPT_EIGEN_JOINT_VALU
     bool implicit_tips = false;    // PML_OPT_IMPLICIT_TIP_POSTERIORS
-    bool tip_post_missing = false; // the last top-down sweep left the observed tips' posteriors implicit
     const PmlUnit* d_unit_lists[L_COUNT] = {};   // the unit lists of the F81 kernels by PmlList (pml_tree_upload)
     const int* d_list_offsets[L_COUNT] = {};     // ... and the level tables of those that several-level launches walk
 
