@@ -331,6 +331,28 @@ int pml_expected_counts(pml_ctx* ctx, int32_t col_begin, int32_t col_end, const 
                         double* same_out);
 
 /*
+ * The exact gradient of ln L of the columns [col_begin, col_end) under the F81 family (F81, JC, EFT), from the vectors of the
+ * marginal pass (needs pml_bottom_up (marginal) and pml_top_down_marginals first, PML_ERR_INVALID otherwise) -- no sweep, no
+ * finite differences.  Per column, with mu = 1 / (1 - pi . pi), t'_n = (d_n + tau) tau_factor sf the transformed length of the
+ * branch above the non-root node n, e_n = exp(-mu t'_n), v_n the bottom-up vector of n (a tip: its 0/1 mask), s_n = pi . v_n,
+ * m_n[i] = (1 - e_n) s_n + e_n v_n[i] and q_p the marginal posterior of n's parent, for every non-root n with e_n < 1:
+ *   A_n = sum_i q_p[i] / m_n[i],  B_n = sum_i q_p[i] v_n[i] / m_n[i]          (terms with q_p[i] == 0 are zero)
+ *   h_n = -mu e_n (B_n - s_n A_n)  = d ln L / d t'_n,   T0 = sum_n h_n,   T1 = sum_n h_n t'_n
+ *   E[m] = sum_n (1 - e_n) A_n v_n[m] + sum over the roots r of v_r[m] / (pi . v_r)
+ *   d_rates_out[col][3] = { T1 / sf,  T0 tau_factor sf  (d / d tau at FIXED tau_factor),  T1 / tau_factor }
+ *   d_pi_out[col][k]    = E[m] + 2 mu pi_m T1        (every pi_m treated as free; the dependence of mu on pi is included)
+ *   n_flat_out[col]     = the number of branches whose e_n is exactly 1.0 as a double (t' = 0, or below 1e-16)
+ * Such a flat branch adds nothing to T1 and E (its factors t' and 1 - e vanish), but its share of T0 cannot be recovered from
+ * stored posteriors: the tau component of a column is valid only where its n_flat is 0.  The masks are those the marginal pass ran
+ * with.  PML_ERR_UNSUPPORTED: a context of HKY or eigen models.  PML_ERR_INVALID: no marginal pass, k < 2, or a column whose
+ * pi . pi >= 1 (mu infinite).  No atomics: the nodes are walked in the caller's numbering in pieces whose size depends on k only,
+ * the partials are summed in piece order, and the result's bits do not depend on launch geometry, on the schedule switches, on the
+ * library's numbering or on which other columns are in the call.  The results of the marginal pass stay as they are.
+ */
+int pml_loglik_gradient(pml_ctx* ctx, int32_t col_begin, int32_t col_end, double* d_rates_out, double* d_pi_out,
+                        int32_t* n_flat_out);
+
+/*
  * Maximum parsimony of n_cols characters of k states (k <= 512) on the uploaded forest: the bottom-up pass
  * (pastml/parsimony.py:92-122) and, per bit of methods, ACCTRAN (:125-158), DOWNPASS (:161-210) and DELTRAN (:213-242, on
  * the DOWNPASS sets), each with the number of state changes its sets need (:360-380, summed over the trees) and the number

@@ -201,6 +201,7 @@ class CharacterBatch(object):
         self._uploaded = None
         self._uploaded_models = None
         self.n_sweeps = 0
+        self.resident_loglik = None   # ln L [m] of the last marginal_pass_resident
         self.pij_window = 0   # branches of the P(t) window of this batch's contexts (run_tasks; 0: the whole-tree batch)
 
     # ------------------------------------------------------------------------------------------------ resources
@@ -378,7 +379,8 @@ class CharacterBatch(object):
         """
         What marginal_counts / expected_counts need before they count: zero-branch alteration of the characters with
         tau == 0 (kept: alter=False semantics of ml.py:700-703 afterwards), then the marginal pass with every result left on the
-        device (nothing is copied out).  Returns the altered (character, node) flags, bool [m, N].
+        device (nothing is copied out but ln L [m], kept in ``resident_loglik``).  Returns the altered (character, node) flags,
+        bool [m, N].
         """
         rows = np.array([0 == mdl.tau for mdl in models], dtype=bool)
         altered = self.alter(rows) if rows.any() else np.zeros((self.m, self.N), dtype=bool)
@@ -388,11 +390,26 @@ class CharacterBatch(object):
         eng.set_initial_masks(None)
         self.n_sweeps += self.m
         try:
-            eng.marginal_pass(posterior=False, lh=False)
+            self.resident_loglik = np.array(eng.marginal_pass(posterior=False, lh=False)[0], dtype=np.float64)
         except hip.ZeroLikelihoodError as e:
             first = int(np.flatnonzero(e.err_child >= 0)[0])
             raise LikelihoodError(first, int(e.err_parent[first]), int(e.err_child[first]))
         return altered
+
+    def loglik_gradient(self, models):
+        """
+        Exact gradient of ln L of every character under its F81-family model (``pml_loglik_gradient``): the marginal pass with
+        the masks altered for the characters with tau == 0 -- what ``bottom_up(models, is_marginal=True, alter=True)`` evaluates,
+        the optimiser's objective --, the gradient pass over what it left on the device, then the masks restored as
+        ``bottom_up`` restores them.  Returns (ln L [m], d_rates [m, 3], d_pi [m, k], n_flat [m]) as Engine.loglik_gradient
+        describes them.
+        """
+        altered = self.marginal_pass_resident(models)
+        try:
+            d_rates, d_pi, n_flat = self.engine.loglik_gradient()
+        finally:
+            self.unalter(altered)
+        return self.resident_loglik, d_rates, d_pi, n_flat
 
     def joint_states(self):
         """Joint state of every node after a joint sweep (ml.py:598-622): int64 [m, N]."""

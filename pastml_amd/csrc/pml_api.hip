@@ -1899,6 +1899,38 @@ int pml_expected_counts(pml_ctx* ctx, int32_t col_begin, int32_t col_end, const 
     return mem.finish();
 }
 
+// Exact gradient of ln L of the columns [col_begin, col_end) under the F81 family (pml_launch_gradient.hip): one streaming pass
+// over the vectors the marginal pass left on the device, no sweep.  The masks are those the pass ran with.
+int pml_loglik_gradient(pml_ctx* ctx, int32_t col_begin, int32_t col_end, double* d_rates_out, double* d_pi_out,
+                        int32_t* n_flat_out) {
+    PML_TRY(require_model(ctx));
+    PML_TRY(check_cols(ctx, col_begin, col_end));
+    if (!d_rates_out || !d_pi_out || !n_flat_out) return fail(PML_ERR_INVALID, "pml_loglik_gradient: an output array is NULL");
+    if (ctx->kind != PML_MODEL_F81)
+        return fail(PML_ERR_UNSUPPORTED, "pml_loglik_gradient is for the F81 family (F81, JC, EFT): this context's model kind is %s",
+                    ctx->kind == PML_MODEL_HKY ? "HKY" : "eigen");
+    PML_TRY(need_marginal_pass(ctx, "pml_loglik_gradient"));
+    if (ctx->k < 2) return fail(PML_ERR_INVALID, "pml_loglik_gradient: k = %d, a character of one state has no gradient", ctx->k);
+    const double* mu = ctx->h_params + (size_t)ctx->C * (ctx->ks + 3);
+    for (int c = col_begin; c < col_end; ++c)
+        if (!std::isfinite(mu[c]) || !(mu[c] > 0.0))
+            return fail(PML_ERR_INVALID, "pml_loglik_gradient: column %d has pi . pi >= 1 (mu is not finite)", c);
+    PML_TRY(wait_pending(ctx, true));   // (a pass that ended in a spin on the completion word may have left the stream busy)
+    PML_TRY(write_marginal_pass(ctx));
+    const size_t k = ctx->k, cols = (size_t)(col_end - col_begin);
+    CallScope mem(ctx->stream, false);
+    double *d_rates, *d_pi;
+    int* d_flat;
+    PML_TRY(mem.get(&d_rates, cols * 3));
+    PML_TRY(mem.get(&d_pi, cols * k));
+    PML_TRY(mem.get(&d_flat, cols));
+    PML_TRY(launch_gradient(ctx, mem, col_begin, col_end, d_rates, d_pi, d_flat));
+    HIP_TRY(hipMemcpyAsync(d_rates_out, d_rates, cols * 3 * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(hipMemcpyAsync(d_pi_out, d_pi, cols * k * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(hipMemcpyAsync(n_flat_out, d_flat, cols * sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
+    return mem.finish();
+}
+
 // n_repetitions scenarios of column col drawn forward from the roots (pml_launch_simulate.hip).  Needs a model, no sweep: the
 // per-branch e = exp(-mu t') (F81 family) or P(t) is prepared here.  The states are written in the caller's numbering on the
 // device, in rows padded to a multiple of 4 repetitions, and copied out without the padding.

@@ -218,6 +218,9 @@ PML_INTERNAL int launch_timeline(pml_ctx* ctx, const pml_timeline_in& in, const 
 // ---- pml_launch_expected.hip: exact expected transition counts of the columns [cb, ce) (pml_expected_counts); d_alt [N] in the
 //      library's numbering or null, d_out [cols][k][k], d_same [cols][N][k] in the caller's numbering (zeroed) or null
 PML_INTERNAL int launch_expected(pml_ctx* ctx, int cb, int ce, const unsigned char* d_alt, double* d_out, double* d_same);
+// ---- pml_launch_gradient.hip: exact gradient of ln L of the F81 family for the columns [cb, ce) (pml_loglik_gradient); device
+//      arrays d_rates [cols][3], d_pi [cols][k], d_flat [cols]; queued only: the partials go into the caller's scope, which waits
+PML_INTERNAL int launch_gradient(pml_ctx* ctx, CallScope& mem, int cb, int ce, double* d_rates, double* d_pi, int* d_flat);
 
 // More than 64 KB of dynamic LDS must be asked for: once per kernel, device and size (the largest asked for so far is what is
 // set) -- not per launch: the call is not free and should not sit inside a stream capture.  (A template: one table per kernel

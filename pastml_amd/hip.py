@@ -110,6 +110,7 @@ SIGNATURES = {
     'pml_marginal_counts_altered': [_ctx_p, ctypes.c_int32, ctypes.c_int32, ctypes.c_uint64, ctypes.POINTER(ctypes.c_uint8),
                                     _c_double_p, _c_int32_p, _c_int32_p],
     'pml_expected_counts': [_ctx_p, ctypes.c_int32, ctypes.c_int32, ctypes.POINTER(ctypes.c_uint8), _c_double_p, _c_double_p],
+    'pml_loglik_gradient': [_ctx_p, ctypes.c_int32, ctypes.c_int32, _c_double_p, _c_double_p, _c_int32_p],
     'pml_simulate_states': [_ctx_p, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_uint64, ctypes.c_void_p],
     'pml_sample_scenarios': [_ctx_p, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_uint64, ctypes.c_void_p,
                              ctypes.POINTER(ctypes.c_int64)],
@@ -835,6 +836,24 @@ class Engine(BareContext):
         _check(self._lib.pml_expected_counts(self._ctx, col_begin, col_end, _ptr(alt, ctypes.c_uint8),
                                              _ptr(out, ctypes.c_double), _ptr(same, ctypes.c_double)))
         return out, same
+
+    def loglik_gradient(self, col_begin=0, col_end=None):
+        """
+        Exact gradient of ln L of the columns [col_begin, col_end) after a marginal pass, F81 family only (pml_loglik_gradient:
+        one streaming pass over the vectors of the pass, no finite differences).  Returns (d_rates [cols, 3] -- d/d sf, d/d tau
+        at fixed tau_factor, d/d tau_factor --, d_pi [cols, k] with every frequency treated as free, n_flat [cols] int32: the
+        branches whose exp(-mu t') is exactly 1.0; the tau component of a column is valid only where its n_flat is 0).
+        """
+        col_end = self.n_cols if col_end is None else col_end
+        if not 0 <= col_begin < col_end <= self.n_cols:
+            raise ValueError('bad column range')
+        cols = col_end - col_begin
+        d_rates = np.empty((cols, 3), dtype=np.float64)
+        d_pi = np.empty((cols, self.k), dtype=np.float64)
+        n_flat = np.empty(cols, dtype=np.int32)
+        _check(self._lib.pml_loglik_gradient(self._ctx, col_begin, col_end, _ptr(d_rates, ctypes.c_double),
+                                             _ptr(d_pi, ctypes.c_double), _ptr(n_flat, ctypes.c_int32)))
+        return d_rates, d_pi, n_flat
 
     def simulate_states(self, n_repetitions, seed, col=0, rep_offset=0):
         """

@@ -737,3 +737,72 @@ def expected_counts(forest, characters, models):
                     results[members[c + j]] = counts
                 c = e
     return results[0] if single else results
+
+
+# =====================================================================================================================
+# loglikelihood_gradient
+# =====================================================================================================================
+
+def loglikelihood_gradient(forest, characters, models):
+    """
+    Exact gradient of the marginal log-likelihood ln L of one character or a list of them under F81-family models (F81, JC,
+    EFT): what ``get_bottom_up_loglikelihood(..., is_marginal=True, alter=True)`` evaluates, differentiated in closed form --
+    no finite differences.  The likelihood is multilinear in the per-branch matrices, so the gradient is one streaming pass
+    (``pml_loglik_gradient``, HIP; include/pastml_hip.h has the sums) over the vectors a marginal pass leaves on the device.
+
+    Characters are grouped by their number of states; a group is one batch on the device: one marginal pass (masks altered
+    where tau == 0, restored afterwards) and one gradient pass over its columns.
+
+    :param characters: a character (feature name) or a list of them; models: a model or a list, one per character
+    :return: per character a dict with ``log_likelihood``; the natural derivatives ``sf``, ``tau`` (total: through the branch
+        transform and its tau factor) and ``frequencies`` ([k], every frequency treated as free, the dependence of mu on them
+        included); ``parameters``: the gradient with respect to ``model.get_optimised_parameters()``, in its order (None for a
+        model with frequency smoothing, whose chain rule is not implemented), with ``parameter_names``; and
+        ``n_zero_length_branches``: the branches with exp(-mu t') == 1.  Where that count is not zero, ``tau`` (and its entry
+        of ``parameters``) is NaN: such a branch leaves no trace of its share in the stored posteriors.
+    """
+    from pastml_amd import sharding
+    from pastml_amd.batch import CharacterBatch, LikelihoodError, annotation_words, likelihood_error
+    from pastml_amd.models import KIND_F81
+    if isinstance(forest, TreeNode):
+        forest = [forest]
+    single = isinstance(characters, str)
+    if single:
+        characters, models = [characters], [models]
+    characters, models = list(characters), list(models)
+    if len(characters) != len(models):
+        raise ValueError('one model per character expected')
+    for character, model in zip(characters, models):
+        if model.kernel_spec()['kind'] != KIND_F81:
+            raise NotImplementedError('Character {}: loglikelihood_gradient is for the F81 family (F81, JC, EFT), not for {} '
+                                      '(PML_ERR_UNSUPPORTED).'.format(character, getattr(model, 'name', type(model).__name__)))
+    world = sharding.rank_world()[1]
+    if world > 1:
+        raise NotImplementedError('loglikelihood_gradient is not supported under a multi-process launch ({} ranks): run it in '
+                                  'a single process'.format(world))
+    flat = get_flat_forest(forest)
+    groups = {}
+    for i, model in enumerate(models):
+        groups.setdefault(len(model.states), []).append(i)
+    results = [None] * len(characters)
+    for k, members in groups.items():
+        group_models = [models[i] for i in members]
+        with CharacterBatch(flat, k, len(members)) as batch:
+            for c, i in enumerate(members):
+                batch.set_annotation(c, *annotation_words(flat, characters[i], models[i].states))
+            batch.initialize_allowed_states()
+            try:
+                lnl, d_rates, d_pi, n_flat = batch.loglik_gradient(group_models)
+            except LikelihoodError as e:
+                raise likelihood_error(flat, e)
+        for c, i in enumerate(members):
+            model = models[i]
+            flat_branches = int(n_flat[c])
+            tau = model.loglik_gradient_tau(d_rates[c], flat_branches)
+            parameters, names = None, None
+            if not model.frequency_smoothing_is_free():   # (the one case whose chain rule is refused)
+                parameters, names = model.loglik_gradient_parameters(d_rates[c], d_pi[c], flat_branches), \
+                    model.optimised_parameter_names()
+            results[i] = dict(log_likelihood=float(lnl[c]), sf=float(d_rates[c, 0]), tau=float(tau), frequencies=d_pi[c].copy(),
+                              parameters=parameters, parameter_names=names, n_zero_length_branches=flat_branches)
+    return results[0] if single else results

@@ -36,6 +36,53 @@ class F81Model(ModelWithFrequencies):
             mu = np.float64(1.) / (np.float64(1.) - pi.dot(pi))
         return dict(kind=KIND_F81, pi=pi, mu=float(mu))
 
+    def optimised_parameter_names(self):
+        """Names of the entries of get_optimised_parameters(), in its order: the file keys of the scalars, and
+        'frequency_<state>/<last state>' for the ratios that encode free frequencies."""
+        names = [p.key for p in self._free(self.LEADING)]
+        if not self.extra_params_fixed():
+            if self._optimise_frequencies:
+                names += ['frequency_{}/{}'.format(s, self.states[-1]) for s in self.states[:-1]]
+            elif self._frequency_smoothing:
+                names.append('frequency_smoothing')
+        return names
+
+    def frequency_smoothing_is_free(self):
+        """The optimiser's vector carries the frequency-smoothing parameter: loglik_gradient_parameters refuses it."""
+        return bool(self._frequency_smoothing) and not self.extra_params_fixed()
+
+    def loglik_gradient_tau(self, d_rates, n_flat):
+        """The total derivative of ln L with respect to tau from pml_loglik_gradient's d_rates: the one at fixed tau factor plus
+        d/d tau_factor times the derivative of calc_tau_factor's L / (L + tau (N - 1)); NaN where n_flat > 0."""
+        if n_flat > 0:
+            return np.nan
+        fs = self._forest_stats
+        tf = fs.forest_length / (fs.forest_length + self._tau * (fs.num_nodes - 1))
+        return float(d_rates[1]) - float(d_rates[2]) * tf * tf * (fs.num_nodes - 1) / fs.forest_length
+
+    def loglik_gradient_parameters(self, d_rates, d_pi, n_flat):
+        """
+        The chain rule from the natural derivatives of ln L (pml_loglik_gradient: d_rates = d/d sf, d/d tau at fixed
+        tau_factor, d/d tau_factor; d_pi [k] with every frequency treated as free; n_flat: branches with exp(-mu t') == 1) to
+        the gradient with respect to get_optimised_parameters(), in that vector's order, for the parameters that are free.
+        tau: the total derivative adds d/d tau_factor times the derivative of calc_tau_factor's L / (L + tau (N - 1)), and is
+        NaN where n_flat > 0 (a branch with t' = 0 keeps no trace of its share in the stored posteriors).
+        Frequencies are encoded as x_i = pi_i / pi_last: d/d x_i = (g_i - pi . g) / (1 + sum x).
+        """
+        if self.frequency_smoothing_is_free():
+            raise NotImplementedError('The gradient with respect to the frequency-smoothing parameter is not implemented: '
+                                      'smoothing is applied to the current frequencies, not to fixed ones.')
+        out = []
+        if self._optimise_sf:
+            out.append(float(d_rates[0]))
+        if self._optimise_tau:
+            out.append(self.loglik_gradient_tau(d_rates, n_flat))
+        if not self.extra_params_fixed() and self._optimise_frequencies:
+            pi = np.asarray(self.frequencies, dtype=np.float64)
+            g = np.asarray(d_pi, dtype=np.float64)
+            out.extend((g[:-1] - pi.dot(g)) / (1. + (pi[:-1] / pi[-1]).sum()))
+        return np.array(out, dtype=np.float64)
+
     def kernel_points(self, vectors):
         # All vectors of a batch decoded at once (the arithmetic of set_params_from_optimised, row by row: scalars
         # first, then pi = (ratios, 1) / their sum): a character's gradient is k + 1 points per optimiser step, and
