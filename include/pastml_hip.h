@@ -256,12 +256,20 @@ int pml_bottom_up_collect(pml_ctx* ctx, int is_marginal, double* loglik_out, int
  * marginal pml_bottom_up with the same masks.  Outputs are optional (NULL = keep on the device only):
  * posterior_out[n_cols][n_nodes][k], lh_sum_out / lh_sf_out[n_cols][n_nodes] such that
  * log10(lh_sum) - lh_sf is the node's total log10-likelihood (the invariant of pastml/ml.py:468-483).
+ * F81 family, k <= 64: the posterior row of an observed tip (one allowed state) is the unit vector of its mask and depends on
+ * nothing else.  It is written by the first top-down sweep after the masks were set and not rewritten while it provably stands
+ * (nothing wrote the masks, reallocated the table, changed the model kind, an option or a tunable, no pass failed or wrote
+ * NaNs there): sweeps after a change of the parameters alone skip those stores.  The table a caller sees is unchanged -- after
+ * every sweep every row is in memory, bit for bit what a sweep that writes them all leaves.  PASTML_HIP_NO_KEEP_TIP_ROWS (a
+ * tunable) makes every sweep write every row.
  */
 int pml_top_down_marginals(pml_ctx* ctx, double* posterior_out, double* lh_sum_out, double* lh_sf_out);
 /*
  * pml_bottom_up(marginal) + pml_top_down_marginals in one call: both sweeps are submitted before the host waits, so a
  * marginal pass costs one host round trip instead of two (what pastml/ml.py:700-707 does per tree in ml_acr).  Same
- * outputs and statuses as the two calls; on PML_ZERO_LIKELIHOOD the top-down results are invalid.
+ * outputs and statuses as the two calls; on PML_ZERO_LIKELIHOOD the top-down results are invalid.  The observed tips'
+ * posterior rows are kept across passes as pml_top_down_marginals says: a loop that re-sends parameters and calls this writes
+ * them once; a pass that returns an error makes the next one write them all.
  */
 int pml_marginal_pass(pml_ctx* ctx, double* loglik_out, int32_t* err_parent, int32_t* err_child,
                       double* posterior_out, double* lh_sum_out, double* lh_sf_out);

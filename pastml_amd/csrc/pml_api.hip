@@ -179,6 +179,7 @@ int pml_ctx_set_option(pml_ctx* ctx, int option, int value) {
         if ((value != 0) != ctx->keep_td) {
             drop_graph(ctx->td_graph);
             drop_graph(ctx->mp_graph);
+            ctx->results.tip_rows_unknown();   // (any change of an option: rare, and a blunt rule is enough)
         }
         ctx->keep_td = value != 0;
         return PML_OK;
@@ -187,6 +188,7 @@ int pml_ctx_set_option(pml_ctx* ctx, int option, int value) {
         if ((value != 0) != ctx->eig_fused_opt) {
             drop_sweep_graphs(ctx);
             ctx->results.inputs_changed();
+            ctx->results.tip_rows_unknown();
         }
         ctx->eig_fused_opt = value != 0;
         return PML_OK;
@@ -195,6 +197,7 @@ int pml_ctx_set_option(pml_ctx* ctx, int option, int value) {
         if ((value != 0) != ctx->eigj_valu_opt) {
             drop_graph(ctx->bu_graph[0]);
             ctx->results.inputs_changed();
+            ctx->results.tip_rows_unknown();
         }
         ctx->eigj_valu_opt = value != 0;
         return PML_OK;
@@ -203,6 +206,7 @@ int pml_ctx_set_option(pml_ctx* ctx, int option, int value) {
         if ((value != 0) != ctx->implicit_tips) {
             drop_graph(ctx->td_graph);
             drop_graph(ctx->mp_graph);
+            ctx->results.tip_rows_unknown();   // (on: rows are left out of memory; off again: the next sweep writes them all)
         }
         ctx->implicit_tips = value != 0;
         return PML_OK;
@@ -224,6 +228,7 @@ int pml_ctx_set_tunable(pml_ctx* ctx, const char* name, int64_t value, int is_se
         drop_sweep_graphs(ctx);
         drop_graph(ctx->bt_graph);
         ctx->results.inputs_changed();
+        ctx->results.tip_rows_unknown();
         return PML_OK;
     }
     return fail(PML_ERR_INVALID, "unknown tunable %s", name);
@@ -539,7 +544,7 @@ int pml_chars_alloc(pml_ctx* ctx, int32_t n_cols, int32_t k) {
     }
     const size_t CN = (size_t)n_cols * ctx->N;
     PML_TRY(dev_alloc(ctx, &ctx->d_masks, CN * ctx->W));
-    ctx->n_params = (size_t)n_cols * (ctx->ks + 6);  // pi, sf, tau, tau factor, mu, kappa, active
+    ctx->n_params = (size_t)n_cols * (ctx->ks + 6) + 1;  // pi, sf, tau, tau factor, mu, kappa, active; the observed tips' rows are kept
     PML_TRY(dev_alloc(ctx, &ctx->d_params, ctx->n_params));
     HIP_TRY(hipHostMalloc((void**)&ctx->h_params, sizeof(double) * ctx->n_params));
     memset(ctx->h_params, 0, sizeof(double) * ctx->n_params);
@@ -554,7 +559,9 @@ int pml_chars_alloc(pml_ctx* ctx, int32_t n_cols, int32_t k) {
     ctx->active_partial = false;
     ctx->n_active = ctx->sched_cols = n_cols;
     PML_TRY(dev_alloc(ctx, &ctx->d_err, n_cols));
-    HIP_TRY(hipHostMalloc((void**)&ctx->h_loglik, sizeof(double) * n_cols));
+    HIP_TRY(hipHostMalloc((void**)&ctx->h_loglik, sizeof(double) * n_cols + sizeof(u64)));
+    ctx->h_bad_tip = reinterpret_cast<u64*>(ctx->h_loglik + n_cols);
+    *ctx->h_bad_tip = 0;
     HIP_TRY(hipHostMalloc((void**)&ctx->h_err, sizeof(u64) * n_cols));
     HIP_TRY(hipHostMalloc((void**)&ctx->h_done, 64));
     *ctx->h_done = 0;
@@ -580,6 +587,7 @@ int pml_chars_alloc(pml_ctx* ctx, int32_t n_cols, int32_t k) {
     ctx->eig_sym_all = false;
     ctx->tips_observed.assign(n_cols, 0);
     ctx->results.inputs_changed();
+    ctx->results.tip_rows_unknown();   // (the table is allocated anew)
     // Thin ends of a large forest.  A level is thin while a launch of its own is mostly latency: up to 4 096 units, and up to
     // THIN_BYTES (20 MB) of state vectors over all columns -- beyond, the level kernels stream it faster than workgroups
     // that walk subtrees.  Measured (profiles/r05u_thin_ends.txt, THIN_UNITS sweeps): k = 4 x 32 columns 4 096 (16 384 loses
@@ -645,6 +653,7 @@ int pml_masks_upload(pml_ctx* ctx, int32_t col_begin, int32_t col_end, const uin
         rows_to_internal(ctx, src, reordered.data(), (size_t)ctx->W, (size_t)(col_end - col_begin));
         src = reordered.data();
     }
+    ctx->results.tip_rows_unknown();   // (before the write: whichever columns and nodes it changes, and whether it goes through)
     PML_TRY(upload(ctx, ctx->d_masks + col_begin * per_col, src, per_col * (col_end - col_begin)));
     HIP_TRY(hipStreamSynchronize(ctx->stream));
     note_tips_observed(ctx, col_begin, col_end, false);
@@ -669,6 +678,7 @@ int pml_masks_from_tip_states(pml_ctx* ctx, int32_t col_begin, int32_t col_end, 
     }
     for (size_t i = 0; i < (size_t)nc * n_tips; ++i)
         if (states[i] >= ctx->k) return fail(PML_ERR_INVALID, "state %d out of range (k = %d)", states[i], ctx->k);
+    ctx->results.tip_rows_unknown();   // (before the write, as pml_masks_upload)
     dim3 grid(grid_for(ctx, (int)std::min<size_t>((size_t)ctx->N * ctx->W, 1u << 30), PML_BLOCK, nc), nc);
     hipLaunchKernelGGL(masks_fill_kernel, grid, dim3(PML_BLOCK), 0, ctx->stream, ctx->N, ctx->W, ctx->k, ctx->d_masks,
                        col_begin);
@@ -735,6 +745,7 @@ static int set_common(pml_ctx* ctx, int kind, int cb, int ce, const double* pi, 
         // one model kind per ctx; setting ALL columns at once may change it (a pooled ctx serving the next analysis)
         if (cb != 0 || ce != ctx->C) return fail(PML_ERR_INVALID, "all columns of a ctx must use one model kind");
         drop_sweep_graphs(ctx);
+        ctx->results.tip_rows_unknown();
     }
     if (kind == PML_MODEL_HKY && ctx->k != 4) return fail(PML_ERR_INVALID, "HKY needs k = 4");
     const int nc = ce - cb;
@@ -1556,9 +1567,32 @@ int pml_bottom_up_collect(pml_ctx* ctx, int is_marginal, double* loglik_out, int
     return collect_bottom_up(ctx, is_marginal, loglik_out, err_parent, err_child);
 }
 
+// The observed tips' rows and a top-down sweep about to go on the stream (before its capture or replay, never inside one).
+// Where the record says that the rows stand (PmlResults::tip_rows_kept) the F81 kernels of one mask word leave their stores
+// out: the word travels at the end of the parameter block, whose copy is part of a captured sweep, so a replayed graph reads the
+// word of the day as it reads the flags of the active columns.  PASTML_HIP_NO_KEEP_TIP_ROWS: every sweep writes every row.  The
+// bad-tip word is cleared here and read by end_top_down.
+static bool tip_rows_skipped(const pml_ctx* ctx) { return ctx->h_params != nullptr && ctx->h_params[ctx->n_params - 1] != 0.0; }
+static void begin_top_down(pml_ctx* ctx) {
+    const bool skip = ctx->results.tip_rows_kept() && !ctx->tune.on(T_NO_KEEP_TIP_ROWS) && !ctx->implicit_tips &&
+                      ctx->kind == PML_MODEL_F81 && ctx->W == 1;
+    if (skip != tip_rows_skipped(ctx)) {
+        ctx->h_params[ctx->n_params - 1] = skip ? 1.0 : 0.0;
+        ctx->params_dirty = true;
+    }
+    *reinterpret_cast<volatile u64*>(ctx->h_bad_tip) = 0;
+}
+// behind the wait every top-down entry ends in: the sweep's rows stand unless it wrote NaNs over one of them
+static void end_top_down(pml_ctx* ctx) { ctx->results.top_down_waited(__atomic_load_n(ctx->h_bad_tip, __ATOMIC_ACQUIRE) != 0); }
+
 // what a top-down sweep leaves behind (a replayed pml_marginal_pass runs no run_top_down)
 static void note_top_down(pml_ctx* ctx) {
-    ctx->results.top_down_submitted(ctx->kind != PML_MODEL_F81 || ctx->keep_td, state_of(ctx).implicit_tips);
+    const bool f81_one_word = ctx->kind == PML_MODEL_F81 && ctx->W == 1;
+    if (ctx->tune.on(T_DEBUG))
+        fprintf(stderr, "pml plan: top-down sweep, observed tips' rows %s\n",
+                !f81_one_word ? "written (not the F81 kernels of one mask word)" : state_of(ctx).implicit_tips ? "implicit"
+                : tip_rows_skipped(ctx) ? "kept" : "written");
+    ctx->results.top_down_submitted(ctx->kind != PML_MODEL_F81 || ctx->keep_td, state_of(ctx).implicit_tips, f81_one_word);
 }
 
 // the top-down launches (shared by pml_top_down_marginals and the lazy TD materialisation of pml_download), as
@@ -1576,6 +1610,10 @@ static int run_top_down(pml_ctx* ctx, bool wants_signal = false, PmlCapture capt
         PML_TRY(dev_alloc(ctx, &ctx->d_lhe, CN));
     }
     const bool td_small = single_launch_sweeps(ctx) && ctx->kind == PML_MODEL_F81;
+    if (capture != CAP_PASS) {   // (a captured pass: pml_marginal_pass did this before the capture began)
+        begin_top_down(ctx);
+        PML_TRY(params_push(ctx));   // only where the word changed: a sweep of its own holds no copy of the block
+    }
     auto enqueue = [&](PmlCapture, PmlSweepOutcome* o) -> int {   // (a replayed graph plans nothing)
         const std::vector<PmlLaunch> plan = pml_plan_top_down(ctx->forest, schedules_of(ctx), sweep_traits(ctx), wants_signal);
         *o = pml_plan_outcome(plan);
@@ -1611,8 +1649,11 @@ static int materialize_td(pml_ctx* ctx) {
             drop_graph(ctx->td_graph);
             drop_graph(ctx->mp_graph);
         }
+        const hipError_t waited = status == PML_OK ? hipStreamSynchronize(ctx->stream) : hipSuccess;
+        if (status != PML_OK || waited != hipSuccess) ctx->results.tip_rows_unknown();
         PML_TRY(status);
-        HIP_TRY(hipStreamSynchronize(ctx->stream));
+        HIP_TRY(waited);
+        end_top_down(ctx);
     }
     if (ctx->results.td_fill_missing()) {
         const bool f81 = ctx->kind == PML_MODEL_F81;
@@ -1660,14 +1701,27 @@ static int fetch_marginals(pml_ctx* ctx, double* posterior_out, double* lh_sum_o
 int pml_top_down_marginals(pml_ctx* ctx, double* posterior_out, double* lh_sum_out, double* lh_sf_out) {
     PML_TRY(require_model(ctx));
     if (!ctx->results.has_marginal()) return fail(PML_ERR_INVALID, "pml_top_down_marginals needs a successful marginal pml_bottom_up first");
-    PML_TRY(run_top_down(ctx));
-    return fetch_marginals(ctx, posterior_out, lh_sum_out, lh_sf_out);
+    int status = run_top_down(ctx);
+    if (status == PML_OK) status = fetch_marginals(ctx, posterior_out, lh_sum_out, lh_sf_out);   // synchronises
+    if (status == PML_OK) end_top_down(ctx);
+    else ctx->results.tip_rows_unknown();
+    return status;
 }
+
+static int marginal_pass(pml_ctx* ctx, double* loglik_out, int32_t* err_parent, int32_t* err_child, double* posterior_out,
+                         double* lh_sum_out, double* lh_sf_out);
 
 int pml_marginal_pass(pml_ctx* ctx, double* loglik_out, int32_t* err_parent, int32_t* err_child, double* posterior_out,
                       double* lh_sum_out, double* lh_sf_out) {
     PML_TRY(require_model(ctx));
     if (!loglik_out) return fail(PML_ERR_INVALID, "loglik_out is NULL");
+    const int status = marginal_pass(ctx, loglik_out, err_parent, err_child, posterior_out, lh_sum_out, lh_sf_out);
+    if (status != PML_OK) ctx->results.tip_rows_unknown();   // a zero likelihood, a HIP failure: whatever the sweep wrote
+    return status;
+}
+
+static int marginal_pass(pml_ctx* ctx, double* loglik_out, int32_t* err_parent, int32_t* err_child, double* posterior_out,
+                         double* lh_sum_out, double* lh_sf_out) {
     // both sweeps go on the stream before the host looks at anything: the top-down sweep does not wait for a round trip.
     // Latency-bound forests (the sweeps replay as hipGraphs): ONE graph holds both sweeps -- one launch call, no gap
     // between the last bottom-up kernel and the first top-down one.  (F81 family, once the buffers of a top-down sweep
@@ -1683,6 +1737,7 @@ int pml_marginal_pass(pml_ctx* ctx, double* loglik_out, int32_t* err_parent, int
     u64 generation = 0;
     PML_TRY(generation_before(ctx, &generation));
     set_active_columns(ctx, nullptr);  // (the replayed pass does not go through submit_bottom_up)
+    begin_top_down(ctx);               // (nor through run_top_down; the word goes out with the bottom-up sweep's copy of the block)
     PmlSweepOutcome pass;
     if (one_graph) {
         PML_TRY(run_captured(ctx, ctx->mp_graph, CAP_NONE, [&](PmlCapture, PmlSweepOutcome* o) -> int {
@@ -1724,6 +1779,7 @@ int pml_marginal_pass(pml_ctx* ctx, double* loglik_out, int32_t* err_parent, int
     } else {
         fetched = fetch_marginals(ctx, posterior_out, lh_sum_out, lh_sf_out);  // synchronises
     }
+    if (fetched == PML_OK) end_top_down(ctx);   // (the bad-tip word lies behind the completion word, as ln L does)
     const int status = collect_bottom_up(ctx, 1, loglik_out, err_parent, err_child);
     if (status != PML_OK) {
         ctx->results.no_results();  // a column without likelihood: its top-down results mean nothing
@@ -2152,6 +2208,7 @@ int pml_select_states(pml_ctx* ctx, int method, int force_joint, const uint64_t*
         }
         PML_TRY(mem.put(&d_lh_mask, src, CN * ctx->W));
     }
+    ctx->results.tip_rows_unknown();   // (before the masks are rewritten)
     PML_TRY(dispatch_select(ctx, method, force_joint, d_lh_mask));   // pml_launch_matrix.hip
     HIP_TRY(hipGetLastError());
     PML_TRY(fetch_rows(ctx, (const u64*)ctx->d_masks, (size_t)ctx->W, (size_t)ctx->W, (size_t)ctx->C, (u64*)masks_out));

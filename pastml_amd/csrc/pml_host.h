@@ -184,8 +184,12 @@ struct pml_ctx {
     GraphSlot mp_graph;            // bottom-up + top-down of pml_marginal_pass as ONE graph
     bool graphs = true;
     double* h_loglik = nullptr;  // pinned staging of the per-column results
+    // behind them, in the same allocation: the bad-tip word of the F81 top-down kernels (post_onehot).  The host clears it before
+    // a top-down sweep goes on the stream and reads it behind the wait for that sweep (begin_top_down / end_top_down).
+    u64* h_bad_tip = nullptr;
     // pi, sf, tau, tau factor, mu, kappa of all columns live in ONE device block with a pinned host mirror of the same
-    // layout: a parameter update (every optimiser step) is one asynchronous copy and no synchronisation
+    // layout: a parameter update (every optimiser step) is one asynchronous copy and no synchronisation.  Behind them the
+    // flags of the active columns and, last, one word for the top-down sweep: the observed tips' rows are kept.
     double *d_params = nullptr, *h_params = nullptr;
     bool params_dirty = false;  // the pinned mirror holds values the device block has not seen (params_push sends them)
     size_t n_params = 0;
@@ -299,6 +303,7 @@ static void free_all(pml_ctx* ctx) {
     if (ctx->h_params) (void)hipHostFree(ctx->h_params);
     ctx->h_params = nullptr;
     ctx->h_loglik = nullptr;
+    ctx->h_bad_tip = nullptr;
     ctx->h_err = nullptr;
     for (void* p : ctx->allocs) (void)hipFree(p);
     if (ctx->d_stage) (void)hipFree(ctx->d_stage);
@@ -445,6 +450,8 @@ static PmlState state_of(const pml_ctx* c) {
     s.te = td_stored ? c->d_te : nullptr;
     s.post = c->d_post;
     s.implicit_tips = c->implicit_tips && c->kind == PML_MODEL_F81 && c->W == 1;
+    s.keep_tips = c->d_params ? c->d_params + (c->n_params - 1) : nullptr;   // last word of the block (begin_top_down sets it)
+    s.bad_tip = c->h_bad_tip;
     s.lhsum = c->d_lhsum;
     s.lhe = c->d_lhe;
     s.J = c->d_J;

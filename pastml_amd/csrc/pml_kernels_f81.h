@@ -52,7 +52,11 @@ struct PmlState {
     double* lhsum;  // [C][N]
     i64* lhe;       // [C][N]
     bool implicit_tips;  // top-down sweep: the unit-vector posteriors of observed tips are not written (PML_OPT_IMPLICIT_TIP_POSTERIORS)
-    pml_jt* J;      // [C][N][ks]  joint argmax tables (one byte per entry: k <= 256; two where jt16)
+    // ... nor where this word of the parameter block is non-zero: the rows stand in the table from an earlier sweep over the same
+    // masks (PmlResults::tip_rows_kept).  In the block, not by value: a captured sweep is replayed with the word of the day.
+    const double* keep_tips;
+    u64* bad_tip;   // pinned host word, raised where an observed tip's row is written as NaNs (over a kept unit row, possibly)
+    pml_jt* J;     // [C][N][ks]  joint argmax tables (one byte per entry: k <= 256; two where jt16)
     bool jt16;      // more than 256 states: the entries of J are unsigned shorts
     int* js;        // [C][N]      joint states
     u64* err;       // [C]         min over failing (post_rank << 32 | child id)
@@ -145,7 +149,8 @@ struct LaneCtx {
     int* stst;
     double* ssum;  // staged lhsum / lhe of the six slots (null: not staged)
     i64* sexp;
-    bool implicit_tips;  // observed tips' posteriors stay implicit (their mask says which unit vector it is)
+    bool implicit_tips;  // observed tips' unit rows are not written: left implicit, or kept from an earlier sweep (PmlState)
+    u64* bad_tip;
     __device__ __forceinline__ int st(int r) const { return R == 1 ? g : ((r >> 1) * 2 * G + 2 * g + (r & 1)); }
 };
 
@@ -175,7 +180,8 @@ __device__ __forceinline__ void lane_ctx_init(LaneCtx<G, R>& L, const PmlTree& t
     L.stst = nullptr;
     L.ssum = nullptr;
     L.sexp = nullptr;
-    L.implicit_tips = st.implicit_tips;
+    L.implicit_tips = st.implicit_tips || (st.keep_tips != nullptr && *st.keep_tips != 0.0);
+    L.bad_tip = st.bad_tip;
 #pragma unroll
     for (int r = 0; r < R; ++r) {
         L.pi_r[r] = (L.st(r) < c.k) ? c.pi[(size_t)L.col * c.ks + L.st(r)] : 0.0;
@@ -354,6 +360,12 @@ template <int G, int R>
 __device__ __forceinline__ bool post_onehot(const LaneCtx<G, R>& L, const PmlCols& c, int slot, int tip, int s,
                                             const double (&oh)[R], bool ok) {
     if (L.implicit_tips && ok) return false;  // the row is the unit vector of the tip's one allowed state: not written
+    if (!ok && L.g == 0 && L.bad_tip != nullptr) {
+        // NaNs, which depend on the parameters, go where a unit row may be kept: the host must not count on that row after this
+        // sweep.  Behind the host's wait for the sweep, the spin on the completion word included (pml_signal_done).
+        __hip_atomic_store(L.bad_tip, 1ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "");
+    }
     if (G <= PML_TD_STAGE_MAX_G && L.srow != nullptr && slot >= 2 && slot < 6 && ok) {
         if (L.g == 0) {
             L.stid[slot - 2] = tip;

@@ -21,6 +21,10 @@ struct PmlResults {
     bool td_vectors_missing() const { return !td_vec_valid; }  // the last top-down sweep ran without the TD stores
     bool td_fill_missing() const { return !td_filled; }      // the TD vectors of the nodes no sweep stores (td_fill_kernel)
     bool tip_posteriors_missing() const { return tip_post_missing; }  // the observed tips' rows were left implicit
+    // ---- what may a sweep leave alone?
+    // The unit-vector rows of ALL observed tips of ALL columns are in the posterior table and match the current masks: a top-down
+    // sweep of the F81 family with one mask word need not store them again (they depend on the masks and on nothing else).
+    bool tip_rows_kept() const { return tip_rows; }
 
     // ---- inputs
     // masks, model parameters, columns, the eigen options, any tunable: P(t) is stale and no sweep's result stands
@@ -53,13 +57,28 @@ struct PmlResults {
         bu_absorbed = (marginal && f81 && two_level) || (some_columns && bu_absorbed);
     }
     void bottom_up_collected(bool marginal) { bu_mode = marginal ? 1 : 0; }   // (not on zero likelihood)
-    // A top-down sweep is on the stream.  vectors_stored: with the TD stores; tips_implicit: observed tips' posteriors left out.
-    void top_down_submitted(bool vectors_stored, bool tips_implicit) {
+    // A top-down sweep is on the stream.  vectors_stored: with the TD stores; tips_implicit: observed tips' posteriors left out
+    // of memory; f81_one_word: by the kernels of the F81 family with one mask word, which write an observed tip's row as the unit
+    // vector of its mask -- or leave the store out where the row is kept -- and raise the bad-tip word where they write NaNs
+    // instead.  Any other family writes every row itself: its bits are not assumed.
+    void top_down_submitted(bool vectors_stored, bool tips_implicit, bool f81_one_word) {
         td_valid = post_ever = true;
         td_vec_valid = vectors_stored;
         td_filled = false;
         tip_post_missing = tips_implicit;
+        tip_sweep = f81_one_word && !tips_implicit;
+        if (!tip_sweep) tip_rows = false;
     }
+    void top_down_submitted(bool vectors_stored, bool tips_implicit) { top_down_submitted(vectors_stored, tips_implicit, false); }
+    // the host has waited for that sweep and read its bad-tip word: raised = some observed tip's row is NaNs now
+    void top_down_waited(bool bad_tip) {
+        if (tip_sweep) tip_rows = !bad_tip;
+        tip_sweep = false;
+    }
+    // The observed tips' rows may not stand any more, or not match the masks: the masks were written, the table may have been
+    // reallocated, the model kind, an option or a tunable changed, a pass returned an error.  (A change of the model's
+    // parameters is none of these: inputs_changed leaves the fact alone.)
+    void tip_rows_unknown() { tip_rows = tip_sweep = false; }
     void joint_states_fetched() { js_valid = js_ever = true; }
     // a sweep is about to overwrite the buffers, or a pass found a column without likelihood: nothing in them means anything
     void no_results() {
@@ -80,4 +99,6 @@ private:
     bool prep_dirty = true;
     bool bu_fused = false, bu_fused_joint = false, bu_absorbed = false;
     bool td_vec_valid = false, td_filled = false, tip_post_missing = false;
+    bool tip_rows = false;    // the observed tips' unit rows stand in the table
+    bool tip_sweep = false;   // the sweep on the stream makes that so unless its bad-tip word comes back raised
 };
