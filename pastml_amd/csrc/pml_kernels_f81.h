@@ -1949,6 +1949,25 @@ __device__ __forceinline__ void f81_finish_child(const LaneCtx<G, R>& L, const P
 // pi . X = (P - pi_s prod_s) / c0 + pi_s prod_s / c1 with P = pi . prod (computed once per parent), the tip's
 // TD_s = (1 - e) pi . X + e prod_s / c1, its marginal likelihood vector is TD_s pi_s at s and 0 elsewhere, and its
 // posterior is exactly the unit vector (what lh / lh.sum() gives in the reference, ml.py:500).
+// The scalar part of that closed form: P = pi . prod, ps = prod_s, the tip's e and pi_s, the parent's exponent pe ->
+// the tip's marginal likelihood lhs, whether it is a positive finite number, and the two scalars stored for the tip.
+// One text for every caller: the compiler contracts a * b + c per statement, so the statements are the arithmetic.
+__device__ __forceinline__ void f81_tip_closed_form(double P, double ps, double e, double pis, i64 pe, double& lhs,
+                                                    bool& ok, double& lsum, i64& le) {
+    const double q = pis * ps;
+    double c0 = (1.0 - e) * pis;
+    const double c1 = c0 + e;
+    if (!(c0 > 0.0)) c0 = 1.0;
+    const double r1 = rcp1(c1);
+    const double sx = (P - q) * rcp1(c0) + q * r1;
+    const double tds = (1.0 - e) * sx + e * (ps * r1);
+    lhs = tds * pis;
+    ok = lhs > 0.0 && !isinf(lhs);
+    const int lex = ok ? exponent_of(lhs) : 0;
+    lsum = __builtin_ldexp(lhs, -lex);
+    le = pe + lex;
+}
+
 // Observed-tip closed form / general tip, given the tip's data (single mask word without bits >= k: k <= 64).
 template <int G, int R>
 __device__ __forceinline__ void f81_finish_tip_word(const LaneCtx<G, R>& L, const PmlCols& c, const double (&prod)[R],
@@ -1966,22 +1985,16 @@ __device__ __forceinline__ void f81_finish_tip_word(const LaneCtx<G, R>& L, cons
 #pragma unroll
         for (int r = 0; r < R; ++r) pick = fma(oh[r], prod[r], pick);
         const double ps = group_sum<G>(pick);
-        const double q = pis * ps;
-        double c0 = (1.0 - e) * pis;
-        const double c1 = c0 + e;
-        if (!(c0 > 0.0)) c0 = 1.0;
-        const double r1 = rcp1(c1);
-        const double sx = (P - q) * rcp1(c0) + q * r1;
-        const double tds = (1.0 - e) * sx + e * (ps * r1);
-        const double lhs = tds * pis;
-        const bool ok = lhs > 0.0 && !isinf(lhs);
-        const int lex = ok ? exponent_of(lhs) : 0;
+        double lhs, lsum;
+        bool ok;
+        i64 le;
+        f81_tip_closed_form(P, ps, e, pis, pe, lhs, ok, lsum, le);
         if (!ok) {
 #pragma unroll
             for (int r = 0; r < R; ++r) oh[r] = __builtin_nan("");
         }
         const bool staged = post_onehot<G, R>(L, c, slot, tip, (int)__builtin_ctzll(word), oh, ok);
-        post_scalars<G, R>(L, staged ? slot : -1, tip, __builtin_ldexp(lhs, -lex), pe + lex);
+        post_scalars<G, R>(L, staged ? slot : -1, tip, lsum, le);
     } else {
         double mt[R], tdt[R], pt[R], lt;
         clean_word_to_vec<G, R>(L, c, word, mt);
@@ -2645,9 +2658,41 @@ td_f81_kernel(PmlTree t, PmlCols c, PmlState st, const PmlUnit* __restrict__ uni
 // exponent it has just produced: what the next level launch would have read back.  The two children of p are adjacent
 // units of one wavefront, so p's row comes from memory once.  Same functions, same arguments, same lane shape as the
 // level kernels: the same bits.
+//
+// The four observed tips of the child, finished in lanes (LANES; ps_row: a row of G * R doubles of LDS per unit).
+// f81_finish_tip_word finishes one tip in all lanes of the unit: every lane repeats the tip's scalar closed form, after
+// a masked dot product and a butterfly whose only purpose is to pick prod_s.  The gather has left tip q of cherry jx in
+// lane jx * GC + q (e, pi_s, mask word), so that lane runs f81_tip_closed_form for its own tip -- the four tips at once
+// -- and stores the tip's two scalars itself.  It gets ps = prod_s from the cherry's prod, staged in the unit's LDS row
+// in state order, instead of from sum_r oh_r prod_r.
+// Same bits: that sum adds +0.0 terms (0 x prod_r) to prod_s, which gives prod_s exactly when every prod_r is finite
+// (prod_s >= +0: a posterior times a sum of likelihoods over pi); a non-finite prod_r elsewhere would have poisoned it
+// with 0 x inf.  P = pi . prod finite implies every prod_r finite: for pi_r > 0 the term pi_r prod_r is finite, and for
+// pi_r = 0, ipi_r = 0 makes prod_r = po_r x 0, non-finite only if po_r is, and then 0 x prod_r is a NaN in P.  So the
+// unit takes this path only when the four mask words are one-hot, P of both cherries is finite and the four likelihoods
+// are positive finite numbers; every other unit (NaN rows, the bad_tip word, ambiguous tips) runs the one-by-one loop.
+// Rows, where they are written, are the unit vectors built from the state index: 1.0 at s, 0.0 elsewhere, as the mask
+// bits give them.
+
+// the one-by-one loop over the two tips of cherry jx of such a unit: every lane of the unit, tip after tip
 template <int G, int R>
+__device__ __forceinline__ void td_f81_super_tips(const LaneCtx<G, R>& L, const PmlCols& c, const double (&prod3)[R],
+                                                  i64 le, int cfc, const TipLane& tl, int jx) {
+    constexpr int GC = Gather<G>::GC;
+    double P3 = 0.0;
+    bool have_P3 = false;
+#pragma unroll
+    for (int q = 0; q < 2; ++q) {
+        const int ts = L.group_base + jx * GC + q;
+        f81_finish_tip_word<G, R>(L, c, prod3, le, P3, have_P3, cfc + q, __shfl(tl.mask, ts, 64), __shfl(tl.e, ts, 64),
+                                  __shfl(tl.s, ts, 64));
+    }
+}
+
+// the two-level unit of child j (see above)
+template <int G, int R, bool LANES>
 __device__ __forceinline__ void td_f81_super_unit(const LaneCtx<G, R>& L, const PmlTree& t, const PmlCols& c,
-                                                  const PmlState& st, const SuperRegs& s, int j) {
+                                                  const PmlState& st, const SuperRegs& s, int j, double* ps_row) {
     const u64 kbits = state_bits(c.k);
     const int ch = s.fc + j;
     const UnitRegs u = super_child<G>(s, j, L.g);
@@ -2685,6 +2730,11 @@ __device__ __forceinline__ void td_f81_super_unit(const LaneCtx<G, R>& L, const 
     }
     // the child's own unit: td_f81_fast_children for two cherries of two tips, with the cherries' vectors at hand
     constexpr int GC = Gather<G>::GC;
+    const bool tip_lane = (L.g & ~(GC | 1)) == 0;  // lanes jx * GC + q, jx < 2, q < 2
+    const int tjx = (L.g / GC) & 1;
+    bool lanes = LANES && c.W == 1 && !group_any<G>(tip_lane && __popcll(ld.tl.mask) != 1);
+    double prod3[2][R], P3[2], ps = 0.0;
+    i64 le3[2];
 #pragma unroll
     for (int jx = 0; jx < 2; ++jx) {
         const int src = L.group_base + jx;
@@ -2694,31 +2744,68 @@ __device__ __forceinline__ void td_f81_super_unit(const LaneCtx<G, R>& L, const 
         double mb[R], tdc[R], po[R], ls;
         const bool full = word == kbits;
         if (!full) clean_word_to_vec<G, R>(L, c, word, mb);
-        i64 xe, le;
-        const int cfc = __shfl(u.cfc, L.group_base + jx * GC, 64);
+        i64 xe;
         f81_finish_child<G, R>(L, c, prod2, pe2, cch, ce, __shfl(ld.cl.s, src, 64), ck.e[jx], ck.v[jx], full, mb, tdc, xe, po,
-                               ls, le);
-        double prod3[R];
+                               ls, le3[jx]);
 #pragma unroll
-        for (int r = 0; r < R; ++r) prod3[r] = po[r] * (ls * L.ipi_r[r]);
-        double P3 = 0.0;
-        bool have_P3 = false;
+        for (int r = 0; r < R; ++r) prod3[jx][r] = po[r] * (ls * L.ipi_r[r]);
+        if (!lanes) {
+            td_f81_super_tips<G, R>(L, c, prod3[jx], le3[jx], __shfl(u.cfc, L.group_base + jx * GC, 64), ld.tl, jx);
+            continue;
+        }
+        P3[jx] = pi_dot<G, R>(L, prod3[jx]);
 #pragma unroll
-        for (int q = 0; q < 2; ++q) {
-            const int ts = L.group_base + jx * GC + q;
-            f81_finish_tip_word<G, R>(L, c, prod3, le, P3, have_P3, cfc + q, __shfl(ld.tl.mask, ts, 64),
-                                      __shfl(ld.tl.e, ts, 64), __shfl(ld.tl.s, ts, 64));
+        for (int r = 0; r < R; r += 2) {
+            double2 t2;
+            t2.x = prod3[jx][r];
+            t2.y = prod3[jx][r + 1];
+            *reinterpret_cast<double2*>(ps_row + L.st(r)) = t2;
+        }
+        wave_sync_lds();
+        if (tip_lane && tjx == jx) ps = ps_row[__builtin_ctzll(ld.tl.mask)];
+        wave_sync_lds();  // (the row is the next cherry's, and the next unit's)
+    }
+    if (!lanes) return;
+    // lane jx * GC + q: tip q of cherry jx, with the data it gathered
+    double lhs, lsum;
+    bool ok;
+    i64 le;
+    f81_tip_closed_form(tjx ? P3[1] : P3[0], ps, ld.tl.e, ld.tl.s, tjx ? le3[1] : le3[0], lhs, ok, lsum, le);
+    lanes = !isinf(P3[0]) && !isnan(P3[0]) && !isinf(P3[1]) && !isnan(P3[1]) && !group_any<G>(tip_lane && !ok);
+    if (!lanes) {
+#pragma unroll
+        for (int jx = 0; jx < 2; ++jx)
+            td_f81_super_tips<G, R>(L, c, prod3[jx], le3[jx], __shfl(u.cfc, L.group_base + jx * GC, 64), ld.tl, jx);
+        return;
+    }
+    if (tip_lane) {
+        const int tip = u.cfc + (L.g & 1);
+        L.lhsum[tip] = lsum;
+        L.lhe[tip] = le;
+    }
+    if (!L.implicit_tips) {
+        const int ts = (int)__builtin_ctzll(ld.tl.mask | (1ull << 63));  // (other lanes: any state, not used)
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+            const int sq = __shfl(ts, L.group_base + (q >> 1) * GC + (q & 1), 64);
+            double oh[R];
+#pragma unroll
+            for (int r = 0; r < R; ++r) oh[r] = L.st(r) == sq ? 1.0 : 0.0;
+            node_store_vec_nt<G, R>(L, c, L.post, s.t0 + 4 * j + q, oh);
         }
     }
 }
 
-// n_level = number of two-level nodes; unit i is child i & 1 of node i >> 1
-template <int G, int R>
+// n_level = number of two-level nodes; unit i is child i & 1 of node i >> 1.  LANES: the observed tips are finished in
+// lanes (td_f81_super_unit), through one row of G * R doubles of LDS per unit; off = PASTML_HIP_NO_TIP_LANES.
+template <int G, int R, bool LANES>
 __global__ void __launch_bounds__(PML_BLOCK)
 td_f81_super_kernel(PmlTree t, PmlCols c, PmlState st, const PmlUnit* __restrict__ units, int n_level) {
     constexpr int UW = 64 / G;
     const int wave = threadIdx.x >> 6;
     const int sub = (threadIdx.x & 63) / G;
+    __shared__ __attribute__((aligned(16))) double tip_rows[LANES ? PML_BLOCK * R : 2];
+    double* const ps_row = LANES ? tip_rows + (wave * UW + sub) * (G * R) : nullptr;
     LaneCtx<G, R> L;
     lane_ctx_init<G, R>(L, t, c, st);
     const int n_units = 2 * n_level;
@@ -2728,7 +2815,7 @@ td_f81_super_kernel(PmlTree t, PmlCols c, PmlState st, const PmlUnit* __restrict
     for (int base = idx - sub; base < n_units; base += stride) {
         const int nxt_idx = idx + stride;
         const SuperRegs nxt = load_super(units, nxt_idx < n_units ? nxt_idx >> 1 : 0);
-        if (idx < n_units) td_f81_super_unit<G, R>(L, t, c, st, cur, idx & 1);
+        if (idx < n_units) td_f81_super_unit<G, R, LANES>(L, t, c, st, cur, idx & 1, ps_row);
         cur = nxt;
         idx = nxt_idx;
     }

@@ -11,8 +11,10 @@ static void launch_super_f81(pml_ctx* ctx, bool bottom_up) {
     dim3 grid(grid_for(ctx, bottom_up ? ctx->sup.n : 2 * ctx->sup.n, upb, ctx->C, bottom_up), ctx->C), block(PML_BLOCK);
     if (bottom_up)
         hipLaunchKernelGGL((bu_f81_super_kernel<G, R>), grid, block, 0, ctx->stream, t, c, st, ctx->sup.d_units, ctx->sup.n);
-    else
-        hipLaunchKernelGGL((td_f81_super_kernel<G, R>), grid, block, 0, ctx->stream, t, c, st, ctx->sup.d_units, ctx->sup.n);
+    else if (ctx->tune.on(T_NO_TIP_LANES))
+        hipLaunchKernelGGL((td_f81_super_kernel<G, R, false>), grid, block, 0, ctx->stream, t, c, st, ctx->sup.d_units, ctx->sup.n);
+    else  // the four observed tips of a unit finished in lanes (pml_kernels_f81.h)
+        hipLaunchKernelGGL((td_f81_super_kernel<G, R, true>), grid, block, 0, ctx->stream, t, c, st, ctx->sup.d_units, ctx->sup.n);
 }
 
 // stacked units of bottom-up level / depth `level` (pml_kernels_f81.h)
