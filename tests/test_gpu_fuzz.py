@@ -3,9 +3,15 @@ Randomised GPU parity sweep (``-m gpu``): many small random forests -- polytomie
 missing / ambiguous tips, restricted internal nodes, one to three columns with their own parameters -- through the
 C-ABI, against the oracle.  Shapes are drawn so that every kernel variant is hit: the F81 lane shapes (k from 2 to 130),
 cherry fusion with 1-6 tips per cherry, units that leave the lane-parallel gather (more than four children, stored
-children beyond the first two), the fused matrix-core sweeps of the eigen models (16 <= k <= 32) next to the
-materialised-P kernels (HKY, other k), and forests small enough for the single-launch kernels as well as larger ones.
+children beyond the first two), the sweeps of the eigen models -- the sum sweeps as two matrix-core GEMMs per 16 nodes that
+never form P(t) (2 <= k <= 64 with A and A^-1 as operands, 65 <= k <= 128 with one matrix in LDS), the joint sweep on the
+vector units (k <= 64), and both on P(t) materialised in HBM beyond those (k = 140; the joint sweep from 65 states on) --, HKY
+with P(t) built in registers, and forests small enough for the single-launch kernels as well as larger ones.
 A case whose likelihood is zero must raise on both sides and name the same pair of nodes.
+
+Which lane shapes of the eigen sum sweeps these draws reach is a matter of the seeds (most forests here run the tip launch and
+the several-levels-per-launch kernel only): every state count from 2 to 64, in level and narrow launches, is held to exact
+arithmetic by tests/test_gpu_eigen_shapes.py.
 """
 import numpy as np
 import pytest
