@@ -369,8 +369,9 @@ static void pick_group(const pml_ctx* ctx, int k, int& G, int& R) {
 }
 
 // Blocks along x for a level of n_units units per column (grid-stride loops take the rest).  The cap on the total
-// number of blocks was measured on cfg4 (MI355X): the pipelined bottom-up kernels like ~8192 (a wave then walks several
-// units and its prefetch stage pays off), everything else 32768; persistent-size grids (768-2048) were 5-15 % slower.
+// number of blocks was measured on cfg4 (MI355X): the pipelined kernels (bottom-up, and the top-down two-level kernel)
+// like ~8192 (a wave then walks several units and its prefetch stage pays off), everything else 32768; persistent-size
+// grids (768-2048) were 5-15 % slower.
 static int grid_for(const pml_ctx* ctx, int n_units, int units_per_block, int C, bool pipelined = false) {
     int blocks = (n_units + units_per_block - 1) / units_per_block;
     const int cap_env = (int)ctx->tune.get(T_GRID_CAP, 0);

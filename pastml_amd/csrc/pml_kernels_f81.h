@@ -2689,22 +2689,65 @@ __device__ __forceinline__ void td_f81_super_tips(const LaneCtx<G, R>& L, const 
     }
 }
 
-// the two-level unit of child j (see above)
-template <int G, int R, bool LANES>
+// Everything the two-level unit of child j reads from memory, so that the kernel can issue it one unit ahead.
+template <int R>
+struct TdSuperLoads {
+    double po[R];  // the two-level node's posterior row, its sum and exponent (f81_parent_prod)
+    double ls;
+    i64 pe;
+    double e, s;   // E, S, exponent and mask word of the child
+    i64 be;
+    u64 own;
+    ChildLane cl;  // the gather of the child's cherries and their tips
+    TipLane tl;
+};
+
+// Valid for every descriptor of the list and either j: all addresses are those of existing nodes.
+template <int G, int R>
+__device__ __forceinline__ void td_f81_super_issue(const LaneCtx<G, R>& L, const PmlCols& c, const SuperRegs& s, int j,
+                                                   TdSuperLoads<R>& ld) {
+    const int ch = s.fc + j;
+    node_load_vec<G, R>(L, c, L.post, s.n, ld.po);
+    ld.ls = L.lhsum[s.n];
+    ld.pe = L.lhe[s.n];
+    ld.e = L.E[ch];
+    ld.s = L.S[ch];
+    ld.be = L.be[ch];
+    ld.own = L.mask[(unsigned)ch];
+    f81_gather_issue<G, R>(L, super_child<G>(s, j, L.g), ld.cl, ld.tl);
+}
+
+// one wait for exactly this unit's loads (see bu_loads_arrived): the next unit's stay in flight
+template <int R>
+__device__ __forceinline__ void td_super_loads_arrived(TdSuperLoads<R>& ld) {
+#pragma unroll
+    for (int r = 0; r < R; ++r) asm volatile("" : "+v"(ld.po[r]));
+    asm volatile("" : "+v"(ld.ls), "+v"(ld.pe), "+v"(ld.e), "+v"(ld.s), "+v"(ld.be), "+v"(ld.own));
+    asm volatile("" : "+v"(ld.cl.e), "+v"(ld.cl.s), "+v"(ld.cl.mask), "+v"(ld.cl.be), "+v"(ld.tl.e), "+v"(ld.tl.s),
+                      "+v"(ld.tl.mask));
+}
+
+// the two-level unit of child j (see above) on the loads td_f81_super_issue issued for (s, j).  PIPE: they were issued
+// one unit ahead, and the unit begins with the one wait for them.
+template <int G, int R, bool LANES, bool PIPE>
 __device__ __forceinline__ void td_f81_super_unit(const LaneCtx<G, R>& L, const PmlTree& t, const PmlCols& c,
-                                                  const PmlState& st, const SuperRegs& s, int j, double* ps_row) {
+                                                  const PmlState& st, const SuperRegs& s, int j, TdSuperLoads<R>& in,
+                                                  double* ps_row) {
+    if (PIPE) td_super_loads_arrived<R>(in);
     const u64 kbits = state_bits(c.k);
     const int ch = s.fc + j;
     const UnitRegs u = super_child<G>(s, j, L.g);
     double prod[R];
-    i64 pe;
-    f81_parent_prod<G, R>(L, c, s.n, prod, pe);
-    const double e = L.E[ch];
-    const double s_child = L.S[ch];
-    const i64 bec = L.be[ch];
+    const i64 pe = in.pe;
+#pragma unroll
+    for (int r = 0; r < R; ++r) prod[r] = in.po[r] * (in.ls * L.ipi_r[r]);  // f81_parent_prod
+    const double e = in.e;
+    const double s_child = in.s;
+    const i64 bec = in.be;
     BuLoads<R> ld;
-    ld.own = L.mask[(unsigned)ch];
-    f81_gather_issue<G, R>(L, u, ld.cl, ld.tl);
+    ld.own = in.own;
+    ld.cl = in.cl;
+    ld.tl = in.tl;
     f81_gather_finish<G, R>(L, ld.cl, ld.tl);
     ld.own &= kbits;
     const bool all_ones = __all(c.k == G * R && ld.own == kbits && ld.cl.mask == kbits);
@@ -2798,8 +2841,14 @@ __device__ __forceinline__ void td_f81_super_unit(const LaneCtx<G, R>& L, const 
 
 // n_level = number of two-level nodes; unit i is child i & 1 of node i >> 1.  LANES: the observed tips are finished in
 // lanes (td_f81_super_unit), through one row of G * R doubles of LDS per unit; off = PASTML_HIP_NO_TIP_LANES.
-template <int G, int R, bool LANES>
+// PIPE: the two-stage software pipeline of bu_f81_super_kernel -- the loads of unit i + 1 and the descriptor of unit
+// i + 2 are in flight while unit i is computed and stored; off = PASTML_HIP_NO_TD_SUPER_PIPE.  An index past the end is
+// clamped to unit 0, so every address of a prefetch is that of an existing node even in lanes that have no unit.
+// (eight states per lane with the prefetch: held to two waves per SIMD, the 256 registers it then fills exactly -- left
+// free the allocator takes 259 and the second wave is gone; four states per lane: 187, two waves instead of three)
+template <int G, int R, bool LANES, bool PIPE>
 __global__ void __launch_bounds__(PML_BLOCK)
+    __attribute__((amdgpu_waves_per_eu(PIPE && R == 8 ? 2 : 1, PIPE && R == 8 ? 2 : 8)))
 td_f81_super_kernel(PmlTree t, PmlCols c, PmlState st, const PmlUnit* __restrict__ units, int n_level) {
     constexpr int UW = 64 / G;
     const int wave = threadIdx.x >> 6;
@@ -2809,15 +2858,55 @@ td_f81_super_kernel(PmlTree t, PmlCols c, PmlState st, const PmlUnit* __restrict
     LaneCtx<G, R> L;
     lane_ctx_init<G, R>(L, t, c, st);
     const int n_units = 2 * n_level;
-    const int stride = gridDim.x * PML_WAVES_PER_BLOCK * UW;
+    const int stride = gridDim.x * PML_WAVES_PER_BLOCK * UW;  // (even: unit i + stride is the same child j as unit i)
     int idx = (blockIdx.x * PML_WAVES_PER_BLOCK + wave) * UW + sub;
-    SuperRegs cur = load_super(units, idx < n_units ? idx >> 1 : 0);
-    for (int base = idx - sub; base < n_units; base += stride) {
-        const int nxt_idx = idx + stride;
-        const SuperRegs nxt = load_super(units, nxt_idx < n_units ? nxt_idx >> 1 : 0);
-        if (idx < n_units) td_f81_super_unit<G, R, LANES>(L, t, c, st, cur, idx & 1, ps_row);
-        cur = nxt;
-        idx = nxt_idx;
+    const int j = idx & 1;
+    int base = idx - sub;
+    if (!PIPE) {
+        SuperRegs cur = load_super(units, idx < n_units ? idx >> 1 : 0);
+        for (; base < n_units; base += stride) {
+            const int nxt_idx = idx + stride;
+            const SuperRegs nxt = load_super(units, nxt_idx < n_units ? nxt_idx >> 1 : 0);
+            if (idx < n_units) {
+                TdSuperLoads<R> ld;
+                td_f81_super_issue<G, R>(L, c, cur, j, ld);
+                td_f81_super_unit<G, R, LANES, false>(L, t, c, st, cur, j, ld, ps_row);
+            }
+            cur = nxt;
+            idx = nxt_idx;
+        }
+        return;
+    }
+    // Prefetching is safe: a unit stores only the rows, sums and exponents of its child, the child's cherries and their
+    // tips (and td / te of the child when asked), while a unit reads the row, sum and exponent of its two-level node and
+    // E, S, the bottom-up exponents and the masks.  A two-level node is never the child, a cherry or a tip of a
+    // two-level node (two_level_root, pml_schedule.cpp: its children are parents of cherries), and the top-down sweep
+    // writes neither E, S, the bottom-up exponents nor the masks: nothing a unit stores is read by a later unit of the
+    // launch.
+    SuperRegs ua = load_super(units, idx < n_units ? idx >> 1 : 0);
+    SuperRegs ub = load_super(units, idx + stride < n_units ? (idx + stride) >> 1 : 0);
+    TdSuperLoads<R> la, lb;
+    td_f81_super_issue<G, R>(L, c, ua, j, la);
+    while (base < n_units) {
+        {
+            const int i2 = idx + 2 * stride;
+            const SuperRegs un = load_super(units, i2 < n_units ? i2 >> 1 : 0);
+            td_f81_super_issue<G, R>(L, c, ub, j, lb);
+            if (idx < n_units) td_f81_super_unit<G, R, LANES, true>(L, t, c, st, ua, j, la, ps_row);
+            ua = un;
+            idx += stride;
+            base += stride;
+        }
+        if (base >= n_units) break;
+        {
+            const int i2 = idx + 2 * stride;
+            const SuperRegs un = load_super(units, i2 < n_units ? i2 >> 1 : 0);
+            td_f81_super_issue<G, R>(L, c, ua, j, la);
+            if (idx < n_units) td_f81_super_unit<G, R, LANES, true>(L, t, c, st, ub, j, lb, ps_row);
+            ub = un;
+            idx += stride;
+            base += stride;
+        }
     }
 }
 

@@ -45,7 +45,7 @@ struct __attribute__((aligned(32))) PmlUnit {
     X(PIJ_STAGE_ROWS, 0, 0) X(PIJ_BLOCKS, 0, 0) X(NO_HEIGHT_ORDER, 1, 1) X(NO_TD_TAIL, 1, 0) X(NO_PIJ_VALU, 1, 0) X(PIJ_VALU, 1, 0) X(NO_PIJ_WIDE, 1, 0) X(NO_EIGJ_PIPE, 1, 0) \
     X(THIN_UNITS, 0, 1) X(THIN_BYTES, 0, 1) X(THIN_BLOCK_NODES, 0, 1) X(NO_THIN, 1, 0) X(NO_THIN_WIDE, 1, 0) X(BU_WIDE, 0, 1) X(SORT_LEVELS, 0, 1) X(NO_WIDE_LEAN, 1, 0) X(SHAPE_ORDER, 0, 1) \
     X(PARS_MAX_COLS, 0, 0) X(PARS_THIN, 0, 0) X(COMPRESS_MAX_COLS, 0, 0) X(COMPRESS_PLAIN_ATOMICS, 1, 0) \
-    X(PIJ_WINDOW, 0, 0) X(NO_KEEP_TIP_ROWS, 1, 0) X(NO_TIP_LANES, 1, 0)
+    X(PIJ_WINDOW, 0, 0) X(NO_KEEP_TIP_ROWS, 1, 0) X(NO_TIP_LANES, 1, 0) X(NO_TD_SUPER_PIPE, 1, 0)
 enum PmlTunable {
 #define X(name, flag, tree) T_##name,
     PML_TUNABLES(X)
