@@ -361,6 +361,31 @@ int pml_loglik_gradient(pml_ctx* ctx, int32_t col_begin, int32_t col_end, double
                         int32_t* n_flat_out);
 
 /*
+ * The exact expected dwell times and Markov jumps of the columns [col_begin, col_end) under the F81 family (F81, JC, EFT), taken
+ * under the posterior over whole histories, from the vectors of the marginal pass (needs pml_bottom_up (marginal) and
+ * pml_top_down_marginals first, PML_ERR_INVALID otherwise) -- no sweep, no sampling.  Where pml_expected_counts compares the two
+ * ends of a branch, this counts events: a change undone on the same branch is counted twice here and not at all there.
+ * In the notation of pml_loglik_gradient, with L_n = (d_n + tau) tau_factor the smoothed length of the branch above the non-root
+ * node n, x_n = mu t'_n, e_n = exp(-x_n), S_n = pi . v_n, o_n[i] = q_p[i] / m_n[i] (0 where q_p[i] == 0), O_n = sum_i o_n[i] and
+ *   g = (1 - e) / x,   c0 = 1 - 2 g + e,   c1 = g - e                                   (g = 1, c0 = c1 = 0 at x = 0)
+ *   a_n[i] = pi_i O_n S_n c0 + o_n[i] S_n c1,     b_n[i] = pi_i O_n c1 + o_n[i] e_n
+ *   times_out[col][s]        = sum_n L_n (a_n[s] + b_n[s] v_n[s])          (units of smoothed length; their sum is sum_n L_n)
+ *   jumps_out[col][i][j]     = sum_n x_n pi_j (a_n[i] + b_n[i] v_n[j]) for i != j, 0 on the diagonal: the expected number of
+ *                              jumps i -> j
+ *   branch_jumps_out[col][n] = x_n sum_i (a_n[i] (1 - pi_i) + b_n[i] (S_n - pi_i v_n[i])): the expected number of jumps on the
+ *                              branch above n, in the caller's numbering; 0 for a root
+ * Every term is non-negative; a branch with t' = 0 adds nothing.  jumps_out and branch_jumps_out may be NULL: what is not asked
+ * for is not computed (without jumps_out the call is one streaming pass), and times_out has the same bits either way.  The masks
+ * are those the marginal pass ran with.  PML_ERR_UNSUPPORTED: a context of HKY or eigen models, or k > 512.  PML_ERR_INVALID: no
+ * marginal pass, k < 2, or a column whose pi . pi >= 1 (mu infinite).  No atomics: the nodes are walked in the caller's numbering
+ * in pieces whose size depends on k only, the partials are summed in piece order, and the bits of every output do not depend on
+ * launch geometry, on the schedule switches, on the library's numbering, on which other columns are in the call or on how often
+ * it is called.  The results of the marginal pass stay as they are.
+ */
+int pml_expected_history(pml_ctx* ctx, int32_t col_begin, int32_t col_end, double* times_out, double* jumps_out,
+                         double* branch_jumps_out);
+
+/*
  * Maximum parsimony of n_cols characters of k states (k <= 512) on the uploaded forest: the bottom-up pass
  * (pastml/parsimony.py:92-122) and, per bit of methods, ACCTRAN (:125-158), DOWNPASS (:161-210) and DELTRAN (:213-242, on
  * the DOWNPASS sets), each with the number of state changes its sets need (:360-380, summed over the trees) and the number

@@ -411,6 +411,20 @@ class CharacterBatch(object):
             self.unalter(altered)
         return self.resident_loglik, d_rates, d_pi, n_flat
 
+    def expected_history(self, models, jumps=True, branch_jumps=False):
+        """
+        Exact expected dwell times and Markov jumps of every character under its F81-family model (``pml_expected_history``):
+        the marginal pass with the masks altered for the characters with tau == 0, the pass over what it left on the device,
+        then the masks restored as ``bottom_up`` restores them.  Returns (ln L [m], times [m, k], jumps [m, k, k] or None,
+        branch_jumps [m, N] or None) as Engine.expected_history describes them.
+        """
+        altered = self.marginal_pass_resident(models)
+        try:
+            times, jumps_out, branch_out = self.engine.expected_history(jumps=jumps, branch_jumps=branch_jumps)
+        finally:
+            self.unalter(altered)
+        return self.resident_loglik, times, jumps_out, branch_out
+
     def joint_states(self):
         """Joint state of every node after a joint sweep (ml.py:598-622): int64 [m, N]."""
         return self.engine.joint_backtrace().astype(np.int64)

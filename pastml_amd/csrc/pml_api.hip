@@ -1987,6 +1987,40 @@ int pml_loglik_gradient(pml_ctx* ctx, int32_t col_begin, int32_t col_end, double
     return mem.finish();
 }
 
+// Exact expected dwell times and Markov jumps of the columns [col_begin, col_end) under the F81 family (pml_launch_history.hip):
+// one streaming pass over the vectors the marginal pass left on the device, and the jump product where jumps_out is given.  The
+// masks are those the pass ran with.
+int pml_expected_history(pml_ctx* ctx, int32_t col_begin, int32_t col_end, double* times_out, double* jumps_out,
+                         double* branch_jumps_out) {
+    PML_TRY(require_model(ctx));
+    PML_TRY(check_cols(ctx, col_begin, col_end));
+    if (!times_out) return fail(PML_ERR_INVALID, "pml_expected_history: times_out is NULL");
+    if (ctx->kind != PML_MODEL_F81)
+        return fail(PML_ERR_UNSUPPORTED, "pml_expected_history is for the F81 family (F81, JC, EFT): this context's model kind is %s",
+                    ctx->kind == PML_MODEL_HKY ? "HKY" : "eigen");
+    if (ctx->k > 512) return fail(PML_ERR_UNSUPPORTED, "pml_expected_history: k = %d, the F81 family holds at most 512 states", ctx->k);
+    PML_TRY(need_marginal_pass(ctx, "pml_expected_history"));
+    if (ctx->k < 2) return fail(PML_ERR_INVALID, "pml_expected_history: k = %d, a character of one state has no history", ctx->k);
+    const double* mu = ctx->h_params + (size_t)ctx->C * (ctx->ks + 3);
+    for (int c = col_begin; c < col_end; ++c)
+        if (!std::isfinite(mu[c]) || !(mu[c] > 0.0))
+            return fail(PML_ERR_INVALID, "pml_expected_history: column %d has pi . pi >= 1 (mu is not finite)", c);
+    PML_TRY(wait_pending(ctx, true));   // (a pass that ended in a spin on the completion word may have left the stream busy)
+    PML_TRY(write_marginal_pass(ctx));
+    const size_t k = ctx->k, N = (size_t)ctx->N, cols = (size_t)(col_end - col_begin);
+    CallScope mem(ctx->stream, false);
+    double *d_times, *d_jumps = nullptr, *d_branch = nullptr;
+    PML_TRY(mem.get(&d_times, cols * k));
+    if (jumps_out) PML_TRY(mem.get(&d_jumps, cols * k * k));
+    if (branch_jumps_out) PML_TRY(mem.get(&d_branch, cols * N));
+    PML_TRY(launch_history(ctx, mem, col_begin, col_end, d_times, d_jumps, d_branch));
+    HIP_TRY(hipMemcpyAsync(times_out, d_times, cols * k * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+    if (jumps_out) HIP_TRY(hipMemcpyAsync(jumps_out, d_jumps, cols * k * k * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+    if (branch_jumps_out)
+        HIP_TRY(hipMemcpyAsync(branch_jumps_out, d_branch, cols * N * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+    return mem.finish();
+}
+
 // n_repetitions scenarios of column col drawn forward from the roots (pml_launch_simulate.hip).  Needs a model, no sweep: the
 // per-branch e = exp(-mu t') (F81 family) or P(t) is prepared here.  The states are written in the caller's numbering on the
 // device, in rows padded to a multiple of 4 repetitions, and copied out without the padding.

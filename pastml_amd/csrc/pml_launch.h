@@ -221,6 +221,10 @@ PML_INTERNAL int launch_expected(pml_ctx* ctx, int cb, int ce, const unsigned ch
 // ---- pml_launch_gradient.hip: exact gradient of ln L of the F81 family for the columns [cb, ce) (pml_loglik_gradient); device
 //      arrays d_rates [cols][3], d_pi [cols][k], d_flat [cols]; queued only: the partials go into the caller's scope, which waits
 PML_INTERNAL int launch_gradient(pml_ctx* ctx, CallScope& mem, int cb, int ce, double* d_rates, double* d_pi, int* d_flat);
+// ---- pml_launch_history.hip: exact expected dwell times and Markov jumps of the F81 family for the columns [cb, ce)
+//      (pml_expected_history); device arrays d_times [cols][k], d_jumps [cols][k][k] or null, d_branch [cols][N] in the caller's
+//      numbering or null; queued only: partials and staged scalars go into the caller's scope, which waits
+PML_INTERNAL int launch_history(pml_ctx* ctx, CallScope& mem, int cb, int ce, double* d_times, double* d_jumps, double* d_branch);
 
 // More than 64 KB of dynamic LDS must be asked for: once per kernel, device and size (the largest asked for so far is what is
 // set) -- not per launch: the call is not free and should not sit inside a stream capture.  (A template: one table per kernel

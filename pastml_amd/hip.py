@@ -111,6 +111,7 @@ SIGNATURES = {
                                     _c_double_p, _c_int32_p, _c_int32_p],
     'pml_expected_counts': [_ctx_p, ctypes.c_int32, ctypes.c_int32, ctypes.POINTER(ctypes.c_uint8), _c_double_p, _c_double_p],
     'pml_loglik_gradient': [_ctx_p, ctypes.c_int32, ctypes.c_int32, _c_double_p, _c_double_p, _c_int32_p],
+    'pml_expected_history': [_ctx_p, ctypes.c_int32, ctypes.c_int32, _c_double_p, _c_double_p, _c_double_p],
     'pml_simulate_states': [_ctx_p, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_uint64, ctypes.c_void_p],
     'pml_sample_scenarios': [_ctx_p, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_uint64, ctypes.c_void_p,
                              ctypes.POINTER(ctypes.c_int64)],
@@ -854,6 +855,26 @@ class Engine(BareContext):
         _check(self._lib.pml_loglik_gradient(self._ctx, col_begin, col_end, _ptr(d_rates, ctypes.c_double),
                                              _ptr(d_pi, ctypes.c_double), _ptr(n_flat, ctypes.c_int32)))
         return d_rates, d_pi, n_flat
+
+    def expected_history(self, col_begin=0, col_end=None, jumps=True, branch_jumps=False):
+        """
+        Exact expected dwell times and Markov jumps of the columns [col_begin, col_end) after a marginal pass, under the posterior
+        over whole histories, F81 family only (pml_expected_history; include/pastml_hip.h has the sums).  Returns (times
+        [cols, k] in units of smoothed branch length, jumps [cols, k, k] -- the expected number of jumps i -> j, zero diagonal --
+        or None, branch_jumps [cols, n_nodes] in this engine's node numbering -- the expected number of jumps on the branch above
+        each node, 0 for a root -- or None).  What is not asked for is not computed.
+        """
+        col_end = self.n_cols if col_end is None else col_end
+        if not 0 <= col_begin < col_end <= self.n_cols:
+            raise ValueError('bad column range')
+        cols = col_end - col_begin
+        times = np.empty((cols, self.k), dtype=np.float64)
+        jumps_out = np.empty((cols, self.k, self.k), dtype=np.float64) if jumps else None
+        branch_out = np.empty((cols, self.n_nodes), dtype=np.float64) if branch_jumps else None
+        _check(self._lib.pml_expected_history(self._ctx, col_begin, col_end, _ptr(times, ctypes.c_double),
+                                              None if jumps_out is None else _ptr(jumps_out, ctypes.c_double),
+                                              None if branch_out is None else _ptr(branch_out, ctypes.c_double)))
+        return times, jumps_out, branch_out
 
     def simulate_states(self, n_repetitions, seed, col=0, rep_offset=0):
         """
