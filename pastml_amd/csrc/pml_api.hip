@@ -432,7 +432,7 @@ int pml_tree_upload(pml_ctx* ctx, int32_t n_nodes, int32_t n_roots, const int32_
     return PML_OK;
 }
 
-// The thin ends of a large forest (pml_plan_thin_ends); thin: the most units a thin level holds (pml_chars_alloc: by the
+// The thin ends of a large forest (pml_plan_thin_ends); thin: the most units a thin level holds (pml_plan_columns: by the
 // bytes a level of that many units moves).
 static int build_thin_ends(pml_ctx* ctx, int thin) {
     PmlThinPlan P = pml_plan_thin_ends(ctx->forest, ctx->tune, thin);
@@ -457,105 +457,39 @@ static int build_thin_ends(pml_ctx* ctx, int thin) {
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
+static_assert(PML_COLUMNS_MAX_STATES == PML_MAX_STATES, "the column planner and the kernels disagree on the most states");
+// pml_plan_columns' reasons: a bad argument is invalid, a layout the kernels cannot hold or address unsupported
+static int column_plan_status(const std::string& why) {
+    return why.rfind("k = ", 0) == 0 || why.rfind("n_nodes", 0) == 0 ? PML_ERR_UNSUPPORTED : PML_ERR_INVALID;
+}
+
+// Plans the layout (pml_plan_columns: every rule is there), then allocates and fills what the plan describes.
 int pml_chars_alloc(pml_ctx* ctx, int32_t n_cols, int32_t k) {
     if (!ctx || ctx->N == 0) return fail(PML_ERR_INVALID, "upload the tree first");
-    if (n_cols <= 0 || n_cols > 65535) return fail(PML_ERR_INVALID, "n_cols must be in 1..65535");
-    if (k <= 0) return fail(PML_ERR_INVALID, "k must be positive");
-    if (k > PML_MAX_STATES) return fail(PML_ERR_UNSUPPORTED, "k = %d states; at most %d are supported", k, PML_MAX_STATES);
     if (ctx->C != 0) return fail(PML_ERR_INVALID, "columns already allocated for this tree (upload the tree again to reset)");
+    PmlColumnPlan plan;
+    const std::string why = pml_plan_columns(ctx->forest, ctx->tune, n_cols, k, plan);
+    if (!why.empty()) return fail(column_plan_status(why), "%s", why.c_str());
     HIP_TRY(hipSetDevice(ctx->device));
-    ctx->C = n_cols;
-    ctx->k = k;
-    pick_group(ctx, k, ctx->G, ctx->R);
-    ctx->ks = (k + ctx->R - 1) / ctx->R * ctx->R;
-    {
-        // F81 family: 4 states per lane (two 16-byte pairs).  Most of a unit's work is scalar (per child, per tip), so
-        // the top-down kernels, which have the most of it, take 8 states per lane for 32 < k <= 64: 8 units per
-        // wavefront share each scalar instruction.  PASTML_HIP_F81_R / PASTML_HIP_F81_TD_R = 2 / 4 / 8: tuning variants
-        // Forests with many nodes of three or four children (15 % of the nodes with grandchildren) take 16 lanes per unit where
-        // k allows it: the lane-parallel gather of a unit's children (Gather<G>) takes G / 4 of them -- two with 8 lanes, four
-        // with 16 --, a unit with more walks them one after the other and holds up the other units of its wavefront.
-        const bool polytomies = ctx->forest.polytomies;
-        auto shape = [&](int var, int dflt, int& G, int& R) {
-            int rf = k >= 3 ? dflt : k;
-            // Up to 8 states: two per lane (2 or 4 lanes per unit).  In the latency-bound schedules -- small and mid-size
-            // forests -- a level is one wavefront's instruction stream, and half the states per lane are a shorter one
-            // (HIV1C tree, 14 columns: bottom-up sweep k = 4 0.111 -> 0.094 ms, k = 8 0.107 -> 0.095; marginal pass
-            // 0.290 -> 0.262, 0.319 -> 0.262; cfg2 0.0765 -> 0.0713 ms); the level kernels of large forests are
-            // indifferent (262 144 tips x 32 characters, k = 4: balanced 0.73 -> 0.77 ms, ragged 2.46 -> 2.34).  One state
-            // per lane is another 3 - 5 % on the small forests and costs the large balanced one a third: not taken.
-            if (k >= 3 && k <= 8 && dflt == 4) rf = 2;
-            // 16 < k <= 32 on forests with polytomies: 16 lanes x 2 states instead of 8 x 4 (100 000 tips, at most 3 children, x 16
-            // columns, k = 20 / 32: marginal pass 1.33 -> 0.95 / 1.34 -> 0.96 ms; at most 5 children: no change; binary trees lose 6 %)
-            if (k > 16 && k <= 32 && dflt == 4 && polytomies) rf = 2;
-            if (ctx->tune.on(var)) {
-                const int v = (int)ctx->tune.get(var, 0);
-                if ((v == 2 || v == 4 || v == 8) && k > 32 && k <= 64) rf = v;
-                if ((v == 2 || v == 4) && k >= 3 && k <= 8) rf = v;
-                if ((v == 2 || v == 4) && k > 16 && k <= 32) rf = v;   // (16 lanes x 2 states or 8 x 4)
-            }
-            if (k > 256) rf = 8;   // (a wavefront per unit: 64 lanes x 8 states, k <= 512)
-            R = rf;
-            const int need = (k + rf - 1) / rf;
-            G = 1;
-            while (G < need) G <<= 1;
-        };
-        shape(T_F81_R, 4, ctx->Gf, ctx->Rf);
-        // Balanced parts (PmlForest::balanced_parts): counted on the topology alone, whatever the switches, so that the lane
-        // shape, and with it a column's bits, is a function of k and the forest.
-        const bool balanced_parts = ctx->forest.balanced_parts;
-        // 8 states per lane bottom-up (32 < k <= 64) where the forest has such parts (cfg4: the level that rebuilds cherries
-        // 1.80 -> 1.58 ms; 262 144-tip balanced tree x 32: bottom-up 0.77 -> 0.63 ms) and few nodes of three or four children
-        // (8 lanes gather two children in parallel, see below); elsewhere 4: polytomies x 16 columns bottom-up 0.64 -> 0.50 ms
-        // (at most 3 children), 0.61 -> 0.52 (at most 5); random binary 40 000 tips x 8 0.184 -> 0.161; 262 144 x 16 1.17 -> 1.13
-        // (profiles/r05y_lane_shapes_and_sorted_levels.txt).
-        ctx->bu_wide_lanes = k > 32 && k <= 64 && ctx->Rf == 4 && !ctx->tune.on(T_F81_R) && balanced_parts && !polytomies;
-        if (ctx->tune.on(T_BU_WIDE)) ctx->bu_wide_lanes = k > 32 && k <= 64 && ctx->Rf == 4 && ctx->tune.get(T_BU_WIDE, 1) != 0;
-        // Level launches walk the lists sorted by shape inside every level (pml_tree_upload) from 4 lanes per unit on: 262 144
-        // tips x 32, marginal pass: k = 8 1.82 -> 1.78 ms, k = 12 2.35 -> 2.26, k = 16 2.38 -> 2.26, k = 20 3.49 -> 3.06, k = 32
-        // 3.53 -> 3.11; polytomies k = 12 1.36 -> 1.28, k = 20 1.55 -> 1.36; two lanes per unit (k <= 4) lose 11 % and keep id order.
-        ctx->level_lists_sorted = ctx->Gf >= 4 || ctx->forest.shape_ordered;   // (narrow units too where the numbering follows the shapes)
-        if (ctx->tune.on(T_SORT_LEVELS)) ctx->level_lists_sorted = ctx->tune.get(T_SORT_LEVELS, 1) != 0;
-        // Top-down: 8 states per lane for 32 < k <= 64 (above) unless the forest has many nodes of three or four children
-        // (15 % of those with grandchildren): the lane-parallel gather of a unit's children takes
-        // G / 4 of them (Gather<G>::CH: two with 8 lanes, four with 16), a unit with more walks them one after the other and
-        // holds up the other units of its wavefront.  Measured, marginal pass, k = 64 (profiles/r05y_lane_shapes_and_sorted_levels.txt):
-        // 100 000 tips, at most 3 children per node, x 8 / 16 / 32 columns 1.37 -> 0.93 / 1.79 -> 1.38 / 2.84 -> 2.26 ms; at
-        // most 5 children x 16 2.12 -> 1.90; at most 8 2.52 -> 2.28; binary trees lose 5 % with 4 states per lane.  The shape
-        // follows k and the forest, never the columns.
-        shape(T_F81_TD_R, (k > 32 && k <= 64 && !polytomies) ? 8 : 4, ctx->Gt, ctx->Rt);
-        if (k >= 2 && (ctx->ks & 1)) ctx->ks += 1;  // 16-byte lane accesses
-        {
-            const int g = ctx->bu_wide_lanes ? 8 : ctx->Gf;
-            const int nl = (int)ctx->forest.bu_offsets_f.size() - 1;
-            long long passes = 0;
-            for (int l = 0; l < nl; ++l)
-                passes += ((long long)(ctx->forest.bu_offsets_f[l + 1] - ctx->forest.bu_offsets_f[l]) * g + PML_SMALL_BLOCK - 1) / PML_SMALL_BLOCK;
-            // (up to 4 lanes per unit, k <= 16: with wider units one workgroup per column is too little parallelism --
-            // HIV1C tree, 64 columns: k = 12 0.28 against 0.32 ms with level launches, k = 20 0.27 against 0.22)
-            ctx->levels_fit_workgroup = nl > 0 && g <= 4 && passes * 4 <= (long long)nl * 5;
-        }
-    }
-    ctx->W = (k + 63) / 64;
-    if ((size_t)ctx->N * ctx->ks >= (1ull << 31)) {
-        // the kernels address one column's slab with 32-bit element offsets
-        ctx->C = 0;
-        return fail(PML_ERR_UNSUPPORTED, "n_nodes * k = %zu exceeds 2^31 elements per column", (size_t)ctx->N * ctx->ks);
-    }
+    ctx->cols = plan;
+    ctx->C = plan.C;
+    ctx->k = plan.k;
+    ctx->ks = plan.ks;
+    ctx->W = plan.W;
+    const PmlParamBlock& B = plan.params;
     const size_t CN = (size_t)n_cols * ctx->N;
     PML_TRY(dev_alloc(ctx, &ctx->d_masks, CN * ctx->W));
-    ctx->n_params = (size_t)n_cols * (ctx->ks + 6) + 1;  // pi, sf, tau, tau factor, mu, kappa, active; the observed tips' rows are kept
-    PML_TRY(dev_alloc(ctx, &ctx->d_params, ctx->n_params));
-    HIP_TRY(hipHostMalloc((void**)&ctx->h_params, sizeof(double) * ctx->n_params));
-    memset(ctx->h_params, 0, sizeof(double) * ctx->n_params);
-    for (int i = 0; i < n_cols; ++i) ctx->h_params[(size_t)n_cols * (ctx->ks + 5) + i] = 1.0;  // every column active
-    ctx->d_pi = ctx->d_params;
-    ctx->d_sf = ctx->d_pi + (size_t)n_cols * ctx->ks;
-    ctx->d_tau = ctx->d_sf + n_cols;
-    ctx->d_tauf = ctx->d_tau + n_cols;
-    ctx->d_mu = ctx->d_tauf + n_cols;
-    ctx->d_kappa = ctx->d_mu + n_cols;
-    ctx->d_active = ctx->d_kappa + n_cols;
+    PML_TRY(dev_alloc(ctx, &ctx->d_params, B.count));
+    HIP_TRY(hipHostMalloc((void**)&ctx->h_params, sizeof(double) * B.count));
+    memset(ctx->h_params, 0, sizeof(double) * B.count);
+    std::fill_n(ctx->h_params + B.active, n_cols, 1.0);  // every column active
+    ctx->d_pi = ctx->d_params + B.pi;
+    ctx->d_sf = ctx->d_params + B.sf;
+    ctx->d_tau = ctx->d_params + B.tau;
+    ctx->d_tauf = ctx->d_params + B.tauf;
+    ctx->d_mu = ctx->d_params + B.mu;
+    ctx->d_kappa = ctx->d_params + B.kappa;
+    ctx->d_active = ctx->d_params + B.active;
     ctx->active_partial = false;
     ctx->n_active = ctx->sched_cols = n_cols;
     PML_TRY(dev_alloc(ctx, &ctx->d_err, n_cols));
@@ -573,7 +507,7 @@ int pml_chars_alloc(pml_ctx* ctx, int32_t n_cols, int32_t k) {
     PML_TRY(dev_alloc(ctx, &ctx->d_S, CN));
     PML_TRY(dev_alloc(ctx, &ctx->d_be, CN));
     PML_TRY(dev_alloc(ctx, &ctx->d_E, CN));
-    HIP_TRY(hipMemcpyAsync(ctx->d_params, ctx->h_params, ctx->n_params * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
+    HIP_TRY(hipMemcpyAsync(ctx->d_params, ctx->h_params, ctx->cols.params.count * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
     HIP_TRY(hipMemsetAsync(ctx->d_be, 0, CN * sizeof(i64), ctx->stream));
     // default masks: everything allowed
     {
@@ -588,18 +522,7 @@ int pml_chars_alloc(pml_ctx* ctx, int32_t n_cols, int32_t k) {
     ctx->tips_observed.assign(n_cols, 0);
     ctx->results.inputs_changed();
     ctx->results.tip_rows_unknown();   // (the table is allocated anew)
-    // Thin ends of a large forest.  A level is thin while a launch of its own is mostly latency: up to 4 096 units, and up to
-    // THIN_BYTES (20 MB) of state vectors over all columns -- beyond, the level kernels stream it faster than workgroups
-    // that walk subtrees.  Measured (profiles/r05u_thin_ends.txt, THIN_UNITS sweeps): k = 4 x 32 columns 4 096 (16 384 loses
-    // 20 %); k = 64: x 32 columns 1 024 - 2 048, x 16 2 048, x 8 4 096; k = 20 x 32 4 096.
-    if (!wide_states(ctx) && !ctx->forest.bu_offsets_f.empty() && (ctx->forest.bu_offsets_f.back() > 2048 || ctx->tune.on(T_THIN_UNITS)) && !ctx->tune.on(T_NO_THIN)) {
-        long long thin = ctx->tune.get(T_THIN_UNITS, 0);
-        if (!ctx->tune.on(T_THIN_UNITS)) {
-            const long long bytes = ctx->tune.get(T_THIN_BYTES, 20ll << 20);
-            thin = std::min(4096ll, std::max(256ll, bytes / ((long long)n_cols * ctx->ks * 8)));
-        }
-        PML_TRY(build_thin_ends(ctx, (int)thin));
-    }
+    if (plan.thin_units > 0) PML_TRY(build_thin_ends(ctx, plan.thin_units));
     return PML_OK;
 }
 
@@ -755,15 +678,16 @@ static int set_common(pml_ctx* ctx, int kind, int cb, int ce, const double* pi, 
     ctx->kind = kind;
     // into the pinned mirror (the caller's arrays need not outlive the call); params_flush sends it
     double* h = ctx->h_params;
-    const size_t C = ctx->C, ks = ctx->ks, k = ctx->k;
+    const size_t ks = ctx->ks, k = ctx->k;
     for (int i = 0; i < nc; ++i) {
         double* row = h + (size_t)(cb + i) * ks;
         memcpy(row, pi + (size_t)i * k, k * sizeof(double));
         for (size_t q = k; q < ks; ++q) row[q] = 0.0;
     }
-    memcpy(h + C * ks + cb, sf, nc * sizeof(double));
-    memcpy(h + C * ks + C + cb, tau, nc * sizeof(double));
-    memcpy(h + C * ks + 2 * C + cb, tauf, nc * sizeof(double));
+    const PmlParamBlock& B = ctx->cols.params;
+    memcpy(h + B.sf + cb, sf, nc * sizeof(double));
+    memcpy(h + B.tau + cb, tau, nc * sizeof(double));
+    memcpy(h + B.tauf + cb, tauf, nc * sizeof(double));
     for (int i = cb; i < ce; ++i) ctx->model_set[i] = 1;
     ctx->results.inputs_changed();
     return PML_OK;
@@ -784,7 +708,7 @@ static int params_flush(pml_ctx* ctx) {
 // the mirror counts as sent whenever the graph is launched, run_captured)
 static int params_push(pml_ctx* ctx, PmlCapture capture = CAP_NONE, PmlSweepOutcome* outcome = nullptr) {
     if (capture == CAP_NONE && !ctx->params_dirty) return PML_OK;
-    HIP_TRY(hipMemcpyAsync(ctx->d_params, ctx->h_params, ctx->n_params * sizeof(double), hipMemcpyHostToDevice,
+    HIP_TRY(hipMemcpyAsync(ctx->d_params, ctx->h_params, ctx->cols.params.count * sizeof(double), hipMemcpyHostToDevice,
                            ctx->stream));
     if (capture == CAP_NONE) ctx->params_dirty = false;
     else if (outcome) outcome->has_params = true;
@@ -795,7 +719,7 @@ int pml_model_set_f81(pml_ctx* ctx, int32_t col_begin, int32_t col_end, const do
                       const double* tau, const double* tau_factor) {
     PML_TRY(set_common(ctx, PML_MODEL_F81, col_begin, col_end, pi, sf, tau, tau_factor));
     const int nc = col_end - col_begin;
-    double* mu = ctx->h_params + (size_t)ctx->C * (ctx->ks + 3) + col_begin;
+    double* mu = ctx->h_params + ctx->cols.params.mu + col_begin;
     for (int c = 0; c < nc; ++c) {
         // mu = 1 / (1 - sum pi^2), F81Model.py:18-26 (numpy dot)
         double dot = 0.0;
@@ -809,7 +733,7 @@ int pml_model_set_hky(pml_ctx* ctx, int32_t col_begin, int32_t col_end, const do
                       const double* sf, const double* tau, const double* tau_factor) {
     if (!kappa) return fail(PML_ERR_INVALID, "kappa is NULL");
     PML_TRY(set_common(ctx, PML_MODEL_HKY, col_begin, col_end, pi, sf, tau, tau_factor));
-    memcpy(ctx->h_params + (size_t)ctx->C * (ctx->ks + 4) + col_begin, kappa, (col_end - col_begin) * sizeof(double));
+    memcpy(ctx->h_params + ctx->cols.params.kappa + col_begin, kappa, (col_end - col_begin) * sizeof(double));
     return params_flush(ctx);
 }
 
@@ -1166,10 +1090,10 @@ static PmlSweepTraits sweep_traits(const pml_ctx* ctx) {
     t.n_cherries = ctx->n_cherries;
     t.has_init = ctx->has_init;
     t.fuse = ctx->fuse;
-    t.Gf = ctx->Gf;
-    t.Gt = ctx->Gt;
-    t.bu_wide_lanes = ctx->bu_wide_lanes;
-    t.level_lists_sorted = ctx->level_lists_sorted;
+    t.Gf = ctx->cols.Gf;
+    t.Gt = ctx->cols.Gt;
+    t.bu_wide_lanes = ctx->cols.bu_wide_lanes;
+    t.level_lists_sorted = ctx->cols.level_lists_sorted;
     t.single_launch = single_launch_sweeps(ctx);
     t.blocks = block_schedule(ctx);
     t.super = super_sweeps(ctx);
@@ -1393,7 +1317,7 @@ static int run_captured(pml_ctx* ctx, pml_ctx::GraphSlot& slot, PmlCapture captu
 // inside the captured sweep when it is replayed), so they are written while no sweep is in flight, like the parameters.
 static void set_active_columns(pml_ctx* ctx, const uint8_t* active) {
     if (!ctx->h_params) return;
-    double* flags = ctx->h_params + (size_t)ctx->C * (ctx->ks + 5);
+    double* flags = ctx->h_params + ctx->cols.params.active;
     if (active == nullptr && !ctx->active_partial) {  // (all ones already)
         ctx->n_active = ctx->C;
         return;
@@ -1523,7 +1447,7 @@ static int collect_bottom_up(pml_ctx* ctx, int is_marginal, double* loglik_out, 
     memcpy(loglik_out, ctx->h_loglik, sizeof(double) * ctx->C);
     const u64* err = ctx->h_err;
     int status = PML_OK;
-    const double* flags = ctx->h_params + (size_t)ctx->C * (ctx->ks + 5);
+    const double* flags = ctx->h_params + ctx->cols.params.active;
     for (int c = 0; c < ctx->C; ++c) {
         int ep = -1, ec = -1;
         if (err[c] != ~0ull && flags[c] != 0.0) {  // (a column that sat the sweep out reports nothing)
@@ -1572,12 +1496,12 @@ int pml_bottom_up_collect(pml_ctx* ctx, int is_marginal, double* loglik_out, int
 // out: the word travels at the end of the parameter block, whose copy is part of a captured sweep, so a replayed graph reads the
 // word of the day as it reads the flags of the active columns.  PASTML_HIP_NO_KEEP_TIP_ROWS: every sweep writes every row.  The
 // bad-tip word is cleared here and read by end_top_down.
-static bool tip_rows_skipped(const pml_ctx* ctx) { return ctx->h_params != nullptr && ctx->h_params[ctx->n_params - 1] != 0.0; }
+static bool tip_rows_skipped(const pml_ctx* ctx) { return ctx->h_params != nullptr && ctx->h_params[ctx->cols.params.keep_tips] != 0.0; }
 static void begin_top_down(pml_ctx* ctx) {
     const bool skip = ctx->results.tip_rows_kept() && !ctx->tune.on(T_NO_KEEP_TIP_ROWS) && !ctx->implicit_tips &&
                       ctx->kind == PML_MODEL_F81 && ctx->W == 1;
     if (skip != tip_rows_skipped(ctx)) {
-        ctx->h_params[ctx->n_params - 1] = skip ? 1.0 : 0.0;
+        ctx->h_params[ctx->cols.params.keep_tips] = skip ? 1.0 : 0.0;
         ctx->params_dirty = true;
     }
     *reinterpret_cast<volatile u64*>(ctx->h_bad_tip) = 0;
@@ -1955,6 +1879,21 @@ int pml_expected_counts(pml_ctx* ctx, int32_t col_begin, int32_t col_end, const 
     return mem.finish();
 }
 
+// What the exact entries of the F81 family (`entry`, which computes a `what`) ask of the context: that model kind, a marginal
+// pass, two states or more, and a finite positive mu in every column of [cb, ce).
+static int need_f81_pass(pml_ctx* ctx, const char* entry, const char* what, int cb, int ce) {
+    if (ctx->kind != PML_MODEL_F81)
+        return fail(PML_ERR_UNSUPPORTED, "%s is for the F81 family (F81, JC, EFT): this context's model kind is %s", entry,
+                    ctx->kind == PML_MODEL_HKY ? "HKY" : "eigen");
+    PML_TRY(need_marginal_pass(ctx, entry));
+    if (ctx->k < 2) return fail(PML_ERR_INVALID, "%s: k = %d, a character of one state has no %s", entry, ctx->k, what);
+    const double* mu = ctx->h_params + ctx->cols.params.mu;
+    for (int c = cb; c < ce; ++c)
+        if (!std::isfinite(mu[c]) || !(mu[c] > 0.0))
+            return fail(PML_ERR_INVALID, "%s: column %d has pi . pi >= 1 (mu is not finite)", entry, c);
+    return PML_OK;
+}
+
 // Exact gradient of ln L of the columns [col_begin, col_end) under the F81 family (pml_launch_gradient.hip): one streaming pass
 // over the vectors the marginal pass left on the device, no sweep.  The masks are those the pass ran with.
 int pml_loglik_gradient(pml_ctx* ctx, int32_t col_begin, int32_t col_end, double* d_rates_out, double* d_pi_out,
@@ -1962,15 +1901,7 @@ int pml_loglik_gradient(pml_ctx* ctx, int32_t col_begin, int32_t col_end, double
     PML_TRY(require_model(ctx));
     PML_TRY(check_cols(ctx, col_begin, col_end));
     if (!d_rates_out || !d_pi_out || !n_flat_out) return fail(PML_ERR_INVALID, "pml_loglik_gradient: an output array is NULL");
-    if (ctx->kind != PML_MODEL_F81)
-        return fail(PML_ERR_UNSUPPORTED, "pml_loglik_gradient is for the F81 family (F81, JC, EFT): this context's model kind is %s",
-                    ctx->kind == PML_MODEL_HKY ? "HKY" : "eigen");
-    PML_TRY(need_marginal_pass(ctx, "pml_loglik_gradient"));
-    if (ctx->k < 2) return fail(PML_ERR_INVALID, "pml_loglik_gradient: k = %d, a character of one state has no gradient", ctx->k);
-    const double* mu = ctx->h_params + (size_t)ctx->C * (ctx->ks + 3);
-    for (int c = col_begin; c < col_end; ++c)
-        if (!std::isfinite(mu[c]) || !(mu[c] > 0.0))
-            return fail(PML_ERR_INVALID, "pml_loglik_gradient: column %d has pi . pi >= 1 (mu is not finite)", c);
+    PML_TRY(need_f81_pass(ctx, "pml_loglik_gradient", "gradient", col_begin, col_end));
     PML_TRY(wait_pending(ctx, true));   // (a pass that ended in a spin on the completion word may have left the stream busy)
     PML_TRY(write_marginal_pass(ctx));
     const size_t k = ctx->k, cols = (size_t)(col_end - col_begin);
@@ -1995,16 +1926,8 @@ int pml_expected_history(pml_ctx* ctx, int32_t col_begin, int32_t col_end, doubl
     PML_TRY(require_model(ctx));
     PML_TRY(check_cols(ctx, col_begin, col_end));
     if (!times_out) return fail(PML_ERR_INVALID, "pml_expected_history: times_out is NULL");
-    if (ctx->kind != PML_MODEL_F81)
-        return fail(PML_ERR_UNSUPPORTED, "pml_expected_history is for the F81 family (F81, JC, EFT): this context's model kind is %s",
-                    ctx->kind == PML_MODEL_HKY ? "HKY" : "eigen");
     if (ctx->k > 512) return fail(PML_ERR_UNSUPPORTED, "pml_expected_history: k = %d, the F81 family holds at most 512 states", ctx->k);
-    PML_TRY(need_marginal_pass(ctx, "pml_expected_history"));
-    if (ctx->k < 2) return fail(PML_ERR_INVALID, "pml_expected_history: k = %d, a character of one state has no history", ctx->k);
-    const double* mu = ctx->h_params + (size_t)ctx->C * (ctx->ks + 3);
-    for (int c = col_begin; c < col_end; ++c)
-        if (!std::isfinite(mu[c]) || !(mu[c] > 0.0))
-            return fail(PML_ERR_INVALID, "pml_expected_history: column %d has pi . pi >= 1 (mu is not finite)", c);
+    PML_TRY(need_f81_pass(ctx, "pml_expected_history", "history", col_begin, col_end));
     PML_TRY(wait_pending(ctx, true));   // (a pass that ended in a spin on the completion word may have left the stream busy)
     PML_TRY(write_marginal_pass(ctx));
     const size_t k = ctx->k, N = (size_t)ctx->N, cols = (size_t)(col_end - col_begin);

@@ -22,6 +22,7 @@
 
 #include "pml_model.h"   // PmlTree, PmlCols, PmlState, PmlUnit, PmlModel (and the F81 / miscellaneous kernels' headers below it)
 #include "pml_schedule.h" // PmlTune, the schedules' host side, PmlForest
+#include "pml_columns.h"  // PmlColumnPlan: lane shapes, padding, the parameter block's layout
 #include "pml_pij_window.h" // PmlWindowStep
 #include "pml_results.h"   // PmlResults: what the result buffers hold
 
@@ -115,18 +116,14 @@ struct pml_ctx {
     EigenTiers eig_tiers;
     BacktraceTiers bt_tiers;
     bool small = false;  // forest small enough for the one-launch-per-sweep kernels
-    bool levels_fit_workgroup = false;  // (nearly) every fused level is one pass of a 512-thread workgroup
     std::vector<char> bu_level_vec_f;  // per fused bottom-up level: some unit has a stored node as child 0 or 1
     std::vector<int> td_cherry_prefix; // over the fused top-down units: how many before it have a cherry as child 0 or 1
     std::vector<char> bu_level_vec;    // the same for the plain levels (joint sweep: every internal node is stored)
     int n_cherries = 0;
 
     // columns
-    int C = 0, k = 0, ks = 0, W = 0, G = 0, R = 0;
-    int Gf = 0, Rf = 0;  // lane-group shape of the F81-family bottom-up kernels (chunked state ownership)
-    bool bu_wide_lanes = false;  // 32 < k <= 64: most bottom-up levels run with 8 states per lane (see dispatch_sweep)
-    bool level_lists_sorted = false;  // 32 < k <= 64: the level launches walk the lists sorted by shape (pml_tree_upload)
-    int Gt = 0, Rt = 0;  // ... and of the F81-family top-down kernels
+    PmlColumnPlan cols;   // what pml_plan_columns decided (pml_chars_alloc): lane shapes, flags, the parameter block's layout
+    int C = 0, k = 0, ks = 0, W = 0;   // copies of the plan's, read everywhere
     u64 *d_masks = nullptr, *d_masks_init = nullptr;
     bool has_init = false;
     int kind = -1;
@@ -188,11 +185,11 @@ struct pml_ctx {
     // a top-down sweep goes on the stream and reads it behind the wait for that sweep (begin_top_down / end_top_down).
     u64* h_bad_tip = nullptr;
     // pi, sf, tau, tau factor, mu, kappa of all columns live in ONE device block with a pinned host mirror of the same
-    // layout: a parameter update (every optimiser step) is one asynchronous copy and no synchronisation.  Behind them the
-    // flags of the active columns and, last, one word for the top-down sweep: the observed tips' rows are kept.
+    // layout (cols.params, PmlParamBlock): a parameter update (every optimiser step) is one asynchronous copy and no
+    // synchronisation.  Behind them the flags of the active columns and, last, one word for the top-down sweep: the observed
+    // tips' rows are kept.
     double *d_params = nullptr, *h_params = nullptr;
     bool params_dirty = false;  // the pinned mirror holds values the device block has not seen (params_push sends them)
-    size_t n_params = 0;
     u64* h_err = nullptr;
     // completion of a bottom-up sweep whose last launch is the single-workgroup-per-column kernel: that kernel raises a
     // word in pinned memory when its last column is done (bu_f81_small_kernel), and the collect spins on it
@@ -360,14 +357,6 @@ static int put(pml_ctx* ctx, T** dst, const std::vector<T>& v) {
     return put(ctx, dst, v.data(), v.size());
 }
 
-static void pick_group(const pml_ctx* ctx, int k, int& G, int& R) {
-    R = k <= 32 ? 1 : (k <= 128 ? 2 : (k <= 256 ? 4 : 8));   // (beyond 256 states: the F81 family only, a wavefront per unit)
-    if (k > 16 && k <= 32) R = 4;  // 8 lanes per unit: 8 units per wavefront
-    const int need = (k + R - 1) / R;
-    G = 1;
-    while (G < need) G <<= 1;
-}
-
 // Blocks along x for a level of n_units units per column (grid-stride loops take the rest).  The cap on the total
 // number of blocks was measured on cfg4 (MI355X): the pipelined kernels (bottom-up, and the top-down two-level kernel)
 // like ~8192 (a wave then walks several units and its prefetch stage pays off), everything else 32768; persistent-size
@@ -397,7 +386,7 @@ static inline bool wide_states(const pml_ctx* c) { return c->k > 256; }
 static bool single_launch_sweeps(const pml_ctx* c) {
     if (wide_states(c)) return false;
     const int many = (int)c->tune.get(T_SMALL_MANY_NODES, 16384);
-    return c->small || (c->sched_cols >= 64 && c->N <= many && c->levels_fit_workgroup);
+    return c->small || (c->sched_cols >= 64 && c->N <= many && c->cols.levels_fit_workgroup);
 }
 
 // The subtree-block schedule pays where a sweep is a chain of latency-bound launches; once the levels carry enough work
@@ -451,7 +440,7 @@ static PmlState state_of(const pml_ctx* c) {
     s.te = td_stored ? c->d_te : nullptr;
     s.post = c->d_post;
     s.implicit_tips = c->implicit_tips && c->kind == PML_MODEL_F81 && c->W == 1;
-    s.keep_tips = c->d_params ? c->d_params + (c->n_params - 1) : nullptr;   // last word of the block (begin_top_down sets it)
+    s.keep_tips = PmlParamBlock::at(c->d_params, c->cols.params.keep_tips);   // last word of the block (begin_top_down sets it)
     s.bad_tip = c->h_bad_tip;
     s.lhsum = c->d_lhsum;
     s.lhe = c->d_lhe;
@@ -474,7 +463,7 @@ static bool eigen_fused(const pml_ctx* c) {
 // HKY sweeps build P(t) in registers (pml_kernels_matrix.h, PML_P_HKY); PASTML_HIP_NO_HKY_FUSED reads the batch.
 static bool hky_fused(const pml_ctx* c) {
     const bool off = c->tune.on(T_NO_HKY_FUSED);
-    return !off && c->kind == PML_MODEL_HKY && c->k == 4 && c->ks == 4 && c->G == 4 && c->R == 1 && c->W == 1;
+    return !off && c->kind == PML_MODEL_HKY && c->k == 4 && c->ks == 4 && c->cols.G == 4 && c->cols.R == 1 && c->W == 1;
 }
 
 static PmlModel model_of(const pml_ctx* c) {

@@ -3106,8 +3106,8 @@ td_f81_stack_kernel(PmlTree t, PmlCols c, PmlState st, const PmlUnit* __restrict
 // between them, so a sweep costs one kernel launch instead of one per level (a 150-tip tree has ~16 levels of a few
 // nodes each: the level-per-launch schedule is pure launch latency there, and the optimiser repeats the bottom-up
 // sweep hundreds of times, pastml/ml.py:174-237).  Same unit functions, hence the same bits as the level kernels.
+// (PML_SMALL_BLOCK threads per workgroup: pml_schedule.h)
 // ---------------------------------------------------------------------------------------------------------------------
-#define PML_SMALL_BLOCK 512
 
 // ln L of one column (ml.py:112-121), shared by loglik_kernel and the single-launch kernels
 __device__ __forceinline__ double column_loglik(const PmlTree& t, const PmlCols& c, const PmlState& st, int col,

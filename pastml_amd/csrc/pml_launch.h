@@ -1,6 +1,6 @@
 // What pml_api.hip (schedules, C-ABI) calls of the kernel launchers, which live in translation units of their own
-// (pml_launch_*.hip, one per kernel family, compiled in parallel): the dispatch functions, the lane-shape rules they share
-// and the predicates that say which family a context's sweeps take.
+// (pml_launch_*.hip, one per kernel family, compiled in parallel): the dispatch functions, the cases of lane shapes they are
+// instantiated for (the shapes themselves: pml_columns.h) and the predicates that say which family a context's sweeps take.
 #pragma once
 #include "pml_host.h"
 
@@ -42,30 +42,13 @@
     X(16, 4)               \
     X(8, 8)
 
-// lane shape of the kernels that walk several levels in one launch.  Bottom-up: the shape the level kernels use for
-// levels of this size (dispatch_sweep: 8 states per lane up to 65 536 units when 32 < k <= 64).  The reductions over a
-// unit's lanes associate differently in different shapes, so a level must get the same shape whether it runs here or in
-// a level launch: where the narrow end begins depends on the number of columns, and a column's bits must not.
-static void multi_level_shape(const pml_ctx* ctx, bool bottom_up, int& g, int& r) {
-    g = bottom_up ? (ctx->bu_wide_lanes ? 8 : ctx->Gf) : ctx->Gt;
-    r = bottom_up ? (ctx->bu_wide_lanes ? 8 : ctx->Rf) : ctx->Rt;
-}
-
-
 // Two-level units run in the lane shape the level kernels give the levels they replace where those do not stream stored
-// vectors (bottom-up: 8 states per lane for 32 < k <= 64) -- units of 8 lanes and more, single-word masks.
-static void super_shape(const pml_ctx* ctx, bool bottom_up, int& g, int& r) {
-    g = bottom_up ? (ctx->bu_wide_lanes ? 8 : ctx->Gf) : ctx->Gt;
-    r = bottom_up ? (ctx->bu_wide_lanes ? 8 : ctx->Rf) : ctx->Rt;
-}
-
+// vectors (PmlColumnPlan::bu_shape) -- units of 8 lanes and more, single-word masks.
 static bool super_units(const pml_ctx* ctx) {
     if (!ctx->sup.ok || ctx->kind != PML_MODEL_F81 || ctx->W != 1) return false;
-    int g, r;
-    super_shape(ctx, true, g, r);
-    if (g < 8 || (g == 16 && r == 2)) return false;   // (16 x 2: the shape of forests with polytomies, no two-level kernels)
-    super_shape(ctx, false, g, r);
-    return g >= 8 && !(g == 16 && r == 2);
+    for (const PmlLaneShape s : {ctx->cols.bu_shape(), ctx->cols.td_shape()})
+        if (s.g < 8 || (s.g == 16 && s.r == 2)) return false;   // (16 x 2: the shape of forests with polytomies, no two-level kernels)
+    return true;
 }
 
 // the sweeps of this context run the level schedule with two-level units (not one launch per sweep, not subtree blocks)
@@ -79,10 +62,10 @@ static bool super_sweeps(const pml_ctx* ctx) {
 // k = 12 2.54 -> 2.49, k = 20 3.50 -> 3.43 (there the wide levels dominate).  NO_THIN_WIDE: units of fewer than 8 lanes only.
 static bool thin_bottom_up(const pml_ctx* ctx) {
     return ctx->thin.ok && ctx->kind == PML_MODEL_F81 && !ctx->tune.on(T_NO_THIN) &&
-           ((!ctx->bu_wide_lanes && ctx->Gf < 8) || !ctx->tune.on(T_NO_THIN_WIDE));
+           (ctx->cols.bu_shape().g < 8 || !ctx->tune.on(T_NO_THIN_WIDE));
 }
 static bool deep_top_down(const pml_ctx* ctx) {
-    return ctx->deep.ok && ctx->kind == PML_MODEL_F81 && !ctx->tune.on(T_NO_THIN) && (ctx->Gt < 8 || !ctx->tune.on(T_NO_THIN_WIDE));
+    return ctx->deep.ok && ctx->kind == PML_MODEL_F81 && !ctx->tune.on(T_NO_THIN) && (ctx->cols.Gt < 8 || !ctx->tune.on(T_NO_THIN_WIDE));
 }
 
 

@@ -59,8 +59,7 @@ static void launch_blocks_f81(pml_ctx* ctx, bool bottom_up, int which, bool sign
 
 
 int dispatch_blocks_f81(pml_ctx* ctx, bool bottom_up, int which, bool signal) {
-    int g, r;
-    multi_level_shape(ctx, bottom_up, g, r);
+    const auto [g, r] = ctx->cols.shape(bottom_up);
 #define X(G_, R_)                                           \
     if (g == G_ && r == R_) {                               \
         launch_blocks_f81<G_, R_>(ctx, bottom_up, which, signal);   \

@@ -26,8 +26,7 @@ static void launch_small_f81(pml_ctx* ctx, bool bottom_up, bool signal, int do_p
 // units / d_offsets: the level table to walk (default: the fused lists of the whole forest from first_level on)
 int dispatch_small_f81(pml_ctx* ctx, bool bottom_up, bool signal, int do_prep, int first_level, int n_levels,
                               const PmlUnit* units, const int* d_offsets, int skip_roots) {
-    int g, r;
-    multi_level_shape(ctx, bottom_up, g, r);
+    const auto [g, r] = ctx->cols.shape(bottom_up);
     const int reset_err = (units == nullptr && first_level == 0) ? 1 : 0;
     if (units == nullptr) {
         // (the lists sorted by shape inside every level where the forest has them: a wave of one shape runs that shape's

@@ -46,8 +46,7 @@ static void launch_stack_f81(pml_ctx* ctx, bool bottom_up, int a, int n) {
 
 int dispatch_super_f81(pml_ctx* ctx, bool bottom_up) {
     if (ctx->sup.n <= 0) return PML_OK;  // (a schedule of stacked units only)
-    int g, r;
-    super_shape(ctx, bottom_up, g, r);
+    const auto [g, r] = ctx->cols.shape(bottom_up);
 #define X(G_, R_)                                   \
     if (g == G_ && r == R_) {                       \
         launch_super_f81<G_, R_>(ctx, bottom_up);   \
@@ -64,8 +63,7 @@ int dispatch_stack_f81(pml_ctx* ctx, bool bottom_up, int level) {
     if (ctx->sup.n_stack == 0 || level + 1 >= (int)off.size()) return PML_OK;
     const int a = off[level], n = off[level + 1] - a;
     if (n <= 0) return PML_OK;
-    int g, r;
-    super_shape(ctx, bottom_up, g, r);
+    const auto [g, r] = ctx->cols.shape(bottom_up);
 #define X(G_, R_)                                         \
     if (g == G_ && r == R_) {                             \
         launch_stack_f81<G_, R_>(ctx, bottom_up, a, n);   \

@@ -13,7 +13,7 @@ static void launch_sweep(pml_ctx* ctx, SweepKind what, const int* level, int n_l
     const PmlModel m = model_of(ctx);
     if (window >= 0) {
         // P(t) of this launch's children from the window (pml_pij_window.h): eigen models beyond 32 states, whose lane shapes
-        // are 32 x 2, 64 x 2 and 64 x 4 (pick_group)
+        // are 32 x 2, 64 x 2 and 64 x 4 (pml_plan_columns)
         constexpr bool wide = G * R > 32 && R >= 2;
         constexpr int GG = wide ? G : 64, RR = wide ? R : 2;   // (keeps the other shapes from instantiating it)
         const PmlPWindow w = {ctx->d_pij_window, ctx->d_win_slot[window], ctx->pij_window};
@@ -89,25 +89,25 @@ int dispatch_sweep_matrix(pml_ctx* ctx, SweepKind what, const int* level, int n_
     if (n_level <= 0) return PML_OK;
     if (window >= 0) {
         const bool sweep = what == SW_BU_MARG || what == SW_BU_JOINT || what == SW_TD;
-        if (!sweep || ctx->pij_window <= 0 || !ctx->d_pij_window || !ctx->d_win_slot[window] || (long long)ctx->G * ctx->R <= 32 || ctx->R < 2)
-            return fail(PML_ERR_INVALID, "no P(t) window for sweep kind %d of a context with G=%d R=%d", (int)what, ctx->G, ctx->R);
+        if (!sweep || ctx->pij_window <= 0 || !ctx->d_pij_window || !ctx->d_win_slot[window] || (long long)ctx->cols.G * ctx->cols.R <= 32 || ctx->cols.R < 2)
+            return fail(PML_ERR_INVALID, "no P(t) window for sweep kind %d of a context with G=%d R=%d", (int)what, ctx->cols.G, ctx->cols.R);
     }
 #define X(G_, R_)                                             \
-    if (ctx->G == G_ && ctx->R == R_) {                       \
+    if (ctx->cols.G == G_ && ctx->cols.R == R_) {                       \
         launch_sweep<G_, R_>(ctx, what, level, n_level, window); \
         HIP_TRY(hipGetLastError());                           \
         return PML_OK;                                        \
     }
     PML_GR_CASES(X)
 #undef X
-    return fail(PML_ERR_UNSUPPORTED, "no kernel for G=%d R=%d", ctx->G, ctx->R);
+    return fail(PML_ERR_UNSUPPORTED, "no kernel for G=%d R=%d", ctx->cols.G, ctx->cols.R);
 }
 
 // lane shape of the selection kernel: 8 states per lane up to k = 64 (8 units per wavefront share the scalar work
 // and the arg-max butterflies stay inside a 16-lane row: 3.2 -> 2.6 ms per pass of 4 columns at cfg4 size),
 // else the matrix shapes
 int dispatch_select(pml_ctx* ctx, int method, int force_joint, const u64* d_lh_mask) {
-    int sg = ctx->G, sr = ctx->R;
+    int sg = ctx->cols.G, sr = ctx->cols.R;
     if (ctx->k <= 64) {
         sr = 8;
         sg = 1;
@@ -125,5 +125,5 @@ int dispatch_select(pml_ctx* ctx, int method, int force_joint, const u64* d_lh_m
     X(8, 8)
     X(64, 8)
 #undef X
-    return fail(PML_ERR_UNSUPPORTED, "no selection kernel for G=%d R=%d", ctx->G, ctx->R);
+    return fail(PML_ERR_UNSUPPORTED, "no selection kernel for G=%d R=%d", ctx->cols.G, ctx->cols.R);
 }

@@ -1,5 +1,6 @@
 // Host-side planning of the tree schedules (pml_schedule.h).
 #include "pml_schedule.h"
+#include "pml_columns.h"   // pml_bu_lanes
 
 #include <algorithm>
 #include <cstdarg>
@@ -359,7 +360,7 @@ PmlForest pml_plan_forest(PmlTreeArrays& t, const PmlTune& tune, bool fuse, PmlN
             if (f.kind[t.td_parents[q]] == PML_KIND_STORED) f.tdp.push_back(t.td_parents[q]);
         f.td_parent_offsets_f[l + 1] = (int)f.tdp.size();
     }
-    // Balanced parts (pml_chars_alloc: the lane shape of the bottom-up kernels) -- counted on the topology alone, whatever
+    // Balanced parts (pml_plan_columns: the lane shape of the bottom-up kernels) -- counted on the topology alone, whatever
     // the switches, so that the lane shape, and with it a column's bits, is a function of k and the forest.
     long long n_two = 0;
     for (int i = 0; i < N; ++i) n_two += two_level_root(t.first_child, t.n_children, i);
@@ -875,9 +876,9 @@ static int narrow_levels(const PmlSweepTraits& t, const std::vector<int>& off, i
         // ... but never below half a pass of the walking workgroup (512 threads, g lanes per unit): such a level is one
         // wavefront's work per SIMD either way, and a launch of its own costs 5 - 10 us where a level step inside the
         // walk costs 2.  Random 262 144-tip tree x 32 characters, marginal pass: k = 4 1.66 -> 1.52 ms, k = 12 2.56 -> 2.37,
-        // k = 64 unchanged (profiles/r05j_narrow_units.txt, r05l_narrow_ab.txt); same bits (multi_level_shape).
+        // k = 64 unchanged (profiles/r05j_narrow_units.txt, r05l_narrow_ab.txt); same bits (PmlColumnPlan::bu_shape).
         const bool td = top_down < 0 ? from_front : top_down != 0;   // (which sweep's lane shape walks the levels)
-        const int g = td ? t.Gt : (t.bu_wide_lanes ? 8 : t.Gf);
+        const int g = td ? t.Gt : pml_bu_lanes(t.bu_wide_lanes, t.Gf);
         limit = std::max(limit, 256 / std::max(1, g));
     }
     int n = 0;

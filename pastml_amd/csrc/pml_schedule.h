@@ -1,7 +1,8 @@
 // Tree schedules, planned on the host: the library's numbering of a forest, its fused level lists, the unit descriptors and
 // every schedule the sweeps walk (eigen joint tiers, back-trace tiers, two-level and stacked units, subtree blocks, thin
-// ends).  Plain C++ over plain tables: pml_tree_upload and pml_chars_alloc (pml_api.hip) call the planners and upload what
-// they return.  No HIP here, so that the planning can be built, tested and sanitised on any host.
+// ends).  Plain C++ over plain tables: pml_tree_upload (pml_api.hip) calls the tree's planners and uploads what they return;
+// pml_chars_alloc calls pml_plan_columns (pml_columns.h) and, where that plan asks for thin ends, pml_plan_thin_ends; the
+// sweeps call the launch planners.  No HIP here, so that the planning can be built, tested and sanitised on any host.
 #pragma once
 #include <cstdlib>
 #include <string>
@@ -25,6 +26,10 @@ struct __attribute__((aligned(32))) PmlUnit {
 };
 
 #define PML_PACKED_TWO_STORED ((1 << 11) | (1 << 8) | (3 << 4) | 2)  // two children, both stored nodes
+
+// threads of the workgroup that walks several levels in one launch (pml_kernels_f81.h: the single-launch kernels and the
+// subtree blocks); here because pml_plan_columns counts a level's passes of it
+#define PML_SMALL_BLOCK 512
 
 // ---------------------------------------------------------------------------------------------------------------------
 // Every switch of the schedules in one table per context.  The defaults come from the environment (PASTML_HIP_<NAME>) when
@@ -327,7 +332,7 @@ struct PmlSweepTraits {
     int k, W, C, sched_cols, n_roots, n_cherries;
     bool has_init, fuse;
     int Gf, Gt;
-    bool bu_wide_lanes, level_lists_sorted;
+    bool bu_wide_lanes, level_lists_sorted;   // (these four: copies of the PmlColumnPlan's, pml_columns.h)
     bool single_launch, blocks, super, thin, deep;   // single_launch_sweeps, block_schedule, super_sweeps, thin_bottom_up, deep_top_down
     int narrow_units;                                // NARROW_UNITS (0: not set)
     bool no_td_tail, no_eigg_tiers, no_spin_wait;
