@@ -596,6 +596,48 @@ int pml_simulate_states(pml_ctx* ctx, int32_t col, int32_t n_repetitions, int32_
 int pml_sample_scenarios(pml_ctx* ctx, int32_t col, int32_t n_repetitions, int32_t rep_offset, uint64_t seed,
                          void* states_out, int64_t* n_fallback_out);
 
+/*
+ * Stochastic character maps: n_repetitions whole histories of column col under the F81 family (F81, JC, EFT; k <= 512), drawn
+ * on the device.  Where pml_expected_history gives the posterior means of the dwell times and of the Markov jumps, this gives
+ * draws of them, for credible intervals.  The call draws the scenarios of pml_sample_scenarios (the same seed, the same bits;
+ * they stay on the device unless states_out asks for them) and then, for every branch, a history between its two end states.
+ * Q = mu (1 pi^T - I) is a Poisson process of rate mu whose events redraw the state from pi, so no rejection, no
+ * uniformisation bound and no matrix is needed.  In the notation of pml_expected_history -- L_n = (d_n + tau) tau_factor,
+ * x_n = mu t'_n, e_n the stored exp(-x_n) of the marginal pass -- for repetition g = rep_offset + r and a non-root node n whose
+ * parent is in state a and which is in state b:
+ *   1. the number of redraw events M.  x_n == 0: M = 0.  Otherwise q = 1.0 - e_n and u = draw 0.  a != b: target = u q.
+ *      a == b: Wa = q pi[a] + e_n, t = u Wa; t < e_n: M = 0; else target = (t - e_n) / pi[a].  M >= 1 by inversion over the terms
+ *      e x^m / m! (a zero-truncated Poisson):
+ *          term = e_n x_n; cum = term; m = 1
+ *          while cum <= target:  m += 1;  term = (term x_n) / m;  if cum + term == cum or m == 4096: stop;  cum += term
+ *          M = m
+ *   2. the spacings.  M >= 1: draws 1 .. M + 1 give w_i = -log((X_i + 0.5) 2^-32), i = 0 .. M (X the 32-bit word), Wsum their
+ *      sum left to right, dwell_i = (L_n w_i) / Wsum (normalised exponentials: the spacings of M uniform order statistics).
+ *      M = 0: the whole L_n is spent in a, no draw.
+ *   3. the states.  s_0 = a, s_M = b; draws M + 2 .. 2 M give s_1 .. s_{M-1}, each the bisection of the cumulative table of pi
+ *      (the one pml_simulate_states draws a root from) at u times its last entry, u = X 2^-32.  Interval i adds dwell_i to
+ *      times_out[r][s_i]; every i >= 1 with s_{i-1} != s_i adds 1 to jumps_out[r][s_{i-1}][s_i] and to branch_jumps_out[n][r].
+ *      Virtual events, which redraw the state they find, count nowhere.
+ * Draw d of (n, g) is word d & 3 of Philox-4x32-10 keyed by the seed with the counter (g, caller's id of n, d >> 2, a tag of this
+ * sampler's own); u = X 2^-32.  Every operation is rounded on its own.  The result is a pure function of (seed, node, global
+ * repetition): launch geometry, chunking and the library's numbering never show, and calls with consecutive rep_offsets make
+ * up one larger call.
+ *   states_out       [n_nodes][n_repetitions] as pml_sample_scenarios writes them, or NULL
+ *   times_out        [n_repetitions][k], units of smoothed branch length; a row sums to sum_n L_n
+ *   jumps_out        [n_repetitions][k][k] or NULL: the number of jumps i -> j, zero diagonal
+ *   branch_jumps_out [n_nodes][n_repetitions], caller's numbering, or NULL: the jumps on the branch above n; 0 for a root
+ *   n_fallback_out   as pml_sample_scenarios
+ * What is not asked for is not computed, and times_out has the same bits either way: no floating-point atomics -- the nodes are
+ * walked in the caller's numbering in pieces whose size depends on n_nodes only, one thread adds the dwells of a repetition in
+ * node order, and the pieces are summed in piece order.  The results of the marginal pass stay as they are.
+ * PML_ERR_INVALID: no marginal pml_bottom_up and pml_top_down_marginals before, k < 2, pi . pi >= 1.  PML_ERR_UNSUPPORTED: a
+ * context of HKY or eigen models, k > 512, or a branch with x_n > 512 (beyond it e_n leaves the normal doubles and the inversion
+ * loses its meaning: such branches are not drawn, and the message carries their number).
+ */
+int pml_sample_histories(pml_ctx* ctx, int32_t col, int32_t n_repetitions, int32_t rep_offset, uint64_t seed,
+                         void* states_out, double* times_out, uint32_t* jumps_out, uint16_t* branch_jumps_out,
+                         int64_t* n_fallback_out);
+
 /* ---- multi-GPU (one process per GPU) ----------------------------------------------------------------------------------- */
 /*
  * The characters of a run are independent (pastml/acr.py:213-231 hands them to a pool one by one, each with its own

@@ -1998,6 +1998,56 @@ int pml_sample_scenarios(pml_ctx* ctx, int32_t col, int32_t n_repetitions, int32
     return PML_OK;
 }
 
+// n_repetitions histories of column col under the F81 family (pml_launch_history_sample.hip): the scenarios of
+// pml_sample_scenarios, written to a device buffer in the same call (the same seed, the same bits; they go through the host only
+// if states_out asks for them), then on every branch the events between its two end states.
+int pml_sample_histories(pml_ctx* ctx, int32_t col, int32_t n_repetitions, int32_t rep_offset, uint64_t seed, void* states_out,
+                         double* times_out, uint32_t* jumps_out, uint16_t* branch_jumps_out, int64_t* n_fallback_out) {
+    PML_TRY(require_model(ctx));
+    if (col < 0 || col >= ctx->C || !times_out || !n_fallback_out) return fail(PML_ERR_INVALID, "pml_sample_histories: bad column / output");
+    if (n_repetitions <= 0) return fail(PML_ERR_INVALID, "pml_sample_histories: n_repetitions must be positive");
+    if (rep_offset < 0) return fail(PML_ERR_INVALID, "pml_sample_histories: rep_offset must not be negative");
+    if (ctx->k > 512) return fail(PML_ERR_UNSUPPORTED, "pml_sample_histories: k = %d, the F81 family holds at most 512 states", ctx->k);
+    PML_TRY(need_f81_pass(ctx, "pml_sample_histories", "history", col, col + 1));
+    PML_TRY(wait_pending(ctx, true));   // (a pass that ended in a spin on the completion word may have left the stream busy)
+    PML_TRY(write_marginal_pass(ctx));
+    const size_t k = ctx->k, N = (size_t)ctx->N, R = (size_t)n_repetitions;
+    const size_t es = k > 256 ? 2 : 1;
+    const size_t rs = (R + 3) / 4 * 4;
+    unsigned long long counters[2] = {0, 0};   // the scenarios' fallbacks, the branches not drawn
+    CallScope mem(ctx->stream, false);
+    unsigned char* d_states;
+    unsigned long long* d_counters;
+    double* d_times;
+    unsigned* d_jumps = nullptr;
+    unsigned short* d_branch = nullptr;
+    PML_TRY(mem.get(&d_states, N * rs * es));
+    PML_TRY(mem.get(&d_counters, 2));
+    PML_TRY(mem.get(&d_times, R * k));
+    HIP_TRY(hipMemsetAsync(d_counters, 0, sizeof(counters), ctx->stream));
+    if (jumps_out) {
+        PML_TRY(mem.get(&d_jumps, R * k * k));
+        HIP_TRY(hipMemsetAsync(d_jumps, 0, R * k * k * sizeof(unsigned), ctx->stream));
+    }
+    if (branch_jumps_out) PML_TRY(mem.get(&d_branch, N * R));
+    PML_TRY(launch_scenarios(ctx, col, n_repetitions, rep_offset, seed, d_states, rs, d_counters));
+    PML_TRY(launch_history_sample(ctx, mem, col, n_repetitions, rep_offset, seed, d_states, rs, d_times, d_jumps, d_branch,
+                                  d_counters + 1));
+    if (states_out)
+        HIP_TRY(hipMemcpy2DAsync(states_out, R * es, d_states, rs * es, R * es, N, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(hipMemcpyAsync(times_out, d_times, R * k * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+    if (jumps_out) HIP_TRY(hipMemcpyAsync(jumps_out, d_jumps, R * k * k * sizeof(unsigned), hipMemcpyDeviceToHost, ctx->stream));
+    if (branch_jumps_out)
+        HIP_TRY(hipMemcpyAsync(branch_jumps_out, d_branch, N * R * sizeof(unsigned short), hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(hipMemcpyAsync(counters, d_counters, sizeof(counters), hipMemcpyDeviceToHost, ctx->stream));
+    PML_TRY(mem.finish());
+    *n_fallback_out = (int64_t)counters[0];
+    if (counters[1])
+        return fail(PML_ERR_UNSUPPORTED, "pml_sample_histories: %llu branches have x = mu t' > 512 (PML_HSAMP_MAX_X), where exp(-x) leaves the "
+                    "normal doubles: they were not drawn and the outputs are not histories", counters[1]);
+    return PML_OK;
+}
+
 // Maximum parsimony of n_cols characters on the uploaded forest (pml_launch_parsimony.hip).  Needs the tree only: no columns,
 // no model, no likelihood vectors -- the scratch of the call is freed before it returns.
 int pml_parsimony(pml_ctx* ctx, int32_t n_cols, int32_t k, const uint64_t* given, int methods, uint64_t* sets_out,

@@ -32,7 +32,7 @@ struct PmlComm;  // pml_comm.h (pml_api.hip only)
 // sweep's own graph, or into the one graph of a whole marginal pass (the sweeps inside it keep no graphs of their own).
 enum PmlCapture { CAP_NONE, CAP_OWN, CAP_PASS };
 
-#define PML_VERSION 103
+#define PML_VERSION 104
 
 // internal linkage across the library's translation units (not part of the C-ABI)
 #define PML_INTERNAL __attribute__((visibility("hidden")))

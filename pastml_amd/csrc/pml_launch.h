@@ -208,6 +208,13 @@ PML_INTERNAL int launch_gradient(pml_ctx* ctx, CallScope& mem, int cb, int ce, d
 //      (pml_expected_history); device arrays d_times [cols][k], d_jumps [cols][k][k] or null, d_branch [cols][N] in the caller's
 //      numbering or null; queued only: partials and staged scalars go into the caller's scope, which waits
 PML_INTERNAL int launch_history(pml_ctx* ctx, CallScope& mem, int cb, int ce, double* d_times, double* d_jumps, double* d_branch);
+// ---- pml_launch_history_sample.hip: histories of column col drawn on the scenarios d_states [N][rs] that launch_scenarios left
+//      on the device (pml_sample_histories); device arrays d_times [n_rep][k], d_jumps [n_rep][k][k] (zeroed) or null, d_branch
+//      [N][n_rep] in the caller's numbering or null, d_skipped: one counter (zeroed); queued only: the partials go into the
+//      caller's scope, which waits
+PML_INTERNAL int launch_history_sample(pml_ctx* ctx, CallScope& mem, int col, int n_rep, int rep_offset, u64 seed, const void* d_states,
+                                       size_t rs, double* d_times, unsigned* d_jumps, unsigned short* d_branch,
+                                       unsigned long long* d_skipped);
 
 // More than 64 KB of dynamic LDS must be asked for: once per kernel, device and size (the largest asked for so far is what is
 // set) -- not per launch: the call is not free and should not sit inside a stream capture.  (A template: one table per kernel

@@ -115,6 +115,9 @@ SIGNATURES = {
     'pml_simulate_states': [_ctx_p, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_uint64, ctypes.c_void_p],
     'pml_sample_scenarios': [_ctx_p, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_uint64, ctypes.c_void_p,
                              ctypes.POINTER(ctypes.c_int64)],
+    'pml_sample_histories': [_ctx_p, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_uint64, ctypes.c_void_p,
+                             _c_double_p, ctypes.POINTER(ctypes.c_uint32), ctypes.POINTER(ctypes.c_uint16),
+                             ctypes.POINTER(ctypes.c_int64)],
     'pml_parsimony': [_ctx_p, ctypes.c_int32, ctypes.c_int32, _c_uint64_p, ctypes.c_int, _c_uint64_p,
                       ctypes.POINTER(ctypes.c_int64), ctypes.POINTER(ctypes.c_int64)],
     'pml_parsimony_info': [_ctx_p, ctypes.POINTER(ctypes.c_int64), _c_double_p],
@@ -903,6 +906,31 @@ class Engine(BareContext):
         _check(self._lib.pml_sample_scenarios(self._ctx, col, int(count), int(rep_offset), ctypes.c_uint64(int(seed)),
                                               out.ctypes.data_as(ctypes.c_void_p), ctypes.byref(fallen)))
         return out, fallen.value
+
+    def sample_histories(self, count, seed, rep_offset=0, col=0, jumps=True, branch_jumps=False, states=True):
+        """
+        count histories of column col drawn after a marginal pass, F81 family only (pml_sample_histories; include/pastml_hip.h
+        has the law): the scenarios of sample_scenarios for the same seed and, on every branch, the events between its two end
+        states.  Returns (states [n_nodes, count] as sample_scenarios gives them or None, times [count, k] in units of smoothed
+        branch length, jumps [count, k, k] uint32 -- the number of jumps i -> j, zero diagonal -- or None, branch_jumps
+        [n_nodes, count] uint16 in this engine's node numbering -- the jumps on the branch above each node -- or None, the
+        scenarios' n_fallback).  What is not asked for is not computed or not copied; times has the same bits either way.
+        Repetition r is keyed by (seed, node, rep_offset + r): consecutive calls with consecutive rep_offsets make up one call.
+        """
+        count = int(count)
+        dtype = np.uint8 if self.k <= 256 else np.uint16
+        states_out = np.empty((self.n_nodes, count), dtype=dtype) if states else None
+        times = np.empty((count, self.k), dtype=np.float64)
+        jumps_out = np.empty((count, self.k, self.k), dtype=np.uint32) if jumps else None
+        branch_out = np.empty((self.n_nodes, count), dtype=np.uint16) if branch_jumps else None
+        fallen = ctypes.c_int64(0)
+        _check(self._lib.pml_sample_histories(self._ctx, col, count, int(rep_offset), ctypes.c_uint64(int(seed)),
+                                              None if states_out is None else states_out.ctypes.data_as(ctypes.c_void_p),
+                                              _ptr(times, ctypes.c_double),
+                                              None if jumps_out is None else _ptr(jumps_out, ctypes.c_uint32),
+                                              None if branch_out is None else _ptr(branch_out, ctypes.c_uint16),
+                                              ctypes.byref(fallen)))
+        return states_out, times, jumps_out, branch_out, fallen.value
 
     @classmethod
     def tree_only(cls, flat, device=None, tune=None):
