@@ -386,6 +386,49 @@ int pml_expected_history(pml_ctx* ctx, int32_t col_begin, int32_t col_end, doubl
                          double* branch_jumps_out);
 
 /*
+ * pml_expected_history per time interval, with the number of lineages in each state at every boundary: exact, F81 family, from
+ * the vectors of the marginal pass (needs one, PML_ERR_INVALID otherwise).  Notation of pml_expected_history: x_n, L_n, S_n,
+ * o_n, O_n, v_n, the stored e_n inside m_n.
+ * Inputs: node_time[N], a time per node in the caller's numbering and in any unit (dates, root distances); a child must not be
+ * earlier than its parent.  boundaries[M + 1], T_0 < ... < T_M: bin m is [T_m, T_{m+1}), the last bin also contains T_M.
+ * Segments: a non-root node n with parent p and extent h = node_time[n] - node_time[p] > 0 has in every bin with
+ * lo = max(T_m, time_p) < hi = min(T_{m+1}, time_n) one segment with the fractions
+ *   s1 = (lo - time_p) / h,   w = (hi - lo) / h,   r = (time_n - hi) / h
+ * each formed exactly so, as one quotient of one difference of the given doubles (never as s2 - s1: a sliver next to a node keeps
+ * its digits).  A branch with h == 0 has smoothed length only: one segment s1 = 0, w = 1, r = 0 in the bin that contains time_n,
+ * none if no bin does.  What lies outside [T_0, T_M] is not counted.
+ * Per segment, with y = w x_n, (e_y, c0_y, c1_y) the e, c0, c1 of pml_expected_history at y (their series below 1),
+ * A = -expm1(-s1 x_n), B = -expm1(-r x_n):
+ *   C0  = w (c0_y + (A + B) c1_y + A B e_y)        multiplies pi_i O S
+ *   C1a = w (1 - A) (c1_y + B e_y)                 multiplies o_i S
+ *   C1b = w (1 - B) (c1_y + A e_y)                 multiplies pi_i O v_j
+ *   Cee = w (1 - A) (1 - B) e_y                    multiplies o_i v_j
+ *   a[i] = pi_i O S C0 + o_i S C1a,   b[i] = pi_i O C1b + o_i Cee
+ *   times_out[col][m][s]    += L_n (a[s] + b[s] v_n[s])
+ *   jumps_out[col][m][i][j] += x_n pi_j (a[i] + b[i] v_n[j])      (i != j; the diagonal is 0)
+ * Every term is non-negative, C0 + C1a + C1b + Cee = w, and with s1 = r = 0, w = 1 they are c0, c1, c1, e of
+ * pml_expected_history: the bins of a call that covers the tree sum to its outputs.
+ * Lineages: at every boundary T_m, over the branches with time_p <= T_m < time_n, at s = (T_m - time_p) / h, with
+ * A = -expm1(-s x), B = -expm1(-(1 - s) x), 1 - s formed as (time_n - T_m) / h:
+ *   lineages_out[col][m][j] += (1-A)(1-B) o_j v_j + (1-A) B o_j S + A (1-B) pi_j O v_j + A B pi_j O S
+ * the posterior of the state at that point of the branch, which sums over j to 1: sum_j lineages_out[col][m][j] is the number of
+ * branches alive at T_m.
+ * Outputs: times_out [cols][M][k]; jumps_out [cols][M][k][k] or NULL; lineages_out [cols][M + 1][k] or NULL.  What is NULL is
+ * not computed and times_out has the same bits either way; an empty bin is exact zeros.
+ * PML_ERR_UNSUPPORTED: a context of HKY or eigen models, k > 512, or M k^2 > 2^24 (PML_HIST_TIME_MAX_CELLS: every non-empty bin
+ * leaves at least one k x k partial per column in the call's scratch, 128 MiB per column at the bound).  PML_ERR_INVALID: no
+ * marginal pass, k < 2, a column whose pi . pi >= 1, M < 1, boundaries that are not strictly ascending, a child earlier than its
+ * parent (the message names the node), a value that is not finite.  A refused call leaves the context and the results of the
+ * marginal pass as they were.  No atomics: the segments are sorted by (bin, caller's id) and summed in pieces whose size depends
+ * on k only and which never straddle two bins, so the bits of every output do not depend on launch geometry, on the schedule
+ * switches, on the library's numbering, on which other columns are in the call or on how often it is called -- and a bin's rows
+ * of times_out and jumps_out do not depend on the other bins.
+ */
+#define PML_HIST_TIME_MAX_CELLS (1 << 24)
+int pml_history_through_time(pml_ctx* ctx, int32_t col_begin, int32_t col_end, const double* node_time, const double* boundaries,
+                             int32_t M, double* times_out, double* jumps_out, double* lineages_out);
+
+/*
  * Maximum parsimony of n_cols characters of k states (k <= 512) on the uploaded forest: the bottom-up pass
  * (pastml/parsimony.py:92-122) and, per bit of methods, ACCTRAN (:125-158), DOWNPASS (:161-210) and DELTRAN (:213-242, on
  * the DOWNPASS sets), each with the number of state changes its sets need (:360-380, summed over the trees) and the number

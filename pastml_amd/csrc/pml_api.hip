@@ -1944,6 +1944,54 @@ int pml_expected_history(pml_ctx* ctx, int32_t col_begin, int32_t col_end, doubl
     return mem.finish();
 }
 
+// The same per time interval, with the lineages at every boundary (pml_launch_history_time.hip).  The segment plan is made
+// here, on the host and in the caller's numbering (pml_time_segments.h) -- it does not depend on the column --, and uploaded
+// through the call's scope; plan and pieces are declared before the scope, whose wait ends the copies that read them.
+int pml_history_through_time(pml_ctx* ctx, int32_t col_begin, int32_t col_end, const double* node_time, const double* boundaries,
+                             int32_t M, double* times_out, double* jumps_out, double* lineages_out) {
+    PML_TRY(require_model(ctx));
+    PML_TRY(check_cols(ctx, col_begin, col_end));
+    if (!times_out || !node_time || !boundaries)
+        return fail(PML_ERR_INVALID, "pml_history_through_time: node_time, boundaries or times_out is NULL");
+    if (ctx->k > 512)
+        return fail(PML_ERR_UNSUPPORTED, "pml_history_through_time: k = %d, the F81 family holds at most 512 states", ctx->k);
+    PML_TRY(need_f81_pass(ctx, "pml_history_through_time", "history", col_begin, col_end));
+    if (M >= 1 && (long long)M * ctx->k * ctx->k > (long long)PML_HIST_TIME_MAX_CELLS)
+        return fail(PML_ERR_UNSUPPORTED, "pml_history_through_time: M k^2 = %lld is beyond %d (PML_HIST_TIME_MAX_CELLS): the partials "
+                    "of the bins would not fit the call's scratch; ask for fewer bins per call", (long long)M * ctx->k * ctx->k,
+                    PML_HIST_TIME_MAX_CELLS);
+    const size_t k = ctx->k, N = (size_t)ctx->N, cols = (size_t)(col_end - col_begin);
+    PmlTimeSegments plan;
+    PmlTimePieces pieces, jpieces;
+    {
+        std::vector<int> parent(N);   // the caller's numbering
+        const bool same = ctx->new_of_old.empty();
+        for (size_t i = 0; i < N; ++i) {
+            const int p = ctx->forest.parent[same ? i : (size_t)ctx->new_of_old[i]];
+            parent[i] = (p < 0 || same) ? p : ctx->old_of_new[p];
+        }
+        const std::string why = pml_plan_time_segments(parent.data(), node_time, (int)N, boundaries, M, plan);
+        if (!why.empty()) return fail(PML_ERR_INVALID, "pml_history_through_time: %s", why.c_str());
+    }
+    pieces = pml_cut_time_pieces(plan, history_time_piece(ctx->k), true);
+    if (jumps_out) jpieces = pml_cut_time_pieces(plan, history_time_jump_piece(ctx->k), false);
+    PML_TRY(wait_pending(ctx, true));   // (a pass that ended in a spin on the completion word may have left the stream busy)
+    PML_TRY(write_marginal_pass(ctx));
+    const size_t bins = (size_t)M;
+    CallScope mem(ctx->stream, false);
+    double *d_times, *d_jumps = nullptr, *d_lineages = nullptr;
+    PML_TRY(mem.get(&d_times, cols * bins * k));
+    if (jumps_out) PML_TRY(mem.get(&d_jumps, cols * bins * k * k));
+    if (lineages_out) PML_TRY(mem.get(&d_lineages, cols * (bins + 1) * k));
+    PML_TRY(launch_history_time(ctx, mem, col_begin, col_end, plan, pieces, jpieces, d_times, d_jumps, d_lineages));
+    HIP_TRY(hipMemcpyAsync(times_out, d_times, cols * bins * k * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+    if (jumps_out)
+        HIP_TRY(hipMemcpyAsync(jumps_out, d_jumps, cols * bins * k * k * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+    if (lineages_out)
+        HIP_TRY(hipMemcpyAsync(lineages_out, d_lineages, cols * (bins + 1) * k * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+    return mem.finish();
+}
+
 // n_repetitions scenarios of column col drawn forward from the roots (pml_launch_simulate.hip).  Needs a model, no sweep: the
 // per-branch e = exp(-mu t') (F81 family) or P(t) is prepared here.  The states are written in the caller's numbering on the
 // device, in rows padded to a multiple of 4 repetitions, and copied out without the padding.

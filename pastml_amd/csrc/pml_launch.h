@@ -3,6 +3,7 @@
 // instantiated for (the shapes themselves: pml_columns.h) and the predicates that say which family a context's sweeps take.
 #pragma once
 #include "pml_host.h"
+#include "pml_time_segments.h"
 
 // ---------------------------------------------------------------------------------------------------------------------
 // (G, R) dispatch
@@ -215,6 +216,14 @@ PML_INTERNAL int launch_history(pml_ctx* ctx, CallScope& mem, int cb, int ce, do
 PML_INTERNAL int launch_history_sample(pml_ctx* ctx, CallScope& mem, int col, int n_rep, int rep_offset, u64 seed, const void* d_states,
                                        size_t rs, double* d_times, unsigned* d_jumps, unsigned short* d_branch,
                                        unsigned long long* d_skipped);
+// ---- pml_launch_history_time.hip: the same per time interval, with the lineages at every boundary (pml_history_through_time).
+//      plan: the segments (pml_time_segments.h); pieces / jpieces: its cut by history_time_piece(k) with the pseudo-bin and by
+//      history_time_jump_piece(k) without -- all three the caller's, alive until its scope has waited.  Device arrays d_times
+//      [cols][M][k], d_jumps [cols][M][k][k] or null, d_lineages [cols][M + 1][k] or null; queued only
+PML_INTERNAL int history_time_piece(int k);
+PML_INTERNAL int history_time_jump_piece(int k);
+PML_INTERNAL int launch_history_time(pml_ctx* ctx, CallScope& mem, int cb, int ce, const PmlTimeSegments& plan, const PmlTimePieces& pieces,
+                                     const PmlTimePieces& jpieces, double* d_times, double* d_jumps, double* d_lineages);
 
 // More than 64 KB of dynamic LDS must be asked for: once per kernel, device and size (the largest asked for so far is what is
 // set) -- not per launch: the call is not free and should not sit inside a stream capture.  (A template: one table per kernel

@@ -112,6 +112,8 @@ SIGNATURES = {
     'pml_expected_counts': [_ctx_p, ctypes.c_int32, ctypes.c_int32, ctypes.POINTER(ctypes.c_uint8), _c_double_p, _c_double_p],
     'pml_loglik_gradient': [_ctx_p, ctypes.c_int32, ctypes.c_int32, _c_double_p, _c_double_p, _c_int32_p],
     'pml_expected_history': [_ctx_p, ctypes.c_int32, ctypes.c_int32, _c_double_p, _c_double_p, _c_double_p],
+    'pml_history_through_time': [_ctx_p, ctypes.c_int32, ctypes.c_int32, _c_double_p, _c_double_p, ctypes.c_int32, _c_double_p,
+                                 _c_double_p, _c_double_p],
     'pml_simulate_states': [_ctx_p, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_uint64, ctypes.c_void_p],
     'pml_sample_scenarios': [_ctx_p, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_uint64, ctypes.c_void_p,
                              ctypes.POINTER(ctypes.c_int64)],
@@ -878,6 +880,35 @@ class Engine(BareContext):
                                               None if jumps_out is None else _ptr(jumps_out, ctypes.c_double),
                                               None if branch_out is None else _ptr(branch_out, ctypes.c_double)))
         return times, jumps_out, branch_out
+
+    def history_through_time(self, node_times, boundaries, col_begin=0, col_end=None, jumps=True, lineages=True):
+        """
+        expected_history per time interval, and the lineages in each state at every boundary, of the columns [col_begin, col_end)
+        after a marginal pass, F81 family only (pml_history_through_time; include/pastml_hip.h has the sums).  node_times [n_nodes]:
+        a time per node in this engine's node numbering, in any unit (dates, root distances), no child earlier than its parent;
+        boundaries [M + 1], strictly ascending: bin m is [T_m, T_m+1), the last one also contains T_M.  Returns (times
+        [cols, M, k], jumps [cols, M, k, k] or None, lineages [cols, M + 1, k] or None -- the expected number of branches in each
+        state at each boundary).  What is not asked for is not computed.
+        """
+        col_end = self.n_cols if col_end is None else col_end
+        if not 0 <= col_begin < col_end <= self.n_cols:
+            raise ValueError('bad column range')
+        node_times = np.ascontiguousarray(node_times, dtype=np.float64)
+        if node_times.shape != (self.n_nodes,):
+            raise ValueError('one time per node expected')
+        boundaries = np.ascontiguousarray(boundaries, dtype=np.float64)
+        if boundaries.ndim != 1:
+            raise ValueError('boundaries must be a sequence of numbers')
+        M = len(boundaries) - 1
+        cols = col_end - col_begin
+        times = np.empty((cols, max(M, 0), self.k), dtype=np.float64)
+        jumps_out = np.empty((cols, max(M, 0), self.k, self.k), dtype=np.float64) if jumps else None
+        lineages_out = np.empty((cols, max(M, 0) + 1, self.k), dtype=np.float64) if lineages else None
+        _check(self._lib.pml_history_through_time(self._ctx, col_begin, col_end, _ptr(node_times, ctypes.c_double),
+                                                  _ptr(boundaries, ctypes.c_double), M, _ptr(times, ctypes.c_double),
+                                                  None if jumps_out is None else _ptr(jumps_out, ctypes.c_double),
+                                                  None if lineages_out is None else _ptr(lineages_out, ctypes.c_double)))
+        return times, jumps_out, lineages_out
 
     def simulate_states(self, n_repetitions, seed, col=0, rep_offset=0):
         """

@@ -876,3 +876,109 @@ def expected_history(forest, characters, models, branch_jumps=False):
                 result['branch_jumps'] = per_branch[c].copy()
             results[i] = result
     return results[0] if single else results
+
+
+# =====================================================================================================================
+# expected_history_through_time
+# =====================================================================================================================
+
+def time_bin_fractions(flat, node_times, boundaries):
+    """
+    float64 [M, N]: the fraction w of the branch above every node that lies in each time bin, formed as the segment plan of
+    ``pml_history_through_time`` forms it: (min(T_m+1, time_n) - max(T_m, time_p)) / (time_n - time_p) where that is positive; a
+    branch without extent counts whole in the bin that contains its time (the last bin contains the last boundary); a root: 0.
+    """
+    T = np.asarray(boundaries, dtype=np.float64)
+    t = np.asarray(node_times, dtype=np.float64)
+    M = len(T) - 1
+    has_parent = flat.parent >= 0
+    tn = t
+    tp = np.where(has_parent, t[np.maximum(flat.parent, 0)], t)
+    h = tn - tp
+    flat_branch = has_parent & (h == 0)
+    safe = np.where(h > 0, h, 1.0)
+    out = np.zeros((M, flat.n_nodes), dtype=np.float64)
+    for m in range(M):
+        lo, hi = np.maximum(T[m], tp), np.minimum(T[m + 1], tn)
+        out[m] = np.where(has_parent & (h > 0) & (hi > lo), (hi - lo) / safe, 0.0)
+        inside = (T[m] <= tn) & ((tn < T[m + 1]) | ((m == M - 1) & (tn == T[M])))
+        out[m][flat_branch & inside] = 1.0
+    return out
+
+
+def expected_history_through_time(forest, characters, models, boundaries, root_dates=None, node_dates=None, jumps=True):
+    """
+    ``expected_history`` per time interval: the exact expected dwell time in each state and number of jumps i -> j inside every
+    bin of a dated forest, and the expected number of lineages in each state at every boundary, for one character or a list of
+    them under F81-family models (F81, JC, EFT) -- ``pml_history_through_time``, HIP; include/pastml_hip.h has the sums.  A
+    branch that crosses a boundary is split inside the branch, in closed form; jumps divided by dwell time is a rate per interval.
+
+    Node times come from ``pastml_amd.tree.annotate_dates(flat, root_dates, given=node_dates)``: the distance from the root
+    where nothing is given.  Characters are grouped by their number of states; a group is one batch on the device: one marginal
+    pass (masks altered where tau == 0, restored afterwards) and one pass over its columns.  HKY and the eigen models, the
+    file-level front end and sharding over ranks are not covered.
+
+    :param characters: a character (feature name) or a list of them; models: a model or a list, one per character
+    :param boundaries: an ascending sequence T_0 < ... < T_M -- bin m is [T_m, T_m+1), the last one also contains T_M --, or an
+        int M for M equal bins from the earliest root to the latest tip
+    :param root_dates, node_dates: as ``annotate_dates`` takes them (node_dates: float64 [N] in FlatForest node order, NaN where
+        no date is given)
+    :param jumps: False leaves the jumps out (``jumps`` is None then)
+    :return: per character a dict with ``log_likelihood``; ``states``; ``boundaries`` [M + 1]; ``times`` [M, k] in units of
+        smoothed branch length ((dist + tau) * tau_factor), a row summing to its ``bin_length``; ``jumps`` [M, k, k], zero
+        diagonals; ``lineages`` [M + 1, k], a row summing to the number of branches alive at that boundary; ``bin_length`` [M]:
+        the smoothed tree length inside each bin; and ``tree_length``.
+    """
+    from pastml_amd import sharding
+    from pastml_amd.batch import CharacterBatch, LikelihoodError, annotation_words, likelihood_error
+    from pastml_amd.models import KIND_F81
+    from pastml_amd.tree import annotate_dates
+    if isinstance(forest, TreeNode):
+        forest = [forest]
+    single = isinstance(characters, str)
+    if single:
+        characters, models = [characters], [models]
+    characters, models = list(characters), list(models)
+    if len(characters) != len(models):
+        raise ValueError('one model per character expected')
+    for character, model in zip(characters, models):
+        if model.kernel_spec()['kind'] != KIND_F81:
+            raise NotImplementedError('Character {}: expected_history_through_time is for the F81 family (F81, JC, EFT), not for {} '
+                                      '(PML_ERR_UNSUPPORTED).'.format(character, getattr(model, 'name', type(model).__name__)))
+    world = sharding.rank_world()[1]
+    if world > 1:
+        raise NotImplementedError('expected_history_through_time is not supported under a multi-process launch ({} ranks): run '
+                                  'it in a single process'.format(world))
+    flat = get_flat_forest(forest)
+    node_times = annotate_dates(flat, root_dates, given=node_dates)
+    if isinstance(boundaries, (int, np.integer)):
+        if boundaries < 1:
+            raise ValueError('at least one time bin is needed')
+        boundaries = np.linspace(node_times[flat.parent < 0].min(), node_times[flat.tips].max(), int(boundaries) + 1)
+    boundaries = np.array(boundaries, dtype=np.float64)
+    if boundaries.ndim != 1 or len(boundaries) < 2 or not np.isfinite(boundaries).all() or not (np.diff(boundaries) > 0).all():
+        raise ValueError('boundaries must be two or more finite, strictly ascending numbers')
+    groups = {}
+    for i, model in enumerate(models):
+        groups.setdefault(len(model.states), []).append(i)
+    results = [None] * len(characters)
+    has_parent = flat.parent >= 0
+    fractions = time_bin_fractions(flat, node_times, boundaries)
+    for k, members in groups.items():
+        group_models = [models[i] for i in members]
+        with CharacterBatch(flat, k, len(members)) as batch:
+            for c, i in enumerate(members):
+                batch.set_annotation(c, *annotation_words(flat, characters[i], models[i].states))
+            batch.initialize_allowed_states()
+            try:
+                lnl, times, jumps_out, lineages = batch.history_through_time(group_models, node_times, boundaries, jumps=jumps)
+            except LikelihoodError as e:
+                raise likelihood_error(flat, e)
+        for c, i in enumerate(members):
+            _, tau, tau_factor = models[i].rate_params()
+            length = np.where(has_parent, (flat.dist + tau) * tau_factor, 0.0)
+            results[i] = dict(log_likelihood=float(lnl[c]), states=np.array(models[i].states), boundaries=boundaries.copy(),
+                              times=times[c].copy(), jumps=None if jumps_out is None else jumps_out[c].copy(),
+                              lineages=lineages[c].copy(), bin_length=fractions.dot(length),
+                              tree_length=float(((flat.dist[has_parent] + tau) * tau_factor).sum()))
+    return results[0] if single else results
