@@ -681,6 +681,53 @@ int pml_sample_histories(pml_ctx* ctx, int32_t col, int32_t n_repetitions, int32
                          void* states_out, double* times_out, uint32_t* jumps_out, uint16_t* branch_jumps_out,
                          int64_t* n_fallback_out);
 
+/*
+ * pml_sample_histories per time interval: the sampled counterpart of pml_history_through_time, for credible intervals of the
+ * rate i -> j in a period and of the number of lineages in a state at a date.  Repetition g = rep_offset + r of node n has
+ * exactly the history pml_sample_histories draws for the same seed -- the same scenarios, the same draws (the same Philox counter),
+ * the same event count M, exponentials w_0 .. w_M, Wsum and states s_0 = a, .., s_M = b.  New is only where on the branch the
+ * events lie and how the history is cut at the boundaries.  node_time, boundaries, M and the bins are those of
+ * pml_history_through_time, and so are the segments of a branch: s1, w, the flag `starts` (the branch is alive at the boundary
+ * the bin begins with) and the zero-width point segments of the pseudo-bin M at T_M.
+ *   Positions.  c_0 = 0; P_i = w_0 + .. + w_{i-1}, summed left to right, and c_i = P_i / Wsum for i = 1 .. M; c_{M+1} = 1, set and
+ *      not computed.  History interval i is [c_i, c_{i+1}) in state s_i; event i >= 1 happens at c_i.
+ *   Upper ends.  s2 of a segment is the s1 of the same branch's segment in the next bin (for a branch that leaves the range: of its
+ *      point segment at T_M) -- the same quotient (T_{m+1} - time_p) / h, hence the same double; never s1 + w or 1 - r.  Where
+ *      the branch ends inside the bin (every branch with h == 0 as well) s2 = 1 with the end included.  The segments of a branch
+ *      tile it without gap or overlap, in bits: a position c belongs to the one segment with s1 <= c < s2 (<= 1 for the last).
+ *      What lies outside [T_0, T_M] counts nowhere.
+ *   Dwell.  Interval i gives segment (n, m) the time L_n w -- the segment's own w: a sliver keeps its digits, and a branch
+ *      without events gives L_n w with no draw beyond draw 0 -- if c_i <= s1 and s2 <= c_{i+1}; otherwise lo = max(c_i, s1),
+ *      hi = min(c_{i+1}, s2), v = hi - lo and, where v > 0, the time L_n v.  It is added to times_out[r][m][s_i].
+ *   Jumps.  Event i >= 1 with s_{i-1} != s_i whose position belongs to segment (n, m) adds 1 to jumps_out[r][m][s_{i-1}][s_i].
+ *      Virtual events count nowhere.
+ *   Lineages.  Every segment with `starts`, those of the pseudo-bin M included, adds 1 to lineages_out[r][m][s_i] for the largest
+ *      i with c_i <= s1: an event exactly at the boundary has already happened, and a branch that begins at the boundary
+ *      (s1 == 0) shows its parent's state.  sum_j lineages_out[r][m][j] is the number of branches alive at T_m.
+ * Every operation is rounded on its own.  With bins that cover the tree, the jumps of a repetition sum over the bins to
+ * pml_sample_histories' exactly and its times to rounding.
+ *   states_out     [n_nodes][n_repetitions] as pml_sample_scenarios writes them, or NULL
+ *   times_out      [n_repetitions][M][k], units of smoothed branch length
+ *   jumps_out      [n_repetitions][M][k][k] or NULL, zero diagonal
+ *   lineages_out   [n_repetitions][M + 1][k] or NULL
+ *   n_fallback_out as pml_sample_scenarios
+ * What is NULL is not computed, and times_out has the same bits either way.  No floating-point atomics: the segments are sorted
+ * by (bin, caller's id) and cut into pieces whose size depends on n_nodes only and which never straddle two bins; one thread adds
+ * the dwells of a repetition in segment order and the pieces of a bin are summed in piece order.  The bits of every output are a
+ * pure function of (seed, node, global repetition, the times, the boundaries): launch geometry, the schedule switches, the
+ * library's numbering and chunking never show, calls with consecutive rep_offsets make up one larger call, and the rows of a bin
+ * do not depend on the other bins.  The generator is counter-based: a branch that spans B bins is derived B times.  The results
+ * of the marginal pass stay as they are.
+ * PML_ERR_INVALID: what pml_sample_histories and pml_history_through_time answer with it (no marginal pass, k < 2, pi . pi >= 1;
+ * M < 1, boundaries that are not strictly ascending, a child earlier than its parent -- the message names the node --, a value
+ * that is not finite).  PML_ERR_UNSUPPORTED: a context of HKY or eigen models, k > 512, M k^2 > PML_HIST_TIME_MAX_CELLS, or a
+ * branch with x_n > 512 (not drawn; the message carries their number, over the whole forest).  A refused call leaves the context
+ * answering.
+ */
+int pml_sample_histories_through_time(pml_ctx* ctx, int32_t col, int32_t n_repetitions, int32_t rep_offset, uint64_t seed,
+                                      const double* node_time, const double* boundaries, int32_t M, void* states_out,
+                                      double* times_out, uint32_t* jumps_out, uint32_t* lineages_out, int64_t* n_fallback_out);
+
 /* ---- multi-GPU (one process per GPU) ----------------------------------------------------------------------------------- */
 /*
  * The characters of a run are independent (pastml/acr.py:213-231 hands them to a pool one by one, each with its own

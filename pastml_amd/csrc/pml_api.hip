@@ -2096,6 +2096,80 @@ int pml_sample_histories(pml_ctx* ctx, int32_t col, int32_t n_repetitions, int32
     return PML_OK;
 }
 
+// The same histories cut at the boundaries of M time bins (pml_launch_history_time_sample.hip): the scenarios as above, the
+// segment plan of pml_history_through_time with its upper ends (pml_time_segments.h), made on the host in the caller's numbering.
+// The plan and the tables derived from it are declared before the scope, whose wait ends the copies that read them.
+int pml_sample_histories_through_time(pml_ctx* ctx, int32_t col, int32_t n_repetitions, int32_t rep_offset, uint64_t seed,
+                                      const double* node_time, const double* boundaries, int32_t M, void* states_out,
+                                      double* times_out, uint32_t* jumps_out, uint32_t* lineages_out, int64_t* n_fallback_out) {
+    PML_TRY(require_model(ctx));
+    if (col < 0 || col >= ctx->C || !times_out || !n_fallback_out)
+        return fail(PML_ERR_INVALID, "pml_sample_histories_through_time: bad column / output");
+    if (!node_time || !boundaries) return fail(PML_ERR_INVALID, "pml_sample_histories_through_time: node_time or boundaries is NULL");
+    if (n_repetitions <= 0) return fail(PML_ERR_INVALID, "pml_sample_histories_through_time: n_repetitions must be positive");
+    if (rep_offset < 0) return fail(PML_ERR_INVALID, "pml_sample_histories_through_time: rep_offset must not be negative");
+    if (ctx->k > 512)
+        return fail(PML_ERR_UNSUPPORTED, "pml_sample_histories_through_time: k = %d, the F81 family holds at most 512 states", ctx->k);
+    PML_TRY(need_f81_pass(ctx, "pml_sample_histories_through_time", "history", col, col + 1));
+    if (M >= 1 && (long long)M * ctx->k * ctx->k > (long long)PML_HIST_TIME_MAX_CELLS)
+        return fail(PML_ERR_UNSUPPORTED, "pml_sample_histories_through_time: M k^2 = %lld is beyond %d (PML_HIST_TIME_MAX_CELLS): the "
+                    "jump tables of a repetition would not fit the call's scratch; ask for fewer bins per call",
+                    (long long)M * ctx->k * ctx->k, PML_HIST_TIME_MAX_CELLS);
+    const size_t k = ctx->k, N = (size_t)ctx->N, R = (size_t)n_repetitions;
+    HistoryTimeSamplePlan host;
+    {
+        std::vector<int> parent(N);   // the caller's numbering
+        const bool same = ctx->new_of_old.empty();
+        for (size_t i = 0; i < N; ++i) {
+            const int p = ctx->forest.parent[same ? i : (size_t)ctx->new_of_old[i]];
+            parent[i] = (p < 0 || same) ? p : ctx->old_of_new[p];
+        }
+        const std::string why = pml_plan_time_segments(parent.data(), node_time, (int)N, boundaries, M, host.plan);
+        if (!why.empty()) return fail(PML_ERR_INVALID, "pml_sample_histories_through_time: %s", why.c_str());
+    }
+    host.ends = pml_time_segment_ends(host.plan);
+    host.pieces = pml_cut_time_pieces(host.plan, history_time_sample_piece(ctx->N), lineages_out != nullptr);
+    PML_TRY(wait_pending(ctx, true));   // (a pass that ended in a spin on the completion word may have left the stream busy)
+    PML_TRY(write_marginal_pass(ctx));
+    const size_t bins = (size_t)M;
+    const size_t es = k > 256 ? 2 : 1;
+    const size_t rs = (R + 3) / 4 * 4;
+    unsigned long long counters[2] = {0, 0};   // the scenarios' fallbacks, the branches not drawn
+    CallScope mem(ctx->stream, false);
+    unsigned char* d_states;
+    unsigned long long* d_counters;
+    double* d_times;
+    unsigned *d_jumps = nullptr, *d_lineages = nullptr;
+    PML_TRY(mem.get(&d_states, N * rs * es));
+    PML_TRY(mem.get(&d_counters, 2));
+    PML_TRY(mem.get(&d_times, R * bins * k));
+    HIP_TRY(hipMemsetAsync(d_counters, 0, sizeof(counters), ctx->stream));
+    if (jumps_out) {
+        PML_TRY(mem.get(&d_jumps, R * bins * k * k));
+        HIP_TRY(hipMemsetAsync(d_jumps, 0, R * bins * k * k * sizeof(unsigned), ctx->stream));
+    }
+    if (lineages_out) {
+        PML_TRY(mem.get(&d_lineages, R * (bins + 1) * k));
+        HIP_TRY(hipMemsetAsync(d_lineages, 0, R * (bins + 1) * k * sizeof(unsigned), ctx->stream));
+    }
+    PML_TRY(launch_history_time_sample(ctx, mem, col, n_repetitions, rep_offset, seed, d_states, rs, host, d_times, d_jumps,
+                                       d_lineages, d_counters, d_counters + 1));
+    if (states_out)
+        HIP_TRY(hipMemcpy2DAsync(states_out, R * es, d_states, rs * es, R * es, N, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(hipMemcpyAsync(times_out, d_times, R * bins * k * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+    if (jumps_out)
+        HIP_TRY(hipMemcpyAsync(jumps_out, d_jumps, R * bins * k * k * sizeof(unsigned), hipMemcpyDeviceToHost, ctx->stream));
+    if (lineages_out)
+        HIP_TRY(hipMemcpyAsync(lineages_out, d_lineages, R * (bins + 1) * k * sizeof(unsigned), hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(hipMemcpyAsync(counters, d_counters, sizeof(counters), hipMemcpyDeviceToHost, ctx->stream));
+    PML_TRY(mem.finish());
+    *n_fallback_out = (int64_t)counters[0];
+    if (counters[1])
+        return fail(PML_ERR_UNSUPPORTED, "pml_sample_histories_through_time: %llu branches have x = mu t' > 512 (PML_HSAMP_MAX_X), where "
+                    "exp(-x) leaves the normal doubles: they were not drawn and the outputs are not histories", counters[1]);
+    return PML_OK;
+}
+
 // Maximum parsimony of n_cols characters on the uploaded forest (pml_launch_parsimony.hip).  Needs the tree only: no columns,
 // no model, no likelihood vectors -- the scratch of the call is freed before it returns.
 int pml_parsimony(pml_ctx* ctx, int32_t n_cols, int32_t k, const uint64_t* given, int methods, uint64_t* sets_out,

@@ -224,6 +224,23 @@ PML_INTERNAL int history_time_piece(int k);
 PML_INTERNAL int history_time_jump_piece(int k);
 PML_INTERNAL int launch_history_time(pml_ctx* ctx, CallScope& mem, int cb, int ce, const PmlTimeSegments& plan, const PmlTimePieces& pieces,
                                      const PmlTimePieces& jpieces, double* d_times, double* d_jumps, double* d_lineages);
+// ---- pml_launch_history_time_sample.hip: the histories of launch_history_sample cut at the boundaries of time bins
+//      (pml_sample_histories_through_time), launch_scenarios into d_states [N][rs] included (d_fallback: its counter, zeroed).  host: the caller's -- plan, ends and pieces (cut by history_time_sample_piece(N), with
+//      the pseudo-bin if the lineages are asked for) filled in, the tables the launcher derives from them left to it --, alive until
+//      the caller's scope has waited.  Device arrays d_times [n_rep][M][k], d_jumps [n_rep][M][k][k] (zeroed) or null, d_lineages
+//      [n_rep][M + 1][k] (zeroed) or null, d_skipped: one counter (zeroed); queued only
+struct HistoryTimeSamplePlan {
+    PmlTimeSegments plan;
+    PmlTimeSegmentEnds ends;
+    PmlTimePieces pieces;
+    std::vector<int> flags, piece_bin;
+    std::vector<double> pos;
+};
+PML_INTERNAL int history_time_sample_piece(int N);
+PML_INTERNAL int launch_history_time_sample(pml_ctx* ctx, CallScope& mem, int col, int n_rep, int rep_offset, u64 seed,
+                                            void* d_states, size_t rs, HistoryTimeSamplePlan& host, double* d_times,
+                                            unsigned* d_jumps, unsigned* d_lineages, unsigned long long* d_fallback,
+                                            unsigned long long* d_skipped);
 
 // More than 64 KB of dynamic LDS must be asked for: once per kernel, device and size (the largest asked for so far is what is
 // set) -- not per launch: the call is not free and should not sit inside a stream capture.  (A template: one table per kernel

@@ -89,3 +89,22 @@ PmlTimePieces pml_cut_time_pieces(const PmlTimeSegments& plan, int piece, bool w
     }
     return out;
 }
+
+PmlTimeSegmentEnds pml_time_segment_ends(const PmlTimeSegments& plan) {
+    PmlTimeSegmentEnds out;
+    const size_t total = (size_t)plan.n_segments();
+    out.s2.assign(total, 1.0);
+    out.ends.assign(total, 1);
+    for (int m = 0; m < plan.M; ++m) {
+        // the ids ascend within a bin: the branch's segment of the next bin by bisection
+        const int* next = plan.node.data() + plan.bin_off[m + 1];
+        const int* next_end = plan.node.data() + plan.bin_off[m + 2];
+        for (int i = plan.bin_off[m]; i < plan.bin_off[m + 1]; ++i) {
+            const int* at = std::lower_bound(next, next_end, plan.node[i]);
+            if (at == next_end || *at != plan.node[i]) continue;
+            out.s2[i] = plan.frac[4 * (size_t)(at - plan.node.data())];
+            out.ends[i] = 0;
+        }
+    }
+    return out;
+}

@@ -44,3 +44,15 @@ struct PmlTimePieces {
     int n_pieces() const { return piece_off.empty() ? 0 : (int)piece_off.size() - 1; }
 };
 PML_PLAN PmlTimePieces pml_cut_time_pieces(const PmlTimeSegments& plan, int piece, bool with_points);
+
+// The upper ends of the segments, for what places points on a branch (pml_sample_histories_through_time): s2 of a segment is
+// the s1 of the same branch's segment in the next bin -- the same quotient (T_{m+1} - time_p) / h, hence the same double --,
+// for a branch that leaves the range the s1 of its point segment at T_M.  Where the branch ends inside the bin (no segment in
+// the next bin: r == 0, every h == 0 branch, every point segment) s2 = 1 and `ends` is set: the end belongs to the segment.  The
+// segments of a branch then tile it without gap or overlap, in bits: a point c lies in the one segment with s1 <= c < s2 (or,
+// with `ends`, s1 <= c).  Never s1 + w or 1 - r: neighbours would disagree by an ulp.  From the plan alone.
+struct PmlTimeSegmentEnds {
+    std::vector<double> s2;   // [segments]
+    std::vector<int> ends;    // [segments]
+};
+PML_PLAN PmlTimeSegmentEnds pml_time_segment_ends(const PmlTimeSegments& plan);

@@ -120,6 +120,10 @@ SIGNATURES = {
     'pml_sample_histories': [_ctx_p, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_uint64, ctypes.c_void_p,
                              _c_double_p, ctypes.POINTER(ctypes.c_uint32), ctypes.POINTER(ctypes.c_uint16),
                              ctypes.POINTER(ctypes.c_int64)],
+    'pml_sample_histories_through_time': [_ctx_p, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_uint64, _c_double_p,
+                                          _c_double_p, ctypes.c_int32, ctypes.c_void_p, _c_double_p,
+                                          ctypes.POINTER(ctypes.c_uint32), ctypes.POINTER(ctypes.c_uint32),
+                                          ctypes.POINTER(ctypes.c_int64)],
     'pml_parsimony': [_ctx_p, ctypes.c_int32, ctypes.c_int32, _c_uint64_p, ctypes.c_int, _c_uint64_p,
                       ctypes.POINTER(ctypes.c_int64), ctypes.POINTER(ctypes.c_int64)],
     'pml_parsimony_info': [_ctx_p, ctypes.POINTER(ctypes.c_int64), _c_double_p],
@@ -962,6 +966,39 @@ class Engine(BareContext):
                                               None if branch_out is None else _ptr(branch_out, ctypes.c_uint16),
                                               ctypes.byref(fallen)))
         return states_out, times, jumps_out, branch_out, fallen.value
+
+    def sample_histories_through_time(self, node_times, boundaries, count, seed, rep_offset=0, col=0, jumps=True, lineages=True,
+                                      states=True):
+        """
+        The histories of sample_histories for the same seed, cut at the boundaries of time bins (pml_sample_histories_through_time;
+        include/pastml_hip.h has the law): the sampled counterpart of history_through_time, whose node_times and boundaries these
+        are.  Returns (states [n_nodes, count] as sample_scenarios gives them or None, times [count, M, k] in units of smoothed
+        branch length, jumps [count, M, k, k] uint32 or None, lineages [count, M + 1, k] uint32 -- the branches in each state at
+        each boundary -- or None, the scenarios' n_fallback).  What is not asked for is not computed or not copied; times has the
+        same bits either way.  Consecutive calls with consecutive rep_offsets make up one call.
+        """
+        count = int(count)
+        node_times = np.ascontiguousarray(node_times, dtype=np.float64)
+        if node_times.shape != (self.n_nodes,):
+            raise ValueError('one time per node expected')
+        boundaries = np.ascontiguousarray(boundaries, dtype=np.float64)
+        if boundaries.ndim != 1:
+            raise ValueError('boundaries must be a sequence of numbers')
+        M = len(boundaries) - 1
+        bins = max(M, 0)
+        dtype = np.uint8 if self.k <= 256 else np.uint16
+        states_out = np.empty((self.n_nodes, max(count, 0)), dtype=dtype) if states else None
+        times = np.empty((max(count, 0), bins, self.k), dtype=np.float64)
+        jumps_out = np.empty((max(count, 0), bins, self.k, self.k), dtype=np.uint32) if jumps else None
+        lineages_out = np.empty((max(count, 0), bins + 1, self.k), dtype=np.uint32) if lineages else None
+        fallen = ctypes.c_int64(0)
+        _check(self._lib.pml_sample_histories_through_time(
+            self._ctx, col, count, int(rep_offset), ctypes.c_uint64(int(seed)), _ptr(node_times, ctypes.c_double),
+            _ptr(boundaries, ctypes.c_double), M,
+            None if states_out is None else states_out.ctypes.data_as(ctypes.c_void_p), _ptr(times, ctypes.c_double),
+            None if jumps_out is None else _ptr(jumps_out, ctypes.c_uint32),
+            None if lineages_out is None else _ptr(lineages_out, ctypes.c_uint32), ctypes.byref(fallen)))
+        return states_out, times, jumps_out, lineages_out, fallen.value
 
     @classmethod
     def tree_only(cls, flat, device=None, tune=None):
