@@ -1,7 +1,7 @@
 """
-TEST INFRASTRUCTURE: the inputs on which the sum sweeps of the matrix models (eigen models, HKY) are held to exact arithmetic
-(tests/matrix_exact_ref.py), shared by tests/test_matrix_exact_ref.py (the oracle, CPU) and tests/test_gpu_eigen_shapes.py (the
-device).  Host arithmetic only.
+TEST INFRASTRUCTURE: the inputs on which the sum sweeps and the joint sweep of the matrix models (eigen models, HKY) are held to
+exact arithmetic (tests/matrix_exact_ref.py), shared by tests/test_matrix_exact_ref.py (the oracle, CPU) and
+tests/test_gpu_eigen_shapes.py, tests/test_gpu_joint_shapes.py (the device).  Host arithmetic only.
 
 For a state count k:
 
@@ -13,6 +13,9 @@ For a state count k:
                tail of the pair loop over children.  Top-down the depths hold 2, 8, 136 and 272 nodes: the first two are the
                narrow launch (a single narrow depth gets no launch of its own kind -- pml_schedule.cpp, narrow_levels -- which is
                why the 8 hang under 2 nodes and not under the root), the cherries and the tips a level launch each.
+    forest J   (joint sweep) by hand: a root, 2 children, n cherries under them: one level launch of the joint kernels over n nodes,
+               n chosen per k for three passes per wave (j_cherries), and the narrow launch above.
+    forest T   (joint sweep beyond 64 states) ((a,b),(c,d),e).
     column 0   every tip observed (the gathered first product of the tip launch), tau = 0, tf = 1.
     column 1   random_masks: missing and ambiguous tips, restricted internal nodes; tau > 0, tf < 1.  Its own model and rates.
 
@@ -233,6 +236,184 @@ def polytomy_forest(k):
         masks[index[key]] = 0
         masks[index[key], s] = 1
     return dict(flat=flat, spec=spec, rates=rates, masks=masks, fan=fan, polytomies=np.array([index[id(n)] for n in polys]))
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# the joint (max-product) sweep: tests/test_gpu_joint_shapes.py, and the oracle in tests/test_matrix_exact_ref.py
+# ---------------------------------------------------------------------------------------------------------------------
+JOINT_WAVES = 4             # PML_WAVES_PER_BLOCK
+JOINT_MIN_BLOCKS = 8        # launch_eigen_joint / launch_eigen_joint_tips: cap = max(8, EIGJ_BLOCKS / C)
+J_TUNE = dict(EIGJ_BLOCKS=1, EIGJ_TIP_BLOCKS=1)
+HKY_J_CHERRIES = 258        # above the plain narrow limit max(8, 512 / C) = 256 at two columns
+
+
+def joint_narrow_limit(k):
+    """Nodes per level up to which the joint sweep's levels next to the roots share one launch (pml_plan_bottom_up, BU_EIGJ)."""
+    return JOINT_WAVES * (64 // k)
+
+
+def j_cherries(k):
+    """
+    The width n of forest J(k)'s level of cherries.
+
+    Up to 32 states, under J_TUNE: launch_eigen_joint takes blocks = min(ceil(n / (4 npw)), max(8, 1 / C)) = 8 workgroups of 4
+    waves, and eigen_joint_kernel gives wave w the nodes [w npw + p stride, w npw + p stride + npw) in its pass p, with stride =
+    32 npw.  With n = 64 npw + npw + 1 every wave makes two full passes (the prologue and one steady-state iteration that
+    prefetches a third descriptor), wave 0 a third full pass (the nodes from 64 npw on), wave 1 a third pass of a single node,
+    and the waves 2 .. 31 end after two (j_passes restates this arithmetic, and the device test asserts it).  n is odd where npw
+    is even -- an even n leaves no partly filled wave at npw = 2 --, so the two halves of the forest differ by one cherry there.
+    The tips kernels see 2 n tips: passes_total = ceil(2 n / npw) >= 130 over 32 waves, cp = min(ceil(passes_total / 32), 64 / npw)
+    >= 2 passes per chunk (j_tip_chunk_passes).
+    Beyond 32 states (one node per wave, the plain loop) 6 cherries with the default grid: two workgroups, the second one half idle.
+    """
+    if k > 32:
+        return 6
+    npw = 64 // k
+    return 64 * npw + npw + 1
+
+
+def j_tip_chunk_passes(k, n_tips, blocks_cap=JOINT_MIN_BLOCKS):
+    """cp of eigen_joint_obs_tips_kernel / eigen_joint_tips_kernel: the passes a wave makes per chunk of tips."""
+    npw = 64 // k
+    blocks = min(-(-n_tips // (JOINT_WAVES * npw)), blocks_cap)
+    passes_total = -(-n_tips // npw)
+    return min(-(-passes_total // (blocks * JOINT_WAVES)), 64 // npw)
+
+
+def j_passes(k, n):
+    """(passes of wave 0, nodes in the last pass of the last wave that makes as many) of the level launch over n nodes under
+    J_TUNE -- the arithmetic of launch_eigen_joint and eigen_joint_kernel restated."""
+    npw = 64 // k
+    blocks = min(-(-n // (JOINT_WAVES * npw)), JOINT_MIN_BLOCKS)
+    stride = blocks * JOINT_WAVES * npw
+    passes = -(-n // stride)
+    left = n - (passes - 1) * stride          # nodes of the last pass, over the waves in order
+    return passes, left - (-(-left // npw) - 1) * npw
+
+
+@functools.lru_cache(maxsize=None)
+def forest_j(n):
+    """By hand, as forest L: a root, 2 children with n / 2 children each (rounded up and down), every one of those n a cherry of
+    two tips.  Bottom-up the levels hold n, 2 and 1 nodes."""
+    rng = np.random.default_rng(733 + n)
+
+    def grow(nodes, fans):
+        return [m.add_child(dist=float(rng.uniform(0.02, 0.3))) for m, fan in zip(nodes, fans) for _ in range(fan)]
+    root = TreeNode(name='r', dist=0.0)
+    halves = grow([root], [2])
+    cherries = grow(halves, [n - n // 2, n // 2])
+    grow(cherries, [2] * n)
+    flat = FlatForest.from_trees([root])
+    assert flat.n_nodes == 3 + 3 * n and flat.n_tips == 2 * n
+    assert list(np.diff(flat.bu_offsets)) == [n, 2, 1]
+    return flat
+
+
+@functools.lru_cache(maxsize=None)
+def forest_t():
+    """((a,b),(c,d),e): two non-root internal nodes."""
+    root = TreeNode(name='r', dist=0.0)
+    for name, dist in (('ab', 0.11), ('cd', 0.07)):
+        inner = root.add_child(name=name, dist=dist)
+        inner.add_child(name=name[0], dist=0.19)
+        inner.add_child(name=name[1], dist=0.05)
+    root.add_child(name='e', dist=0.23)
+    flat = FlatForest.from_trees([root])
+    assert flat.n_nodes == 8 and flat.n_tips == 5
+    return flat
+
+
+@functools.lru_cache(maxsize=None)
+def build_joint(k, which, kind='EIGEN'):
+    """The inputs of a joint case, as build(): 'S' (build's own), 'J' (forest J(k); for HKY the J-shaped forest of 258 cherries),
+    'T' (more than 64 states: every tip observed in column 0, one missing tip in column 1)."""
+    if which == 'S':
+        return build(k, 'S', kind)
+    rng = np.random.default_rng(8600 + 2 * k + (which == 'T'))
+    specs = [random_spec(kind, k, rng) for _ in range(2)]
+    rates = [(float(rng.uniform(0.5, 3)), 0.0, 1.0), (float(rng.uniform(0.5, 3)), 0.01, 0.9)]
+    if which == 'J':
+        flat = forest_j(HKY_J_CHERRIES if kind == 'HKY' else j_cherries(k))
+        observed = synthetic.one_hot_masks(flat, k, rng.integers(0, k, size=flat.n_tips))
+        masks = np.stack([np.asarray(observed, dtype=np.int8), random_masks(flat, k, rng)])
+    else:
+        flat = forest_t()
+        observed = np.asarray(synthetic.one_hot_masks(flat, k, rng.integers(0, k, size=flat.n_tips)), dtype=np.int8)
+        missing = observed.copy()
+        missing[flat.tips[int(rng.integers(flat.n_tips))]] = 1
+        masks = np.stack([observed, missing])
+    return dict(k=k, which=which, flat=flat, specs=specs, rates=rates, masks=masks)
+
+
+@functools.lru_cache(maxsize=None)
+def joint_exact(k, which, c, kind='EIGEN'):
+    b = build_joint(k, which, kind)
+    return exact.joint_pass(b['flat'], b['masks'][c], b['specs'][c], *b['rates'][c])
+
+
+@functools.lru_cache(maxsize=None)
+def deep_joint_exact(kind, k):
+    d = deep_caterpillar(kind, k)
+    return exact.joint_pass(d['flat'], d['masks'], d['spec'], *d['rates'])
+
+
+@functools.lru_cache(maxsize=None)
+def polytomy_joint_exact(k):
+    d = polytomy_forest(k)
+    return exact.joint_pass(d['flat'], d['masks'], d['spec'], *d['rates'])
+
+
+def tree_sizes(flat):
+    """Nodes per tree, in the order of flat.roots (parents have smaller ids than their children)."""
+    root_of = np.arange(flat.n_nodes)
+    for n in range(flat.n_nodes):
+        if flat.parent[n] >= 0:
+            root_of[n] = root_of[flat.parent[n]]
+    return [int((root_of == r).sum()) for r in flat.roots]
+
+
+def joint_errors(got, want, flat, masks, spec, rates):
+    """
+    got: dict(loglik (float), bu_log10 [N, k], table [N, k], states [N]) of the implementation under test, want: joint_pass.
+    Asserts what has no tolerance to choose: equal zero patterns of the internal nodes' vectors, every table entry of every non-root
+    node a maximum of the exact products up to products equal to 1e-12 (choice_is_a_maximum), every back-traced state allowed by its
+    mask.  Returns the worst errors, dict(
+        lnl: |ln L - exact| / |exact|,  log10: the largest |difference| of a finite log10 entry of an internal node's vector,
+        scenario: the largest, over the trees, of (exact maximum - ln probability of the back-traced scenario) / nodes of the tree,
+            in units of 1e-12: each choice within 1e-12 relative of its row's best puts the product within (1 + 1e-12)^n).
+    """
+    k = np.asarray(masks).shape[1]
+    out = dict(lnl=exact.rel_error(got['loglik'], want['loglik']))
+    inner = ~flat.is_tip
+    a, b = got['bu_log10'][inner], want['bu_log10'][inner]
+    assert not np.isnan(b).any()
+    assert np.array_equal(np.isneginf(a), np.isneginf(b)), 'bottom-up vectors: zero patterns differ'
+    fin = np.isfinite(b)
+    out['log10'] = float(np.abs(a[fin] - b[fin]).max())
+    for n in np.flatnonzero(flat.parent >= 0):
+        for i in range(k):
+            assert exact.choice_is_a_maximum(want['products'], int(n), i, int(got['table'][n, i])), ('table', int(n), i)
+    states = np.asarray(got['states'])
+    assert np.all((states >= 0) & (states < k)) and np.all(np.asarray(masks)[np.arange(flat.n_nodes), states] != 0), \
+        'a back-traced state is not allowed by its mask'
+    worst = 0.0
+    for lp, best, size in zip(exact.scenario_log_probability(flat, masks, spec, *rates, states=states), want['loglik_per_tree'],
+                              tree_sizes(flat)):
+        assert lp.is_finite(), 'the back-traced scenario has probability zero'
+        gap = float(best - lp)
+        assert gap > -1e-40, 'a scenario above the exact maximum: {}'.format(gap)
+        worst = max(worst, gap / size / 1e-12)
+    out['scenario'] = worst
+    return out
+
+
+def oracle_joint(flat, masks, spec, rates):
+    """The oracle's joint sweep and back-trace in the terms of joint_errors."""
+    r = orc.bottom_up(flat, np.asarray(masks).astype(int), spec, *rates, is_marginal=False)
+    with np.errstate(divide='ignore'):
+        bu_log10 = np.log10(r['bu']) - r['bu_sf'][:, None]
+    return dict(loglik=r['loglik'], bu_log10=bu_log10, table=r['joint_table'],
+                states=orc.joint_backtrace(flat, r['bu'], r['joint_table'], spec['pi']))
 
 
 @functools.lru_cache(maxsize=None)

@@ -233,7 +233,11 @@ def joint_pass(flat, masks, spec, sf=1., tau=0., tf=1.):
     columns j where v_n[j] is not zero (an observed tip: one column): message_n[i] = max_j P_n[i, j] v_n[j].
     Returns dict(loglik (Decimal: sum over the trees of ln max_i pi_i v_root[i]), loglik_per_tree,
     products: per non-root node n (columns [m], [k, m] object array of the exact products P_n[i, j] v_n[j]), for judging arg-max
-    choices; None for the roots).
+    choices; None for the roots,
+    bu_log10 [N, k] float: log10 of the exact max-product vectors (-inf for zeros),
+    min_best_ratio (float): over the non-root nodes, the smallest row maximum of the node's products (an entry of its message) over
+        the largest -- while it is far above the rounding of float64 the sweeps' clamp of negative P(t) dust cannot have acted on a
+        maximum, and the relative tie test of choice_is_a_maximum is meaningful in every row).
     """
     parent, first_child, n_children = flat.parent, flat.first_child, flat.n_children
     N, k = np.asarray(masks).shape
@@ -244,6 +248,8 @@ def joint_pass(flat, masks, spec, sf=1., tau=0., tf=1.):
         v = [None] * N
         message = [None] * N
         products = [None] * N
+        worst = None
+        columns = {}
         for n in reversed(range(N)):
             row = np.array([ONE if a else ZERO for a in allowed[n]], dtype=object)
             fc = int(first_child[n])
@@ -252,10 +258,53 @@ def joint_pass(flat, masks, spec, sf=1., tau=0., tf=1.):
             v[n] = row
             if parent[n] >= 0:
                 nz = [j for j, x in enumerate(row) if x != 0]
-                products[n] = (nz, op.pij_columns(n, nz) * row[nz][None, :])
+                # (branches of the same length share the columns of P(t'): the spine of a caterpillar, the tips of a polytomy)
+                key = (op.t[n], tuple(nz))
+                if key not in columns:
+                    columns[key] = op.pij_columns(n, nz)
+                products[n] = (nz, columns[key] * row[nz][None, :])
                 message[n] = products[n][1].max(axis=1)
+                worst = _ratio(message[n], worst)
         per_tree = [_ln(max(pi * v[int(r)])) for r in flat.roots]
-    return dict(loglik=sum(per_tree, ZERO), loglik_per_tree=per_tree, products=products)
+        bu_log10 = _log10_rows(v)
+    return dict(loglik=sum(per_tree, ZERO), loglik_per_tree=per_tree, products=products, bu_log10=bu_log10,
+                min_best_ratio=float(worst) if worst is not None else 1.0)
+
+
+def scenario_log_probability(flat, masks, spec, sf, tau, tf, states):
+    """
+    ln of the probability of one assignment of states to all nodes (states [N]), per tree, as a list of Decimals:
+    ln(pi[s_root] prod over the tree's non-root nodes n of P_n[s_parent(n), s_n]), P(t') built exactly row by row (pij_row);
+    -Infinity for a tree in which a state is not allowed by its node's mask (or the product is not positive).  The largest value
+    over all assignments is joint_pass's loglik_per_tree.
+    """
+    parent = flat.parent
+    N = len(parent)
+    allowed = np.asarray(masks) != 0
+    states = [int(s) for s in np.asarray(states)]
+    with decimal.localcontext(_CONTEXT):
+        op = operator(spec, flat.dist, sf, tau, tf)
+        pi = _dec_array(spec['pi'])
+        tree_of = [0] * N   # the root of the node's tree
+        total = {}
+        rows = {}
+        for n in range(N):   # parents first
+            p = int(parent[n])
+            s = states[n]
+            tree_of[n] = n if p < 0 else tree_of[p]
+            ok = 0 <= s < allowed.shape[1] and allowed[n, s]
+            if p < 0:
+                factor = pi[s] if ok else ZERO
+            elif not ok:
+                factor = ZERO
+            else:
+                key = (op.t[n], states[p])
+                if key not in rows:
+                    rows[key] = op.pij_row(n, states[p])
+                factor = rows[key][s]
+            r = tree_of[n]
+            total[r] = factor if p < 0 else total[r] * factor
+        return [_ln(total[int(r)]) for r in flat.roots]
 
 
 def choice_is_a_maximum(products, n, i, j, rtol=Decimal('1e-12')):

@@ -237,21 +237,21 @@ def test_rescaling_inside_a_level_launch(k, capfd):
 
 @pytest.mark.parametrize('k', cases.JOINT_STATES)
 def test_joint_sweep_at_the_state_counts_of_the_new_shapes(k):
-    """bottom_up(False) on forest S, both columns: ln L against the exact max-product value (P(t') built exactly, in the columns a
-    node's vector has), and every entry of the arg-max tables is a maximum of the exact products up to products equal to 1e-12."""
+    """bottom_up(False) on forest S, both columns, without the DEBUG switch: ln L against the exact max-product value, and the
+    assertions of cases.joint_errors (tables, vectors' zero patterns, the back-traced scenario).  Every state count, the plans, the
+    level launches and the other forms of the joint sweep: tests/test_gpu_joint_shapes.py."""
     b = cases.build(k, 'S')
     flat = b['flat']
-    wants = [exact.joint_pass(flat, b['masks'][c], b['specs'][c], *b['rates'][c]) for c in range(2)]
+    wants = [cases.joint_exact(k, 'S', c) for c in range(2)]
     assert all(w['loglik'].is_finite() for w in wants)
     with hip.Engine(flat, 2, k) as eng:
         eng.set_models(list(zip(b['specs'], b['rates'])))
         eng.set_masks(b['masks'])
         lnl = eng.bottom_up(False)
-        tables = [eng.download(hip.BUF_JOINT_TABLE, c) for c in range(2)]
+        got = [dict(loglik=float(lnl[c]), table=eng.download(hip.BUF_JOINT_TABLE, c),
+                    bu_log10=log_true(eng.download(hip.BUF_BU, c), eng.download(hip.BUF_BU_SF, c))) for c in range(2)]
+        states = eng.joint_backtrace()
     for c in range(2):
-        err = exact.rel_error(lnl[c], wants[c]['loglik'])
-        print('eigen-shapes joint k={} column={}: lnl {:.3g} ({:.3g} of tol)'.format(k, c, err, err / LNL_RTOL))
-        assert err < LNL_RTOL
-        for n in np.flatnonzero(flat.parent >= 0):
-            for i in range(k):
-                assert exact.choice_is_a_maximum(wants[c]['products'], int(n), i, int(tables[c][n, i])), (c, n, i)
+        err = cases.joint_errors(dict(got[c], states=states[c]), wants[c], flat, b['masks'][c], b['specs'][c], b['rates'][c])
+        print('eigen-shapes joint k={} column={}: lnl {:.3g} ({:.3g} of tol)'.format(k, c, err['lnl'], err['lnl'] / LNL_RTOL))
+        assert err['lnl'] < LNL_RTOL and err['log10'] < LOG10_ATOL and err['scenario'] < 1, err

@@ -1715,7 +1715,7 @@ def test_eigen_joint_sweep_follows_the_masks_through_graph_replay():
                 assert np.array_equal(eng.joint_backtrace(), ref[2])
 
 
-@pytest.mark.parametrize('k', [5, 20, 32])
+@pytest.mark.parametrize('k', [5, 20, 32, 47, 64])   # (47, 64: the joint kernels with A^-1 at stride 64 and the plain column loop)
 def test_eigen_tiers_give_the_bits_of_one_launch_per_level(k):
     """Eigen models: the thin levels of the joint sweep and of the marginal bottom-up sweep run in tiers of subtree blocks
     (one launch per tier); PASTML_HIP_NO_EIGJ_TIERS=1 gives every level its own launch.  Same passes over the same nodes:

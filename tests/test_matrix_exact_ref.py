@@ -5,7 +5,10 @@ tests/test_gpu_eigen_shapes.py (tests/eigen_shape_cases.py) -- the condition und
 against exact values, are meaningful: a float64 implementation of the reference's operation sequence passes them with two to
 three orders of magnitude to spare.  On every case the smallest message entry stays above 1e-9 of its vector's largest, so that
 no clamp of the sweeps (fmax(., 0); contrib <= 0 -> 1) acts on either side.  The worst error / tolerance is printed (pytest -s).
+The joint (max-product) sweep likewise: the oracle's ln L, vectors, arg-max tables and back-traced scenario against joint_pass and
+scenario_log_probability, by the assertions tests/test_gpu_joint_shapes.py makes of the device (cases.joint_errors).
 """
+import itertools
 from decimal import Decimal
 
 import numpy as np
@@ -53,6 +56,47 @@ def test_two_tip_tree_by_hand():
         best = int(np.argmax(Pb[i] * masks[2]))
         assert exact.choice_is_a_maximum(j['products'], 2, i, best)
         assert not exact.choice_is_a_maximum(j['products'], 2, i, 4 - best) and not exact.choice_is_a_maximum(j['products'], 2, i, 1)
+
+
+def test_scenario_log_probability_by_brute_force():
+    """Every assignment of states to the three nodes of the tree above: ln(pi_r P_a[r, s_a] P_b[r, s_b]) with P(t) of the oracle, -inf
+    where a mask forbids a state; the largest of them is joint_pass's ln L, and joint_pass's other results are those of the tree."""
+    k = 5
+    rng = np.random.default_rng(1)
+    spec = cases.random_spec('EIGEN', k, rng)
+    root = TreeNode(name='r', dist=0.0)
+    root.add_child(name='a', dist=0.3)
+    root.add_child(name='b', dist=0.7)
+    flat = FlatForest.from_trees([root])
+    masks = np.zeros((3, k), dtype=np.int8)
+    masks[0] = 1
+    masks[0, 3] = 0   # (a restricted root)
+    masks[1, 2] = 1
+    masks[2, [0, 4]] = 1
+    rates = (1.7, 0.01, 0.9)
+    Pa, Pb = orc.pij(spec, 0.3, *rates), orc.pij(spec, 0.7, *rates)
+    best = -np.inf
+    for r, a, b in itertools.product(range(k), repeat=3):
+        got, = exact.scenario_log_probability(flat, masks, spec, *rates, states=[r, a, b])
+        if masks[0, r] and masks[1, a] and masks[2, b]:
+            want = np.log(spec['pi'][r] * Pa[r, a] * Pb[r, b])
+            np.testing.assert_allclose(float(got), want, rtol=1e-11)
+            best = max(best, want)
+        else:
+            assert got == exact.MINUS_INFINITY
+    j = exact.joint_pass(flat, masks, spec, *rates)
+    np.testing.assert_allclose(float(j['loglik']), best, rtol=1e-12)
+    assert len(j['loglik_per_tree']) == 1 and abs(j['loglik_per_tree'][0] - j['loglik']) < Decimal('1e-25')
+    v_root = masks[0] * Pa[:, 2] * np.maximum(Pb[:, 0], Pb[:, 4])
+    assert np.array_equal(np.isneginf(j['bu_log10']), masks == 0)
+    np.testing.assert_allclose(j['bu_log10'][0][masks[0] != 0], np.log10(v_root[masks[0] != 0]), rtol=0, atol=1e-12)
+    messages = np.stack([Pa[:, 2], np.maximum(Pb[:, 0], Pb[:, 4])])
+    np.testing.assert_allclose(j['min_best_ratio'], (messages.min(axis=1) / messages.max(axis=1)).min(), rtol=1e-10)
+    # the scenario of the arg-max choices attains the maximum
+    r = int(np.argmax(spec['pi'] * v_root))
+    b = 0 if Pb[r, 0] > Pb[r, 4] else 4
+    got, = exact.scenario_log_probability(flat, masks, spec, *rates, states=[r, 2, b])
+    assert abs(got - j['loglik']) < Decimal('1e-25')   # (the difference is taken at decimal's default 28 digits)
 
 
 @pytest.mark.parametrize('k', [3, 20])
@@ -149,3 +193,73 @@ def test_oracle_on_the_forest_of_polytomies(k):
     print('k = {}, polytomies of {} tips: worst error / tol of the oracle: {}'.format(
         k, d['fan'], ', '.join('{} {:.3g}'.format(a, worst[a]) for a in sorted(worst))))
     assert max(worst.values()) < 1, worst
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# the joint sweep
+# ---------------------------------------------------------------------------------------------------------------------
+def oracle_joint_ratios(label, flat, masks, spec, rates, want):
+    """The oracle against the exact joint pass, by the assertions the device gets (tests/test_gpu_joint_shapes.py): the preconditions,
+    tables / zero patterns / masks (cases.joint_errors), then error / tolerance of ln L (LNL_RTOL), the vectors (LOG10_ATOL) and
+    the scenario (nodes of the tree x 1e-12 in ln)."""
+    assert want['loglik'].is_finite() and want['min_best_ratio'] > cases.MIN_MESSAGE_RATIO, want['min_best_ratio']
+    err = cases.joint_errors(cases.oracle_joint(flat, masks, spec, rates), want, flat, masks, spec, rates)
+    ratio = dict(lnl=err['lnl'] / cases.LNL_RTOL, log10=err['log10'] / cases.LOG10_ATOL, scenario=err['scenario'])
+    print('{}: oracle, joint: {}'.format(label, '  '.join('{} {:.3g} ({:.3g} of tol)'.format(a, err[a], ratio[a]) for a in sorted(err))))
+    return ratio
+
+
+JOINT_CASES = [(k, 'S') for k in cases.CPU_STATES] + [(k, 'J') for k in cases.CPU_STATES_L]
+
+
+@pytest.mark.parametrize('k,which', JOINT_CASES)
+def test_oracle_joint_sweep_stays_inside_the_tolerances_of_the_joint_shape_tests(k, which):
+    """Forest S and the level forest J(k), both columns."""
+    b = cases.build_joint(k, which)
+    flat = b['flat']
+    assert np.all(b['masks'][0][flat.is_tip].sum(axis=1) == 1)
+    if which == 'J' and k <= 32:
+        assert cases.j_passes(k, cases.j_cherries(k)) == (3, 1) and cases.j_tip_chunk_passes(k, flat.n_tips) > 1
+    for c in range(2):
+        ratio = oracle_joint_ratios('k = {} forest {} column {}'.format(k, which, c), flat, b['masks'][c], b['specs'][c], b['rates'][c],
+                                    cases.joint_exact(k, which, c))
+        assert max(ratio.values()) < 1, ratio
+
+
+@pytest.mark.parametrize('k', [65, 128, 129])
+def test_oracle_joint_sweep_beyond_64_states(k):
+    b = cases.build_joint(k, 'T')
+    assert b['masks'][0][b['flat'].is_tip].sum() == b['flat'].n_tips and b['masks'][1][b['flat'].is_tip].sum() == b['flat'].n_tips - 1 + k
+    for c in range(2):
+        ratio = oracle_joint_ratios('k = {} forest T column {}'.format(k, c), b['flat'], b['masks'][c], b['specs'][c], b['rates'][c],
+                                    cases.joint_exact(k, 'T', c))
+        assert max(ratio.values()) < 1, ratio
+
+
+@pytest.mark.parametrize('which', ['S', 'J'])
+def test_oracle_joint_sweep_of_hky(which):
+    b = cases.build_joint(4, which, 'HKY')
+    assert which == 'S' or list(np.diff(b['flat'].bu_offsets)) == [cases.HKY_J_CHERRIES, 2, 1]
+    for c in range(2):
+        ratio = oracle_joint_ratios('HKY forest {} column {}'.format(which, c), b['flat'], b['masks'][c], b['specs'][c], b['rates'][c],
+                                    cases.joint_exact(4, which, c, 'HKY'))
+        assert max(ratio.values()) < 1, ratio
+
+
+@pytest.mark.parametrize('kind,k', [('EIGEN', 11), ('EIGEN', 20), ('EIGEN', 43), ('HKY', 4)])
+def test_oracle_joint_sweep_on_the_deep_caterpillars(kind, k):
+    """The max-product vectors lie below the sum vectors: the root is below 2^-800 here too."""
+    d = cases.deep_caterpillar(kind, k)
+    want = cases.deep_joint_exact(kind, k)
+    assert want['bu_log10'][0].max() * exact.LOG2_OF_10 < cases.DEEP_LOG2
+    ratio = oracle_joint_ratios('deep {} k = {} depth {}'.format(kind, k, d['depth']), d['flat'], d['masks'], d['spec'], d['rates'], want)
+    assert max(ratio.values()) < 1, ratio
+
+
+@pytest.mark.parametrize('k', [5, 20])
+def test_oracle_joint_sweep_on_the_forest_of_polytomies(k):
+    d = cases.polytomy_forest(k)
+    want = cases.polytomy_joint_exact(k)
+    assert np.all(want['bu_log10'][d['polytomies']].max(axis=1) * exact.LOG2_OF_10 < -200)
+    ratio = oracle_joint_ratios('polytomies k = {} fan {}'.format(k, d['fan']), d['flat'], d['masks'], d['spec'], d['rates'], want)
+    assert max(ratio.values()) < 1, ratio
