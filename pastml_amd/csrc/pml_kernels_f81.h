@@ -2703,13 +2703,16 @@ struct TdSuperLoads {
 };
 
 // Valid for every descriptor of the list and either j: all addresses are those of existing nodes.
-template <int G, int R>
+// ROW = false: without the two-level node's row, sum and exponent, which td_f81_chain_kernel takes from LDS (td_chain_row_load).
+template <int G, int R, bool ROW = true>
 __device__ __forceinline__ void td_f81_super_issue(const LaneCtx<G, R>& L, const PmlCols& c, const SuperRegs& s, int j,
                                                    TdSuperLoads<R>& ld) {
     const int ch = s.fc + j;
-    node_load_vec<G, R>(L, c, L.post, s.n, ld.po);
-    ld.ls = L.lhsum[s.n];
-    ld.pe = L.lhe[s.n];
+    if (ROW) {
+        node_load_vec<G, R>(L, c, L.post, s.n, ld.po);
+        ld.ls = L.lhsum[s.n];
+        ld.pe = L.lhe[s.n];
+    }
     ld.e = L.E[ch];
     ld.s = L.S[ch];
     ld.be = L.be[ch];
@@ -3022,10 +3025,51 @@ bu_f81_stack_kernel(PmlTree t, PmlCols c, PmlState st, const PmlUnit* __restrict
     }
 }
 
-// top-down: unit i is child i & 1 of stacked node i >> 1
+// Where td_f81_stack_unit hands on what it has just stored for grandchild jx of its child -- the posterior row, its sum and
+// exponent -- besides storing it: nowhere (td_f81_stack_kernel), or to the LDS slot from which the two-level units of that
+// grandchild take it in the same launch (td_f81_chain_kernel).
+struct TdRowNowhere {
+    template <int G, int R>
+    __device__ __forceinline__ void operator()(const LaneCtx<G, R>&, const PmlCols&, int, const double (&)[R], double, i64) const {}
+};
+// LDS slot of a two-level node's row: G * R doubles in state order, then the sum and the exponent
+#define PML_TD_CHAIN_SLOT(G, R) ((G) * (R) + 2)
+struct TdRowToLds {
+    double* slots;  // of the unit's two grandchildren
+    template <int G, int R>
+    __device__ __forceinline__ void operator()(const LaneCtx<G, R>& L, const PmlCols& c, int jx, const double (&po)[R], double ls,
+                                               i64 le) const {
+        double* row = slots + jx * PML_TD_CHAIN_SLOT(G, R);
+        // what node_load_vec reads back of the row node_store_vec_nt stored: states from ks on were not stored and read as 0
+#pragma unroll
+        for (int r = 0; r < R; r += 2) {
+            double2 t2;
+            t2.x = L.st(r) < c.ks ? po[r] : 0.0;
+            t2.y = L.st(r) < c.ks ? po[r + 1] : 0.0;
+            *reinterpret_cast<double2*>(row + L.st(r)) = t2;
+        }
+        if (L.g == 0) {
+            row[G * R] = ls;
+            *reinterpret_cast<i64*>(row + G * R + 1) = le;
+        }
+    }
+};
 template <int G, int R>
+__device__ __forceinline__ void td_chain_row_load(const LaneCtx<G, R>& L, const double* row, TdSuperLoads<R>& ld) {
+#pragma unroll
+    for (int r = 0; r < R; r += 2) {
+        const double2 t2 = *reinterpret_cast<const double2*>(row + L.st(r));
+        ld.po[r] = t2.x;
+        ld.po[r + 1] = t2.y;
+    }
+    ld.ls = row[G * R];
+    ld.pe = *reinterpret_cast<const i64*>(row + G * R + 1);
+}
+
+// top-down: unit i is child i & 1 of stacked node i >> 1
+template <int G, int R, class RowSink = TdRowNowhere>
 __device__ __forceinline__ void td_f81_stack_unit(const LaneCtx<G, R>& L, const PmlTree& t, const PmlCols& c,
-                                                  const PmlState& st, const StackRegs& s, int j) {
+                                                  const PmlState& st, const StackRegs& s, int j, const RowSink& sink = RowSink()) {
     const u64 kbits = state_bits(c.k);
     const int ch = s.fc + j;
     const int first = j ? s.g1 : s.g0;
@@ -3073,6 +3117,7 @@ __device__ __forceinline__ void td_f81_stack_unit(const LaneCtx<G, R>& L, const 
         i64 xe, le;
         f81_finish_child<G, R>(L, c, prod2, pe2, first + jx, __shfl(ld.cl.e, src, 64), __shfl(ld.cl.s, src, 64),
                                __shfl(ld.cl.be, src, 64), jx ? g1v : g0v, full, mb, tdc, xe, po, ls, le);
+        sink(L, c, jx, po, ls, le);
         if (st.td != nullptr) {
             node_store_vec<G, R>(L, c, L.td, first + jx, tdc);
             if (L.g == 0) L.te[first + jx] = xe;
@@ -3098,6 +3143,94 @@ td_f81_stack_kernel(PmlTree t, PmlCols c, PmlState st, const PmlUnit* __restrict
         if (idx < n_units) td_f81_stack_unit<G, R>(L, t, c, st, cur, idx & 1);
         cur = nxt;
         idx = nxt_idx;
+    }
+}
+
+// The stacked units of the deepest stacked depth and the two-level units below them in ONE launch
+// (PmlSuperSchedule::chain_depth: stacked child-unit i finishes the two-level nodes 2 i and 2 i + 1 of `units`, so n_level =
+// 4 x the stacked nodes of `stack_units`).  A wave owns tiles: tile q is the UW stacked child-units q UW .. q UW + UW - 1 (phase
+// A, td_f81_stack_unit as td_f81_stack_kernel runs it, stores included) and then the 4 UW child-units of the 2 UW two-level
+// nodes they have just finished (phase B: four wave passes of td_f81_super_unit as td_f81_super_kernel<PIPE> runs it).  Phase A
+// leaves row, sum and exponent of those nodes in the wave's LDS slots (TdRowToLds) as well, the values node_load_vec and the two
+// scalar loads of td_f81_super_issue would have read back in the next launch, and phase B takes them from there
+// (td_chain_row_load): the rows are written to memory once and not read again.  The same unit functions with the same
+// arguments in the same lane shape, and a wave pass holds the same UW aligned units as in the two kernels: the same bits.
+// Everything else a two-level unit reads is issued one pass ahead, as in td_f81_super_kernel; the loads of a tile's first pass
+// are issued before the arithmetic of its phase A (in the last pass of the wave's tile before).
+// Prefetching is safe, and phase A needs nothing of phase B: the launch stores rows, sums and exponents of the stacked nodes'
+// children and grandchildren (phase A), of the two-level nodes' children, their cherries and tips (phase B), and td / te of
+// those when asked.  From memory it reads the row, sum and exponent of the stacked nodes -- which are none of these: a
+// stacked node of the depth is neither below another one of the same depth nor below a two-level node -- and E, S, the
+// bottom-up exponents, vectors and the masks, which the top-down sweep does not write.  A two-level node's row, sum and
+// exponent come from the slot the same wave wrote in phase A, ordered by wave_sync_lds: a wave reads only slots it wrote.
+// An index past the end is clamped to entry 0, so that a prefetch's addresses are those of existing nodes, and that lane group
+// does no work; its two slots stay unwritten and are read only by lane groups that are past the end too.
+template <int G, int R, bool LANES>
+__global__ void __launch_bounds__(PML_BLOCK) __attribute__((amdgpu_waves_per_eu(R == 8 ? 2 : 1, R == 8 ? 2 : 8)))
+td_f81_chain_kernel(PmlTree t, PmlCols c, PmlState st, const PmlUnit* __restrict__ units, int n_level,
+                    const PmlUnit* __restrict__ stack_units) {
+    constexpr int UW = 64 / G, SLOT = PML_TD_CHAIN_SLOT(G, R);
+    const int wave = threadIdx.x >> 6;
+    const int sub = (threadIdx.x & 63) / G;
+    __shared__ __attribute__((aligned(16))) double tip_rows[LANES ? PML_BLOCK * R : 2];
+    __shared__ __attribute__((aligned(16))) double node_rows[PML_WAVES_PER_BLOCK * 2 * UW * SLOT];
+    double* const ps_row = LANES ? tip_rows + (wave * UW + sub) * (G * R) : nullptr;
+    double* const wave_rows = node_rows + wave * (2 * UW * SLOT);
+    LaneCtx<G, R> L;
+    lane_ctx_init<G, R>(L, t, c, st);
+    const int n_units = 2 * n_level;        // child-units of the two-level nodes
+    const int n_stack_units = n_level / 2;  // child-units of the stacked nodes
+    const int n_tiles = (n_stack_units + UW - 1) / UW;
+    const int stride = gridDim.x * PML_WAVES_PER_BLOCK;
+    const int j = sub & 1;  // (UW is even: child j of its node in either phase)
+    const TdRowToLds sink = {wave_rows + 2 * sub * SLOT};
+    auto stack_desc = [&](int q) {
+        const int i = q * UW + sub;
+        return load_stack(stack_units, i < n_stack_units ? i >> 1 : 0);
+    };
+    auto super_desc = [&](int q, int p) {   // pass p of tile q
+        const int i = (4 * q + p) * UW + sub;
+        return load_super(units, i < n_units ? i >> 1 : 0);
+    };
+    auto pass = [&](int q, int p, const SuperRegs& s, TdSuperLoads<R>& ld) {
+        td_chain_row_load<G, R>(L, wave_rows + ((p * UW + sub) >> 1) * SLOT, ld);
+        if ((4 * q + p) * UW + sub < n_units) td_f81_super_unit<G, R, LANES, true>(L, t, c, st, s, j, ld, ps_row);
+    };
+    int q = blockIdx.x * PML_WAVES_PER_BLOCK + wave;
+    StackRegs sk = stack_desc(q);
+    SuperRegs ua = super_desc(q, 0), ub = super_desc(q, 1);
+    TdSuperLoads<R> la, lb;
+    td_f81_super_issue<G, R, false>(L, c, ua, j, la);
+    for (; q < n_tiles; q += stride) {
+        const StackRegs sk_next = stack_desc(q + stride);
+        if (q * UW + sub < n_stack_units) td_f81_stack_unit<G, R>(L, t, c, st, sk, j, sink);
+        wave_sync_lds();
+        {
+            const SuperRegs un = super_desc(q, 2);
+            td_f81_super_issue<G, R, false>(L, c, ub, j, lb);
+            pass(q, 0, ua, la);
+            ua = un;
+        }
+        {
+            const SuperRegs un = super_desc(q, 3);
+            td_f81_super_issue<G, R, false>(L, c, ua, j, la);
+            pass(q, 1, ub, lb);
+            ub = un;
+        }
+        {
+            const SuperRegs un = super_desc(q + stride, 0);
+            td_f81_super_issue<G, R, false>(L, c, ub, j, lb);
+            pass(q, 2, ua, la);
+            ua = un;
+        }
+        {
+            const SuperRegs un = super_desc(q + stride, 1);
+            td_f81_super_issue<G, R, false>(L, c, ua, j, la);   // (the next tile's first pass: in flight across its phase A)
+            pass(q, 3, ub, lb);
+            ub = un;
+        }
+        wave_sync_lds();   // (the slots are the next tile's)
+        sk = sk_next;
     }
 }
 

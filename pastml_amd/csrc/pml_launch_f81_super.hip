@@ -7,11 +7,27 @@ static void launch_td_super_f81(pml_ctx* ctx, dim3 grid, const PmlTree& t, const
                        ctx->sup.n);
 }
 
+// The chained top-down launch (td_f81_chain_kernel): the stacked units of depth chain_depth, n of them from entry a of the
+// top-down stacked list, and the two-level units below them.  A wave's unit of work is a tile, one pass of stacked child-units
+// and four of two-level child-units, on the grid of the pipelined kernels.
 template <int G, int R>
-static void launch_super_f81(pml_ctx* ctx, bool bottom_up) {
+static void launch_td_chain_f81(pml_ctx* ctx, int a, const PmlTree& t, const PmlCols& c, const PmlState& st) {
+    const int tiles = (2 * ctx->sup.n + 4 * (64 / G) - 1) / (4 * (64 / G));
+    dim3 grid(grid_for(ctx, tiles, PML_WAVES_PER_BLOCK, ctx->C, true), ctx->C);
+    if (!ctx->tune.on(T_NO_TIP_LANES))
+        hipLaunchKernelGGL((td_f81_chain_kernel<G, R, true>), grid, dim3(PML_BLOCK), 0, ctx->stream, t, c, st, ctx->sup.d_units,
+                           ctx->sup.n, ctx->sup.d_stack_td + a);
+    else
+        hipLaunchKernelGGL((td_f81_chain_kernel<G, R, false>), grid, dim3(PML_BLOCK), 0, ctx->stream, t, c, st, ctx->sup.d_units,
+                           ctx->sup.n, ctx->sup.d_stack_td + a);
+}
+
+template <int G, int R>
+static void launch_super_f81(pml_ctx* ctx, bool bottom_up, int chain_first) {
     const PmlTree t = tree_of(ctx, true);
     const PmlCols c = cols_of(ctx, bottom_up);
     const PmlState st = state_of(ctx);
+    if (chain_first >= 0) return launch_td_chain_f81<G, R>(ctx, chain_first, t, c, st);
     const int upb = PML_WAVES_PER_BLOCK * (64 / G);
     // Top-down: one unit per child of a two-level node.  Every lane shape loads one unit ahead (td_f81_super_kernel's PIPE,
     // profiles/td_super_pipeline.txt) and then likes the grid of the pipelined bottom-up kernels.
@@ -44,14 +60,23 @@ static void launch_stack_f81(pml_ctx* ctx, bool bottom_up, int a, int n) {
         hipLaunchKernelGGL((td_f81_stack_kernel<G, R>), grid, block, 0, ctx->stream, t, c, st, ctx->sup.d_stack_td + a, n);
 }
 
-int dispatch_super_f81(pml_ctx* ctx, bool bottom_up) {
+int dispatch_super_f81(pml_ctx* ctx, bool bottom_up, int chain_depth) {
     if (ctx->sup.n <= 0) return PML_OK;  // (a schedule of stacked units only)
+    int chain_first = -1;
+    if (chain_depth >= 0) {
+        // (the planner chains a depth only when its stacked range covers the two-level list: pml_plan_tree)
+        const std::vector<int>& off = ctx->sup.stack_td_offsets;
+        if (bottom_up || chain_depth != ctx->sup.chain_depth || chain_depth + 1 >= (int)off.size() ||
+            (long long)(off[chain_depth + 1] - off[chain_depth]) * 4 != ctx->sup.n)
+            return fail(PML_ERR_INVALID, "no chained two-level launch for depth %d", chain_depth);
+        chain_first = off[chain_depth];
+    }
     const auto [g, r] = ctx->cols.shape(bottom_up);
-#define X(G_, R_)                                   \
-    if (g == G_ && r == R_) {                       \
-        launch_super_f81<G_, R_>(ctx, bottom_up);   \
-        HIP_TRY(hipGetLastError());                 \
-        return PML_OK;                              \
+#define X(G_, R_)                                                \
+    if (g == G_ && r == R_) {                                    \
+        launch_super_f81<G_, R_>(ctx, bottom_up, chain_first);   \
+        HIP_TRY(hipGetLastError());                              \
+        return PML_OK;                                           \
     }
     PML_SUPER_CASES(X)
 #undef X

@@ -567,7 +567,18 @@ static void plan_super(const PmlForest& f, const PmlTune& tune, PmlTreePlan& P) 
         P.sup.stack_td = describe(f, by_depth);
         P.sup.stack_children = describe(f, stack_children);
         U.n_stack = (int)stack_list.size();
-        if (tune.on(T_DEBUG)) fprintf(stderr, "pastml_hip: %d stacked units\n", U.n_stack);
+        // the chained top-down launch: the deepest stacked depth, when its grandchildren are the two-level nodes in list order
+        int deepest = n_td_levels - 1;
+        while (deepest >= 0 && U.stack_td_offsets[deepest + 1] == U.stack_td_offsets[deepest]) --deepest;
+        const int a = U.stack_td_offsets[deepest], cnt = U.stack_td_offsets[deepest + 1] - a;
+        bool lined_up = (long long)cnt * 4 == (long long)sup_list.size();
+        for (int m = 0; m < cnt && lined_up; ++m) {
+            const int n = by_depth[a + m], g0 = fc[fc[n]], g1 = fc[fc[n] + 1];
+            lined_up = sup_list[4 * m] == g0 && sup_list[4 * m + 1] == g0 + 1 && sup_list[4 * m + 2] == g1 &&
+                       sup_list[4 * m + 3] == g1 + 1;
+        }
+        if (lined_up) U.chain_depth = deepest;
+        if (tune.on(T_DEBUG)) fprintf(stderr, "pastml_hip: %d stacked units, chain depth %d\n", U.n_stack, U.chain_depth);
     }
     if (sup_list.empty() && stack_list.empty()) return;   // (the plain level lists, nothing to build)
     // rest lists: the level structure of the fused lists, without the nodes the two-level units take over
@@ -1101,10 +1112,13 @@ std::vector<PmlLaunch> pml_plan_top_down(const PmlForest& f, const PmlSchedules&
         if (head < 2) head = 0;
         roots(L_REST_TD, head);
         // (the children of the stacked nodes of a depth: their rows come from the depth above)
+        // (td_chain: the stacked units of chain_depth run inside the two-level launch, which takes their grandchildren's
+        // rows from LDS -- no record of their own, the closing record says which depth it carries)
+        const int chained = t.td_chain && U.n > 0 ? U.chain_depth : -1;
         p.levels(OP_LEVEL, t.level_lists_sorted ? L_REST_TD_SORTED : L_REST_TD, U.td_offsets_r, head, nd, false, td_fused_kind,
-                 [&](int l) { add_stack(p, U, U.stack_td_offsets, l); });
+                 [&](int l) { if (l != chained) add_stack(p, U, U.stack_td_offsets, l); });
         p.bracket = 3;
-        if (U.n > 0) p.add(OP_SUPER, L_NONE, 0, U.n);
+        if (U.n > 0) p.add(OP_SUPER, L_NONE, 0, U.n).arg = chained + 1;
         return p.v;
     }
     // F81 family: the roots and the levels right below them in one launch
