@@ -386,6 +386,36 @@ int pml_expected_history(pml_ctx* ctx, int32_t col_begin, int32_t col_end, doubl
                          double* branch_jumps_out);
 
 /*
+ * The same quantities -- exact expected dwell times and Markov jumps under the posterior over whole histories -- for a context of
+ * eigen-decomposed models (pml_model_set_eigen: JTT, CUSTOM_RATES, HKY handed over by its d, A, Ainv), 2 <= k <= 256, from the
+ * vectors of the marginal pass (needs pml_bottom_up (marginal) and pml_top_down_marginals first, PML_ERR_INVALID otherwise) by the
+ * eigenbasis integral of Minin & Suchard / Hobolth & Jensen -- no sweep, no sampling and no P(t): memory is O(N k), and a context
+ * with a P(t) window keeps no batch.  Per column, d[k], A[k][k], Ainv[k][k] the doubles of pml_model_set_eigen, Q = A diag(d) Ainv,
+ * t'_n = (dist_n + tau) tau_factor sf, L_n = t'_n / sf; for every non-root node n with parent p and t'_n > 0:
+ *   v_n      bottom-up vector of n (a tip: its 0/1 mask; any scaling cancels)
+ *   r_n    = Ainv v_n,   E_n = exp(d t'_n) elementwise,   m_n = A (E_n o r_n)   (= P(t'_n) v_n)
+ *   o_n[a] = q_p[a] / m_n[a] (0 where q_p[a] == 0), q_p the marginal posterior of p,   l_n = A^T o_n
+ *   Phi_cd(t) = integral_0^t exp(d_c u) exp(d_d (t - u)) du = t exp(d_d t) phi((d_c - d_d) t),  phi(z) = expm1(z) / z, phi(0) = 1
+ *               (= (E[c] - E[d]) / (d_c - d_d) where |z| >= 0.5; below, the series of phi at |z| times the smaller exponential)
+ *   X_n[c][d] = l_n[c] Phi_cd(t'_n) r_n[d],   W = sum_n X_n,   G = diag(d) - Ainv diag(Q_ii) A
+ *   times_out[col][s]        = (1 / sf) sum_cd Ainv[c][s] W[c][d] A[s][d]   (units of smoothed length; their sum is sum_n L_n)
+ *   jumps_out[col][i][j]     = Q_ij sum_cd Ainv[c][i] W[c][d] A[j][d]       (i != j; the diagonal exactly 0)
+ *   branch_jumps_out[col][n] = sum_cd G[c][d] X_n[c][d]       (caller's numbering; a root and a branch with t' = 0: exactly 0)
+ * A branch with t' = 0 adds nothing.  The sums are not sums of non-negative terms: an entry that rounding leaves below zero is
+ * returned as 0.0.  Output shapes and the optional NULLs are those of pml_expected_history: what is not asked for is not computed,
+ * and times_out has the same bits either way.  The masks are those the marginal pass ran with.
+ * PML_ERR_UNSUPPORTED: an F81 context (pml_expected_history serves it), an HKY context (hand the model over as an eigen model),
+ * k > 256.  PML_ERR_INVALID: no marginal pass, k < 2, a column whose sf is not finite and positive or whose d is not finite (the
+ * message names the column; a sub-range call serves the others).  A refused call leaves the context as it was.
+ * No atomics: the nodes are walked in the caller's numbering in pieces of 512 ids, the partials are summed in piece order, and the
+ * bits of every output do not depend on launch geometry, on which other columns are in the call, on the column a character sits
+ * in, on which outputs are asked for or on how often it is called.  They do follow the schedule switches, which change the bits
+ * of the eigen sweeps' posteriors.  The results of the marginal pass stay as they are.
+ */
+int pml_expected_history_eigen(pml_ctx* ctx, int32_t col_begin, int32_t col_end, double* times_out, double* jumps_out,
+                               double* branch_jumps_out);
+
+/*
  * pml_expected_history per time interval, with the number of lineages in each state at every boundary: exact, F81 family, from
  * the vectors of the marginal pass (needs one, PML_ERR_INVALID otherwise).  Notation of pml_expected_history: x_n, L_n, S_n,
  * o_n, O_n, v_n, the stored e_n inside m_n.

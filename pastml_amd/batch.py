@@ -425,6 +425,20 @@ class CharacterBatch(object):
             self.unalter(altered)
         return self.resident_loglik, times, jumps_out, branch_out
 
+    def expected_history_eigen(self, models, jumps=True, branch_jumps=False):
+        """
+        expected_history for characters under eigen models (``pml_expected_history_eigen``): the marginal pass with the masks
+        altered for the characters with tau == 0, the pass over what it left on the device, then the masks restored as
+        ``bottom_up`` restores them.  Returns (ln L [m], times [m, k], jumps [m, k, k] or None, branch_jumps [m, N] or None) as
+        Engine.expected_history_eigen describes them.
+        """
+        altered = self.marginal_pass_resident(models)
+        try:
+            times, jumps_out, branch_out = self.engine.expected_history_eigen(jumps=jumps, branch_jumps=branch_jumps)
+        finally:
+            self.unalter(altered)
+        return self.resident_loglik, times, jumps_out, branch_out
+
     def history_through_time(self, models, node_times, boundaries, jumps=True, lineages=True):
         """
         expected_history per time interval, with the lineages at every boundary, of every character under its F81-family model

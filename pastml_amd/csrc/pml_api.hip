@@ -754,6 +754,8 @@ int pml_model_set_eigen(pml_ctx* ctx, int32_t col_begin, int32_t col_end, const 
     const int nc = col_end - col_begin;
     PML_TRY(params_flush(ctx));
     PML_TRY(upload(ctx, ctx->d_d + col_begin * k, d, nc * k));
+    if (ctx->h_eig_d.size() != (size_t)ctx->C * k) ctx->h_eig_d.assign((size_t)ctx->C * k, 0.0);
+    memcpy(ctx->h_eig_d.data() + col_begin * k, d, nc * k * sizeof(double));
     PML_TRY(upload(ctx, ctx->d_A + col_begin * k * k, A, nc * k * k));
     PML_TRY(upload(ctx, ctx->d_Ainv + col_begin * k * k, Ainv, nc * k * k));
     if (k > 64 && k <= 128) {
@@ -1940,6 +1942,50 @@ int pml_expected_history(pml_ctx* ctx, int32_t col_begin, int32_t col_end, doubl
     if (jumps_out) PML_TRY(mem.get(&d_jumps, cols * k * k));
     if (branch_jumps_out) PML_TRY(mem.get(&d_branch, cols * N));
     PML_TRY(launch_history(ctx, mem, col_begin, col_end, d_times, d_jumps, d_branch));
+    HIP_TRY(hipMemcpyAsync(times_out, d_times, cols * k * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+    if (jumps_out) HIP_TRY(hipMemcpyAsync(jumps_out, d_jumps, cols * k * k * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+    if (branch_jumps_out)
+        HIP_TRY(hipMemcpyAsync(branch_jumps_out, d_branch, cols * N * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+    return mem.finish();
+}
+
+// Exact expected dwell times and Markov jumps of the columns [col_begin, col_end) under the eigen-decomposed models
+// (pml_launch_history_eigen.hip): the eigenbasis integral over the vectors the marginal pass left on the device.  No P(t): the
+// bottom-up vectors and the posteriors are made complete, the batch (or the window) is not touched.  The masks are those the pass
+// ran with.
+int pml_expected_history_eigen(pml_ctx* ctx, int32_t col_begin, int32_t col_end, double* times_out, double* jumps_out,
+                               double* branch_jumps_out) {
+    const char* entry = "pml_expected_history_eigen";
+    PML_TRY(require_model(ctx));
+    PML_TRY(check_cols(ctx, col_begin, col_end));
+    if (!times_out) return fail(PML_ERR_INVALID, "%s: times_out is NULL", entry);
+    if (ctx->kind == PML_MODEL_F81)
+        return fail(PML_ERR_UNSUPPORTED, "%s is for the eigen-decomposed models: this context's model kind is F81 (F81, JC, EFT), "
+                    "which pml_expected_history serves", entry);
+    if (ctx->kind == PML_MODEL_HKY)
+        return fail(PML_ERR_UNSUPPORTED, "%s is for the eigen-decomposed models: this context's model kind is HKY; hand the model "
+                    "over as an eigen model (pml_model_set_eigen with the d, A, Ainv of its rate matrix)", entry);
+    PML_TRY(need_marginal_pass(ctx, entry));
+    if (ctx->k < 2) return fail(PML_ERR_INVALID, "%s: k = %d, a character of one state has no history", entry, ctx->k);
+    if (ctx->k > 256) return fail(PML_ERR_UNSUPPORTED, "%s: k = %d, the matrix models hold at most 256 states", entry, ctx->k);
+    const size_t k = ctx->k, N = (size_t)ctx->N, cols = (size_t)(col_end - col_begin);
+    const double* sf = ctx->h_params + ctx->cols.params.sf;
+    for (int c = col_begin; c < col_end; ++c) {
+        if (!std::isfinite(sf[c]) || !(sf[c] > 0.0))
+            return fail(PML_ERR_INVALID, "%s: column %d has a scaling factor that is not finite and positive", entry, c);
+        for (size_t m = 0; m < k; ++m)
+            if (ctx->h_eig_d.size() != (size_t)ctx->C * k || !std::isfinite(ctx->h_eig_d[(size_t)c * k + m]))
+                return fail(PML_ERR_INVALID, "%s: column %d has an eigenvalue that is not finite", entry, c);
+    }
+    PML_TRY(wait_pending(ctx, true));   // (a pass that ended in a spin on the completion word may have left the stream busy)
+    PML_TRY(materialize_cherries(ctx));
+    PML_TRY(materialize_tip_posteriors(ctx));
+    CallScope mem(ctx->stream, false);
+    double *d_times, *d_jumps = nullptr, *d_branch = nullptr;
+    PML_TRY(mem.get(&d_times, cols * k));
+    if (jumps_out) PML_TRY(mem.get(&d_jumps, cols * k * k));
+    if (branch_jumps_out) PML_TRY(mem.get(&d_branch, cols * N));
+    PML_TRY(launch_history_eigen(ctx, mem, col_begin, col_end, d_times, d_jumps, d_branch));
     HIP_TRY(hipMemcpyAsync(times_out, d_times, cols * k * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
     if (jumps_out) HIP_TRY(hipMemcpyAsync(jumps_out, d_jumps, cols * k * k * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
     if (branch_jumps_out)

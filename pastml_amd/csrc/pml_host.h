@@ -132,6 +132,7 @@ struct pml_ctx {
     bool active_partial = false;  // ... some column does (pml_bottom_up_submit_columns)
     int n_active = 0;             // columns that take part in the next sweep
     int sched_cols = 0;           // the number of columns the schedule of a sweep is chosen for (C; 32 for a few active ones)
+    std::vector<double> h_eig_d;  // [C][k]: the eigenvalues pml_model_set_eigen was given (pml_expected_history_eigen checks them)
     double* d_Asym = nullptr;   // [C][k][k], 65 <= k <= 128: the one matrix of the sum sweeps (eig_sym_kernel)
     double* d_eigT = nullptr;   // [C][k][k]: scratch of that kernel
     std::vector<double> h_symA; // [C][k k + k]: the A and pi d_Asym was made from (an unchanged model is not orthonormalised again)

@@ -210,6 +210,9 @@ PML_INTERNAL int launch_gradient(pml_ctx* ctx, CallScope& mem, int cb, int ce, d
 //      (pml_expected_history); device arrays d_times [cols][k], d_jumps [cols][k][k] or null, d_branch [cols][N] in the caller's
 //      numbering or null; queued only: partials and staged scalars go into the caller's scope, which waits
 PML_INTERNAL int launch_history(pml_ctx* ctx, CallScope& mem, int cb, int ce, double* d_times, double* d_jumps, double* d_branch);
+// ---- pml_launch_history_eigen.hip: the same for the eigen-decomposed models, 2 <= k <= 256 (pml_expected_history_eigen); the
+//      same device arrays; queued only: the staged vectors and the partials go into the caller's scope, which waits
+PML_INTERNAL int launch_history_eigen(pml_ctx* ctx, CallScope& mem, int cb, int ce, double* d_times, double* d_jumps, double* d_branch);
 // ---- pml_launch_history_sample.hip: histories of column col drawn on the scenarios d_states [N][rs] that launch_scenarios left
 //      on the device (pml_sample_histories); device arrays d_times [n_rep][k], d_jumps [n_rep][k][k] (zeroed) or null, d_branch
 //      [N][n_rep] in the caller's numbering or null, d_skipped: one counter (zeroed); queued only: the partials go into the

@@ -112,6 +112,7 @@ SIGNATURES = {
     'pml_expected_counts': [_ctx_p, ctypes.c_int32, ctypes.c_int32, ctypes.POINTER(ctypes.c_uint8), _c_double_p, _c_double_p],
     'pml_loglik_gradient': [_ctx_p, ctypes.c_int32, ctypes.c_int32, _c_double_p, _c_double_p, _c_int32_p],
     'pml_expected_history': [_ctx_p, ctypes.c_int32, ctypes.c_int32, _c_double_p, _c_double_p, _c_double_p],
+    'pml_expected_history_eigen': [_ctx_p, ctypes.c_int32, ctypes.c_int32, _c_double_p, _c_double_p, _c_double_p],
     'pml_history_through_time': [_ctx_p, ctypes.c_int32, ctypes.c_int32, _c_double_p, _c_double_p, ctypes.c_int32, _c_double_p,
                                  _c_double_p, _c_double_p],
     'pml_simulate_states': [_ctx_p, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_uint64, ctypes.c_void_p],
@@ -883,6 +884,25 @@ class Engine(BareContext):
         _check(self._lib.pml_expected_history(self._ctx, col_begin, col_end, _ptr(times, ctypes.c_double),
                                               None if jumps_out is None else _ptr(jumps_out, ctypes.c_double),
                                               None if branch_out is None else _ptr(branch_out, ctypes.c_double)))
+        return times, jumps_out, branch_out
+
+    def expected_history_eigen(self, col_begin=0, col_end=None, jumps=True, branch_jumps=False):
+        """
+        expected_history for an engine of eigen-decomposed models (JTT, CUSTOM_RATES, HKY handed over as HKYModel.eigen_spec()),
+        2 to 256 states: the eigenbasis integral over the vectors of the marginal pass, no P(t) (pml_expected_history_eigen;
+        include/pastml_hip.h has the sums).  The same return values: (times [cols, k], jumps [cols, k, k] or None, branch_jumps
+        [cols, n_nodes] or None); an entry that rounding leaves below zero is returned as 0.  What is not asked for is not computed.
+        """
+        col_end = self.n_cols if col_end is None else col_end
+        if not 0 <= col_begin < col_end <= self.n_cols:
+            raise ValueError('bad column range')
+        cols = col_end - col_begin
+        times = np.empty((cols, self.k), dtype=np.float64)
+        jumps_out = np.empty((cols, self.k, self.k), dtype=np.float64) if jumps else None
+        branch_out = np.empty((cols, self.n_nodes), dtype=np.float64) if branch_jumps else None
+        _check(self._lib.pml_expected_history_eigen(self._ctx, col_begin, col_end, _ptr(times, ctypes.c_double),
+                                                    None if jumps_out is None else _ptr(jumps_out, ctypes.c_double),
+                                                    None if branch_out is None else _ptr(branch_out, ctypes.c_double)))
         return times, jumps_out, branch_out
 
     def history_through_time(self, node_times, boundaries, col_begin=0, col_end=None, jumps=True, lineages=True):

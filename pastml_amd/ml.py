@@ -878,6 +878,79 @@ def expected_history(forest, characters, models, branch_jumps=False):
     return results[0] if single else results
 
 
+class _AsEigenModel(object):
+    """An HKY model as the batch sees an eigen model: everything is the model's but the kernel description."""
+
+    def __init__(self, model):
+        self._model = model
+
+    def __getattr__(self, name):
+        return getattr(self._model, name)
+
+    def kernel_spec(self):
+        return self._model.eigen_spec()
+
+
+def expected_history_general(forest, characters, models, branch_jumps=False):
+    """
+    ``expected_history`` for every model: the exact expected dwell times and numbers of Markov jumps under the posterior over
+    whole histories, for characters under the F81 family, the eigen models (JTT, CUSTOM_RATES) and HKY alike.
+
+    Characters are grouped by their number of states and by path; a group is one batch on the device.  F81-family characters
+    take ``expected_history``'s path (``pml_expected_history``) and their results are its results bit for bit.  Eigen models
+    take the eigenbasis integral of Minin & Suchard / Hobolth & Jensen over the vectors of the marginal pass
+    (``pml_expected_history_eigen``, HIP; include/pastml_hip.h has the sums; 2 to 256 states; no P(t), memory O(N k)).  HKY
+    runs as an eigen model, built from ``HKYModel.eigen_spec()``: its ``log_likelihood`` is then that of the eigen sweeps, which
+    agrees with the closed-form HKY sweep to rounding, not bit for bit.  The sums of the eigen path have mixed signs: an entry
+    that rounding leaves below zero is returned as 0.
+
+    The file-level front end and sharding over ranks are not covered.  Parameters and return values are ``expected_history``'s.
+    """
+    from pastml_amd import sharding
+    from pastml_amd.batch import CharacterBatch, LikelihoodError, annotation_words, likelihood_error
+    from pastml_amd.models import KIND_F81, KIND_HKY
+    if isinstance(forest, TreeNode):
+        forest = [forest]
+    single = isinstance(characters, str)
+    if single:
+        characters, models = [characters], [models]
+    characters, models = list(characters), list(models)
+    if len(characters) != len(models):
+        raise ValueError('one model per character expected')
+    world = sharding.rank_world()[1]
+    if world > 1:
+        raise NotImplementedError('expected_history_general is not supported under a multi-process launch ({} ranks): run it in '
+                                  'a single process'.format(world))
+    flat = get_flat_forest(forest)
+    groups = {}
+    for i, model in enumerate(models):
+        kind = model.kernel_spec()['kind']
+        groups.setdefault((len(model.states), kind == KIND_F81), []).append(i)
+        if kind == KIND_HKY:
+            models[i] = _AsEigenModel(model)
+    results = [None] * len(characters)
+    has_parent = flat.parent >= 0
+    for (k, f81), members in groups.items():
+        group_models = [models[i] for i in members]
+        with CharacterBatch(flat, k, len(members)) as batch:
+            for c, i in enumerate(members):
+                batch.set_annotation(c, *annotation_words(flat, characters[i], models[i].states))
+            batch.initialize_allowed_states()
+            run = batch.expected_history if f81 else batch.expected_history_eigen
+            try:
+                lnl, times, jumps, per_branch = run(group_models, jumps=True, branch_jumps=branch_jumps)
+            except LikelihoodError as e:
+                raise likelihood_error(flat, e)
+        for c, i in enumerate(members):
+            _, tau, tau_factor = models[i].rate_params()
+            result = dict(log_likelihood=float(lnl[c]), states=np.array(models[i].states), times=times[c].copy(),
+                          jumps=jumps[c].copy(), tree_length=float(((flat.dist[has_parent] + tau) * tau_factor).sum()))
+            if branch_jumps:
+                result['branch_jumps'] = per_branch[c].copy()
+            results[i] = result
+    return results[0] if single else results
+
+
 # =====================================================================================================================
 # expected_history_through_time
 # =====================================================================================================================

@@ -5,7 +5,7 @@ per-branch arithmetic runs on the device (kernel_spec() describes the model to l
 """
 import numpy as np
 
-from pastml_amd.models import Model, ModelWithFrequencies, PointBlock, ScalarParameter, KIND_F81, KIND_HKY
+from pastml_amd.models import Model, ModelWithFrequencies, PointBlock, ScalarParameter, KIND_F81, KIND_HKY, KIND_EIGEN
 
 
 F81 = 'F81'
@@ -266,3 +266,26 @@ class HKYModel(ModelWithFrequencies):
     def kernel_spec(self):
         return dict(kind=KIND_HKY, pi=np.ascontiguousarray(self.frequencies, dtype=np.float64),
                     kappa=float(self.kappa))
+
+    def eigen_spec(self):
+        """
+        The model as an eigen model: dict(kind=KIND_EIGEN, pi, d, A, Ainv) of the rate matrix Q whose exponential is the
+        closed-form P(t) (HKYModel.py:55-82): with beta = .5 / (pi_ag pi_ct + kappa (pi_a pi_g + pi_c pi_t)), Q_ij = kappa beta pi_j
+        for the transitions A <-> G and C <-> T, beta pi_j for the transversions.  Decomposed through the symmetrised matrix
+        diag(sqrt(pi)) Q diag(1 / sqrt(pi)) = U diag(d) U^T (numpy.linalg.eigh): A = diag(1 / sqrt(pi)) U, Ainv = U^T diag(sqrt(pi)),
+        so Ainv[m][j] = A[j][m] pi[j] and a repeated eigenvalue (kappa = 1: F81) still gets an orthogonal basis.  What the entries
+        for the eigen models take (``ml.expected_history_general``); the sweeps of such a context agree with the closed-form ones to
+        rounding, not bit for bit.
+        """
+        pi = np.ascontiguousarray(self.frequencies, dtype=np.float64)
+        kappa = float(self.kappa)
+        a, c, g, t = pi
+        beta = .5 / ((a + g) * (c + t) + kappa * (a * g + c * t))
+        rates = np.ones((4, 4)) - np.eye(4)
+        rates[0, 2] = rates[2, 0] = rates[1, 3] = rates[3, 1] = kappa
+        root = np.sqrt(pi)
+        sym = beta * rates * np.outer(root, root)
+        sym -= np.diag((beta * rates * pi).sum(axis=1))
+        d, u = np.linalg.eigh(sym)
+        return dict(kind=KIND_EIGEN, pi=pi, d=np.ascontiguousarray(d), A=np.ascontiguousarray(u / root[:, None]),
+                    Ainv=np.ascontiguousarray(u.T * root[None, :]))
