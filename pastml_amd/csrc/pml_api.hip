@@ -1110,6 +1110,7 @@ static PmlSweepTraits sweep_traits(const pml_ctx* ctx) {
     t.eig_nb = ks4 % 4 == 0 ? 1 : (ks4 % 2 == 0 ? 2 : 4);   // EigShape::NB (pml_kernels_eigen_mfma.h)
     // (the chained launch is the pipelined kernel's: without the pipeline, the two launches)
     t.td_chain = t.f81 && t.super && ctx->sup.chain_depth >= 0 && !ctx->tune.on(T_NO_TD_CHAIN) && !ctx->tune.on(T_NO_TD_SUPER_PIPE);
+    t.bu_chain = t.f81 && t.super && ctx->sup.bu_chain_level >= 0 && !ctx->tune.on(T_NO_BU_CHAIN);   // (the plan asks: marginal sweep)
     return t;
 }
 
@@ -1165,7 +1166,8 @@ static int run_plan(pml_ctx* ctx, const std::vector<PmlLaunch>& whole_plan, bool
         if (ctx->tune.on(T_DEBUG))
             fprintf(stderr, "pml plan: branch %d op %d list %d kind %d first %d count %d arg %d bracket %d signal %d%s\n", r.branch,
                     r.op, r.list, r.kind, r.first, r.count, r.arg, r.bracket, (int)r.signal,
-                    r.op == OP_SUPER && !bottom_up && r.arg > 0 ? " (chained: with the stacked units of depth arg - 1)" : "");
+                    r.op != OP_SUPER || r.arg <= 0 ? "" : bottom_up ? " (chained: with the stacked units of level arg - 1)"
+                                                                    : " (chained: with the stacked units of depth arg - 1)");
         if (r.bracket != open) {
             if (open != PML_NO_BRACKET) PML_TRY(prof_end(ctx, open, launches));
             if (r.bracket != PML_NO_BRACKET) PML_TRY(prof_begin(ctx));
@@ -1217,7 +1219,7 @@ static int run_plan(pml_ctx* ctx, const std::vector<PmlLaunch>& whole_plan, bool
                 PML_TRY(dispatch_blocks_f81(ctx, bottom_up, r.first, r.signal));
                 break;
             case OP_SUPER:
-                PML_TRY(dispatch_super_f81(ctx, bottom_up, bottom_up ? -1 : r.arg - 1));
+                PML_TRY(dispatch_super_f81(ctx, bottom_up, r.arg - 1));
                 break;
             case OP_STACK:
                 PML_TRY(dispatch_stack_f81(ctx, bottom_up, r.first));

@@ -1794,9 +1794,11 @@ __device__ __forceinline__ void super_loads_arrived(SuperLoads<R>& ld) {
 
 // false: some vector came out all zero (nothing of the failing unit was stored); the caller repeats the three units
 // on the sequential path, which names the pair the reference would.
+// keep: what the node's own unit leaves in registers besides storing it (bu_f81_chain_kernel goes on with it)
 template <int G, int R>
 __device__ __forceinline__ bool bu_f81_super_unit(const LaneCtx<G, R>& L, const PmlTree& t, const PmlCols& c,
-                                                  const PmlState& st, const SuperRegs& s, SuperLoads<R>& ld) {
+                                                  const PmlState& st, const SuperRegs& s, SuperLoads<R>& ld,
+                                                  BuResult<R>* keep = nullptr) {
     super_loads_arrived<R>(ld);
     const u64 kbits = state_bits(c.k);
     bool ones = c.k == G * R;  // (a padding entry must stay 0, and only a mask makes it so)
@@ -1831,7 +1833,7 @@ __device__ __forceinline__ bool bu_f81_super_unit(const LaneCtx<G, R>& L, const 
         top.v0[r] = res[0].v[r];
         top.v1[r] = res[1].v[r];
     }
-    return bu_f81_marg_body<G, R, true, false>(L, t, c, st, super_own(s), top);
+    return bu_f81_marg_body<G, R, true, false>(L, t, c, st, super_own(s), top, keep, true);
 }
 
 template <int G, int R>
@@ -2945,30 +2947,121 @@ __device__ __forceinline__ UnitRegs stack_child(const StackRegs& s, int j) {
     return u;
 }
 
-// what a unit with two stored children reads about them: lane j < 2 holds child j's scalars, the vectors in v0 / v1
+// Where a unit with two stored children takes their bottom-up vectors, pi . v and exponents from: from memory (every kernel
+// but one), or from the LDS slots in which bu_f81_chain_kernel has left them in the same launch (BuKidsFromLds).  j: which child
+// of a stacked node the unit is.
+struct BuKidsFromMemory {
+    template <int G, int R>
+    __device__ __forceinline__ void scalars(const LaneCtx<G, R>& L, int, int ch, double& s, i64& be) const {
+        s = L.S[ch];
+        be = L.be[ch];
+    }
+    template <int G, int R>
+    __device__ __forceinline__ void vectors(const LaneCtx<G, R>& L, const PmlCols& c, int, int first, double (&v0)[R],
+                                            double (&v1)[R]) const {
+        node_load_vec<G, R>(L, c, L.bu, first, v0);
+        node_load_vec<G, R>(L, c, L.bu, first + 1, v1);
+    }
+};
+// LDS slot of a two-level node's bottom-up vector: G * R doubles in state order, then pi . v and the exponent
+#define PML_BU_CHAIN_SLOT(G, R) ((G) * (R) + 2)
+struct BuKidsFromLds {
+    const double* slots;  // of the stacked node's four grandchildren, in order
+    template <int G, int R>
+    __device__ __forceinline__ void scalars(const LaneCtx<G, R>& L, int j, int, double& s, i64& be) const {
+        const double* row = slots + (2 * j + (L.g & 1)) * PML_BU_CHAIN_SLOT(G, R);
+        s = row[G * R];
+        be = *reinterpret_cast<const i64*>(row + G * R + 1);
+    }
+    template <int G, int R>
+    __device__ __forceinline__ void vectors(const LaneCtx<G, R>& L, const PmlCols&, int j, int, double (&v0)[R],
+                                            double (&v1)[R]) const {
+        const double* row = slots + 2 * j * PML_BU_CHAIN_SLOT(G, R);
+#pragma unroll
+        for (int r = 0; r < R; r += 2) {
+            const double2 a = *reinterpret_cast<const double2*>(row + L.st(r));
+            const double2 b = *reinterpret_cast<const double2*>(row + PML_BU_CHAIN_SLOT(G, R) + L.st(r));
+            v0[r] = a.x;
+            v0[r + 1] = a.y;
+            v1[r] = b.x;
+            v1[r + 1] = b.y;
+        }
+    }
+};
+// bu_f81_chain_kernel's source: the slots, or memory for a tile with a unit that took the sequential path (wave-uniform)
+struct BuKidsOfChain {
+    const double* slots;
+    bool from_memory;
+    template <int G, int R>
+    __device__ __forceinline__ void scalars(const LaneCtx<G, R>& L, int j, int ch, double& s, i64& be) const {
+        if (from_memory) BuKidsFromMemory().scalars<G, R>(L, j, ch, s, be);
+        else BuKidsFromLds{slots}.scalars<G, R>(L, j, ch, s, be);
+    }
+    template <int G, int R>
+    __device__ __forceinline__ void vectors(const LaneCtx<G, R>& L, const PmlCols& c, int j, int first, double (&v0)[R],
+                                            double (&v1)[R]) const {
+        if (from_memory) BuKidsFromMemory().vectors<G, R>(L, c, j, first, v0, v1);
+        else BuKidsFromLds{slots}.vectors<G, R>(L, c, j, first, v0, v1);
+    }
+};
+// a two-level node's vector, pi . v and exponent as node_load_vec, L.S and L.be would read them back after bu_f81_marg_body's
+// stores: states from ks on were not stored and read as 0 (as TdRowToLds does for rows)
 template <int G, int R>
+__device__ __forceinline__ void bu_chain_slot_store(const LaneCtx<G, R>& L, const PmlCols& c, double* row, const BuResult<R>& res) {
+#pragma unroll
+    for (int r = 0; r < R; r += 2) {
+        double2 t2;
+        t2.x = L.st(r) < c.ks ? res.v[r] : 0.0;
+        t2.y = L.st(r) < c.ks ? res.v[r + 1] : 0.0;
+        *reinterpret_cast<double2*>(row + L.st(r)) = t2;
+    }
+    if (L.g == 0) {
+        row[G * R] = res.s;
+        *reinterpret_cast<i64*>(row + G * R + 1) = res.e;
+    }
+}
+
+// what a stacked unit reads besides its grandchildren's vectors, pi . v and exponents (lane j < 2: of child / grandchild j)
+struct StackAhead {
+    double e[2], e_top;
+    u64 own[2], own_top;
+};
+template <int G, int R>
+__device__ __forceinline__ void stack_ahead_issue(const LaneCtx<G, R>& L, const StackRegs& s, StackAhead& a) {
+#pragma unroll
+    for (int j = 0; j < 2; ++j) {
+        a.e[j] = L.E[(j ? s.g1 : s.g0) + (L.g & 1)];
+        a.own[j] = L.mask[(unsigned)(s.fc + j)];
+    }
+    a.e_top = L.E[s.fc + (L.g & 1)];
+    a.own_top = L.mask[(unsigned)s.n];
+}
+
+// what a unit with two stored children reads about them: lane j < 2 holds child j's scalars, the vectors in v0 / v1
+// (ahead: E and the mask word were loaded before, stack_ahead_issue)
+template <int G, int R, class Kids = BuKidsFromMemory>
 __device__ __forceinline__ void stack_child_loads(const LaneCtx<G, R>& L, const PmlCols& c, int node, int first,
-                                                  BuLoads<R>& ld) {
+                                                  BuLoads<R>& ld, const Kids& kids = Kids(), int j = 0,
+                                                  const StackAhead* ahead = nullptr) {
     const int ch = first + (L.g & 1);
-    ld.cl.e = L.E[ch];
-    ld.cl.s = L.S[ch];
-    ld.cl.be = L.be[ch];
+    ld.cl.e = ahead != nullptr ? ahead->e[j] : L.E[ch];
+    kids.template scalars<G, R>(L, j, ch, ld.cl.s, ld.cl.be);
     ld.cl.mask = 0ull;
     ld.tl.e = ld.tl.s = ld.tl.a = 0.0;
     ld.tl.mask = 0ull;
-    ld.own = L.mask[(unsigned)node];
-    node_load_vec<G, R>(L, c, L.bu, first, ld.v0);
-    node_load_vec<G, R>(L, c, L.bu, first + 1, ld.v1);
+    ld.own = ahead != nullptr ? ahead->own[j] : L.mask[(unsigned)node];
+    kids.template vectors<G, R>(L, c, j, first, ld.v0, ld.v1);
 }
 
-template <int G, int R>
+template <int G, int R, class Kids = BuKidsFromMemory>
 __device__ __forceinline__ bool bu_f81_stack_unit(const LaneCtx<G, R>& L, const PmlTree& t, const PmlCols& c,
-                                                  const PmlState& st, const StackRegs& s) {
+                                                  const PmlState& st, const StackRegs& s, const Kids& kids = Kids(),
+                                                  const StackAhead* ahead = nullptr) {
     BuLoads<R> ld[2];
 #pragma unroll
-    for (int j = 0; j < 2; ++j) stack_child_loads<G, R>(L, c, s.fc + j, j ? s.g1 : s.g0, ld[j]);
-    const double e_top = L.E[s.fc + (L.g & 1)];
-    const u64 own = L.mask[(unsigned)s.n];
+    for (int j = 0; j < 2; ++j) stack_child_loads<G, R>(L, c, s.fc + j, j ? s.g1 : s.g0, ld[j], kids, j, ahead);
+    const double e_top = ahead != nullptr ? ahead->e_top : L.E[s.fc + (L.g & 1)];
+    const u64 own = ahead != nullptr ? ahead->own_top : L.mask[(unsigned)s.n];
     BuResult<R> res[2];
 #pragma unroll
     for (int j = 0; j < 2; ++j)
@@ -2994,6 +3087,19 @@ __device__ __forceinline__ bool bu_f81_stack_unit(const LaneCtx<G, R>& L, const 
     return bu_f81_marg_body<G, R, true, false>(L, t, c, st, un, top);
 }
 
+// an all-zero vector: the three units on the sequential path, which names the pair the reference would
+template <int G, int R>
+__device__ __forceinline__ void bu_f81_stack_seq(const LaneCtx<G, R>& L, const PmlTree& t, const PmlCols& c,
+                                                 const PmlState& st, const StackRegs& s) {
+    bu_f81_unit_seq<G, R, false>(L, t, c, st, stack_child(s, 0));
+    bu_f81_unit_seq<G, R, false>(L, t, c, st, stack_child(s, 1));
+    __threadfence();
+    UnitRegs un = stack_child(s, 0);
+    un.n = s.n;
+    un.fc = s.fc;
+    bu_f81_unit_seq<G, R, false>(L, t, c, st, un);
+}
+
 template <int G, int R>
 __global__ void __launch_bounds__(PML_BLOCK) __attribute__((amdgpu_waves_per_eu(2, 2)))
 bu_f81_stack_kernel(PmlTree t, PmlCols c, PmlState st, const PmlUnit* __restrict__ units, int n_level) {
@@ -3009,19 +3115,107 @@ bu_f81_stack_kernel(PmlTree t, PmlCols c, PmlState st, const PmlUnit* __restrict
         const int nxt_idx = idx + stride;
         const StackRegs nxt = load_stack(units, nxt_idx < n_level ? nxt_idx : 0);
         if (idx < n_level) {
-            if (!bu_f81_stack_unit<G, R>(L, t, c, st, cur)) {
-                // an all-zero vector: the three units on the sequential path, which names the pair the reference would
-                bu_f81_unit_seq<G, R, false>(L, t, c, st, stack_child(cur, 0));
-                bu_f81_unit_seq<G, R, false>(L, t, c, st, stack_child(cur, 1));
-                __threadfence();
-                UnitRegs un = stack_child(cur, 0);
-                un.n = cur.n;
-                un.fc = cur.fc;
-                bu_f81_unit_seq<G, R, false>(L, t, c, st, un);
-            }
+            if (!bu_f81_stack_unit<G, R>(L, t, c, st, cur)) bu_f81_stack_seq<G, R>(L, t, c, st, cur);
         }
         cur = nxt;
         idx = nxt_idx;
+    }
+}
+
+// The two-level units and the stacked units of the lowest level that has any in ONE launch (PmlSuperSchedule::bu_chain_level:
+// stacked unit m has the two-level nodes 4 m .. 4 m + 3 of `units` as grandchildren, in order, so n_level = 4 x the stacked
+// nodes of `stack_units`).  A wave owns tiles: tile q is the 4 UW two-level nodes 4 q UW .. 4 q UW + 4 UW - 1 (phase A: four
+// wave passes of bu_f81_super_unit as bu_f81_super_kernel runs it, stores included) and then the UW stacked nodes q UW .. q UW +
+// UW - 1 above them (phase B: one wave pass of bu_f81_stack_unit as bu_f81_stack_kernel runs it).  Phase A leaves vector, pi . v
+// and exponent of its nodes in the wave's LDS slots as well (bu_chain_slot_store), the values node_load_vec, L.S and L.be would
+// have read back in the next launch, and phase B takes them from there (BuKidsOfChain): the vectors are written to memory once
+// -- the top-down sweep, the downloads and the other schedules read them -- and not read back.  The same unit functions with the
+// same arguments in the same lane shape, and a wave pass holds the same UW aligned units as in the two kernels: the same bits.
+// Loads as in bu_f81_super_kernel: those of a two-level pass are issued one pass ahead and its descriptor two; the next tile's
+// first pass is issued in the tile's last pass, before phase B's arithmetic.  What phase B still reads from memory (E of the
+// two children and the four grandchildren, three mask words: none of it written by a bottom-up sweep) is issued at the start
+// of phase B, its descriptor at the start of the tile (issued a pass ahead, these twelve registers spill at 8 lanes x 8 states).
+// Fallbacks, decided per wave: a two-level unit whose vector came out all zero repeats on the sequential path, which stores
+// what it gets to; its slot is not written, so a tile with any such unit runs phase B on memory, behind a __threadfence, as the
+// second launch would (one instantiation of the stacked unit whose loads look at a wave-uniform flag: two of them spill at
+// 8 lanes x 8 states).  A stacked unit that comes out all zero takes the three sequential units of bu_f81_stack_kernel.
+// An index past the end is clamped to entry 0, so that a prefetch's addresses are those of existing nodes, and that lane group
+// does no work; its slots stay unwritten and are read only by lane groups that are past the end too.
+// (PML_BU_CHAIN_WAVES waves per workgroup: the slots of two waves are 33 792 B at 8 lanes x 8 states, four workgroups a CU.)
+#define PML_BU_CHAIN_WAVES 2
+template <int G, int R>
+__global__ void __launch_bounds__(64 * PML_BU_CHAIN_WAVES) __attribute__((amdgpu_waves_per_eu(2, 2)))
+bu_f81_chain_kernel(PmlTree t, PmlCols c, PmlState st, const PmlUnit* __restrict__ units, int n_level,
+                    const PmlUnit* __restrict__ stack_units) {
+    constexpr int UW = 64 / G, SLOT = PML_BU_CHAIN_SLOT(G, R);
+    const int wave = threadIdx.x >> 6;
+    const int sub = (threadIdx.x & 63) / G;
+    __shared__ __attribute__((aligned(16))) double node_vecs[PML_BU_CHAIN_WAVES * 4 * UW * SLOT];
+    double* const wave_vecs = node_vecs + wave * (4 * UW * SLOT);
+    LaneCtx<G, R> L;
+    lane_ctx_init<G, R>(L, t, c, st);
+    const int n_stack = n_level / 4;
+    const int n_tiles = (n_stack + UW - 1) / UW;
+    const int stride = gridDim.x * PML_BU_CHAIN_WAVES;
+    auto super_desc = [&](int q, int p) {   // pass p of tile q
+        const int i = (4 * q + p) * UW + sub;
+        return load_super(units, i < n_level ? i : 0);
+    };
+    // pass p of tile q; returns true where the unit took the sequential path
+    auto pass = [&](int q, int p, const SuperRegs& s, SuperLoads<R>& ld) {
+        if ((4 * q + p) * UW + sub >= n_level) return false;
+        BuResult<R> res;
+        if (bu_f81_super_unit<G, R>(L, t, c, st, s, ld, &res)) {
+            bu_chain_slot_store<G, R>(L, c, wave_vecs + (p * UW + sub) * SLOT, res);
+            return false;
+        }
+        bu_f81_super_seq<G, R>(L, t, c, st, s);
+        return true;
+    };
+    int q = blockIdx.x * PML_BU_CHAIN_WAVES + wave;
+    SuperRegs ua = super_desc(q, 0), ub = super_desc(q, 1);
+    SuperLoads<R> la, lb;
+    bu_f81_super_issue<G, R>(L, ua, la);
+    for (; q < n_tiles; q += stride) {
+        bool seq = false;
+        const StackRegs sk = load_stack(stack_units, q * UW + sub < n_stack ? q * UW + sub : 0);
+        {
+            const SuperRegs un = super_desc(q, 2);
+            bu_f81_super_issue<G, R>(L, ub, lb);
+            seq |= pass(q, 0, ua, la);
+            ua = un;
+        }
+        {
+            const SuperRegs un = super_desc(q, 3);
+            bu_f81_super_issue<G, R>(L, ua, la);
+            seq |= pass(q, 1, ub, lb);
+            ub = un;
+        }
+        {
+            const SuperRegs un = super_desc(q + stride, 0);
+            bu_f81_super_issue<G, R>(L, ub, lb);
+            seq |= pass(q, 2, ua, la);
+            ua = un;
+        }
+        const int m = q * UW + sub;
+        {
+            const SuperRegs un = super_desc(q + stride, 1);
+            bu_f81_super_issue<G, R>(L, ua, la);   // (the next tile's first pass: in flight across phase B)
+            seq |= pass(q, 3, ub, lb);
+            ub = un;
+        }
+        StackAhead ahead;
+        stack_ahead_issue<G, R>(L, sk, ahead);
+        wave_sync_lds();
+        const bool from_memory = __any(seq);   // (wave-uniform)
+        if (from_memory) __threadfence();      // (the stacked units read what the wave's phase A has stored)
+        if (m < n_stack) {
+            if (!bu_f81_stack_unit<G, R>(L, t, c, st, sk, BuKidsOfChain{wave_vecs + 4 * sub * SLOT, from_memory}, &ahead)) {
+                if (!from_memory) __threadfence();   // (so do the sequential units)
+                bu_f81_stack_seq<G, R>(L, t, c, st, sk);
+            }
+        }
+        wave_sync_lds();   // (the slots are the next tile's)
     }
 }
 

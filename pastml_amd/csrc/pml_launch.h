@@ -107,8 +107,9 @@ PML_INTERNAL int dispatch_small_f81(pml_ctx* ctx, bool bottom_up, bool signal, i
                                     const PmlUnit* units = nullptr, const int* d_offsets = nullptr, int skip_roots = 0);
 PML_INTERNAL int dispatch_blocks_f81(pml_ctx* ctx, bool bottom_up, int which, bool signal);
 // ---- pml_launch_f81_super.hip: two-level and stacked units
-//      chain_depth >= 0 (top-down): the launch also runs the stacked units of that depth (td_f81_chain_kernel)
-PML_INTERNAL int dispatch_super_f81(pml_ctx* ctx, bool bottom_up, int chain_depth = -1);
+//      chain >= 0: the launch also runs the stacked units of that depth (top-down, td_f81_chain_kernel) or of that level
+//      (bottom-up, bu_f81_chain_kernel)
+PML_INTERNAL int dispatch_super_f81(pml_ctx* ctx, bool bottom_up, int chain = -1);
 PML_INTERNAL int dispatch_stack_f81(pml_ctx* ctx, bool bottom_up, int level);
 // ---- pml_launch_eigen_mfma.hip: fused FP64 matrix-core sweeps of the eigen models, P(t) batch on the matrix cores
 PML_INTERNAL int launch_eigen_fused(pml_ctx* ctx, int mode, const int* nodes, int first, int n, int tips);

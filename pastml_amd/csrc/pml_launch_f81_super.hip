@@ -22,11 +22,23 @@ static void launch_td_chain_f81(pml_ctx* ctx, int a, const PmlTree& t, const Pml
                            ctx->sup.n, ctx->sup.d_stack_td + a);
 }
 
+// The chained bottom-up launch (bu_f81_chain_kernel): the two-level units and the stacked units of level bu_chain_level above
+// them, n / 4 of them from entry a of the bottom-up stacked list.  A wave's unit of work is a tile, four passes of two-level
+// units and one of stacked units, on the grid of the pipelined kernels.
+template <int G, int R>
+static void launch_bu_chain_f81(pml_ctx* ctx, int a, const PmlTree& t, const PmlCols& c, const PmlState& st) {
+    const int tiles = (ctx->sup.n + 4 * (64 / G) - 1) / (4 * (64 / G));
+    dim3 grid(grid_for(ctx, tiles, PML_BU_CHAIN_WAVES, ctx->C, true), ctx->C);
+    hipLaunchKernelGGL((bu_f81_chain_kernel<G, R>), grid, dim3(64 * PML_BU_CHAIN_WAVES), 0, ctx->stream, t, c, st, ctx->sup.d_units,
+                       ctx->sup.n, ctx->sup.d_stack_bu + a);
+}
+
 template <int G, int R>
 static void launch_super_f81(pml_ctx* ctx, bool bottom_up, int chain_first) {
     const PmlTree t = tree_of(ctx, true);
     const PmlCols c = cols_of(ctx, bottom_up);
     const PmlState st = state_of(ctx);
+    if (chain_first >= 0 && bottom_up) return launch_bu_chain_f81<G, R>(ctx, chain_first, t, c, st);
     if (chain_first >= 0) return launch_td_chain_f81<G, R>(ctx, chain_first, t, c, st);
     const int upb = PML_WAVES_PER_BLOCK * (64 / G);
     // Top-down: one unit per child of a two-level node.  Every lane shape loads one unit ahead (td_f81_super_kernel's PIPE,
@@ -60,16 +72,16 @@ static void launch_stack_f81(pml_ctx* ctx, bool bottom_up, int a, int n) {
         hipLaunchKernelGGL((td_f81_stack_kernel<G, R>), grid, block, 0, ctx->stream, t, c, st, ctx->sup.d_stack_td + a, n);
 }
 
-int dispatch_super_f81(pml_ctx* ctx, bool bottom_up, int chain_depth) {
+int dispatch_super_f81(pml_ctx* ctx, bool bottom_up, int chain) {
     if (ctx->sup.n <= 0) return PML_OK;  // (a schedule of stacked units only)
     int chain_first = -1;
-    if (chain_depth >= 0) {
-        // (the planner chains a depth only when its stacked range covers the two-level list: pml_plan_tree)
-        const std::vector<int>& off = ctx->sup.stack_td_offsets;
-        if (bottom_up || chain_depth != ctx->sup.chain_depth || chain_depth + 1 >= (int)off.size() ||
-            (long long)(off[chain_depth + 1] - off[chain_depth]) * 4 != ctx->sup.n)
-            return fail(PML_ERR_INVALID, "no chained two-level launch for depth %d", chain_depth);
-        chain_first = off[chain_depth];
+    if (chain >= 0) {
+        // (the planner chains a depth or a level only when its stacked range covers the two-level list: pml_plan_tree)
+        const std::vector<int>& off = bottom_up ? ctx->sup.stack_bu_offsets : ctx->sup.stack_td_offsets;
+        if (chain != (bottom_up ? ctx->sup.bu_chain_level : ctx->sup.chain_depth) || chain + 1 >= (int)off.size() ||
+            (long long)(off[chain + 1] - off[chain]) * 4 != ctx->sup.n)
+            return fail(PML_ERR_INVALID, "no chained two-level launch for %s %d", bottom_up ? "level" : "depth", chain);
+        chain_first = off[chain];
     }
     const auto [g, r] = ctx->cols.shape(bottom_up);
 #define X(G_, R_)                                                \

@@ -578,7 +578,22 @@ static void plan_super(const PmlForest& f, const PmlTune& tune, PmlTreePlan& P) 
                        sup_list[4 * m + 3] == g1 + 1;
         }
         if (lined_up) U.chain_depth = deepest;
-        if (tune.on(T_DEBUG)) fprintf(stderr, "pastml_hip: %d stacked units, chain depth %d\n", U.n_stack, U.chain_depth);
+        // the chained bottom-up launch: the lowest level with stacked units, under the same condition on its range of stack_list
+        int lowest = 0;
+        while (lowest < max_h && U.stack_bu_offsets[lowest + 1] == U.stack_bu_offsets[lowest]) ++lowest;
+        const int b = U.stack_bu_offsets[lowest], bcnt = U.stack_bu_offsets[lowest + 1] - b;
+        lined_up = (long long)bcnt * 4 == (long long)sup_list.size();
+        for (int m = 0; m < bcnt && lined_up; ++m) {
+            const int n = stack_list[b + m], g0 = fc[fc[n]], g1 = fc[fc[n] + 1];
+            // (and all of one depth: balanced trees of different heights line up by height but not by depth -- such a forest keeps
+            // the two launches in both sweeps)
+            lined_up = sup_list[4 * m] == g0 && sup_list[4 * m + 1] == g0 + 1 && sup_list[4 * m + 2] == g1 &&
+                       sup_list[4 * m + 3] == g1 + 1 && depth_of[n] == depth_of[stack_list[b]];
+        }
+        if (lined_up) U.bu_chain_level = lowest;
+        if (tune.on(T_DEBUG))
+            fprintf(stderr, "pastml_hip: %d stacked units, chain depth %d, bottom-up chain level %d\n", U.n_stack, U.chain_depth,
+                    U.bu_chain_level);
     }
     if (sup_list.empty() && stack_list.empty()) return;   // (the plain level lists, nothing to build)
     // rest lists: the level structure of the fused lists, without the nodes the two-level units take over
@@ -1005,8 +1020,12 @@ std::vector<PmlLaunch> pml_plan_bottom_up(const PmlForest& f, const PmlSchedules
         }
         case BU_SUPER: {   // the two-level units first (they depend on tips only), then the levels of what is left
             const PmlSuperSchedule& U = *s.sup;
+            // (bu_chain: the stacked units of bu_chain_level run inside the two-level launch, which hands them their grandchildren's
+            // vectors through LDS -- all of them two-level nodes, so the launch at the front of the sweep has what they need; no
+            // record of their own, the opening record says which level it carries)
+            const int chained = t.bu_chain && U.n > 0 ? U.bu_chain_level : -1;
             p.bracket = 4;
-            if (U.n > 0) p.add(OP_SUPER, L_NONE, 0, U.n);
+            if (U.n > 0) p.add(OP_SUPER, L_NONE, 0, U.n).arg = chained + 1;
             p.bracket = 0;
             const int n = (int)U.bu_offsets_r.size() - 1;
             int tail = narrow_levels(t, U.bu_offsets_r, n, false, t.sched_cols);
@@ -1019,7 +1038,7 @@ std::vector<PmlLaunch> pml_plan_bottom_up(const PmlForest& f, const PmlSchedules
             if (tail < 2) tail = 0;
             // (a level's stacked units read vectors of two levels down: independent of the level's own launch)
             p.levels(OP_LEVEL, t.level_lists_sorted ? L_REST_BU_SORTED : L_REST_BU, U.bu_offsets_r, 0, n - tail, false,
-                     marg_kind(U.bu_level_vec_r), [&](int l) { add_stack(p, U, U.stack_bu_offsets, l); });
+                     marg_kind(U.bu_level_vec_r), [&](int l) { if (l != chained) add_stack(p, U, U.stack_bu_offsets, l); });
             narrow_end(L_REST_BU, n - tail, tail);
             break;
         }

@@ -50,7 +50,7 @@ struct __attribute__((aligned(32))) PmlUnit {
     X(PIJ_STAGE_ROWS, 0, 0) X(PIJ_BLOCKS, 0, 0) X(NO_HEIGHT_ORDER, 1, 1) X(NO_TD_TAIL, 1, 0) X(NO_PIJ_VALU, 1, 0) X(PIJ_VALU, 1, 0) X(NO_PIJ_WIDE, 1, 0) X(NO_EIGJ_PIPE, 1, 0) \
     X(THIN_UNITS, 0, 1) X(THIN_BYTES, 0, 1) X(THIN_BLOCK_NODES, 0, 1) X(NO_THIN, 1, 0) X(NO_THIN_WIDE, 1, 0) X(BU_WIDE, 0, 1) X(SORT_LEVELS, 0, 1) X(NO_WIDE_LEAN, 1, 0) X(SHAPE_ORDER, 0, 1) \
     X(PARS_MAX_COLS, 0, 0) X(PARS_THIN, 0, 0) X(COMPRESS_MAX_COLS, 0, 0) X(COMPRESS_PLAIN_ATOMICS, 1, 0) \
-    X(PIJ_WINDOW, 0, 0) X(NO_KEEP_TIP_ROWS, 1, 0) X(NO_TIP_LANES, 1, 0) X(NO_TD_SUPER_PIPE, 1, 0) X(NO_TD_CHAIN, 1, 0)
+    X(PIJ_WINDOW, 0, 0) X(NO_KEEP_TIP_ROWS, 1, 0) X(NO_TIP_LANES, 1, 0) X(NO_TD_SUPER_PIPE, 1, 0) X(NO_TD_CHAIN, 1, 0) X(NO_BU_CHAIN, 1, 0)
 enum PmlTunable {
 #define X(name, flag, tree) T_##name,
     PML_TUNABLES(X)
@@ -145,6 +145,12 @@ struct PmlSuperSchedule {
     // has exactly the two-level nodes of entries 4 m .. 4 m + 3 of d_units as grandchildren, in that order, and the range
     // covers all n of them (a balanced forest); a ragged forest keeps the two launches.
     int chain_depth = -1;
+    // Chained bottom-up launch (bu_f81_chain_kernel): the fused level (index into stack_bu_offsets) whose stacked units take their
+    // grandchildren's vectors from the two-level units through LDS, or -1.  It is the lowest level with stacked units, and only
+    // when entry m of its range has exactly the two-level nodes of entries 4 m .. 4 m + 3 of d_units as grandchildren, in that
+    // order, the range covers all n of them and its nodes are of one depth.  (Not chain_depth: the bottom-up lists are ordered by fused height, the top-down
+    // lists by depth, and the two agree on balanced forests only.)
+    int bu_chain_level = -1;
     int *d_bu_offsets_r = nullptr, *d_td_offsets_r = nullptr;
     std::vector<int> bu_offsets_r, td_offsets_r;
     std::vector<char> bu_level_vec_r;
@@ -316,6 +322,7 @@ struct PmlLaunch {
     int first, count;
     int arg;                        // OP_LEVELS: 1 = with the per-branch prep (bottom-up) / the roots are done (top-down); OP_RESET_ERR: 1 = eigen joint;
                                     // OP_SUPER, top-down: d + 1 = the launch also runs the stacked units of depth d (PmlSweepTraits::td_chain), 0 = none
+                                    // OP_SUPER, bottom-up: l + 1 = the launch also runs the stacked units of level l (PmlSweepTraits::bu_chain), 0 = none
 };
 // What an enqueued launch sequence leaves behind for the host that waits for it and reads its results.  A captured graph keeps
 // the outcome of what it holds (pml_ctx::GraphSlot): a replay runs none of the code that enqueued it.
@@ -344,6 +351,7 @@ struct PmlSweepTraits {
     bool no_td_tail, no_eigg_tiers, no_spin_wait;
     int waves, eig_nb;                               // PML_WAVES_PER_BLOCK, EigShape::NB
     bool td_chain;   // the stacked units of PmlSuperSchedule::chain_depth run inside the top-down two-level launch
+    bool bu_chain;   // the stacked units of PmlSuperSchedule::bu_chain_level run inside the bottom-up two-level launch
 };
 struct PmlSchedules {
     const PmlBlockSchedule* blocks;
