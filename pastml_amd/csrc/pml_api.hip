@@ -1,8 +1,8 @@
 // libpastml_hip.so -- C-ABI (include/pastml_hip.h) over the HIP kernels: contexts, tree upload and schedules, the sweeps'
-// launch sequences, downloads, the communicator.  The kernel families are launched through pml_launch.h.  gfx950 only.
+// launch sequences, downloads, the communicator.  The kernel families are launched through pml_launch.h; the entries that read
+// what a marginal pass left on the device are pml_api_readers.hip's.  gfx950 only.
 #define PML_PLAIN_KERNELS   // the kernels that are not templates are this unit's (pml_device.h, PML_GLOBAL)
 #include "pml_launch.h"
-#include "pml_kernels_counts.h"
 #include "pml_kernels_eigen_gemm.h"   // (eig_sym_kernel)
 #include "pml_comm.h"
 #include "pml_pij_window.h"
@@ -62,7 +62,7 @@ static void rows_to_api_inplace(const pml_ctx* ctx, T* buf, size_t width, size_t
 // (round 5 permuted on the host after the copy: +8.6 GB of host memory for 32 columns of 262 144 tips at k = 64).
 // Asynchronous on the ctx's stream; the caller synchronises.
 template <typename T>
-static int fetch_rows(pml_ctx* ctx, const T* d_src, size_t src_width, size_t width, size_t n_cols, T* out) {
+PML_INTERNAL int fetch_rows(pml_ctx* ctx, const T* d_src, size_t src_width, size_t width, size_t n_cols, T* out) {
     static_assert(sizeof(T) % 4 == 0, "rows are moved in 4-byte words");
     if (!out || n_cols == 0) return PML_OK;
     const size_t N = (size_t)ctx->N;
@@ -95,12 +95,13 @@ static int fetch_rows(pml_ctx* ctx, const T* d_src, size_t src_width, size_t wid
     }
     return PML_OK;
 }
+template int fetch_rows<int>(pml_ctx*, const int*, size_t, size_t, size_t, int*);   // (pml_marginal_counts_altered's rows)
 
 static inline int api_id(const pml_ctx* ctx, int internal) { return permuted(ctx) && internal >= 0 ? ctx->old_of_new[internal] : internal; }
 static inline int internal_id(const pml_ctx* ctx, int api) { return permuted(ctx) && api >= 0 ? ctx->new_of_old[api] : api; }
 
 // ---------------------------------------------------------------------------------------------------------------------
-extern "C" {
+// The C-ABI: every pml_* function below is declared extern "C" in include/pastml_hip.h.
 
 const char* pml_last_error(void) { return g_last_error.c_str(); }
 
@@ -526,7 +527,7 @@ int pml_chars_alloc(pml_ctx* ctx, int32_t n_cols, int32_t k) {
     return PML_OK;
 }
 
-static int check_cols(pml_ctx* ctx, int cb, int ce) {
+PML_INTERNAL int check_cols(pml_ctx* ctx, int cb, int ce) {
     if (!ctx || ctx->C == 0) return fail(PML_ERR_INVALID, "allocate the columns first");
     if (cb < 0 || ce > ctx->C || cb >= ce) return fail(PML_ERR_INVALID, "column range [%d, %d) out of 0..%d", cb, ce, ctx->C);
     HIP_TRY(hipSetDevice(ctx->device));
@@ -534,7 +535,7 @@ static int check_cols(pml_ctx* ctx, int cb, int ce) {
 }
 
 // PML_OPT_IMPLICIT_TIP_POSTERIORS: whoever reads the posterior table gets the rows the sweep left implicit first
-static int materialize_tip_posteriors(pml_ctx* ctx) {
+PML_INTERNAL int materialize_tip_posteriors(pml_ctx* ctx) {
     if (!ctx->results.tip_posteriors_missing() || !ctx->d_post || ctx->n_tips == 0) return PML_OK;
     dim3 grid(grid_for(ctx, ctx->n_tips, PML_BLOCK, ctx->C), ctx->C);
     hipLaunchKernelGGL(tip_posteriors_kernel, grid, dim3(PML_BLOCK), 0, ctx->stream, cols_of(ctx), state_of(ctx), ctx->N,
@@ -839,7 +840,7 @@ int pml_model_set_eigen(pml_ctx* ctx, int32_t col_begin, int32_t col_end, const 
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
-static int require_model(pml_ctx* ctx) {
+PML_INTERNAL int require_model(pml_ctx* ctx) {
     if (!ctx || ctx->C == 0) return fail(PML_ERR_INVALID, "allocate the columns first");
     for (int i = 0; i < ctx->C; ++i)
         if (!ctx->model_set[i]) return fail(PML_ERR_INVALID, "model parameters of column %d were never set", i);
@@ -916,7 +917,7 @@ static bool window_eligible(const pml_ctx* ctx) {
 // PASTML_HIP_PIJ_WINDOW (branches; 0: the batch): applied where a sweep is submitted, once per value -- the model kind and the
 // columns are known there.  It is raised to the largest fan-out and capped at the number of nodes; contexts the window is not
 // for (F81, HKY, k <= 32) ignore it.  Not set: what pml_pij_window_set said stands.
-static int window_from_tunable(pml_ctx* ctx) {
+PML_INTERNAL int window_from_tunable(pml_ctx* ctx) {
     // (a switch set after the window took away what the window is built with: back to the batch)
     if (ctx->pij_window > 0 && !window_eligible(ctx)) PML_TRY(window_set(ctx, 0));
     if (!ctx->tune.on(T_PIJ_WINDOW)) return PML_OK;
@@ -960,7 +961,7 @@ static int ensure_transition_storage(pml_ctx* ctx) {
 // What the entries that read P(t) outside a sweep prepare: the batch of the whole tree -- or, on a context with a window
 // (pml_pij_window.h), only the parameters the list build reads: they build their matrices run by run, and no batch is allocated.
 static int run_prep(pml_ctx* ctx, bool force, bool bu_sweep);
-static int consumer_prep(pml_ctx* ctx, bool force = false) {
+PML_INTERNAL int consumer_prep(pml_ctx* ctx, bool force) {
     if (!pij_windowed(ctx)) return run_prep(ctx, force, false);
     return params_push(ctx);
 }
@@ -1361,7 +1362,7 @@ static void note_bottom_up(pml_ctx* ctx, int is_marginal, const PmlSweepOutcome&
 // anything else, it is hipStreamSynchronize.  Everything queued afterwards is ordered behind the sweep by the stream as
 // before.  idle: the caller needs the stream idle, not just the results (the word is raised before its kernel has ended:
 // blocking copies on the NULL stream, the generation the next submission reads).
-static int wait_pending(pml_ctx* ctx, bool idle = false) {
+PML_INTERNAL int wait_pending(pml_ctx* ctx, bool idle) {
     const bool spin = ctx->pending.spin && !idle && ctx->h_done;
     ctx->pending.spin = false;
     if (spin) {
@@ -1561,8 +1562,6 @@ static int run_top_down(pml_ctx* ctx, bool wants_signal = false, PmlCapture capt
     return PML_OK;
 }
 
-static int materialize_cherries(pml_ctx* ctx);
-
 // For inspection (pml_download of the TD buffers): every non-root node gets its top-down vector.  F81 family: the
 // sweep did not write its TD vectors, it is repeated with the stores switched on (same arithmetic); then the vectors of
 // the nodes no sweep stores (tips; fused cherries) are filled in level by level (td_fill_kernel).
@@ -1760,465 +1759,6 @@ int pml_joint_pass(pml_ctx* ctx, double* loglik_out, int32_t* err_parent, int32_
         return status;
     }
     return fetched;
-}
-
-// What pml_marginal_counts, pml_expected_counts and pml_sample_scenarios read: the results of a marginal bottom-up and a top-down
-// sweep (entry: who asks) ...
-static int need_marginal_pass(pml_ctx* ctx, const char* entry) {
-    if (!ctx->results.has_marginal() || !ctx->results.has_top_down())
-        return fail(PML_ERR_INVALID, "%s needs a marginal pml_bottom_up and pml_top_down_marginals first", entry);
-    return PML_OK;
-}
-// ... with every row of them in memory (once the entry knows that it holds this many states: the batch is allocated here)
-static int write_marginal_pass(pml_ctx* ctx) {
-    PML_TRY(materialize_cherries(ctx));  // the conditional probabilities need every bottom-up vector
-    PML_TRY(materialize_tip_posteriors(ctx));   // (a single-tip tree's root; the rows of the scenario sampler's fallback)
-    return consumer_prep(ctx);  // P(t) of every branch (the fused sweeps never materialise it) / exp(-mu t'); or the window
-}
-
-// altered (caller's ids, or null): see counts_level_kernel.  result_out: the k x k sums of the draws (not divided by
-// n_repetitions when altered is given); state_counts_out / same_out: [N][k] in the caller's numbering.
-static int marginal_counts_impl(pml_ctx* ctx, int32_t col, int32_t n_repetitions, uint64_t seed, const uint8_t* altered,
-                                double* result_out, int32_t* state_counts_out, int32_t* same_out) {
-    PML_TRY(require_model(ctx));
-    if (col < 0 || col >= ctx->C || !result_out) return fail(PML_ERR_INVALID, "bad column / output");
-    if (n_repetitions <= 0) return fail(PML_ERR_INVALID, "n_repetitions must be positive");
-    PML_TRY(need_marginal_pass(ctx, "pml_marginal_counts"));
-    if (ctx->k > PML_COUNTS_MAX_K) return fail(PML_ERR_UNSUPPORTED, "k = %d: at most %d states", ctx->k, PML_COUNTS_MAX_K);
-    PML_TRY(write_marginal_pass(ctx));
-    const size_t k = ctx->k, N = (size_t)ctx->N;
-    std::vector<unsigned char> alt;
-    std::vector<long long> h(k * k);
-    CallScope mem(ctx->stream, false);
-    int *d_counts, *d_same = nullptr;
-    long long* d_result;
-    unsigned char* d_alt = nullptr;
-    PML_TRY(mem.get(&d_counts, N * k));
-    PML_TRY(mem.get(&d_result, k * k));
-    HIP_TRY(hipMemsetAsync(d_result, 0, k * k * sizeof(long long), ctx->stream));
-    if (altered != nullptr) {
-        PML_TRY(upload_altered(ctx, mem, altered, alt, &d_alt));
-        PML_TRY(mem.get(&d_same, N * k));
-        HIP_TRY(hipMemsetAsync(d_same, 0, N * k * sizeof(int), ctx->stream));
-    }
-    const PmlTree t = tree_of(ctx);
-    const PmlCols c = cols_of(ctx);
-    const PmlState st = state_of(ctx);
-    const PmlModel m = model_of(ctx);
-    const double* P = ctx->kind == PML_MODEL_F81 ? nullptr : ctx->d_P;
-    // (the draws are keyed by the CALLER's node ids: the library's internal numbering must not show in the result)
-    hipLaunchKernelGGL(counts_roots_kernel, dim3(std::min(ctx->n_roots, 1024)), dim3(64), 0, ctx->stream, t, c, st, col,
-                       n_repetitions, seed, d_counts, ctx->d_old_of_new);
-    if (pij_windowed(ctx)) {
-        // the runs of the top-down sweep (parents of one level whose children fit the window), each behind the build of its
-        // children's matrices for this column: the draws are keyed by the node, so the cuts do not show
-        const PmlPWindow w = {ctx->d_pij_window, ctx->d_win_slot[1], ctx->pij_window};
-        size_t covered = 0;
-        for (const PmlWindowStep& r : ctx->win_td_runs) covered += (size_t)r.launch.count;
-        if (covered != ctx->td_parents.size())
-            return fail(PML_ERR_INVALID, "the window's top-down runs cover %zu of %zu parents", covered, ctx->td_parents.size());
-        for (const PmlWindowStep& r : ctx->win_td_runs) {
-            if (r.build_count > 0)
-                PML_TRY(launch_pij_wide_list(ctx, ctx->d_pij_window, ctx->pij_window, ctx->d_win_branches[1] + r.build_first,
-                                             r.build_count, col, col + 1));
-            hipLaunchKernelGGL(counts_level_kernel<PML_P_WINDOW>, dim3(std::min(r.launch.count, 65536)), dim3(64), 0, ctx->stream,
-                               t, c, st, m, w, col, n_repetitions, seed, ctx->d_td_parents + r.launch.first, r.launch.count, d_counts,
-                               d_result, ctx->d_old_of_new, d_alt, d_same);
-        }
-    } else
-    for (int l = 0; l < ctx->n_td_levels; ++l) {
-        const int a = ctx->forest.td_parent_offsets[l], b = ctx->forest.td_parent_offsets[l + 1];
-        if (b <= a) continue;
-        hipLaunchKernelGGL(counts_level_kernel<>, dim3(std::min(b - a, 65536)), dim3(64), 0, ctx->stream, t, c, st, m, P,
-                           col, n_repetitions, seed, ctx->d_td_parents + a, b - a, d_counts, d_result, ctx->d_old_of_new,
-                           d_alt, d_same);
-    }
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipMemcpyAsync(h.data(), d_result, k * k * sizeof(long long), hipMemcpyDeviceToHost, ctx->stream));
-    if (altered != nullptr) {
-        // (tips' rows of d_counts are written by their parents' passes: every node has its row)
-        PML_TRY(fetch_rows(ctx, d_counts, k, k, 1, state_counts_out));
-        PML_TRY(fetch_rows(ctx, d_same, k, k, 1, same_out));
-    }
-    PML_TRY(mem.finish());
-    for (size_t i = 0; i < k * k; ++i) result_out[i] = altered != nullptr ? (double)h[i] : (double)h[i] / (double)n_repetitions;
-    return PML_OK;
-}
-
-int pml_marginal_counts(pml_ctx* ctx, int32_t col, int32_t n_repetitions, uint64_t seed, double* counts_out) {
-    return marginal_counts_impl(ctx, col, n_repetitions, seed, nullptr, counts_out, nullptr, nullptr);
-}
-
-int pml_marginal_counts_altered(pml_ctx* ctx, int32_t col, int32_t n_repetitions, uint64_t seed, const uint8_t* altered,
-                                double* sums_out, int32_t* state_counts_out, int32_t* same_out) {
-    if (!altered || !state_counts_out || !same_out) return fail(PML_ERR_INVALID, "NULL array");
-    return marginal_counts_impl(ctx, col, n_repetitions, seed, altered, sums_out, state_counts_out, same_out);
-}
-
-// Exact expected transition counts of the columns [col_begin, col_end) (pml_launch_expected.hip): the limit of the sampler above
-// for n_repetitions -> infinity, from the vectors the marginal pass left on the device.  altered (caller's ids, or null): the
-// pairs with an altered end are left out and their parents' same-state sums go to same_out, as in pml_marginal_counts_altered.
-int pml_expected_counts(pml_ctx* ctx, int32_t col_begin, int32_t col_end, const uint8_t* altered, double* counts_out,
-                        double* same_out) {
-    PML_TRY(require_model(ctx));
-    PML_TRY(check_cols(ctx, col_begin, col_end));
-    if (!counts_out) return fail(PML_ERR_INVALID, "counts_out is NULL");
-    PML_TRY(need_marginal_pass(ctx, "pml_expected_counts"));
-    if (ctx->kind != PML_MODEL_F81 && ctx->k > 256)
-        return fail(PML_ERR_UNSUPPORTED, "k = %d: the matrix models hold at most 256 states", ctx->k);
-    PML_TRY(wait_pending(ctx, true));   // (a pass that ended in a spin on the completion word may have left the stream busy)
-    PML_TRY(write_marginal_pass(ctx));
-    const size_t k = ctx->k, N = (size_t)ctx->N, cols = (size_t)(col_end - col_begin);
-    const bool with_same = altered != nullptr && same_out != nullptr;
-    std::vector<unsigned char> alt;
-    CallScope mem(ctx->stream, false);
-    double *d_out, *d_same = nullptr;
-    unsigned char* d_alt = nullptr;
-    PML_TRY(mem.get(&d_out, cols * k * k));
-    if (altered != nullptr) PML_TRY(upload_altered(ctx, mem, altered, alt, &d_alt));
-    if (with_same) {
-        PML_TRY(mem.get(&d_same, cols * N * k));
-        HIP_TRY(hipMemsetAsync(d_same, 0, cols * N * k * sizeof(double), ctx->stream));
-    }
-    PML_TRY(launch_expected(ctx, col_begin, col_end, d_alt, d_out, d_same));
-    HIP_TRY(hipMemcpyAsync(counts_out, d_out, cols * k * k * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
-    if (with_same) HIP_TRY(hipMemcpyAsync(same_out, d_same, cols * N * k * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
-    return mem.finish();
-}
-
-// What the exact entries of the F81 family (`entry`, which computes a `what`) ask of the context: that model kind, a marginal
-// pass, two states or more, and a finite positive mu in every column of [cb, ce).
-static int need_f81_pass(pml_ctx* ctx, const char* entry, const char* what, int cb, int ce) {
-    if (ctx->kind != PML_MODEL_F81)
-        return fail(PML_ERR_UNSUPPORTED, "%s is for the F81 family (F81, JC, EFT): this context's model kind is %s", entry,
-                    ctx->kind == PML_MODEL_HKY ? "HKY" : "eigen");
-    PML_TRY(need_marginal_pass(ctx, entry));
-    if (ctx->k < 2) return fail(PML_ERR_INVALID, "%s: k = %d, a character of one state has no %s", entry, ctx->k, what);
-    const double* mu = ctx->h_params + ctx->cols.params.mu;
-    for (int c = cb; c < ce; ++c)
-        if (!std::isfinite(mu[c]) || !(mu[c] > 0.0))
-            return fail(PML_ERR_INVALID, "%s: column %d has pi . pi >= 1 (mu is not finite)", entry, c);
-    return PML_OK;
-}
-
-// Exact gradient of ln L of the columns [col_begin, col_end) under the F81 family (pml_launch_gradient.hip): one streaming pass
-// over the vectors the marginal pass left on the device, no sweep.  The masks are those the pass ran with.
-int pml_loglik_gradient(pml_ctx* ctx, int32_t col_begin, int32_t col_end, double* d_rates_out, double* d_pi_out,
-                        int32_t* n_flat_out) {
-    PML_TRY(require_model(ctx));
-    PML_TRY(check_cols(ctx, col_begin, col_end));
-    if (!d_rates_out || !d_pi_out || !n_flat_out) return fail(PML_ERR_INVALID, "pml_loglik_gradient: an output array is NULL");
-    PML_TRY(need_f81_pass(ctx, "pml_loglik_gradient", "gradient", col_begin, col_end));
-    PML_TRY(wait_pending(ctx, true));   // (a pass that ended in a spin on the completion word may have left the stream busy)
-    PML_TRY(write_marginal_pass(ctx));
-    const size_t k = ctx->k, cols = (size_t)(col_end - col_begin);
-    CallScope mem(ctx->stream, false);
-    double *d_rates, *d_pi;
-    int* d_flat;
-    PML_TRY(mem.get(&d_rates, cols * 3));
-    PML_TRY(mem.get(&d_pi, cols * k));
-    PML_TRY(mem.get(&d_flat, cols));
-    PML_TRY(launch_gradient(ctx, mem, col_begin, col_end, d_rates, d_pi, d_flat));
-    HIP_TRY(hipMemcpyAsync(d_rates_out, d_rates, cols * 3 * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
-    HIP_TRY(hipMemcpyAsync(d_pi_out, d_pi, cols * k * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
-    HIP_TRY(hipMemcpyAsync(n_flat_out, d_flat, cols * sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
-    return mem.finish();
-}
-
-// Exact expected dwell times and Markov jumps of the columns [col_begin, col_end) under the F81 family (pml_launch_history.hip):
-// one streaming pass over the vectors the marginal pass left on the device, and the jump product where jumps_out is given.  The
-// masks are those the pass ran with.
-int pml_expected_history(pml_ctx* ctx, int32_t col_begin, int32_t col_end, double* times_out, double* jumps_out,
-                         double* branch_jumps_out) {
-    PML_TRY(require_model(ctx));
-    PML_TRY(check_cols(ctx, col_begin, col_end));
-    if (!times_out) return fail(PML_ERR_INVALID, "pml_expected_history: times_out is NULL");
-    if (ctx->k > 512) return fail(PML_ERR_UNSUPPORTED, "pml_expected_history: k = %d, the F81 family holds at most 512 states", ctx->k);
-    PML_TRY(need_f81_pass(ctx, "pml_expected_history", "history", col_begin, col_end));
-    PML_TRY(wait_pending(ctx, true));   // (a pass that ended in a spin on the completion word may have left the stream busy)
-    PML_TRY(write_marginal_pass(ctx));
-    const size_t k = ctx->k, N = (size_t)ctx->N, cols = (size_t)(col_end - col_begin);
-    CallScope mem(ctx->stream, false);
-    double *d_times, *d_jumps = nullptr, *d_branch = nullptr;
-    PML_TRY(mem.get(&d_times, cols * k));
-    if (jumps_out) PML_TRY(mem.get(&d_jumps, cols * k * k));
-    if (branch_jumps_out) PML_TRY(mem.get(&d_branch, cols * N));
-    PML_TRY(launch_history(ctx, mem, col_begin, col_end, d_times, d_jumps, d_branch));
-    HIP_TRY(hipMemcpyAsync(times_out, d_times, cols * k * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
-    if (jumps_out) HIP_TRY(hipMemcpyAsync(jumps_out, d_jumps, cols * k * k * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
-    if (branch_jumps_out)
-        HIP_TRY(hipMemcpyAsync(branch_jumps_out, d_branch, cols * N * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
-    return mem.finish();
-}
-
-// Exact expected dwell times and Markov jumps of the columns [col_begin, col_end) under the eigen-decomposed models
-// (pml_launch_history_eigen.hip): the eigenbasis integral over the vectors the marginal pass left on the device.  No P(t): the
-// bottom-up vectors and the posteriors are made complete, the batch (or the window) is not touched.  The masks are those the pass
-// ran with.
-int pml_expected_history_eigen(pml_ctx* ctx, int32_t col_begin, int32_t col_end, double* times_out, double* jumps_out,
-                               double* branch_jumps_out) {
-    const char* entry = "pml_expected_history_eigen";
-    PML_TRY(require_model(ctx));
-    PML_TRY(check_cols(ctx, col_begin, col_end));
-    if (!times_out) return fail(PML_ERR_INVALID, "%s: times_out is NULL", entry);
-    if (ctx->kind == PML_MODEL_F81)
-        return fail(PML_ERR_UNSUPPORTED, "%s is for the eigen-decomposed models: this context's model kind is F81 (F81, JC, EFT), "
-                    "which pml_expected_history serves", entry);
-    if (ctx->kind == PML_MODEL_HKY)
-        return fail(PML_ERR_UNSUPPORTED, "%s is for the eigen-decomposed models: this context's model kind is HKY; hand the model "
-                    "over as an eigen model (pml_model_set_eigen with the d, A, Ainv of its rate matrix)", entry);
-    PML_TRY(need_marginal_pass(ctx, entry));
-    if (ctx->k < 2) return fail(PML_ERR_INVALID, "%s: k = %d, a character of one state has no history", entry, ctx->k);
-    if (ctx->k > 256) return fail(PML_ERR_UNSUPPORTED, "%s: k = %d, the matrix models hold at most 256 states", entry, ctx->k);
-    const size_t k = ctx->k, N = (size_t)ctx->N, cols = (size_t)(col_end - col_begin);
-    const double* sf = ctx->h_params + ctx->cols.params.sf;
-    for (int c = col_begin; c < col_end; ++c) {
-        if (!std::isfinite(sf[c]) || !(sf[c] > 0.0))
-            return fail(PML_ERR_INVALID, "%s: column %d has a scaling factor that is not finite and positive", entry, c);
-        for (size_t m = 0; m < k; ++m)
-            if (ctx->h_eig_d.size() != (size_t)ctx->C * k || !std::isfinite(ctx->h_eig_d[(size_t)c * k + m]))
-                return fail(PML_ERR_INVALID, "%s: column %d has an eigenvalue that is not finite", entry, c);
-    }
-    PML_TRY(wait_pending(ctx, true));   // (a pass that ended in a spin on the completion word may have left the stream busy)
-    PML_TRY(materialize_cherries(ctx));
-    PML_TRY(materialize_tip_posteriors(ctx));
-    CallScope mem(ctx->stream, false);
-    double *d_times, *d_jumps = nullptr, *d_branch = nullptr;
-    PML_TRY(mem.get(&d_times, cols * k));
-    if (jumps_out) PML_TRY(mem.get(&d_jumps, cols * k * k));
-    if (branch_jumps_out) PML_TRY(mem.get(&d_branch, cols * N));
-    PML_TRY(launch_history_eigen(ctx, mem, col_begin, col_end, d_times, d_jumps, d_branch));
-    HIP_TRY(hipMemcpyAsync(times_out, d_times, cols * k * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
-    if (jumps_out) HIP_TRY(hipMemcpyAsync(jumps_out, d_jumps, cols * k * k * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
-    if (branch_jumps_out)
-        HIP_TRY(hipMemcpyAsync(branch_jumps_out, d_branch, cols * N * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
-    return mem.finish();
-}
-
-// The same per time interval, with the lineages at every boundary (pml_launch_history_time.hip).  The segment plan is made
-// here, on the host and in the caller's numbering (pml_time_segments.h) -- it does not depend on the column --, and uploaded
-// through the call's scope; plan and pieces are declared before the scope, whose wait ends the copies that read them.
-int pml_history_through_time(pml_ctx* ctx, int32_t col_begin, int32_t col_end, const double* node_time, const double* boundaries,
-                             int32_t M, double* times_out, double* jumps_out, double* lineages_out) {
-    PML_TRY(require_model(ctx));
-    PML_TRY(check_cols(ctx, col_begin, col_end));
-    if (!times_out || !node_time || !boundaries)
-        return fail(PML_ERR_INVALID, "pml_history_through_time: node_time, boundaries or times_out is NULL");
-    if (ctx->k > 512)
-        return fail(PML_ERR_UNSUPPORTED, "pml_history_through_time: k = %d, the F81 family holds at most 512 states", ctx->k);
-    PML_TRY(need_f81_pass(ctx, "pml_history_through_time", "history", col_begin, col_end));
-    if (M >= 1 && (long long)M * ctx->k * ctx->k > (long long)PML_HIST_TIME_MAX_CELLS)
-        return fail(PML_ERR_UNSUPPORTED, "pml_history_through_time: M k^2 = %lld is beyond %d (PML_HIST_TIME_MAX_CELLS): the partials "
-                    "of the bins would not fit the call's scratch; ask for fewer bins per call", (long long)M * ctx->k * ctx->k,
-                    PML_HIST_TIME_MAX_CELLS);
-    const size_t k = ctx->k, N = (size_t)ctx->N, cols = (size_t)(col_end - col_begin);
-    PmlTimeSegments plan;
-    PmlTimePieces pieces, jpieces;
-    {
-        std::vector<int> parent(N);   // the caller's numbering
-        const bool same = ctx->new_of_old.empty();
-        for (size_t i = 0; i < N; ++i) {
-            const int p = ctx->forest.parent[same ? i : (size_t)ctx->new_of_old[i]];
-            parent[i] = (p < 0 || same) ? p : ctx->old_of_new[p];
-        }
-        const std::string why = pml_plan_time_segments(parent.data(), node_time, (int)N, boundaries, M, plan);
-        if (!why.empty()) return fail(PML_ERR_INVALID, "pml_history_through_time: %s", why.c_str());
-    }
-    pieces = pml_cut_time_pieces(plan, history_time_piece(ctx->k), true);
-    if (jumps_out) jpieces = pml_cut_time_pieces(plan, history_time_jump_piece(ctx->k), false);
-    PML_TRY(wait_pending(ctx, true));   // (a pass that ended in a spin on the completion word may have left the stream busy)
-    PML_TRY(write_marginal_pass(ctx));
-    const size_t bins = (size_t)M;
-    CallScope mem(ctx->stream, false);
-    double *d_times, *d_jumps = nullptr, *d_lineages = nullptr;
-    PML_TRY(mem.get(&d_times, cols * bins * k));
-    if (jumps_out) PML_TRY(mem.get(&d_jumps, cols * bins * k * k));
-    if (lineages_out) PML_TRY(mem.get(&d_lineages, cols * (bins + 1) * k));
-    PML_TRY(launch_history_time(ctx, mem, col_begin, col_end, plan, pieces, jpieces, d_times, d_jumps, d_lineages));
-    HIP_TRY(hipMemcpyAsync(times_out, d_times, cols * bins * k * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
-    if (jumps_out)
-        HIP_TRY(hipMemcpyAsync(jumps_out, d_jumps, cols * bins * k * k * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
-    if (lineages_out)
-        HIP_TRY(hipMemcpyAsync(lineages_out, d_lineages, cols * (bins + 1) * k * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
-    return mem.finish();
-}
-
-// n_repetitions scenarios of column col drawn forward from the roots (pml_launch_simulate.hip).  Needs a model, no sweep: the
-// per-branch e = exp(-mu t') (F81 family) or P(t) is prepared here.  The states are written in the caller's numbering on the
-// device, in rows padded to a multiple of 4 repetitions, and copied out without the padding.
-int pml_simulate_states(pml_ctx* ctx, int32_t col, int32_t n_repetitions, int32_t rep_offset, uint64_t seed, void* states_out) {
-    PML_TRY(require_model(ctx));
-    if (col < 0 || col >= ctx->C || !states_out) return fail(PML_ERR_INVALID, "bad column / output");
-    if (n_repetitions <= 0) return fail(PML_ERR_INVALID, "n_repetitions must be positive");
-    if (rep_offset < 0) return fail(PML_ERR_INVALID, "rep_offset must not be negative");
-    // (the sweeps may have left E / P(t) in registers only, or for other parameters: prepared afresh; a context with a window
-    // pushes the parameters and builds its matrices run by run)
-    PML_TRY(window_from_tunable(ctx));
-    PML_TRY(consumer_prep(ctx, true));
-    const size_t es = ctx->k > 256 ? 2 : 1;
-    const size_t rs = ((size_t)n_repetitions + 3) / 4 * 4;
-    CallScope mem(ctx->stream, false);
-    unsigned char* d_states;
-    PML_TRY(mem.get(&d_states, (size_t)ctx->N * rs * es));
-    PML_TRY(launch_simulate(ctx, col, rep_offset, seed, d_states, rs));
-    HIP_TRY(hipMemcpy2DAsync(states_out, (size_t)n_repetitions * es, d_states, rs * es, (size_t)n_repetitions * es, (size_t)ctx->N,
-                             hipMemcpyDeviceToHost, ctx->stream));
-    return mem.finish();
-}
-
-// n_repetitions scenarios of column col drawn from the joint posterior (pml_launch_scenarios.hip), from the vectors the marginal
-// pass left on the device.  Rows and copy-out as in pml_simulate_states; n_fallback_out: the draws that found no weight.
-int pml_sample_scenarios(pml_ctx* ctx, int32_t col, int32_t n_repetitions, int32_t rep_offset, uint64_t seed, void* states_out,
-                         int64_t* n_fallback_out) {
-    PML_TRY(require_model(ctx));
-    if (col < 0 || col >= ctx->C || !states_out || !n_fallback_out) return fail(PML_ERR_INVALID, "bad column / output");
-    if (n_repetitions <= 0) return fail(PML_ERR_INVALID, "n_repetitions must be positive");
-    if (rep_offset < 0) return fail(PML_ERR_INVALID, "rep_offset must not be negative");
-    PML_TRY(need_marginal_pass(ctx, "pml_sample_scenarios"));
-    const int most = ctx->kind == PML_MODEL_F81 ? 512 : 256;
-    if (ctx->k > most) return fail(PML_ERR_UNSUPPORTED, "k = %d: pml_sample_scenarios holds at most %d states for this model", ctx->k, most);
-    PML_TRY(wait_pending(ctx, true));   // (a pass that ended in a spin on the completion word may have left the stream busy)
-    PML_TRY(write_marginal_pass(ctx));
-    const size_t es = ctx->k > 256 ? 2 : 1;
-    const size_t rs = ((size_t)n_repetitions + 3) / 4 * 4;
-    unsigned long long fallen = 0;
-    CallScope mem(ctx->stream, false);
-    unsigned char* d_states;
-    unsigned long long* d_fallen;
-    PML_TRY(mem.get(&d_states, (size_t)ctx->N * rs * es));
-    PML_TRY(mem.get(&d_fallen, 1));
-    HIP_TRY(hipMemsetAsync(d_fallen, 0, sizeof(unsigned long long), ctx->stream));
-    PML_TRY(launch_scenarios(ctx, col, n_repetitions, rep_offset, seed, d_states, rs, d_fallen));
-    HIP_TRY(hipMemcpy2DAsync(states_out, (size_t)n_repetitions * es, d_states, rs * es, (size_t)n_repetitions * es, (size_t)ctx->N,
-                             hipMemcpyDeviceToHost, ctx->stream));
-    HIP_TRY(hipMemcpyAsync(&fallen, d_fallen, sizeof(unsigned long long), hipMemcpyDeviceToHost, ctx->stream));
-    PML_TRY(mem.finish());
-    *n_fallback_out = (int64_t)fallen;
-    return PML_OK;
-}
-
-// n_repetitions histories of column col under the F81 family (pml_launch_history_sample.hip): the scenarios of
-// pml_sample_scenarios, written to a device buffer in the same call (the same seed, the same bits; they go through the host only
-// if states_out asks for them), then on every branch the events between its two end states.
-int pml_sample_histories(pml_ctx* ctx, int32_t col, int32_t n_repetitions, int32_t rep_offset, uint64_t seed, void* states_out,
-                         double* times_out, uint32_t* jumps_out, uint16_t* branch_jumps_out, int64_t* n_fallback_out) {
-    PML_TRY(require_model(ctx));
-    if (col < 0 || col >= ctx->C || !times_out || !n_fallback_out) return fail(PML_ERR_INVALID, "pml_sample_histories: bad column / output");
-    if (n_repetitions <= 0) return fail(PML_ERR_INVALID, "pml_sample_histories: n_repetitions must be positive");
-    if (rep_offset < 0) return fail(PML_ERR_INVALID, "pml_sample_histories: rep_offset must not be negative");
-    if (ctx->k > 512) return fail(PML_ERR_UNSUPPORTED, "pml_sample_histories: k = %d, the F81 family holds at most 512 states", ctx->k);
-    PML_TRY(need_f81_pass(ctx, "pml_sample_histories", "history", col, col + 1));
-    PML_TRY(wait_pending(ctx, true));   // (a pass that ended in a spin on the completion word may have left the stream busy)
-    PML_TRY(write_marginal_pass(ctx));
-    const size_t k = ctx->k, N = (size_t)ctx->N, R = (size_t)n_repetitions;
-    const size_t es = k > 256 ? 2 : 1;
-    const size_t rs = (R + 3) / 4 * 4;
-    unsigned long long counters[2] = {0, 0};   // the scenarios' fallbacks, the branches not drawn
-    CallScope mem(ctx->stream, false);
-    unsigned char* d_states;
-    unsigned long long* d_counters;
-    double* d_times;
-    unsigned* d_jumps = nullptr;
-    unsigned short* d_branch = nullptr;
-    PML_TRY(mem.get(&d_states, N * rs * es));
-    PML_TRY(mem.get(&d_counters, 2));
-    PML_TRY(mem.get(&d_times, R * k));
-    HIP_TRY(hipMemsetAsync(d_counters, 0, sizeof(counters), ctx->stream));
-    if (jumps_out) {
-        PML_TRY(mem.get(&d_jumps, R * k * k));
-        HIP_TRY(hipMemsetAsync(d_jumps, 0, R * k * k * sizeof(unsigned), ctx->stream));
-    }
-    if (branch_jumps_out) PML_TRY(mem.get(&d_branch, N * R));
-    PML_TRY(launch_scenarios(ctx, col, n_repetitions, rep_offset, seed, d_states, rs, d_counters));
-    PML_TRY(launch_history_sample(ctx, mem, col, n_repetitions, rep_offset, seed, d_states, rs, d_times, d_jumps, d_branch,
-                                  d_counters + 1));
-    if (states_out)
-        HIP_TRY(hipMemcpy2DAsync(states_out, R * es, d_states, rs * es, R * es, N, hipMemcpyDeviceToHost, ctx->stream));
-    HIP_TRY(hipMemcpyAsync(times_out, d_times, R * k * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
-    if (jumps_out) HIP_TRY(hipMemcpyAsync(jumps_out, d_jumps, R * k * k * sizeof(unsigned), hipMemcpyDeviceToHost, ctx->stream));
-    if (branch_jumps_out)
-        HIP_TRY(hipMemcpyAsync(branch_jumps_out, d_branch, N * R * sizeof(unsigned short), hipMemcpyDeviceToHost, ctx->stream));
-    HIP_TRY(hipMemcpyAsync(counters, d_counters, sizeof(counters), hipMemcpyDeviceToHost, ctx->stream));
-    PML_TRY(mem.finish());
-    *n_fallback_out = (int64_t)counters[0];
-    if (counters[1])
-        return fail(PML_ERR_UNSUPPORTED, "pml_sample_histories: %llu branches have x = mu t' > 512 (PML_HSAMP_MAX_X), where exp(-x) leaves the "
-                    "normal doubles: they were not drawn and the outputs are not histories", counters[1]);
-    return PML_OK;
-}
-
-// The same histories cut at the boundaries of M time bins (pml_launch_history_time_sample.hip): the scenarios as above, the
-// segment plan of pml_history_through_time with its upper ends (pml_time_segments.h), made on the host in the caller's numbering.
-// The plan and the tables derived from it are declared before the scope, whose wait ends the copies that read them.
-int pml_sample_histories_through_time(pml_ctx* ctx, int32_t col, int32_t n_repetitions, int32_t rep_offset, uint64_t seed,
-                                      const double* node_time, const double* boundaries, int32_t M, void* states_out,
-                                      double* times_out, uint32_t* jumps_out, uint32_t* lineages_out, int64_t* n_fallback_out) {
-    PML_TRY(require_model(ctx));
-    if (col < 0 || col >= ctx->C || !times_out || !n_fallback_out)
-        return fail(PML_ERR_INVALID, "pml_sample_histories_through_time: bad column / output");
-    if (!node_time || !boundaries) return fail(PML_ERR_INVALID, "pml_sample_histories_through_time: node_time or boundaries is NULL");
-    if (n_repetitions <= 0) return fail(PML_ERR_INVALID, "pml_sample_histories_through_time: n_repetitions must be positive");
-    if (rep_offset < 0) return fail(PML_ERR_INVALID, "pml_sample_histories_through_time: rep_offset must not be negative");
-    if (ctx->k > 512)
-        return fail(PML_ERR_UNSUPPORTED, "pml_sample_histories_through_time: k = %d, the F81 family holds at most 512 states", ctx->k);
-    PML_TRY(need_f81_pass(ctx, "pml_sample_histories_through_time", "history", col, col + 1));
-    if (M >= 1 && (long long)M * ctx->k * ctx->k > (long long)PML_HIST_TIME_MAX_CELLS)
-        return fail(PML_ERR_UNSUPPORTED, "pml_sample_histories_through_time: M k^2 = %lld is beyond %d (PML_HIST_TIME_MAX_CELLS): the "
-                    "jump tables of a repetition would not fit the call's scratch; ask for fewer bins per call",
-                    (long long)M * ctx->k * ctx->k, PML_HIST_TIME_MAX_CELLS);
-    const size_t k = ctx->k, N = (size_t)ctx->N, R = (size_t)n_repetitions;
-    HistoryTimeSamplePlan host;
-    {
-        std::vector<int> parent(N);   // the caller's numbering
-        const bool same = ctx->new_of_old.empty();
-        for (size_t i = 0; i < N; ++i) {
-            const int p = ctx->forest.parent[same ? i : (size_t)ctx->new_of_old[i]];
-            parent[i] = (p < 0 || same) ? p : ctx->old_of_new[p];
-        }
-        const std::string why = pml_plan_time_segments(parent.data(), node_time, (int)N, boundaries, M, host.plan);
-        if (!why.empty()) return fail(PML_ERR_INVALID, "pml_sample_histories_through_time: %s", why.c_str());
-    }
-    host.ends = pml_time_segment_ends(host.plan);
-    host.pieces = pml_cut_time_pieces(host.plan, history_time_sample_piece(ctx->N), lineages_out != nullptr);
-    PML_TRY(wait_pending(ctx, true));   // (a pass that ended in a spin on the completion word may have left the stream busy)
-    PML_TRY(write_marginal_pass(ctx));
-    const size_t bins = (size_t)M;
-    const size_t es = k > 256 ? 2 : 1;
-    const size_t rs = (R + 3) / 4 * 4;
-    unsigned long long counters[2] = {0, 0};   // the scenarios' fallbacks, the branches not drawn
-    CallScope mem(ctx->stream, false);
-    unsigned char* d_states;
-    unsigned long long* d_counters;
-    double* d_times;
-    unsigned *d_jumps = nullptr, *d_lineages = nullptr;
-    PML_TRY(mem.get(&d_states, N * rs * es));
-    PML_TRY(mem.get(&d_counters, 2));
-    PML_TRY(mem.get(&d_times, R * bins * k));
-    HIP_TRY(hipMemsetAsync(d_counters, 0, sizeof(counters), ctx->stream));
-    if (jumps_out) {
-        PML_TRY(mem.get(&d_jumps, R * bins * k * k));
-        HIP_TRY(hipMemsetAsync(d_jumps, 0, R * bins * k * k * sizeof(unsigned), ctx->stream));
-    }
-    if (lineages_out) {
-        PML_TRY(mem.get(&d_lineages, R * (bins + 1) * k));
-        HIP_TRY(hipMemsetAsync(d_lineages, 0, R * (bins + 1) * k * sizeof(unsigned), ctx->stream));
-    }
-    PML_TRY(launch_history_time_sample(ctx, mem, col, n_repetitions, rep_offset, seed, d_states, rs, host, d_times, d_jumps,
-                                       d_lineages, d_counters, d_counters + 1));
-    if (states_out)
-        HIP_TRY(hipMemcpy2DAsync(states_out, R * es, d_states, rs * es, R * es, N, hipMemcpyDeviceToHost, ctx->stream));
-    HIP_TRY(hipMemcpyAsync(times_out, d_times, R * bins * k * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
-    if (jumps_out)
-        HIP_TRY(hipMemcpyAsync(jumps_out, d_jumps, R * bins * k * k * sizeof(unsigned), hipMemcpyDeviceToHost, ctx->stream));
-    if (lineages_out)
-        HIP_TRY(hipMemcpyAsync(lineages_out, d_lineages, R * (bins + 1) * k * sizeof(unsigned), hipMemcpyDeviceToHost, ctx->stream));
-    HIP_TRY(hipMemcpyAsync(counters, d_counters, sizeof(counters), hipMemcpyDeviceToHost, ctx->stream));
-    PML_TRY(mem.finish());
-    *n_fallback_out = (int64_t)counters[0];
-    if (counters[1])
-        return fail(PML_ERR_UNSUPPORTED, "pml_sample_histories_through_time: %llu branches have x = mu t' > 512 (PML_HSAMP_MAX_X), where "
-                    "exp(-x) leaves the normal doubles: they were not drawn and the outputs are not histories", counters[1]);
-    return PML_OK;
 }
 
 // Maximum parsimony of n_cols characters on the uploaded forest (pml_launch_parsimony.hip).  Needs the tree only: no columns,
@@ -2423,7 +1963,7 @@ static int fetch_exponents(pml_ctx* ctx, const i64* src, int col, double* out) {
 }
 
 // after a fused sweep the cherries' bottom-up vectors only ever existed in registers: compute them for inspection
-static int materialize_cherries(pml_ctx* ctx) {
+PML_INTERNAL int materialize_cherries(pml_ctx* ctx) {
     if (ctx->results.children_missing()) {
         // the children of the two-level units: their own units (two cherries of two tips), from the tips
         PML_TRY(dispatch_sweep(ctx, SW_BU_MARG_FUSED_NOVEC, L_CHILD_UNITS, 0, ctx->sup.n_child_units));  // (nothing if 0)
@@ -2869,6 +2409,4 @@ int pml_timer_stop(pml_ctx* ctx, float* milliseconds) {
     HIP_TRY(hipEventElapsedTime(milliseconds, ctx->ev0, ctx->ev1));
     return PML_OK;
 }
-
-}  // extern "C"
 

@@ -1,5 +1,5 @@
 // What a C-ABI entry that owns device memory for the length of one call shares with the others: the scope of its scratch and
-// events, the rule for the columns of a chunk, the upload of the altered flags.
+// events and of the copies to the caller, the rule for the columns of a chunk, the upload of the altered flags.
 //
 // THE RULE: a call's scratch and events live in one CallScope, which synchronises the stream before it frees.  Host buffers
 // that the call's asynchronous copies read or write are declared BEFORE the scope, so that this synchronisation runs while
@@ -18,6 +18,12 @@ class CallScope {
     bool waited_ = false;   // finish() has run and nothing went through the scope since
     std::vector<void*> mem_;
     std::vector<hipEvent_t> ev_;
+    struct Out {
+        void* host;
+        const void* dev;
+        size_t bytes;
+    };
+    std::vector<Out> out_;   // what finish() copies to the caller, in the order it was asked for
 
 public:
     CallScope(hipStream_t s, bool events_on) : s_(s), events_on_(events_on) {}
@@ -49,6 +55,19 @@ public:
         return PML_OK;
     }
 
+    // ... that the caller gets: finish() copies the `count` elements to `host`, so the size is written once.  A null `host`: the
+    // output is not asked for -- *dev is null, nothing is allocated, nothing copied.  zeroed: the kernels add into it, the
+    // hipMemsetAsync is queued here.  Leaving the scope without finish() copies nothing.
+    template <typename T>
+    int out(T** dev, T* host, size_t count, bool zeroed = false) {
+        *dev = nullptr;
+        if (host == nullptr) return PML_OK;
+        PML_TRY(get(dev, count));
+        if (zeroed) HIP_TRY(hipMemsetAsync(*dev, 0, count * sizeof(T), s_));
+        out_.push_back(Out{host, *dev, count * sizeof(T)});
+        return PML_OK;
+    }
+
     // an event on the stream, if the scope keeps events; elapsed() reads the time between two of them after finish() -- 0
     // where none are kept
     int mark() {
@@ -67,8 +86,13 @@ public:
         return PML_OK;
     }
 
-    // the one wait of the call (or of a chunk): everything queued so far is done, results and events may be read
+    // the one wait of the call (or of a chunk), behind the copies of out() -- each goes once: everything queued so far is done,
+    // results and events may be read
     int finish() {
+        std::vector<Out> outs;
+        outs.swap(out_);
+        // (a copy that fails leaves the wait to the end of the scope: the copies before it write host memory)
+        for (const Out& o : outs) HIP_TRY(hipMemcpyAsync(o.host, o.dev, o.bytes, hipMemcpyDeviceToHost, s_));
         waited_ = true;   // (a stream that fails to synchronise is not waited for again)
         HIP_TRY(hipStreamSynchronize(s_));
         return PML_OK;

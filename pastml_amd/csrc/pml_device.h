@@ -19,9 +19,10 @@
 #define PML_EIG_BU_MARG 0
 #define PML_EIG_BU_JOINT 1
 #define PML_EIG_TD 2
-// A kernel that is not a template: internal linkage, and compiled only by the translation unit that launches it -- all
-// of them are pml_api.hip's, which defines PML_PLAIN_KERNELS (the compiler emits a static kernel whether it is launched or
-// not, so the definitions are left out elsewhere).
+// A kernel that is not a template: internal linkage, and compiled only by the translation unit that launches it (the compiler
+// emits a static kernel whether it is launched or not).  Those of the headers that several units include are pml_api.hip's,
+// which defines PML_PLAIN_KERNELS: their definitions are left out elsewhere.  A header that one launcher alone includes
+// (pml_kernels_counts.h: pml_launch_counts.hip) needs no such guard.
 #define PML_GLOBAL static __global__
 
 typedef unsigned long long u64;

@@ -540,3 +540,16 @@ static int prof_end(pml_ctx* ctx, int which, long long launches) {
     if (ctx->prof_pending.size() >= 4096) PML_TRY(prof_drain(ctx));  // (bounds the number of live events)
     return PML_OK;
 }
+
+// ---------------------------------------------------------------------------------------------------------------------
+// What pml_api.hip defines and the entries that read a marginal pass (pml_api_readers.hip) call as well; each is described where
+// it is defined.
+PML_INTERNAL int require_model(pml_ctx* ctx);
+PML_INTERNAL int check_cols(pml_ctx* ctx, int cb, int ce);
+PML_INTERNAL int wait_pending(pml_ctx* ctx, bool idle = false);
+PML_INTERNAL int window_from_tunable(pml_ctx* ctx);
+PML_INTERNAL int consumer_prep(pml_ctx* ctx, bool force = false);
+PML_INTERNAL int materialize_cherries(pml_ctx* ctx);
+PML_INTERNAL int materialize_tip_posteriors(pml_ctx* ctx);
+template <typename T>
+PML_INTERNAL int fetch_rows(pml_ctx* ctx, const T* d_src, size_t src_width, size_t width, size_t n_cols, T* out);   // (T: double, i64, int)

@@ -40,7 +40,6 @@ __device__ __forceinline__ double wave_inclusive_scan(double v, int lane) {
 }
 
 // counts of the roots: n_rep draws from the posterior of each root (ml.py:786-793)
-#ifdef PML_PLAIN_KERNELS   // (launched by pml_api.hip only: the other translation units leave it out)
 PML_GLOBAL void __launch_bounds__(64)
 counts_roots_kernel(PmlTree t, PmlCols c, PmlState st, int col, int n_rep, u64 seed, int* __restrict__ counts,
                     const int* __restrict__ api_id) {
@@ -77,12 +76,10 @@ counts_roots_kernel(PmlTree t, PmlCols c, PmlState st, int col, int n_rep, u64 s
         __syncthreads();
     }
 }
-#endif
 
 // one depth level: parents[0 .. n_parents), one wavefront (= one 64-thread block) per parent
 // SRC = PML_P_WINDOW (pml_pij_window.h): the parents are one run of the top-down sweep's window plan and the matrices of their
 // children were built into the column's window right before (PmlPWindow: base is the column's, slot the top-down table).
-#ifdef PML_PLAIN_KERNELS   // (launched by pml_api.hip only: the other translation units leave it out)
 template <int SRC = PML_P_MATERIALISED>
 PML_GLOBAL void __launch_bounds__(64)
 counts_level_kernel(PmlTree t, PmlCols c, PmlState st, PmlModel m, typename PmlPSource<SRC>::type P, int col, int n_rep,
@@ -190,4 +187,3 @@ counts_level_kernel(PmlTree t, PmlCols c, PmlState st, PmlModel m, typename PmlP
         __syncthreads();
     }
 }
-#endif

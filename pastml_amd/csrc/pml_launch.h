@@ -1,4 +1,4 @@
-// What pml_api.hip (schedules, C-ABI) calls of the kernel launchers, which live in translation units of their own
+// What pml_api.hip (schedules, C-ABI) and pml_api_readers.hip call of the kernel launchers, which live in translation units of their own
 // (pml_launch_*.hip, one per kernel family, compiled in parallel): the dispatch functions, the cases of lane shapes they are
 // instantiated for (the shapes themselves: pml_columns.h) and the predicates that say which family a context's sweeps take.
 #pragma once
@@ -201,6 +201,12 @@ PML_INTERNAL int launch_compress_trim(pml_ctx* ctx, int L, int n_cols, int W, co
 #define PML_TL_FUSE_WIDTH 512   // levels of at most this many nodes may share a launch of one workgroup (pml_timeline_info reports it)
 PML_INTERNAL int launch_timeline(pml_ctx* ctx, const pml_timeline_in& in, const pml_timeline_out& out);
 
+// ---- pml_launch_counts.hip: n_rep sampled scenarios of column col counted per node and per transition (pml_marginal_counts);
+//      d_alt [N] in the library's numbering or null, d_counts [N][k], d_result [k][k] (zeroed), d_same [N][k] (zeroed) or null, all
+//      in the caller's numbering; queued only.  counts_max_states: the most states its kernels hold
+PML_INTERNAL int counts_max_states();
+PML_INTERNAL int launch_counts(pml_ctx* ctx, int col, int n_rep, u64 seed, const unsigned char* d_alt, int* d_counts, long long* d_result,
+                               int* d_same);
 // ---- pml_launch_expected.hip: exact expected transition counts of the columns [cb, ce) (pml_expected_counts); d_alt [N] in the
 //      library's numbering or null, d_out [cols][k][k], d_same [cols][N][k] in the caller's numbering (zeroed) or null
 PML_INTERNAL int launch_expected(pml_ctx* ctx, int cb, int ce, const unsigned char* d_alt, double* d_out, double* d_same);

@@ -1,5 +1,5 @@
 // Launches of the exact expected transition counts (pml_kernels_expected.h): the branch pass, the pass over the parents and
-// the sum of the partials, for the columns [cb, ce) of the context in one go.  pml_expected_counts (pml_api.hip) checks the
+// the sum of the partials, for the columns [cb, ce) of the context in one go.  pml_expected_counts (pml_api_readers.hip) checks the
 // arguments, makes sure every vector the kernels read is in HBM and copies out.
 #include "pml_launch.h"
 #include "pml_kernels_expected.h"

@@ -1,5 +1,5 @@
 // Launches of the exact gradient of ln L of the F81 family (pml_kernels_gradient.h): the branch pass and the sum of the
-// partials, for the columns [cb, ce) of the context in one go, queued on the context's stream.  pml_loglik_gradient (pml_api.hip) checks the arguments, makes
+// partials, for the columns [cb, ce) of the context in one go, queued on the context's stream.  pml_loglik_gradient (pml_api_readers.hip) checks the arguments, makes
 // sure every vector the kernels read is in HBM and copies out.
 #include "pml_launch.h"
 #include "pml_kernels_gradient.h"

@@ -1,6 +1,6 @@
 // Launches of the exact expected dwell times and Markov jumps of the F81 family (pml_kernels_history.h): the branch pass, the
 // jump product and the sums of the partials, for the columns [cb, ce) of the context in one go, queued on the context's stream.
-// pml_expected_history (pml_api.hip) checks the arguments, makes sure every vector the kernels read is in HBM and copies out.
+// pml_expected_history (pml_api_readers.hip) checks the arguments, makes sure every vector the kernels read is in HBM and copies out.
 #include "pml_launch.h"
 #include "pml_kernels_history.h"
 

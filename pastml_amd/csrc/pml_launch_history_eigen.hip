@@ -1,6 +1,6 @@
 // Launches of the exact expected dwell times and Markov jumps of the eigen-decomposed models (pml_kernels_history_eigen.h): the
 // changes of basis, the pair sum, the sums of the partials and the final transforms, for the columns [cb, ce) of the context in
-// one go, queued on the context's stream.  pml_expected_history_eigen (pml_api.hip) checks the arguments, makes sure every vector
+// one go, queued on the context's stream.  pml_expected_history_eigen (pml_api_readers.hip) checks the arguments, makes sure every vector
 // the kernels read is in HBM and copies out.
 #include "pml_launch.h"
 #include "pml_kernels_history_eigen.h"

@@ -1,6 +1,6 @@
 // Launches of the history sampler of the F81 family (pml_kernels_history_sample.h) for one column: the walk over (piece, tile of
 // repetitions) items and the sum of the pieces' partials, queued on the context's stream behind launch_scenarios, whose states
-// it reads from the device.  pml_sample_histories (pml_api.hip) checks the arguments, makes sure every vector the kernels read
+// it reads from the device.  pml_sample_histories (pml_api_readers.hip) checks the arguments, makes sure every vector the kernels read
 // is in HBM, zeroes the counters and copies out.
 #include "pml_launch.h"
 #include "pml_kernels_history_sample.h"

@@ -1,6 +1,6 @@
 // Launches of the exact dwell times, Markov jumps and lineage counts per time interval of the F81 family
 // (pml_kernels_history_time.h): the segment pass, the jump product and the sums of the partials per bin, for the columns
-// [cb, ce) of the context in one go, queued on the context's stream.  pml_history_through_time (pml_api.hip) checks the
+// [cb, ce) of the context in one go, queued on the context's stream.  pml_history_through_time (pml_api_readers.hip) checks the
 // arguments, plans the segments on the host (pml_time_segments.h), makes sure every vector the kernels read is in HBM and
 // copies out.
 #include "pml_launch.h"

@@ -2,7 +2,7 @@
 // plan, launch_scenarios, whose states the walk reads from the device, the count of the branches that cannot be drawn, the walk
 // over (piece of segments, tile of repetitions) items and the sum of the pieces' partials per bin, queued on the context's
 // stream.  The plan goes up first, so that its copies from pageable memory are not queued behind the scenario kernels.
-// pml_sample_histories_through_time (pml_api.hip) checks the arguments, plans the segments on the host (pml_time_segments.h),
+// pml_sample_histories_through_time (pml_api_readers.hip) checks the arguments, plans the segments on the host (pml_time_segments.h),
 // makes sure every vector the kernels read is in HBM, zeroes the counters and copies out.
 #include "pml_launch.h"
 #include "pml_kernels_history_time_sample.h"

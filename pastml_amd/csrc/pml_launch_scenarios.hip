@@ -1,6 +1,6 @@
 // Launches of the scenario sampler (pml_kernels_scenarios.h) over the forward simulator's schedule: the top depth levels one
 // launch each, the subtrees below the frontier depth in one launch (pml_launch_simulate.hip).  pml_sample_scenarios
-// (pml_api.hip) checks the arguments, makes sure every vector the kernel reads is in HBM and copies out.
+// (pml_api_readers.hip) checks the arguments, makes sure every vector the kernel reads is in HBM and copies out.
 #include "pml_launch.h"
 #include "pml_kernels_scenarios.h"
 

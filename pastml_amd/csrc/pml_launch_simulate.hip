@@ -1,5 +1,5 @@
 // Launches of the forward simulator (pml_kernels_simulate.h): the schedule over the depth levels and the subtrees below a
-// frontier depth.  pml_simulate_states (pml_api.hip) checks the arguments, runs the per-branch preparation and copies out.
+// frontier depth.  pml_simulate_states (pml_api_readers.hip) checks the arguments, runs the per-branch preparation and copies out.
 #include "pml_launch.h"
 #include "pml_kernels_simulate.h"
 

@@ -1,7 +1,7 @@
-// Host-only check of pastml_amd/csrc/pml_call_scope.h: the scope of one call's scratch and events, the rule for the columns of
-// a chunk, the upload of the altered flags.  The HIP names the header uses are counting stand-ins here (a log of the calls in
-// order, a table of the live allocations, "the nth call of this kind fails"); device memory is host memory, so a copy that
-// overruns its allocation is a finding of a sanitizer build.
+// Host-only check of pastml_amd/csrc/pml_call_scope.h: the scope of one call's scratch, events and copies to the caller, the
+// rule for the columns of a chunk, the upload of the altered flags.  The HIP names the header uses are counting stand-ins here (a
+// log of the calls in order, a table of the live allocations and their sizes, "the nth call of this kind fails"); device memory
+// is host memory, so a copy that overruns its allocation is counted here and is a finding of a sanitizer build.
 // Built and run by tests/test_call_scope_host.py; prints FAIL lines and exits 1, or one OK line.
 #include "../include/pastml_hip.h"
 
@@ -9,6 +9,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <map>
 #include <set>
 #include <string>
 #include <type_traits>
@@ -29,11 +30,12 @@ static std::string g_case;
 
 // ---- stand-ins for the HIP runtime --------------------------------------------------------------------------------------
 enum hipError_t { hipSuccess = 0, hipErrorInjected = 7 };
-enum hipMemcpyKind { hipMemcpyHostToDevice = 1 };
+enum hipMemcpyKind { hipMemcpyHostToDevice = 1, hipMemcpyDeviceToHost = 2 };
 typedef struct StreamTag* hipStream_t;
 typedef struct EventTag { int id; }* hipEvent_t;
 
-enum Kind { MALLOC, FREE, COPY, SYNC, EV_CREATE, EV_RECORD, EV_ELAPSED, EV_DESTROY, SET_DEVICE, MEM_INFO, N_KINDS };
+// (COPY: to the device; COPY_OUT: to the host)
+enum Kind { MALLOC, FREE, COPY, COPY_OUT, MEMSET, SYNC, EV_CREATE, EV_RECORD, EV_ELAPSED, EV_DESTROY, SET_DEVICE, MEM_INFO, N_KINDS };
 struct Call {
     Kind kind;
     const void *a, *b;   // pointer / event / stream arguments
@@ -42,9 +44,10 @@ struct Call {
 struct Mock {
     std::vector<Call> log;
     std::set<void*> live, handed_out;
+    std::map<const void*, size_t> bytes_of;   // of every allocation handed out
     std::set<hipEvent_t> live_events;
     int seen[N_KINDS] = {}, fail_at[N_KINDS];
-    int bad_frees = 0, bad_event_uses = 0;
+    int bad_frees = 0, bad_event_uses = 0, overruns = 0;
     size_t free_bytes = 0;
     Mock() {
         for (int& f : fail_at) f = -1;
@@ -53,6 +56,11 @@ struct Mock {
     bool enter(Kind k, const void* a, const void* b, size_t n) {
         log.push_back(Call{k, a, b, n});
         return seen[k]++ == fail_at[k];
+    }
+    // `bytes` of "device" memory from p on: p is a live allocation that holds as many
+    void touches(const void* p, size_t bytes) {
+        const auto it = bytes_of.find(p);
+        if (it == bytes_of.end() || !live.count(const_cast<void*>(p)) || bytes > it->second) ++overruns;
     }
     int count(Kind k) const { return seen[k]; }
     int first(Kind k) const {
@@ -73,6 +81,7 @@ static hipError_t hipMalloc(void** p, size_t bytes) {
     *p = malloc(bytes);
     g_mock->live.insert(*p);
     g_mock->handed_out.insert(*p);
+    g_mock->bytes_of[*p] = bytes;
     return hipSuccess;
 }
 static hipError_t hipFree(void* p) {
@@ -84,9 +93,16 @@ static hipError_t hipFree(void* p) {
     free(p);
     return hipSuccess;
 }
-static hipError_t hipMemcpyAsync(void* dst, const void* src, size_t bytes, hipMemcpyKind, hipStream_t s) {
-    if (g_mock->enter(COPY, dst, s, bytes)) return hipErrorInjected;
+static hipError_t hipMemcpyAsync(void* dst, const void* src, size_t bytes, hipMemcpyKind kind, hipStream_t s) {
+    if (g_mock->enter(kind == hipMemcpyDeviceToHost ? COPY_OUT : COPY, dst, s, bytes)) return hipErrorInjected;
+    g_mock->touches(kind == hipMemcpyDeviceToHost ? src : dst, bytes);
     memcpy(dst, src, bytes);
+    return hipSuccess;
+}
+static hipError_t hipMemsetAsync(void* dst, int value, size_t bytes, hipStream_t s) {
+    if (g_mock->enter(MEMSET, dst, s, bytes)) return hipErrorInjected;
+    g_mock->touches(dst, bytes);
+    memset(dst, value, bytes);
     return hipSuccess;
 }
 static hipError_t hipStreamSynchronize(hipStream_t s) { return g_mock->enter(SYNC, s, nullptr, 0) ? hipErrorInjected : hipSuccess; }
@@ -171,10 +187,14 @@ static void check_clean(const Mock& m) {
     CHECK(m.count(FREE) == (int)m.handed_out.size(), "%d frees of %zu allocations", m.count(FREE), m.handed_out.size());
     CHECK(m.live_events.empty(), "%zu events were never destroyed", m.live_events.size());
     CHECK(m.bad_event_uses == 0, "%d uses of events that were not live", m.bad_event_uses);
-    if (m.count(FREE) > 0 && (m.count(COPY) > 0 || m.count(EV_RECORD) > 0))
+    CHECK(m.overruns == 0, "%d copies or fills outside a live allocation", m.overruns);
+    if (m.count(FREE) > 0 && (m.count(COPY) > 0 || m.count(COPY_OUT) > 0 || m.count(MEMSET) > 0 || m.count(EV_RECORD) > 0))
         CHECK(m.first(SYNC) >= 0 && m.last(SYNC) < m.first(FREE), "a free at %d before the synchronisation at %d", m.first(FREE), m.last(SYNC));
     for (const Call& c : m.log)
-        if (c.kind == SYNC || c.kind == COPY) CHECK((c.kind == SYNC ? c.a : c.b) == STREAM, "a call on another stream");
+        if (c.kind == SYNC || c.kind == COPY || c.kind == COPY_OUT || c.kind == MEMSET)
+            CHECK((c.kind == SYNC ? c.a : c.b) == STREAM, "a call on another stream");
+    // nothing queued is left unwaited for: a copy to the host that the scope freed under would write memory the caller reads
+    if (m.last(COPY_OUT) >= 0) CHECK(m.last(SYNC) > m.last(COPY_OUT), "no synchronisation behind the copy out at %d", m.last(COPY_OUT));
 }
 
 // ---- 1, 2: six requests, the allocation of each failing in turn; a request of 0 elements -----------------------------------
@@ -364,6 +384,160 @@ static void test_finish() {
     }
 }
 
+// ---- 5b: outputs -- device memory tied to its host destination, copied by finish() ----------------------------------------------
+struct Outputs {
+    int a[10];
+    double b[4];         // not asked for in the calls below
+    unsigned c[6];       // zeroed on the device, then added into
+    unsigned short e;    // a request of 0 elements: nothing may be written here
+    long long f[3];
+    Outputs() { memset(this, 0x5a, sizeof(*this)); }
+};
+static const size_t OUT_BYTES[4] = {40, 24, 0, 24};
+
+// the requests, then what the kernels would write; stop_after: the call returns early behind that many requests
+static int four_outputs(CallScope& sc, Outputs& h, int stop_after = 4) {
+    int* d_a;
+    double* d_b = (double*)&h;
+    unsigned* d_c;
+    unsigned short* d_e;
+    long long* d_f;
+    PML_TRY(sc.out(&d_a, h.a, 10));
+    PML_TRY(sc.out(&d_b, (double*)nullptr, 4));
+    CHECK(d_b == nullptr, "an output that is not asked for got a pointer");
+    if (stop_after == 1) return fail(PML_ERR_INVALID, "stopped");
+    PML_TRY(sc.out(&d_c, h.c, 6, true));
+    for (int i = 0; i < 6; ++i) CHECK(d_c[i] == 0, "a zeroed output holds %u", d_c[i]);
+    PML_TRY(sc.out(&d_e, &h.e, 0));
+    CHECK(d_e != nullptr, "a request of 0 elements got no pointer");
+    if (stop_after == 3) return fail(PML_ERR_INVALID, "stopped");
+    PML_TRY(sc.out(&d_f, h.f, 3));
+    for (int i = 0; i < 10; ++i) d_a[i] = 100 + i;
+    for (int i = 0; i < 6; ++i) d_c[i] += 7u * i;
+    for (int i = 0; i < 3; ++i) d_f[i] = -1 - i;
+    return PML_OK;
+}
+
+static bool untouched(const Outputs& h) {
+    const Outputs fresh;
+    return memcmp(&h, &fresh, sizeof(h)) == 0;
+}
+
+static void check_copied(const Outputs& h) {
+    const Outputs fresh;
+    for (int i = 0; i < 10; ++i) CHECK(h.a[i] == 100 + i, "a[%d] = %d", i, h.a[i]);
+    for (int i = 0; i < 6; ++i) CHECK(h.c[i] == 7u * i, "c[%d] = %u", i, h.c[i]);
+    for (int i = 0; i < 3; ++i) CHECK(h.f[i] == -1 - i, "f[%d] = %lld", i, h.f[i]);
+    CHECK(memcmp(h.b, fresh.b, sizeof(h.b)) == 0 && h.e == fresh.e, "an output that was not asked for, or of 0 elements, was written");
+}
+
+static void test_outputs() {
+    g_case = "outputs: order, sizes, one wait";
+    {
+        Mock m;
+        g_mock = &m;
+        Outputs h;   // (before the scope: the rule of the header)
+        {
+            CallScope sc(STREAM, false);
+            CHECK(four_outputs(sc, h) == PML_OK, "failed: %s", g_last_error);
+            CHECK(m.count(COPY_OUT) == 0 && untouched(h), "a copy before finish()");
+            CHECK(m.count(MEMSET) == 1 && m.log[m.first(MEMSET)].n == 24 && m.first(MEMSET) == m.first(MALLOC) + 2,
+                  "the zeroed output was not cleared where it was asked for, in its own size");
+            CHECK(sc.finish() == PML_OK, "finish() failed");
+            check_copied(h);
+        }
+        CHECK(m.count(MALLOC) == 4, "%d allocations for four outputs that are asked for", m.count(MALLOC));
+        const void* dst[4] = {h.a, h.c, &h.e, h.f};
+        size_t seen = 0;
+        for (const Call& c : m.log)
+            if (c.kind == COPY_OUT && seen < 4) {
+                CHECK(c.a == dst[seen] && c.n == OUT_BYTES[seen], "copy %zu goes to another output, or has %zu bytes", seen, c.n);
+                ++seen;
+            }
+        CHECK(m.count(COPY_OUT) == 4, "%d copies out", m.count(COPY_OUT));
+        CHECK(m.count(SYNC) == 1 && m.first(SYNC) > m.last(COPY_OUT), "%d synchronisations, the first at %d, the last copy at %d",
+              m.count(SYNC), m.first(SYNC), m.last(COPY_OUT));
+        check_clean(m);
+    }
+    g_case = "outputs: nothing is copied twice";
+    {
+        Mock m;
+        g_mock = &m;
+        Outputs h, h2;
+        {
+            CallScope sc(STREAM, false);
+            CHECK(four_outputs(sc, h) == PML_OK && sc.finish() == PML_OK, "failed");
+            h.a[0] = -5;   // (the caller's from here on)
+            CHECK(sc.finish() == PML_OK && m.count(COPY_OUT) == 4 && h.a[0] == -5, "a second finish() copied again");
+            // a launcher that waits once per chunk: the next chunk's outputs go with the next wait, the first chunk's do not
+            CHECK(four_outputs(sc, h2) == PML_OK && sc.finish() == PML_OK, "failed");
+            CHECK(m.count(COPY_OUT) == 8 && h.a[0] == -5, "%d copies out behind two chunks", m.count(COPY_OUT));
+            check_copied(h2);
+        }
+        CHECK(m.count(SYNC) == 3, "%d synchronisations", m.count(SYNC));
+        check_clean(m);
+    }
+    for (int stop_after : {1, 3}) {
+        g_case = "outputs: early exit behind request " + std::to_string(stop_after);
+        Mock m;
+        g_mock = &m;
+        Outputs h;
+        {
+            CallScope sc(STREAM, false);
+            CHECK(four_outputs(sc, h, stop_after) == PML_ERR_INVALID, "did not stop");
+        }
+        CHECK(m.count(COPY_OUT) == 0 && untouched(h), "%d copies out on an early exit", m.count(COPY_OUT));
+        CHECK(m.count(SYNC) == 1 && m.count(FREE) == stop_after, "synchronisations %d frees %d", m.count(SYNC), m.count(FREE));
+        check_clean(m);
+    }
+    g_case = "outputs: an allocation fails";
+    {
+        Mock m;
+        g_mock = &m;
+        m.fail_at[MALLOC] = 1;
+        Outputs h;
+        {
+            CallScope sc(STREAM, false);
+            CHECK(four_outputs(sc, h) == PML_ERR_HIP, "no error");
+        }
+        CHECK(m.count(COPY_OUT) == 0 && m.count(MEMSET) == 0 && untouched(h), "a copy or a fill behind a failed allocation");
+        check_clean(m);
+    }
+    g_case = "outputs: the fill fails";
+    {
+        Mock m;
+        g_mock = &m;
+        m.fail_at[MEMSET] = 0;
+        Outputs h;
+        {
+            CallScope sc(STREAM, false);
+            CHECK(four_outputs(sc, h) == PML_ERR_HIP && strstr(g_last_error, "hipMemsetAsync") != nullptr, "message '%s'", g_last_error);
+        }
+        CHECK(m.count(COPY_OUT) == 0 && m.count(FREE) == 2 && untouched(h), "copies %d frees %d", m.count(COPY_OUT), m.count(FREE));
+        check_clean(m);
+    }
+    for (int bad = 0; bad < 8; ++bad) {
+        const bool again = bad >= 4;   // the call goes on to a second finish(), or returns at once
+        g_case = "outputs: copy " + std::to_string(bad % 4) + " fails" + (again ? ", finish again" : "");
+        Mock m;
+        g_mock = &m;
+        m.fail_at[COPY_OUT] = bad % 4;
+        Outputs h;
+        int status;
+        {
+            CallScope sc(STREAM, false);
+            CHECK(four_outputs(sc, h) == PML_OK, "failed");
+            g_last_error[0] = 0;
+            status = sc.finish();
+            CHECK(m.count(SYNC) == 0, "a wait that reports nothing inside the failed finish()");
+            if (again) CHECK(sc.finish() == PML_OK && m.count(COPY_OUT) == bad % 4 + 1, "the copies behind a failed one were tried later");
+        }
+        CHECK(status == PML_ERR_HIP && strstr(g_last_error, "hipMemcpyAsync") != nullptr, "status %d, message '%s'", status, g_last_error);
+        CHECK(m.count(FREE) == 4 && m.count(SYNC) == 1, "frees %d synchronisations %d", m.count(FREE), m.count(SYNC));
+        check_clean(m);   // (a wait behind the copies that went, before the frees)
+    }
+}
+
 // ---- 6: the columns of a chunk.  Expected values by hand from
 //         min(free / 2 / max(1, per_col), cap), then min(., max(1, tunable)) if set, an error below 1, then min(., n_cols) -------
 static void test_chunk_rule() {
@@ -468,12 +642,13 @@ int main() {
     test_allocation_failures();
     test_events();
     test_finish();
+    test_outputs();
     test_chunk_rule();
     test_small_helpers();
     if (g_failures) {
         printf("%d checks failed\n", g_failures);
         return 1;
     }
-    printf("OK: allocation failures, events, finish, chunk rule, helpers\n");
+    printf("OK: allocation failures, events, finish, outputs, chunk rule, helpers\n");
     return 0;
 }

@@ -5,7 +5,11 @@ the library is not loaded -- and checks: with the allocation of each of six requ
 is freed exactly once, after the stream has been waited for, and the error names the bytes asked for; a request of 0 elements
 gets a pointer of its own; no event exists unless events are on, and with them on every mark is created, recorded on the
 scope's stream and destroyed after the frees, a failing hipEventCreate / hipEventRecord included; finish() followed by the end
-of the scope waits once, finish() / put() / end twice, a failing wait is reported and the memory still freed; the columns of
+of the scope waits once, finish() / put() / end twice, a failing wait is reported and the memory still freed; outputs tied to
+their host destination (CallScope::out) are copied by finish() in the order and with the byte counts of their requests, all
+before the one wait, a zeroed one cleared where it is asked for, nothing allocated or copied for a null destination, nothing
+copied twice (a second finish(), a launcher that waits per chunk), nothing copied on an early exit, a failing copy, fill or
+allocation reported with everything still freed once behind a wait, no copy or fill outside its allocation; the columns of
 a chunk against a table worked out by hand from the two expressions the rule replaced (memory to spare, either cap binding,
 the tunable below and above the memory's bound, 0 and negative, nothing per column, a column that does not fit, one column);
 pow2_from; the altered flags in the library's numbering.  (A sanitizer build of the same driver is for running by hand: add

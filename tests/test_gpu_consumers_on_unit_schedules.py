@@ -1,5 +1,5 @@
 """
-The entries that read what a marginal pass left on the device (write_marginal_pass, pml_api.hip, and pml_select_states) on the
+The entries that read what a marginal pass left on the device (Reader::rows, pml_api_readers.hip, and pml_select_states) on the
 schedules that leave rows out of memory: two-level and stacked units and the two chained launches, 17 <= k <= 64.  There the
 cherries' bottom-up vectors, the children of the two-level and of the stacked units and the observed tips' posterior rows are
 filled in lazily, by the first entry that needs them.
