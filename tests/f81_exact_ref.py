@@ -66,7 +66,7 @@ def pij(pi, t, sf=1., tau=0., tf=1.):
         return [[(ONE - e) * pj + (e if i == j else ZERO) for j, pj in enumerate(pi)] for i in range(len(pi))], e
 
 
-def marginal_pass(flat, masks, pi, sf=1., tau=0., tf=1., top_down=False, vectors=None):
+def marginal_pass(flat, masks, pi, sf=1., tau=0., tf=1., top_down=False, vectors=None, raw=False):
     """
     flat: parent / first_child / n_children / dist / roots (pastml_amd.tree.FlatForest); masks: 0/1 [N, k].
     Returns dict(
@@ -74,7 +74,9 @@ def marginal_pass(flat, masks, pi, sf=1., tau=0., tf=1., top_down=False, vectors
         G (Decimal): sum of 1 / (1 - e_n) over the non-root nodes with e_n < 1,
         with vectors (default: with top_down) bu_log10 [N, k] float: log10 of the true bottom-up vectors (-inf for zeros) -- the
         logarithms cost ten times the pass --,
-        and with top_down: td_log10 [N, k], posterior [N, k] (float)).
+        and with top_down: td_log10 [N, k], posterior [N, k] (float)),
+        with raw the Decimals themselves (lists): 'e' [N], 'v' [N][k], and with top_down 'down' [N][k] and 'lh' [N], every
+        node's marginal-likelihood sum (its tree's likelihood).
     """
     parent, first_child, n_children = flat.parent, flat.first_child, flat.n_children
     N, k = np.asarray(masks).shape
@@ -102,10 +104,13 @@ def marginal_pass(flat, masks, pi, sf=1., tau=0., tf=1., top_down=False, vectors
         out = dict(loglik=sum(per_tree, ZERO), loglik_per_tree=per_tree, G=G)
         if top_down if vectors is None else vectors:
             out['bu_log10'] = np.array([_log10_row(row) for row in v])
+        if raw:
+            out.update(e=e, v=v)
         if not top_down:
             return out
         down = [None] * N
         post = np.zeros((N, k))
+        totals = []
         for n in range(N):   # parents first
             p = int(parent[n])
             if p < 0:
@@ -117,11 +122,75 @@ def marginal_pass(flat, masks, pi, sf=1., tau=0., tf=1., top_down=False, vectors
                 down[n] = [base + en * xi for xi in x]
             lh = [a * b * c for a, b, c in zip(v[n], down[n], pi)]   # (v carries the node's mask)
             total = sum(lh, ZERO)
+            totals.append(total)
             post[n] = [float(x / total) for x in lh] if total > 0 else np.nan
         out['posterior'] = post
+        if raw:
+            out.update(down=down, lh=totals)
         if 'bu_log10' in out:
             out['td_log10'] = np.array([_log10_row(row) for row in down])
         return out
+
+
+def joint_pass(flat, masks, pi, sf=1., tau=0., tf=1.):
+    """
+    The joint (max-product) bottom-up sweep, Pupko's variant (ml.py:82-148 with is_marginal False), in the manner of
+    matrix_exact_ref.joint_pass: message_n[i] = max_j P_n[i, j] v_n[j] with P_n[i, j] = (1 - e_n) pi_j + [i == j] e_n, so row i
+    of the products is w_j = (1 - e_n) pi_j v_n[j] off the diagonal and w_i + e_n v_n[i] on it.
+    Returns dict(loglik (Decimal: sum over the trees of ln max_i pi_i v_root[i]), loglik_per_tree,
+    products: per non-root node n the pair (w [k], e_n v_n [k]) of Decimals from which choice_is_a_maximum judges an arg-max choice
+        (None for the roots),
+    first_maximum [N, k] int: the lowest maximising state j per (node, parent state i), as np.argmax picks it; -1 for the roots,
+    root_first_maximum: per tree the lowest state that maximises pi_i v_root[i],
+    bu_log10 [N, k] float: log10 of the exact max-product vectors (-inf for zeros)).
+    """
+    parent, first_child, n_children = flat.parent, flat.first_child, flat.n_children
+    N, k = np.asarray(masks).shape
+    allowed = [[bool(x) for x in row] for row in np.asarray(masks)]
+    e = branch_exponentials(pi, flat.dist, sf, tau, tf)
+    with decimal.localcontext(_CONTEXT):
+        pi = [Decimal(float(x)) for x in pi]
+        v = [None] * N
+        message = [None] * N
+        products = [None] * N
+        first = np.full((N, k), -1, dtype=np.int64)
+        for n in reversed(range(N)):
+            row = [ONE if a else ZERO for a in allowed[n]]
+            fc = int(first_child[n])
+            for c in range(fc, fc + int(n_children[n])):
+                row = [x * m if x else x for x, m in zip(row, message[c])]
+            v[n] = row
+            if parent[n] >= 0:
+                en = e[n]
+                w = [(ONE - en) * p * x for p, x in zip(pi, row)]
+                ev = [en * x for x in row]
+                products[n] = (w, ev)
+                # the two largest of w, lowest index first among equals: row i's best off-diagonal entry is one of them
+                order = sorted(range(k), key=lambda j: (-w[j], j))[:2]
+                msg = []
+                for i in range(k):
+                    j = order[0] if order[0] != i or k == 1 else order[1]
+                    diag = w[i] + ev[i]
+                    if k == 1 or diag > w[j] or (diag == w[j] and i < j):
+                        j, best = i, diag
+                    else:
+                        best = w[j]
+                    msg.append(best)
+                    first[n, i] = j
+                message[n] = msg
+        at_root = [[p * x for p, x in zip(pi, v[int(r)])] for r in flat.roots]
+        per_tree = [_ln(max(row)) for row in at_root]
+        bu_log10 = np.array([_log10_row(row) for row in v])
+    return dict(loglik=sum(per_tree, ZERO), loglik_per_tree=per_tree, products=products, first_maximum=first, bu_log10=bu_log10,
+                root_first_maximum=[row.index(max(row)) for row in at_root])
+
+
+def choice_is_a_maximum(products, n, i, j, rtol=Decimal('1e-12')):
+    """Whether state j is an arg-max of row i of node n's exact products P_n[i, .] v_n, up to products equal to rtol."""
+    w, ev = products[n]
+    with decimal.localcontext(_CONTEXT):
+        best = max(max(w[:i] + w[i + 1:], default=ZERO), w[i] + ev[i])
+        return best - (w[j] + (ev[j] if i == j else ZERO)) <= rtol * best
 
 
 def tolerance(exact, lnl_rtol):
