@@ -2,8 +2,9 @@
 Randomised GPU parity sweep (``-m gpu``): many small random forests -- polytomies, several trees, zero-length branches,
 missing / ambiguous tips, restricted internal nodes, one to three columns with their own parameters -- through the
 C-ABI, against the oracle.  Shapes are drawn so that every kernel variant is hit: the F81 lane shapes (k from 2 to 130),
-cherry fusion with 1-6 tips per cherry, units that leave the lane-parallel gather (more than four children, stored
-children beyond the first two), the sweeps of the eigen models -- the sum sweeps as two matrix-core GEMMs per 16 nodes that
+cherry fusion with 2-6 tips per cherry (FlatForest.random splits a tip into two children at least: cherries of one tip, nodes
+with one child and trees of a single tip are in tests/test_gpu_degenerate_forests.py), units that leave the lane-parallel
+gather (more than four children, stored children beyond the first two), the sweeps of the eigen models -- the sum sweeps as two matrix-core GEMMs per 16 nodes that
 never form P(t) (2 <= k <= 64 with A and A^-1 as operands, 65 <= k <= 128 with one matrix in LDS), the joint sweep on the
 vector units (k <= 64), and both on P(t) materialised in HBM beyond those (k = 140; the joint sweep from 65 states on) --, HKY
 with P(t) built in registers, and forests small enough for the single-launch kernels as well as larger ones.
