@@ -2,6 +2,9 @@
 The parsimony passes on the device (pml_parsimony, pastml_amd.parsimony.parsimonious_acr_batch) against the reference's
 pastml/parsimony.py (tests/golden/parsimony.npz, parsimony_wide.npz) and, at sizes the reference cannot reach in a test,
 against the host path -- unchanged code that the goldens pin to the reference.  Integer work: every comparison is exact.
+The counter widths (arities around 14 / 15, 254 / 255, 65534 / 65535), every lane group W = 1 .. 8, ties across words, unary
+nodes, lone tips and stars: tests/test_gpu_parsimony_shapes.py, on the cases of tests/parsimony_shape_cases.py (host side:
+tests/test_parsimony_shape_cases_host.py, which also pins the host path to the reference on those forests).
 """
 import os
 
