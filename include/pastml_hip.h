@@ -459,6 +459,51 @@ int pml_history_through_time(pml_ctx* ctx, int32_t col_begin, int32_t col_end, c
                              int32_t M, double* times_out, double* jumps_out, double* lineages_out);
 
 /*
+ * pml_history_through_time for a context of eigen-decomposed models (JTT, CUSTOM_RATES, HKY handed over by its d, A, Ainv),
+ * 2 <= k <= 256: pml_expected_history_eigen per time interval, with the number of lineages in each state at every boundary,
+ * from the vectors of the marginal pass (needs one, PML_ERR_INVALID otherwise).  Inputs, bins, segments (s1, w, r, and
+ * u = (time_n - lo) / h, each one quotient of one difference), output shapes and the optional NULLs are those of
+ * pml_history_through_time: what is NULL is not computed and times_out has the same bits either way.  Notation of
+ * pml_expected_history_eigen: d, A, Ainv, t'_n = (dist_n + tau) tau_factor sf, r_n = Ainv v_n, l_n = A^T o_n, o_n = q_p / m_n.
+ * The integral Phi_cd(t) = integral_0^t exp(d_c u) exp(d_d (t - u)) du, u measured from the parent, restricted to the segment
+ * [s1 t', (s1 + w) t'], factorises exactly: Phi_cd^seg = exp(d_c s1 t') Phi_cd(w t') exp(d_d r t'), every exponent <= 0.  Per
+ * segment, with y = w t':
+ *   ls[c] = l_n[c] exp(d_c s1 t'),   Ey[c] = exp(d_c y),   rs[d] = r_n[d] exp(d_d r t')
+ *   X_seg[c][d] = ls[c] Phi_cd(y) rs[d]        (Phi from y, d_c, d_d, Ey[c], Ey[d] as pml_expected_history_eigen forms it: the
+ *                                              difference quotient where |(d_c - d_d) y| >= 0.5, the 15-term series of phi below)
+ *   W_m = sum of X_seg over the segments of bin m
+ *   times_out[col][m][s]    = (1 / sf) sum_cd Ainv[c][s] W_m[c][d] A[s][d]        (a row sums to the smoothed length in the bin)
+ *   jumps_out[col][m][i][j] = Q_ij sum_cd Ainv[c][i] W_m[c][d] A[j][d]            (i != j; the diagonal exactly 0)
+ * A branch with t' = 0 adds nothing to times_out or jumps_out.  A branch with h == 0 is one segment s1 = 0, w = 1, r = 0: ls, Ey,
+ * rs are then l_n, E_n, r_n in bits.  The sums have mixed signs: an entry that rounding leaves below zero is returned as 0.0.  The
+ * bins of a call that covers the tree sum to pml_expected_history_eigen's outputs; an empty bin is exact zeros.
+ * Lineages: at every boundary T_m, over the branches with time_p <= T_m < time_n, with s = (T_m - time_p) / h and
+ * u = (time_n - T_m) / h:
+ *   lineages_out[col][m][j] += (sum_c Ainv[c][j] l_n[c] exp(d_c s t')) (sum_d A[j][d] r_n[d] exp(d_d u t'))
+ * the posterior of the state at that point of the branch, which sums over j to 1.  Where t' = 0 the term is q_p[j], the formula at
+ * P = I.  A row is clamped at 0 after its sum.
+ * Refused in this order.  PML_ERR_INVALID: no model, a bad column range, a NULL node_time, boundaries or times_out.
+ * PML_ERR_UNSUPPORTED: an F81 context (pml_history_through_time serves it), an HKY context (hand the model over as an eigen
+ * model).  PML_ERR_INVALID: no marginal pass, k < 2.  PML_ERR_UNSUPPORTED: k > 256, M k^2 > PML_HIST_TIME_MAX_CELLS.
+ * PML_ERR_INVALID: what the plan refuses (M < 1, boundaries that are not strictly ascending, a child earlier than its parent, a
+ * value that is not finite), then a column whose sf is not finite and positive or whose d is not finite (the message names the
+ * column; a sub-range call serves the others).  A refused call launches nothing and leaves the context and the results of the
+ * marginal pass as they were.
+ * Scratch, per column and in doubles, with N nodes, S segments (N - roots + one per boundary a branch crosses), ks = k padded:
+ * 3 N ks + N for the branches' vectors, 3 S ks + S for the segments', k^2 per piece of 512 segments -- at least one per non-empty
+ * bin, so at most (S / 512 + M) k^2 --, 2 M k^2 for W_m and its first product, and k per 512 flagged segments: O(N k) + O(S k) +
+ * O((S / 512 + M) k^2).  It grows linearly with M through S and through the three M k^2 terms, which the bound on M k^2 holds
+ * to 384 MiB per column.
+ * No atomics: the segments are sorted by (bin, caller's id) and summed in pieces of 512 (tiles of 16 within a piece for the
+ * lineages) that never straddle two bins, so the bits of every output do not depend on launch geometry, on which other columns
+ * are in the call, on the column a character sits in, on which outputs are asked for or on how often it is called -- and a bin's
+ * rows of times_out and jumps_out do not depend on the other bins.  They do follow the schedule switches, which change the bits of
+ * the eigen sweeps' posteriors.
+ */
+int pml_history_through_time_eigen(pml_ctx* ctx, int32_t col_begin, int32_t col_end, const double* node_time,
+                                   const double* boundaries, int32_t M, double* times_out, double* jumps_out, double* lineages_out);
+
+/*
  * Maximum parsimony of n_cols characters of k states (k <= 512) on the uploaded forest: the bottom-up pass
  * (pastml/parsimony.py:92-122) and, per bit of methods, ACCTRAN (:125-158), DOWNPASS (:161-210) and DELTRAN (:213-242, on
  * the DOWNPASS sets), each with the number of state changes its sets need (:360-380, summed over the trees) and the number

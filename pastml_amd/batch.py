@@ -453,6 +453,21 @@ class CharacterBatch(object):
             self.unalter(altered)
         return self.resident_loglik, times, jumps_out, lineages_out
 
+    def history_through_time_eigen(self, models, node_times, boundaries, jumps=True, lineages=True):
+        """
+        history_through_time for characters under eigen models (``pml_history_through_time_eigen``): the marginal pass with the
+        masks altered for the characters with tau == 0, left resident on the device, the pass over it, then the masks restored as
+        ``bottom_up`` restores them.  Returns (ln L [m], times [m, M, k], jumps [m, M, k, k] or None, lineages [m, M + 1, k] or
+        None) as Engine.history_through_time_eigen describes them.
+        """
+        altered = self.marginal_pass_resident(models)
+        try:
+            times, jumps_out, lineages_out = self.engine.history_through_time_eigen(node_times, boundaries, jumps=jumps,
+                                                                                    lineages=lineages)
+        finally:
+            self.unalter(altered)
+        return self.resident_loglik, times, jumps_out, lineages_out
+
     def joint_states(self):
         """Joint state of every node after a joint sweep (ml.py:598-622): int64 [m, N]."""
         return self.engine.joint_backtrace().astype(np.int64)

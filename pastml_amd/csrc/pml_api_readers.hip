@@ -127,6 +127,36 @@ static int history_outputs(pml_ctx* ctx, decltype(launch_history)* launch, int c
     return mem.finish();
 }
 
+// What the two histories of the eigen-decomposed models refuse, each in its place.  eigen_kind: an F81 context (f81_entry serves
+// it), an HKY context; eigen_states: fewer than 2 or more than 256 states; eigen_columns: a column of [cb, ce) whose scaling factor
+// is not finite and positive or whose eigenvalues are not finite.
+static int eigen_kind(const pml_ctx* ctx, const char* entry, const char* f81_entry) {
+    if (ctx->kind == PML_MODEL_F81)
+        return fail(PML_ERR_UNSUPPORTED, "%s is for the eigen-decomposed models: this context's model kind is F81 (F81, JC, EFT), "
+                    "which %s serves", entry, f81_entry);
+    if (ctx->kind == PML_MODEL_HKY)
+        return fail(PML_ERR_UNSUPPORTED, "%s is for the eigen-decomposed models: this context's model kind is HKY; hand the model "
+                    "over as an eigen model (pml_model_set_eigen with the d, A, Ainv of its rate matrix)", entry);
+    return PML_OK;
+}
+static int eigen_states(const pml_ctx* ctx, const char* entry) {
+    if (ctx->k < 2) return fail(PML_ERR_INVALID, "%s: k = %d, a character of one state has no history", entry, ctx->k);
+    if (ctx->k > 256) return fail(PML_ERR_UNSUPPORTED, "%s: k = %d, the matrix models hold at most 256 states", entry, ctx->k);
+    return PML_OK;
+}
+static int eigen_columns(const pml_ctx* ctx, const char* entry, int cb, int ce) {
+    const size_t k = ctx->k;
+    const double* sf = ctx->h_params + ctx->cols.params.sf;
+    for (int c = cb; c < ce; ++c) {
+        if (!std::isfinite(sf[c]) || !(sf[c] > 0.0))
+            return fail(PML_ERR_INVALID, "%s: column %d has a scaling factor that is not finite and positive", entry, c);
+        for (size_t m = 0; m < k; ++m)
+            if (ctx->h_eig_d.size() != (size_t)ctx->C * k || !std::isfinite(ctx->h_eig_d[(size_t)c * k + m]))
+                return fail(PML_ERR_INVALID, "%s: column %d has an eigenvalue that is not finite", entry, c);
+    }
+    return PML_OK;
+}
+
 }   // namespace
 
 // altered (caller's ids, or null): see counts_level_kernel.  result_out: the k x k sums of the draws (not divided by
@@ -242,24 +272,10 @@ int pml_expected_history_eigen(pml_ctx* ctx, int32_t col_begin, int32_t col_end,
     const char* entry = r.entry;
     PML_TRY(r.columns());
     if (!times_out) return fail(PML_ERR_INVALID, "%s: times_out is NULL", entry);
-    if (ctx->kind == PML_MODEL_F81)
-        return fail(PML_ERR_UNSUPPORTED, "%s is for the eigen-decomposed models: this context's model kind is F81 (F81, JC, EFT), "
-                    "which pml_expected_history serves", entry);
-    if (ctx->kind == PML_MODEL_HKY)
-        return fail(PML_ERR_UNSUPPORTED, "%s is for the eigen-decomposed models: this context's model kind is HKY; hand the model "
-                    "over as an eigen model (pml_model_set_eigen with the d, A, Ainv of its rate matrix)", entry);
+    PML_TRY(eigen_kind(ctx, entry, "pml_expected_history"));
     PML_TRY(r.pass());
-    if (ctx->k < 2) return fail(PML_ERR_INVALID, "%s: k = %d, a character of one state has no history", entry, ctx->k);
-    if (ctx->k > 256) return fail(PML_ERR_UNSUPPORTED, "%s: k = %d, the matrix models hold at most 256 states", entry, ctx->k);
-    const size_t k = ctx->k;
-    const double* sf = ctx->h_params + ctx->cols.params.sf;
-    for (int c = col_begin; c < col_end; ++c) {
-        if (!std::isfinite(sf[c]) || !(sf[c] > 0.0))
-            return fail(PML_ERR_INVALID, "%s: column %d has a scaling factor that is not finite and positive", entry, c);
-        for (size_t m = 0; m < k; ++m)
-            if (ctx->h_eig_d.size() != (size_t)ctx->C * k || !std::isfinite(ctx->h_eig_d[(size_t)c * k + m]))
-                return fail(PML_ERR_INVALID, "%s: column %d has an eigenvalue that is not finite", entry, c);
-    }
+    PML_TRY(eigen_states(ctx, entry));
+    PML_TRY(eigen_columns(ctx, entry, col_begin, col_end));
     PML_TRY(r.rows());
     return history_outputs(ctx, launch_history_eigen, col_begin, col_end, times_out, jumps_out, branch_jumps_out);
 }
@@ -286,6 +302,33 @@ int pml_history_through_time(pml_ctx* ctx, int32_t col_begin, int32_t col_end, c
     PML_TRY(mem.out(&d_jumps, jumps_out, cols * bins * k * k));
     PML_TRY(mem.out(&d_lineages, lineages_out, cols * (bins + 1) * k));
     PML_TRY(launch_history_time(ctx, mem, col_begin, col_end, plan, pieces, jpieces, d_times, d_jumps, d_lineages));
+    return mem.finish();
+}
+
+// The same per time interval, with the lineages at every boundary (pml_launch_history_time_eigen.hip): pml_history_through_time
+// for the eigen-decomposed models.  The plan and what is derived from it are declared before the scope, whose wait ends the copies
+// that read them.
+int pml_history_through_time_eigen(pml_ctx* ctx, int32_t col_begin, int32_t col_end, const double* node_time, const double* boundaries,
+                                   int32_t M, double* times_out, double* jumps_out, double* lineages_out) {
+    const Reader r = {ctx, "pml_history_through_time_eigen", col_begin, col_end, nullptr, 0, true, false};
+    const char* entry = r.entry;
+    PML_TRY(r.columns());
+    if (!times_out || !node_time || !boundaries) return fail(PML_ERR_INVALID, "%s: node_time, boundaries or times_out is NULL", entry);
+    PML_TRY(eigen_kind(ctx, entry, "pml_history_through_time"));
+    PML_TRY(r.pass());
+    PML_TRY(eigen_states(ctx, entry));
+    HistoryTimeEigenPlan host;
+    PML_TRY(plan_time_segments(ctx, entry, "the sums of the bins", node_time, boundaries, M, host.plan));
+    PML_TRY(eigen_columns(ctx, entry, col_begin, col_end));
+    history_time_eigen_plan(host);
+    PML_TRY(r.rows());
+    const size_t k = ctx->k, cols = (size_t)(col_end - col_begin), bins = (size_t)M;
+    CallScope mem(ctx->stream, false);
+    double *d_times, *d_jumps, *d_lineages;
+    PML_TRY(mem.out(&d_times, times_out, cols * bins * k));
+    PML_TRY(mem.out(&d_jumps, jumps_out, cols * bins * k * k));
+    PML_TRY(mem.out(&d_lineages, lineages_out, cols * (bins + 1) * k));
+    PML_TRY(launch_history_time_eigen(ctx, mem, col_begin, col_end, host, d_times, d_jumps, d_lineages));
     return mem.finish();
 }
 

@@ -89,6 +89,51 @@ __device__ __forceinline__ double heig_Phi(double t, double dc, double dd, doubl
     return (Ec - Ed) / diff;   // (never 0 / 0: equal eigenvalues take the series)
 }
 
+// What a thread of a tile of 16 vectors owns, and the product of the model's matrix with the tile (heig_basis_kernel below has the
+// layout).  heig_owned: state s and vector b of the idx-th value of this thread; false beyond the tiles.
+template <bool MFMA>
+__device__ __forceinline__ bool heig_owned(int idx, int kp, int& s, int& b) {
+    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    if (MFMA) {
+        const int ta = wave + 4 * (idx >> 2);
+        s = 16 * ta + (lane >> 4) + 4 * (idx & 3);
+        b = lane & 15;
+        return 16 * ta < kp;
+    }
+    s = threadIdx.x >> 4;
+    b = threadIdx.x & 15;
+    return true;
+}
+// res = M X (TR: M^T X) for the values this thread owns; X[b][s] in LDS with the row stride kp + 1
+template <bool MFMA>
+__device__ __forceinline__ void heig_product(const double* M, bool TR, const double* X, int k, double* res) {
+    const int kp = (k + 15) & ~15, LD = kp + 1;
+    if (MFMA) {
+        const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63, lo = lane & 15, hi = lane >> 4;
+        const int T = kp >> 4;
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+            const int ta = wave + 4 * q;
+            pml_v4f64 acc = pml_v4f64{0.0, 0.0, 0.0, 0.0};
+            if (ta < T) {   // (uniform over the wavefront)
+                const int row = 16 * ta + lo, rc = min(row, k - 1);
+                for (int s4 = 0; s4 < kp; s4 += 4) {
+                    const int c = s4 + hi, cc = min(c, k - 1);
+                    const double m = TR ? M[(size_t)cc * k + rc] : M[(size_t)rc * k + cc];
+                    acc = __builtin_amdgcn_mfma_f64_16x16x4f64((row < k && c < k) ? m : 0.0, X[lo * LD + c], acc, 0, 0, 0);
+                }
+            }
+#pragma unroll
+            for (int reg = 0; reg < 4; ++reg) res[4 * q + reg] = acc[reg];
+        }
+    } else {
+        const int s = min((int)(threadIdx.x >> 4), k - 1), b = threadIdx.x & 15;
+        double sum = 0.0;
+        for (int c = 0; c < k; ++c) sum = fma(TR ? M[(size_t)c * k + s] : M[(size_t)s * k + c], X[b * LD + c], sum);
+        res[0] = sum;
+    }
+}
+
 // The changes of basis of 16 branches.  grid (ceil(N / 16), column), 256 threads, dynamic LDS: 16 (kp + 1) + 16 doubles, kp = k
 // rounded up to 16.  X[b][s], row stride kp + 1 (odd: the 16 branches of an MFMA operand fall into different banks).
 // MFMA: a wavefront owns the row tiles ta = wave, wave + 4, ... of the result (at most four up to 256 states); per step of four
@@ -101,52 +146,14 @@ __global__ void __launch_bounds__(256) heig_basis_kernel(PmlHeigArgs A) {
     const int k = A.k, ks = A.ks, kp = (k + 15) & ~15, LD = kp + 1;
     double* X = heig_lds;
     double* tb = heig_lds + 16 * LD;   // t' of the tile's branches; < 0: not a branch (a root, beyond N)
-    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63, lo = lane & 15, hi = lane >> 4;
     const int col = A.col0 + blockIdx.y;
     const size_t colN = (size_t)col * A.N;
     const double* ev = A.ev + (size_t)col * k;
     const double* Am = A.A + (size_t)col * k * k;
     const double* Ai = A.Ainv + (size_t)col * k * k;
     const int i0 = blockIdx.x * 16;
-
-    // state and branch of the idx-th value this thread owns; false beyond the tiles
-    auto owned = [&](int idx, int& s, int& b) -> bool {
-        if (MFMA) {
-            const int ta = wave + 4 * (idx >> 2);
-            s = 16 * ta + hi + 4 * (idx & 3);
-            b = lo;
-            return 16 * ta < kp;
-        }
-        s = threadIdx.x >> 4;
-        b = threadIdx.x & 15;
-        return true;
-    };
-    // res = M X (TR: M^T X) for the values this thread owns
-    auto product = [&](const double* M, bool TR, double* res) {
-        if (MFMA) {
-            const int T = kp >> 4;
-#pragma unroll
-            for (int q = 0; q < 4; ++q) {
-                const int ta = wave + 4 * q;
-                pml_v4f64 acc = pml_v4f64{0.0, 0.0, 0.0, 0.0};
-                if (ta < T) {   // (uniform over the wavefront)
-                    const int row = 16 * ta + lo, rc = min(row, k - 1);
-                    for (int s4 = 0; s4 < kp; s4 += 4) {
-                        const int c = s4 + hi, cc = min(c, k - 1);
-                        const double m = TR ? M[(size_t)cc * k + rc] : M[(size_t)rc * k + cc];
-                        acc = __builtin_amdgcn_mfma_f64_16x16x4f64((row < k && c < k) ? m : 0.0, X[lo * LD + c], acc, 0, 0, 0);
-                    }
-                }
-#pragma unroll
-                for (int reg = 0; reg < 4; ++reg) res[4 * q + reg] = acc[reg];
-            }
-        } else {
-            const int s = min((int)(threadIdx.x >> 4), k - 1), b = threadIdx.x & 15;
-            double sum = 0.0;
-            for (int c = 0; c < k; ++c) sum = fma(TR ? M[(size_t)c * k + s] : M[(size_t)s * k + c], X[b * LD + c], sum);
-            res[0] = sum;
-        }
-    };
+    auto owned = [&](int idx, int& s, int& b) -> bool { return heig_owned<MFMA>(idx, kp, s, b); };
+    auto product = [&](const double* M, bool TR, double* res) { heig_product<MFMA>(M, TR, X, k, res); };
 
     // X = V; t' of the branches
     for (int e = threadIdx.x; e < 16 * kp; e += 256) {

@@ -219,6 +219,8 @@ PML_INTERNAL int launch_gradient(pml_ctx* ctx, CallScope& mem, int cb, int ce, d
 PML_INTERNAL int launch_history(pml_ctx* ctx, CallScope& mem, int cb, int ce, double* d_times, double* d_jumps, double* d_branch);
 // ---- pml_launch_history_eigen.hip: the same for the eigen-decomposed models, 2 <= k <= 256 (pml_expected_history_eigen); the
 //      same device arrays; queued only: the staged vectors and the partials go into the caller's scope, which waits
+//      heig_rows: the values of c a lane of the pair sum keeps in registers at k states
+PML_INTERNAL int heig_rows(int k);
 PML_INTERNAL int launch_history_eigen(pml_ctx* ctx, CallScope& mem, int cb, int ce, double* d_times, double* d_jumps, double* d_branch);
 // ---- pml_launch_history_sample.hip: histories of column col drawn on the scenarios d_states [N][rs] that launch_scenarios left
 //      on the device (pml_sample_histories); device arrays d_times [n_rep][k], d_jumps [n_rep][k][k] (zeroed) or null, d_branch
@@ -235,6 +237,16 @@ PML_INTERNAL int history_time_piece(int k);
 PML_INTERNAL int history_time_jump_piece(int k);
 PML_INTERNAL int launch_history_time(pml_ctx* ctx, CallScope& mem, int cb, int ce, const PmlTimeSegments& plan, const PmlTimePieces& pieces,
                                      const PmlTimePieces& jpieces, double* d_times, double* d_jumps, double* d_lineages);
+// ---- pml_launch_history_time_eigen.hip: launch_history_time for the eigen-decomposed models, 2 <= k <= 256
+//      (pml_history_through_time_eigen).  host: the caller's -- plan filled in, the rest derived from it by
+//      history_time_eigen_plan --, alive until the caller's scope has waited.  The same device arrays; queued only
+struct HistoryTimeEigenPlan {
+    PmlTimeSegments plan, flagged;   // all segments; those that add to the lineages of a boundary, as a plan of their own
+    PmlTimePieces pieces, lpieces;   // of plan without the pseudo-bin; of flagged with it
+};
+PML_INTERNAL void history_time_eigen_plan(HistoryTimeEigenPlan& host);
+PML_INTERNAL int launch_history_time_eigen(pml_ctx* ctx, CallScope& mem, int cb, int ce, const HistoryTimeEigenPlan& host,
+                                           double* d_times, double* d_jumps, double* d_lineages);
 // ---- pml_launch_history_time_sample.hip: the histories of launch_history_sample cut at the boundaries of time bins
 //      (pml_sample_histories_through_time), launch_scenarios into d_states [N][rs] included (d_fallback: its counter, zeroed).  host: the caller's -- plan, ends and pieces (cut by history_time_sample_piece(N), with
 //      the pseudo-bin if the lineages are asked for) filled in, the tables the launcher derives from them left to it --, alive until

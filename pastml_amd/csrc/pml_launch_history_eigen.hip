@@ -8,7 +8,7 @@
 // values of c a lane of the pair sum keeps in registers: the smallest band that covers k up to 32; two bands of 32 up to 64 states
 // (168 registers and three wavefronts per SIMD where one band of 64 takes 256 and runs alone); beyond, bands of 64, which halve
 // the number of tiles that read a branch's staged vectors again.  A pair's sum does not depend on the band it falls into.
-static int heig_rows(int k) { return k <= 4 ? 4 : (k <= 16 ? 16 : (k <= 64 ? 32 : 64)); }
+int heig_rows(int k) { return k <= 4 ? 4 : (k <= 16 ? 16 : (k <= 64 ? 32 : 64)); }
 
 // d_times [cols][k]; d_jumps [cols][k][k] or null; d_branch [cols][N] (caller's numbering) or null.  Queued only: the staged
 // vectors and the partials live in the caller's scope, which makes the call's one wait.

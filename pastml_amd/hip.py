@@ -115,6 +115,8 @@ SIGNATURES = {
     'pml_expected_history_eigen': [_ctx_p, ctypes.c_int32, ctypes.c_int32, _c_double_p, _c_double_p, _c_double_p],
     'pml_history_through_time': [_ctx_p, ctypes.c_int32, ctypes.c_int32, _c_double_p, _c_double_p, ctypes.c_int32, _c_double_p,
                                  _c_double_p, _c_double_p],
+    'pml_history_through_time_eigen': [_ctx_p, ctypes.c_int32, ctypes.c_int32, _c_double_p, _c_double_p, ctypes.c_int32, _c_double_p,
+                                       _c_double_p, _c_double_p],
     'pml_simulate_states': [_ctx_p, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_uint64, ctypes.c_void_p],
     'pml_sample_scenarios': [_ctx_p, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_uint64, ctypes.c_void_p,
                              ctypes.POINTER(ctypes.c_int64)],
@@ -914,6 +916,20 @@ class Engine(BareContext):
         [cols, M, k], jumps [cols, M, k, k] or None, lineages [cols, M + 1, k] or None -- the expected number of branches in each
         state at each boundary).  What is not asked for is not computed.
         """
+        return self._history_through_time(self._lib.pml_history_through_time, node_times, boundaries, col_begin, col_end, jumps,
+                                          lineages)
+
+    def history_through_time_eigen(self, node_times, boundaries, col_begin=0, col_end=None, jumps=True, lineages=True):
+        """
+        history_through_time for an engine of eigen-decomposed models (JTT, CUSTOM_RATES, HKY handed over as
+        HKYModel.eigen_spec()), 2 to 256 states: expected_history_eigen's integral cut at the boundaries inside every branch
+        (pml_history_through_time_eigen; include/pastml_hip.h has the sums).  The same arguments and return values; an entry that
+        rounding leaves below zero is returned as 0.
+        """
+        return self._history_through_time(self._lib.pml_history_through_time_eigen, node_times, boundaries, col_begin, col_end,
+                                          jumps, lineages)
+
+    def _history_through_time(self, entry, node_times, boundaries, col_begin, col_end, jumps, lineages):
         col_end = self.n_cols if col_end is None else col_end
         if not 0 <= col_begin < col_end <= self.n_cols:
             raise ValueError('bad column range')
@@ -928,10 +944,9 @@ class Engine(BareContext):
         times = np.empty((cols, max(M, 0), self.k), dtype=np.float64)
         jumps_out = np.empty((cols, max(M, 0), self.k, self.k), dtype=np.float64) if jumps else None
         lineages_out = np.empty((cols, max(M, 0) + 1, self.k), dtype=np.float64) if lineages else None
-        _check(self._lib.pml_history_through_time(self._ctx, col_begin, col_end, _ptr(node_times, ctypes.c_double),
-                                                  _ptr(boundaries, ctypes.c_double), M, _ptr(times, ctypes.c_double),
-                                                  None if jumps_out is None else _ptr(jumps_out, ctypes.c_double),
-                                                  None if lineages_out is None else _ptr(lineages_out, ctypes.c_double)))
+        _check(entry(self._ctx, col_begin, col_end, _ptr(node_times, ctypes.c_double), _ptr(boundaries, ctypes.c_double), M,
+                     _ptr(times, ctypes.c_double), None if jumps_out is None else _ptr(jumps_out, ctypes.c_double),
+                     None if lineages_out is None else _ptr(lineages_out, ctypes.c_double)))
         return times, jumps_out, lineages_out
 
     def simulate_states(self, n_repetitions, seed, col=0, rep_offset=0):

@@ -1002,9 +1002,34 @@ def expected_history_through_time(forest, characters, models, boundaries, root_d
         diagonals; ``lineages`` [M + 1, k], a row summing to the number of branches alive at that boundary; ``bin_length`` [M]:
         the smoothed tree length inside each bin; and ``tree_length``.
     """
+    return _history_through_time('expected_history_through_time', False, forest, characters, models, boundaries, root_dates,
+                                 node_dates, jumps)
+
+
+def expected_history_through_time_general(forest, characters, models, boundaries, root_dates=None, node_dates=None, jumps=True):
+    """
+    ``expected_history_through_time`` for every model: the counterpart of ``expected_history_general``, for characters under the
+    F81 family, the eigen models (JTT, CUSTOM_RATES) and HKY alike.
+
+    Characters are grouped by their number of states and by path; a group is one batch on the device.  F81-family characters
+    take ``expected_history_through_time``'s path (``pml_history_through_time``) and their results are its results bit for bit.
+    Eigen models take ``expected_history_general``'s eigenbasis integral cut at the boundaries inside every branch
+    (``pml_history_through_time_eigen``, HIP; include/pastml_hip.h has the sums; 2 to 256 states).  HKY runs as an eigen model,
+    built from ``HKYModel.eigen_spec()``.  The sums of the eigen path have mixed signs: an entry that rounding leaves below zero is
+    returned as 0.
+
+    The file-level front end and sharding over ranks are not covered.  Parameters and return values are
+    ``expected_history_through_time``'s.
+    """
+    return _history_through_time('expected_history_through_time_general', True, forest, characters, models, boundaries, root_dates,
+                                 node_dates, jumps)
+
+
+def _history_through_time(name, general, forest, characters, models, boundaries, root_dates, node_dates, jumps):
+    """The two front ends above: ``general`` serves every model kind, else every kind but the F81 family is refused by name."""
     from pastml_amd import sharding
     from pastml_amd.batch import CharacterBatch, LikelihoodError, annotation_words, likelihood_error
-    from pastml_amd.models import KIND_F81
+    from pastml_amd.models import KIND_F81, KIND_HKY
     from pastml_amd.tree import annotate_dates
     if isinstance(forest, TreeNode):
         forest = [forest]
@@ -1014,14 +1039,15 @@ def expected_history_through_time(forest, characters, models, boundaries, root_d
     characters, models = list(characters), list(models)
     if len(characters) != len(models):
         raise ValueError('one model per character expected')
-    for character, model in zip(characters, models):
-        if model.kernel_spec()['kind'] != KIND_F81:
+    kinds = [model.kernel_spec()['kind'] for model in models]
+    for character, model, kind in zip(characters, models, kinds):
+        if not general and kind != KIND_F81:
             raise NotImplementedError('Character {}: expected_history_through_time is for the F81 family (F81, JC, EFT), not for {} '
                                       '(PML_ERR_UNSUPPORTED).'.format(character, getattr(model, 'name', type(model).__name__)))
     world = sharding.rank_world()[1]
     if world > 1:
-        raise NotImplementedError('expected_history_through_time is not supported under a multi-process launch ({} ranks): run '
-                                  'it in a single process'.format(world))
+        raise NotImplementedError('{} is not supported under a multi-process launch ({} ranks): run it in a single '
+                                  'process'.format(name, world))
     flat = get_flat_forest(forest)
     node_times = annotate_dates(flat, root_dates, given=node_dates)
     if isinstance(boundaries, (int, np.integer)):
@@ -1032,19 +1058,22 @@ def expected_history_through_time(forest, characters, models, boundaries, root_d
     if boundaries.ndim != 1 or len(boundaries) < 2 or not np.isfinite(boundaries).all() or not (np.diff(boundaries) > 0).all():
         raise ValueError('boundaries must be two or more finite, strictly ascending numbers')
     groups = {}
-    for i, model in enumerate(models):
-        groups.setdefault(len(model.states), []).append(i)
+    for i, (model, kind) in enumerate(zip(models, kinds)):
+        groups.setdefault((len(model.states), kind == KIND_F81), []).append(i)
+        if kind == KIND_HKY:
+            models[i] = _AsEigenModel(model)
     results = [None] * len(characters)
     has_parent = flat.parent >= 0
     fractions = time_bin_fractions(flat, node_times, boundaries)
-    for k, members in groups.items():
+    for (k, f81), members in groups.items():
         group_models = [models[i] for i in members]
         with CharacterBatch(flat, k, len(members)) as batch:
             for c, i in enumerate(members):
                 batch.set_annotation(c, *annotation_words(flat, characters[i], models[i].states))
             batch.initialize_allowed_states()
+            run = batch.history_through_time if f81 else batch.history_through_time_eigen
             try:
-                lnl, times, jumps_out, lineages = batch.history_through_time(group_models, node_times, boundaries, jumps=jumps)
+                lnl, times, jumps_out, lineages = run(group_models, node_times, boundaries, jumps=jumps)
             except LikelihoodError as e:
                 raise likelihood_error(flat, e)
         for c, i in enumerate(members):
