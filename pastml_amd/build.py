@@ -2,7 +2,9 @@
 
 The library is several translation units -- pml_api.hip (contexts, tree upload, the sweeps, the C-ABI), pml_api_readers.hip (the
 C-ABI entries that read what a marginal pass left on the device), pml_schedule.cpp, pml_columns.cpp, pml_pij_window.cpp and pml_time_segments.cpp (the host-only
-planning of the tree schedules, of the column layout, of the P(t) window and of the time segments, compiled as plain C++) and one pml_launch_*.hip per kernel family -- compiled in parallel into pastml_amd/csrc/build/*.o (kept out of history and off the GPU box) and linked into one
+planning of the tree schedules, of the column layout, of the P(t) window and of the time segments, compiled as plain C++) and one pml_launch_*.hip per kernel family
+(each with its pml_kernels_*.h; what the whole-tree and the per-interval exact histories share is in pml_kernels_history_shared.h and
+pml_kernels_history_eigen_shared.h, which hold no kernel of one entry alone) -- compiled in parallel into pastml_amd/csrc/build/*.o (kept out of history and off the GPU box) and linked into one
 shared object.  An object is recompiled when the digest of what IT is compiled from changes; the library carries the digest
 over everything (pml_build_digest)."""
 import hashlib
@@ -20,7 +22,7 @@ SOURCES = ['pml_launch_f81_level.hip', 'pml_launch_f81_wide.hip', 'pml_launch_f8
            'pml_launch_matrix.hip', 'pml_launch_eigen_mfma.hip', 'pml_launch_eigen_gemm.hip', 'pml_launch_eigen_gemm_wide.hip', 'pml_launch_eigen_joint.hip', 'pml_launch_counts.hip', 'pml_launch_simulate.hip', 'pml_launch_scenarios.hip', 'pml_launch_parsimony.hip', 'pml_launch_expected.hip', 'pml_launch_gradient.hip', 'pml_launch_history.hip', 'pml_launch_history_eigen.hip', 'pml_launch_history_sample.hip', 'pml_launch_history_time.hip', 'pml_launch_history_time_eigen.hip', 'pml_launch_history_time_sample.hip', 'pml_launch_compress.hip', 'pml_launch_compress_horizontal.hip', 'pml_launch_compress_trim.hip', 'pml_launch_timeline.hip',
            'pml_schedule.cpp', 'pml_columns.cpp', 'pml_pij_window.cpp', 'pml_time_segments.cpp', 'pml_api_readers.hip', 'pml_api.hip']
 HEADERS = ['pml_device.h', 'pml_kernels_f81.h', 'pml_kernels_misc.h', 'pml_model.h', 'pml_kernels_matrix.h', 'pml_kernels_pij.h', 'pml_kernels_pij_wide.h',
-           'pml_kernels_counts.h', 'pml_philox.h', 'pml_kernels_simulate.h', 'pml_kernels_scenarios.h', 'pml_kernels_parsimony.h', 'pml_kernels_expected.h', 'pml_kernels_gradient.h', 'pml_kernels_history.h', 'pml_kernels_history_eigen.h', 'pml_kernels_history_sample.h', 'pml_kernels_history_time.h', 'pml_kernels_history_time_eigen.h', 'pml_kernels_history_time_sample.h', 'pml_kernels_compress.h', 'pml_kernels_compress_horizontal.h', 'pml_kernels_compress_trim.h', 'pml_kernels_timeline.h',
+           'pml_kernels_counts.h', 'pml_philox.h', 'pml_kernels_simulate.h', 'pml_kernels_scenarios.h', 'pml_kernels_parsimony.h', 'pml_kernels_expected.h', 'pml_kernels_gradient.h', 'pml_kernels_history_shared.h', 'pml_kernels_history.h', 'pml_kernels_history_eigen_shared.h', 'pml_kernels_history_eigen.h', 'pml_kernels_history_sample.h', 'pml_kernels_history_time.h', 'pml_kernels_history_time_eigen.h', 'pml_kernels_history_time_sample.h', 'pml_kernels_compress.h', 'pml_kernels_compress_horizontal.h', 'pml_kernels_compress_trim.h', 'pml_kernels_timeline.h',
            'pml_kernels_eigen_mfma.h', 'pml_kernels_eigen_gemm.h', 'pml_kernels_eigen_joint.h', 'pml_comm.h', 'pml_schedule.h', 'pml_columns.h', 'pml_pij_window.h', 'pml_time_segments.h', 'pml_host.h', 'pml_call_scope.h', 'pml_results.h',
            'pml_launch.h', 'pml_launch_f81_level.h',
            os.path.join('..', '..', 'include', 'pastml_hip.h')]

@@ -292,8 +292,8 @@ int pml_history_through_time(pml_ctx* ctx, int32_t col_begin, int32_t col_end, c
     PmlTimeSegments plan;
     PmlTimePieces pieces, jpieces;
     PML_TRY(plan_time_segments(ctx, r.entry, "the partials of the bins", node_time, boundaries, M, plan));
-    pieces = pml_cut_time_pieces(plan, history_time_piece(ctx->k), true);
-    if (jumps_out) jpieces = pml_cut_time_pieces(plan, history_time_jump_piece(ctx->k), false);
+    pieces = pml_cut_time_pieces(plan, history_piece(ctx->k), true);
+    if (jumps_out) jpieces = pml_cut_time_pieces(plan, history_jump_piece(ctx->k), false);
     PML_TRY(r.rows());
     const size_t k = ctx->k, cols = (size_t)(col_end - col_begin), bins = (size_t)M;
     CallScope mem(ctx->stream, false);

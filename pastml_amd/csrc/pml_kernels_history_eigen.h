@@ -15,8 +15,10 @@
 //     branch_jumps[n] = sum_cd G[c][d] X_n[c][d]                     (a root and a branch with t' = 0: exactly 0)
 // The sums have mixed signs; an entry that rounding leaves below zero is returned as 0.0.
 //
+// What the sums per time interval (pml_kernels_history_time_eigen.h) share with these -- the arguments, Phi, heig_basis_kernel and
+// its products, the tiles and the epilogue of the pair sum, the transforms of W -- is pml_kernels_history_eigen_shared.h's.
 // heig_basis_kernel: the three changes of basis r = Ainv V, m = A (E o r), l = A^T O for tiles of 16 branches -- from 16 states
-// on on the FP64 matrix cores (v_mfma_f64_16x16x4_f64, operands laid out as in history_jump_kernel: the model's matrix is the A
+// on on the FP64 matrix cores (v_mfma_f64_16x16x4_f64, operands laid out as in hist_jump_product: the model's matrix is the A
 // operand, the tile's vectors the B operand), below that on the vector units.  The matrices are read from global memory: they
 // are per column, 512 KB at most, and stay in L2; the tile's vectors go through one LDS buffer of 16 (k + 1) doubles.
 // It leaves E_n, r_n and l_n in the call's scratch: 3 ks doubles per branch and column, written once and read once per pair
@@ -40,188 +42,7 @@
 // combined are fixed.  Nothing depends on the grid, on the other columns, on the column's position or on which outputs are
 // asked for (W is formed in full either way).  The posteriors this reads are the eigen sweeps': their bits follow the schedule.
 #pragma once
-#include "pml_kernels_history.h"   // (HistSeries, pml_v4f64)
-
-#define PML_HEIG_PIECE 512
-#define PML_HEIG_SWITCH 0.5
-#define PML_HEIG_TERMS 15
-
-struct PmlHeigArgs {
-    const int* parent;              // the library's numbering, as all per-node arrays below
-    const int* n_children;
-    const int* new_of_old;          // caller's id -> library's id; null = the same
-    const double* dist;             // [N]
-    const u64* masks;               // [C][N][W]
-    const double* bu;               // [C][N][ks]   (tips: not stored, their masks as 0/1)
-    const double* post;             // [C][N][ks]
-    const double *ev, *A, *Ainv;    // [C][k], [C][k][k], [C][k][k]
-    const double *sf, *tau, *tauf;  // [C]
-    int N, k, ks, W;
-    int col0;                       // first column of the call; the grid's column index counts from it
-    int n_pieces;
-    int tc, td;                     // tiles of the pairs: tc bands of CR values of c, td bands of 64 values of d
-    double* stage;                  // [cols][N][3][ks], CALLER's numbering: E_n, r_n, l_n (l_n = 0: the branch adds nothing)
-    double* tprime;                 // [cols][N], caller's numbering: t'_n (0 for a root)
-    double* partial;                // [cols][n_pieces][k][k]
-    double* Wsum;                   // [cols][k][k]
-    double* T1;                     // [cols][k][k]: T1[s][d] = sum_c Ainv[c][s] W[c][d]
-    double* qdiag;                  // [cols][k]: Q_ii; null without branch_jumps
-    double* G;                      // [cols][k][k]; null without branch_jumps
-    double* bpart;                  // [cols][tc td][N]: a tile's share of branch_jumps; null without
-    double* times_out;              // [cols][k]
-    double* branch_out;             // [cols][N] caller's numbering, or null
-    double* jumps_out;              // [cols][k][k], or null
-};
-
-// phi(z) = expm1(z) / z for 0 <= z < PML_HEIG_SWITCH: 1 + z / 2! + ... + z^15 / 16!, every term positive
-__device__ __forceinline__ double heig_phi(double z) {
-    constexpr HistSeries T = hist_series_table();   // inv[m] = 1 / (m + 1)!
-    double s = T.inv[PML_HEIG_TERMS];
-#pragma unroll
-    for (int m = PML_HEIG_TERMS - 1; m >= 1; --m) s = fma(s, z, T.inv[m]);
-    return fma(s, z, 1.0);
-}
-
-// Phi_cd(t) from the exponentials and eigenvalues of its two ends
-__device__ __forceinline__ double heig_Phi(double t, double dc, double dd, double Ec, double Ed) {
-    const double diff = dc - dd, z = diff * t, az = fabs(z);
-    if (az < PML_HEIG_SWITCH) return t * (z >= 0.0 ? Ed : Ec) * heig_phi(az);
-    return (Ec - Ed) / diff;   // (never 0 / 0: equal eigenvalues take the series)
-}
-
-// What a thread of a tile of 16 vectors owns, and the product of the model's matrix with the tile (heig_basis_kernel below has the
-// layout).  heig_owned: state s and vector b of the idx-th value of this thread; false beyond the tiles.
-template <bool MFMA>
-__device__ __forceinline__ bool heig_owned(int idx, int kp, int& s, int& b) {
-    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-    if (MFMA) {
-        const int ta = wave + 4 * (idx >> 2);
-        s = 16 * ta + (lane >> 4) + 4 * (idx & 3);
-        b = lane & 15;
-        return 16 * ta < kp;
-    }
-    s = threadIdx.x >> 4;
-    b = threadIdx.x & 15;
-    return true;
-}
-// res = M X (TR: M^T X) for the values this thread owns; X[b][s] in LDS with the row stride kp + 1
-template <bool MFMA>
-__device__ __forceinline__ void heig_product(const double* M, bool TR, const double* X, int k, double* res) {
-    const int kp = (k + 15) & ~15, LD = kp + 1;
-    if (MFMA) {
-        const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63, lo = lane & 15, hi = lane >> 4;
-        const int T = kp >> 4;
-#pragma unroll
-        for (int q = 0; q < 4; ++q) {
-            const int ta = wave + 4 * q;
-            pml_v4f64 acc = pml_v4f64{0.0, 0.0, 0.0, 0.0};
-            if (ta < T) {   // (uniform over the wavefront)
-                const int row = 16 * ta + lo, rc = min(row, k - 1);
-                for (int s4 = 0; s4 < kp; s4 += 4) {
-                    const int c = s4 + hi, cc = min(c, k - 1);
-                    const double m = TR ? M[(size_t)cc * k + rc] : M[(size_t)rc * k + cc];
-                    acc = __builtin_amdgcn_mfma_f64_16x16x4f64((row < k && c < k) ? m : 0.0, X[lo * LD + c], acc, 0, 0, 0);
-                }
-            }
-#pragma unroll
-            for (int reg = 0; reg < 4; ++reg) res[4 * q + reg] = acc[reg];
-        }
-    } else {
-        const int s = min((int)(threadIdx.x >> 4), k - 1), b = threadIdx.x & 15;
-        double sum = 0.0;
-        for (int c = 0; c < k; ++c) sum = fma(TR ? M[(size_t)c * k + s] : M[(size_t)s * k + c], X[b * LD + c], sum);
-        res[0] = sum;
-    }
-}
-
-// The changes of basis of 16 branches.  grid (ceil(N / 16), column), 256 threads, dynamic LDS: 16 (kp + 1) + 16 doubles, kp = k
-// rounded up to 16.  X[b][s], row stride kp + 1 (odd: the 16 branches of an MFMA operand fall into different banks).
-// MFMA: a wavefront owns the row tiles ta = wave, wave + 4, ... of the result (at most four up to 256 states); per step of four
-// states the A operand is M[16 ta + lo][4 s + hi] (TR: M[4 s + hi][16 ta + lo]), the B operand X[lo][4 s + hi]; D: branch = lane
-// & 15, state = 16 ta + (lane >> 4) + 4 reg.  Otherwise (k < 16) thread t owns state t >> 4 of branch t & 15.
-template <bool MFMA>
-__global__ void __launch_bounds__(256) heig_basis_kernel(PmlHeigArgs A) {
-    extern __shared__ double heig_lds[];
-    constexpr int NR = MFMA ? 16 : 1;
-    const int k = A.k, ks = A.ks, kp = (k + 15) & ~15, LD = kp + 1;
-    double* X = heig_lds;
-    double* tb = heig_lds + 16 * LD;   // t' of the tile's branches; < 0: not a branch (a root, beyond N)
-    const int col = A.col0 + blockIdx.y;
-    const size_t colN = (size_t)col * A.N;
-    const double* ev = A.ev + (size_t)col * k;
-    const double* Am = A.A + (size_t)col * k * k;
-    const double* Ai = A.Ainv + (size_t)col * k * k;
-    const int i0 = blockIdx.x * 16;
-    auto owned = [&](int idx, int& s, int& b) -> bool { return heig_owned<MFMA>(idx, kp, s, b); };
-    auto product = [&](const double* M, bool TR, double* res) { heig_product<MFMA>(M, TR, X, k, res); };
-
-    // X = V; t' of the branches
-    for (int e = threadIdx.x; e < 16 * kp; e += 256) {
-        const int b = e / kp, s = e % kp;
-        const int i = min(i0 + b, A.N - 1);
-        const int n = A.new_of_old ? A.new_of_old[i] : i;
-        const size_t row = colN + n;
-        const int ss = min(s, k - 1);
-        const u64 m = A.masks[row * A.W + (ss >> 6)];
-        const double x = A.bu[row * ks + ss];
-        const bool tip = A.n_children[n] == 0;
-        const bool allowed = s < k && ((m >> (ss & 63)) & 1ull);
-        X[b * LD + s] = allowed ? (tip ? 1.0 : x) : 0.0;
-    }
-    if (threadIdx.x < 16) {
-        const int i = min(i0 + (int)threadIdx.x, A.N - 1);
-        const int n = A.new_of_old ? A.new_of_old[i] : i;
-        const bool branch = i0 + (int)threadIdx.x < A.N && A.parent[n] >= 0;
-        const double t = (A.dist[n] + A.tau[col]) * (A.tauf[col] * A.sf[col]);
-        tb[threadIdx.x] = branch ? t : -1.0;
-        if (i0 + (int)threadIdx.x < A.N) A.tprime[(size_t)blockIdx.y * A.N + i] = branch ? t : 0.0;
-    }
-    __syncthreads();
-
-    double res[NR];
-    // r = Ainv V; E; X <- E o r
-    product(Ai, false, res);
-    __syncthreads();
-#pragma unroll
-    for (int idx = 0; idx < NR; ++idx) {
-        int s, b;
-        if (!owned(idx, s, b)) continue;
-        const double t = tb[b];
-        const bool live = s < k && i0 + b < A.N;
-        const double E = exp(ev[min(s, k - 1)] * fmax(t, 0.0));
-        if (live) {
-            double* st = A.stage + ((size_t)blockIdx.y * A.N + (i0 + b)) * 3 * ks;
-            st[s] = E;
-            st[ks + s] = res[idx];
-        }
-        if (s < kp) X[b * LD + s] = s < k ? E * res[idx] : 0.0;
-    }
-    __syncthreads();
-    // m = A (E o r); X <- o = q_p / m
-    product(Am, false, res);
-    __syncthreads();
-#pragma unroll
-    for (int idx = 0; idx < NR; ++idx) {
-        int s, b;
-        if (!owned(idx, s, b)) continue;
-        const int i = min(i0 + b, A.N - 1);
-        const int n = A.new_of_old ? A.new_of_old[i] : i;
-        const int pp = max(A.parent[n], 0);
-        const double q = A.post[(colN + pp) * ks + min(s, k - 1)];
-        const double m = res[idx];
-        const bool on = s < k && tb[b] > 0.0 && q > 0.0 && m > 0.0;
-        if (s < kp) X[b * LD + s] = on ? q / m : 0.0;
-    }
-    __syncthreads();
-    // l = A^T o
-    product(Am, true, res);
-#pragma unroll
-    for (int idx = 0; idx < NR; ++idx) {
-        int s, b;
-        if (!owned(idx, s, b)) continue;
-        if (s < k && i0 + b < A.N) A.stage[((size_t)blockIdx.y * A.N + (i0 + b)) * 3 * ks + 2 * ks + s] = tb[b] > 0.0 ? res[idx] : 0.0;
-    }
-}
+#include "pml_kernels_history_eigen_shared.h"
 
 // Q_ii.  grid (column), thread i
 static __global__ void __launch_bounds__(256) heig_qdiag_kernel(PmlHeigArgs A) {
@@ -247,23 +68,18 @@ static __global__ void __launch_bounds__(256) heig_g_kernel(PmlHeigArgs A) {
     A.G[(size_t)blockIdx.y * k * k + idx] = (c == d ? A.ev[col * k + c] : 0.0) - s;
 }
 
-// The pair sum of one piece and one tile of pairs.  grid (piece, tile, column); tile = band of c (CR values) x band of d (64).
+// The pair sum of one piece of ids and one tile of pairs (heig_tile), with a branch's sum over the tile's pairs for
+// branch_jumps, which stays inside one wavefront.  grid (piece, tile, column)
 template <int CR>
 __global__ void __launch_bounds__(256) heig_pair_kernel(PmlHeigArgs A) {
     __shared__ double buf[CR * 64];   // G's tile in the walk, the wavefronts' sums afterwards
     const int k = A.k, ks = A.ks;
-    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), lane = threadIdx.x & 63;
-    const int tile = blockIdx.y, c0 = (tile / A.td) * CR, d = (tile % A.td) * 64 + lane;
-    const bool d_in = d < k;
-    const int dcl = min(d, k - 1);
-    const int col = A.col0 + blockIdx.z;
-    const double* ev = A.ev + (size_t)col * k;
-    const double ev_d = ev[dcl];
+    const HeigTile t = heig_tile<CR>(A);
     const bool with_branch = A.bpart != nullptr;
     if (with_branch) {
         const double* G = A.G + (size_t)blockIdx.z * k * k;
         for (int e = threadIdx.x; e < CR * 64; e += 256) {
-            const int c = c0 + (e >> 6), dd = (tile % A.td) * 64 + (e & 63);
+            const int c = t.c0 + (e >> 6), dd = t.d0 + (e & 63);
             buf[e] = (c < k && dd < k) ? G[(size_t)min(c, k - 1) * k + min(dd, k - 1)] : 0.0;
         }
         __syncthreads();
@@ -272,92 +88,50 @@ __global__ void __launch_bounds__(256) heig_pair_kernel(PmlHeigArgs A) {
 #pragma unroll
     for (int j = 0; j < CR; ++j) acc[j] = 0.0;
     const int i0 = blockIdx.x * PML_HEIG_PIECE, i1 = min(A.N, i0 + PML_HEIG_PIECE);
-    for (int i = i0 + wave; i < i1; i += 4) {
+    for (int i = i0 + t.wave; i < i1; i += 4) {
         const double* st = A.stage + ((size_t)blockIdx.z * A.N + i) * 3 * ks;
-        const double t = A.tprime[(size_t)blockIdx.z * A.N + i];
-        const double E_d = st[dcl];
-        const double r_d = d_in ? st[ks + dcl] : 0.0;
+        const double tp = A.tprime[(size_t)blockIdx.z * A.N + i];
+        const double E_d = st[t.dcl];
+        const double r_d = t.d_in ? st[ks + t.dcl] : 0.0;
         double bj = 0.0;
 #pragma unroll
         for (int j = 0; j < CR; ++j) {
-            const int c = c0 + j, cc = min(c, k - 1);   // (uniform over the wavefront)
+            const int c = t.c0 + j, cc = min(c, k - 1);   // (uniform over the wavefront)
             const double l_c = c < k ? st[2 * ks + cc] : 0.0;
-            const double x = l_c * heig_Phi(t, ev[cc], ev_d, st[cc], E_d) * r_d;
+            const double x = l_c * heig_Phi(tp, t.ev[cc], t.ev_d, st[cc], E_d) * r_d;
             acc[j] += x;
-            if (with_branch) bj = fma(buf[j * 64 + lane], x, bj);
+            if (with_branch) bj = fma(buf[j * 64 + t.lane], x, bj);
         }
         if (with_branch) {
             bj = group_sum<64>(bj);
-            if (lane == 0) A.bpart[((size_t)blockIdx.z * gridDim.y + tile) * A.N + i] = bj;
+            if (t.lane == 0) A.bpart[((size_t)blockIdx.z * gridDim.y + blockIdx.y) * A.N + i] = bj;
         }
     }
-    // the wavefronts' sums in wavefront order
-    __syncthreads();
-    for (int w = 0; w < 4; ++w) {
-        if (wave == w) {
-#pragma unroll
-            for (int j = 0; j < CR; ++j) buf[j * 64 + lane] = w == 0 ? acc[j] : buf[j * 64 + lane] + acc[j];
-        }
-        __syncthreads();
-    }
-    double* out = A.partial + ((size_t)blockIdx.z * A.n_pieces + blockIdx.x) * k * k;
-    for (int e = threadIdx.x; e < CR * 64; e += 256) {
-        const int c = c0 + (e >> 6), dd = (tile % A.td) * 64 + (e & 63);
-        if (c < k && dd < k) out[(size_t)c * k + dd] = buf[e];
-    }
+    __syncthreads();   // (G's tile has been read)
+    heig_tile_sums<CR>(t, buf, acc, k, A.partial + ((size_t)blockIdx.z * A.n_pieces + blockIdx.x) * k * k);
 }
 
-// W: the pieces' partials in piece order.  grid (k k / 256, column)
+// W: the pieces' partials in piece order.  grid (k k / 256, column), as the two kernels after it
 static __global__ void __launch_bounds__(256) heig_reduce_kernel(PmlHeigArgs A) {
-    const int k = A.k;
-    const int idx = blockIdx.x * 256 + threadIdx.x;
+    const int k = A.k, idx = blockIdx.x * 256 + threadIdx.x;
     if (idx >= k * k) return;
-    const double* part = A.partial + (size_t)blockIdx.y * A.n_pieces * k * k + idx;
-    double s = 0.0;
-    for (int j = 0; j < A.n_pieces; ++j) s += part[(size_t)j * k * k];
-    A.Wsum[(size_t)blockIdx.y * k * k + idx] = s;
+    A.Wsum[(size_t)blockIdx.y * k * k + idx] = pml_piece_sum(A.partial + (size_t)blockIdx.y * A.n_pieces * k * k + idx, (size_t)k * k, 0, A.n_pieces);
 }
 
-// T1[s][d] = sum_c Ainv[c][s] W[c][d], c ascending.  grid (k k / 256, column)
 static __global__ void __launch_bounds__(256) heig_t1_kernel(PmlHeigArgs A) {
-    const int k = A.k;
-    const int idx = blockIdx.x * 256 + threadIdx.x;
-    if (idx >= k * k) return;
-    const int s = idx / k, d = idx % k;
-    const double* Ai = A.Ainv + (size_t)(A.col0 + blockIdx.y) * k * k;
-    const double* W = A.Wsum + (size_t)blockIdx.y * k * k;
-    double sum = 0.0;
-    for (int c = 0; c < k; ++c) sum = fma(Ai[(size_t)c * k + s], W[(size_t)c * k + d], sum);
-    A.T1[(size_t)blockIdx.y * k * k + idx] = sum;
+    const int k = A.k, idx = blockIdx.x * 256 + threadIdx.x;
+    if (idx < k * k) heig_t1(A, blockIdx.y, idx, A.Wsum + (size_t)blockIdx.y * k * k, A.T1 + (size_t)blockIdx.y * k * k);
 }
 
-// times[s] = (1 / sf) sum_d T1[s][d] A[s][d], d ascending.  grid (column), thread s
-static __global__ void __launch_bounds__(256) heig_times_kernel(PmlHeigArgs A) {
-    const int k = A.k, s = threadIdx.x;
-    if (s >= k) return;
-    const size_t col = A.col0 + blockIdx.x;
-    const double* Am = A.A + col * k * k + (size_t)s * k;
-    const double* T1 = A.T1 + (size_t)blockIdx.x * k * k + (size_t)s * k;
-    double sum = 0.0;
-    for (int d = 0; d < k; ++d) sum = fma(T1[d], Am[d], sum);
-    sum /= A.sf[col];
-    A.times_out[(size_t)blockIdx.x * k + s] = sum > 0.0 ? sum : 0.0;
-}
-
-// jumps[i][j] = Q_ij sum_d T1[i][d] A[j][d], Q_ij = sum_m A[i][m] d_m Ainv[m][j]; the diagonal 0.  grid (k k / 256, column)
 static __global__ void __launch_bounds__(256) heig_jumps_kernel(PmlHeigArgs A) {
+    const int k = A.k, idx = blockIdx.x * 256 + threadIdx.x;
+    if (idx < k * k) heig_jumps(A, blockIdx.y, idx, A.T1 + (size_t)blockIdx.y * k * k, A.jumps_out + (size_t)blockIdx.y * k * k);
+}
+
+// grid (column), thread s
+static __global__ void __launch_bounds__(256) heig_times_kernel(PmlHeigArgs A) {
     const int k = A.k;
-    const int idx = blockIdx.x * 256 + threadIdx.x;
-    if (idx >= k * k) return;
-    const int i = idx / k, j = idx % k;
-    const size_t col = A.col0 + blockIdx.y;
-    const double *ev = A.ev + col * k, *Am = A.A + col * k * k, *Ai = A.Ainv + col * k * k;
-    const double* T1 = A.T1 + (size_t)blockIdx.y * k * k + (size_t)i * k;
-    double sum = 0.0, q = 0.0;
-    for (int d = 0; d < k; ++d) sum = fma(T1[d], Am[(size_t)j * k + d], sum);
-    for (int m = 0; m < k; ++m) q = fma(Am[(size_t)i * k + m] * ev[m], Ai[(size_t)m * k + j], q);
-    const double v = q * sum;
-    A.jumps_out[(size_t)blockIdx.y * k * k + idx] = (i != j && v > 0.0) ? v : 0.0;
+    if ((int)threadIdx.x < k) heig_times(A, blockIdx.x, threadIdx.x, A.T1 + (size_t)blockIdx.x * k * k, A.times_out + (size_t)blockIdx.x * k);
 }
 
 // branch_jumps[i] = the tiles' shares in tile order.  grid (N / 256, column)
@@ -365,8 +139,6 @@ static __global__ void __launch_bounds__(256) heig_branch_kernel(PmlHeigArgs A) 
     const int i = blockIdx.x * 256 + threadIdx.x;
     if (i >= A.N) return;
     const int tiles = A.tc * A.td;
-    const double* part = A.bpart + (size_t)blockIdx.y * tiles * A.N + i;
-    double s = 0.0;
-    for (int t = 0; t < tiles; ++t) s += part[(size_t)t * A.N];
+    const double s = pml_piece_sum(A.bpart + (size_t)blockIdx.y * tiles * A.N + i, A.N, 0, tiles);
     A.branch_out[(size_t)blockIdx.y * A.N + i] = s > 0.0 ? s : 0.0;
 }

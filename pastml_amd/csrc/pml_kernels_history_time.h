@@ -15,17 +15,18 @@
 //     lineages[m][j] += (1-A)(1-B) o_j v_j + (1-A) B o_j S + A (1-B) pi_j O v_j + A B pi_j O S            (sums to 1 over j)
 // Every term is non-negative.  The zero-width point segments of the last boundary (pseudo-bin M) add lineages only: w = 0.
 //
-// history_time_segment_kernel has history_branch_kernel's lane shapes and streams v_n and q_p once per segment; it leaves the
-// pieces' partial times, sum x a and lineages, and stages S_n, x O C1b and x Cee per SEGMENT (C1b and Cee differ between the
-// segments of one branch).  history_time_jump_kernel forms sum (x b) (x) v on the FP64 matrix cores, tiled as
-// history_jump_kernel is; the two sum kernels add the partials in piece order per bin.
+// history_time_segment_kernel has history_branch_kernel's lane shapes and front half (hist_front) and streams v_n and q_p
+// once per segment; it leaves the pieces' partial times, sum x a and lineages, and stages S_n, x O C1b and x Cee per SEGMENT
+// (C1b and Cee differ between the segments of one branch).  history_time_jump_kernel forms sum (x b) (x) v on the FP64 matrix
+// cores (hist_jump_product); the two sum kernels add the partials in piece order per bin.  What is shared with the whole-tree
+// sums is pml_kernels_history_shared.h's; none of pml_kernels_history.h's kernels is seen here.
 //
 // Bits.  No floating-point atomics.  The plan sorts the segments by (bin, caller's id) and the pieces are cut PER BIN -- a
 // fixed number of segments that depends on k only, never across a bin's end -- so a bin's sums see the same pieces in the same
 // order whatever other bins the call has, and nothing depends on the grid, the schedule of the sweeps, the library's numbering
 // or the column.
 #pragma once
-#include "pml_kernels_history.h"   // (hist_coefficients, hist_v, group_sum, PmlHistArgs)
+#include "pml_kernels_history_shared.h"
 
 struct PmlHistTimeArgs {
     PmlHistArgs h;                  // the vectors of the marginal pass, the parameters, N, k, ks, W, col0 (hist_v reads it)
@@ -48,26 +49,18 @@ struct PmlHistTimeArgs {
     double* lineages_out;           // [cols][M + 1][k], or null
 };
 
-// The segment pass.  G lanes per segment, R states per lane (state g + G r of lane g), 64 / G segments per wavefront, four
-// wavefronts.  grid (piece, column).
+// The segment pass (the lane shapes: pml_kernels_history_shared.h).  grid (piece, column).
 template <int G, int R>
 __global__ void __launch_bounds__(256) history_time_segment_kernel(PmlHistTimeArgs T) {
-    constexpr int U = 64 / G, UNITS = 4 * U, ROW = 3 * G * R;
-    __shared__ double red[UNITS * ROW];
+    constexpr int U = 64 / G, UNITS = 4 * U;
+    __shared__ double red[UNITS * 3 * G * R];
     const PmlHistArgs& A = T.h;
-    const int k = A.k, ks = A.ks;
     const int lane = threadIdx.x & 63, g = lane % G;
     const int unit = (threadIdx.x >> 6) * U + lane / G;
-    const int col = A.col0 + blockIdx.y;
-    const size_t colN = (size_t)col * A.N;
-    const double mu = A.mu[col], tau = A.tau[col], tauf = A.tauf[col], scale = tauf * A.sf[col];
-    double pi[R], acc_t[R], acc_a[R], acc_l[R];
+    const HistColumn<R> C = hist_column<G, R>(A, A.col0 + blockIdx.y, g);
+    double acc_t[R], acc_a[R], acc_l[R];
 #pragma unroll
-    for (int r = 0; r < R; ++r) {
-        const int b = g + G * r;
-        pi[r] = b < k ? A.pi[(size_t)col * ks + b] : 0.0;
-        acc_t[r] = acc_a[r] = acc_l[r] = 0.0;
-    }
+    for (int r = 0; r < R; ++r) acc_t[r] = acc_a[r] = acc_l[r] = 0.0;
     const int i0 = T.piece_off[blockIdx.x], i1 = T.piece_off[blockIdx.x + 1];   // (a piece holds one segment at least)
     for (int base = i0; base < i1; base += UNITS) {   // (the same trip count in every unit: the lane exchanges below are convergent)
         // (units beyond the piece read its last segment and are zeroed by the selects below: no load waits for a test)
@@ -78,37 +71,11 @@ __global__ void __launch_bounds__(256) history_time_segment_kernel(PmlHistTimeAr
         const double s1 = T.seg_frac[4 * (size_t)i], w = T.seg_frac[4 * (size_t)i + 1], rr = T.seg_frac[4 * (size_t)i + 2],
                      u = T.seg_frac[4 * (size_t)i + 3];
         const int n = A.new_of_old ? A.new_of_old[id] : id;
-        const int pp = max(A.parent[n], 0);   // (the plan holds no root)
-        const bool tip = A.n_children[n] == 0;
-        const size_t row = colN + n;
-        const double e_stored = A.E[row];
-        const double d = A.dist[n] + tau;
-        const double x = inside ? mu * (d * scale) : 0.0;   // (the transform of f81_prep_kernel)
-        const double len = inside ? d * tauf : 0.0;
-        double v[R], q[R];
-#pragma unroll
-        for (int r = 0; r < R; ++r) {
-            const int b = g + G * r, bb = min(b, k - 1);
-            const u64 m = A.masks[row * A.W + (bb >> 6)];
-            const double x_bu = A.bu[row * ks + bb];
-            const double y = A.post[(colN + pp) * ks + bb];
-            const bool allowed = b < k && ((m >> (bb & 63)) & 1ull);
-            v[r] = allowed ? (tip ? 1.0 : x_bu) : 0.0;
-            q[r] = (inside && b < k) ? y : 0.0;
-        }
-        double s = 0.0;
-#pragma unroll
-        for (int r = 0; r < R; ++r) s += pi[r] * v[r];
-        s = group_sum<G>(s);
-        const double rest = (1.0 - e_stored) * s;
-        double o[R], o_sum = 0.0;
-#pragma unroll
-        for (int r = 0; r < R; ++r) {
-            const double m = rest + e_stored * v[r];
-            o[r] = (q[r] > 0.0 && m > 0.0) ? q[r] / m : 0.0;
-            o_sum += o[r];
-        }
-        o_sum = group_sum<G>(o_sum);
+        const double d = A.dist[n] + C.tau;
+        const double x = inside ? C.mu * (d * C.scale) : 0.0;   // (the transform of f81_prep_kernel)
+        const double len = inside ? d * C.tauf : 0.0;
+        double v[R], o[R], s, o_sum;
+        hist_front<G, R>(A, C, g, n, A.parent[n], inside, v, o, s, o_sum);   // (the plan holds no root)
         double ey, c0y, c1y;
         hist_coefficients(w * x, ey, c0y, c1y);
         const double Aa = -expm1(-s1 * x), Bb = -expm1(-rr * x), Bl = -expm1(-u * x);
@@ -122,11 +89,11 @@ __global__ void __launch_bounds__(256) history_time_segment_kernel(PmlHistTimeAr
         const double l_pv = starts ? Aa * (1.0 - Bl) * o_sum : 0.0, l_p = starts ? Aa * Bl * o_sum * s : 0.0;
 #pragma unroll
         for (int r = 0; r < R; ++r) {
-            const double a = pi[r] * os0 + o[r] * sc1;
-            const double b = pi[r] * oc1 + o[r] * Cee;
+            const double a = C.pi[r] * os0 + o[r] * sc1;
+            const double b = C.pi[r] * oc1 + o[r] * Cee;
             acc_t[r] += len * (a + b * v[r]);
             acc_a[r] += x * a;
-            acc_l[r] += (l_ov * o[r] * v[r] + l_o * o[r]) + (l_pv * pi[r] * v[r] + l_p * pi[r]);
+            acc_l[r] += (l_ov * o[r] * v[r] + l_o * o[r]) + (l_pv * C.pi[r] * v[r] + l_p * C.pi[r]);
         }
         if (g == 0 && inside && T.stage != nullptr) {
             double* st = T.stage + ((size_t)blockIdx.y * T.n_segments + i) * 3;
@@ -135,33 +102,16 @@ __global__ void __launch_bounds__(256) history_time_segment_kernel(PmlHistTimeAr
             st[2] = x * Cee;
         }
     }
-    // the units' sums in unit order
-    double* mine = red + unit * ROW;
-#pragma unroll
-    for (int r = 0; r < R; ++r) {
-        mine[g + G * r] = acc_t[r];
-        mine[G * R + g + G * r] = acc_a[r];
-        mine[2 * G * R + g + G * r] = acc_l[r];
-    }
-    __syncthreads();
-    double* out = T.partial + ((size_t)blockIdx.y * T.n_pieces + blockIdx.x) * 3 * k;
-    for (int t = threadIdx.x; t < 3 * k; t += 256) {
-        const int which = t / k, at = which * G * R + (t - which * k);
-        double sum = 0.0;
-        for (int j = 0; j < UNITS; ++j) sum += red[j * ROW + at];
-        out[t] = sum;
-    }
+    hist_unit_sums<G, R>(red, unit, g, A.k, T.partial + ((size_t)blockIdx.y * T.n_pieces + blockIdx.x) * 3 * A.k, acc_t, acc_a, acc_l);
 }
 
 // times, sum x a and lineages of one bin: its pieces' partials in piece order (an empty bin: exact zeros).  grid (M + 1,
 // column); the pseudo-bin M gives the lineages at the last boundary only.  Thread t owns the entries t + 256 h of the 3 k.
 static __global__ void __launch_bounds__(256) history_time_vector_kernel(PmlHistTimeArgs T) {
     const int k = T.h.k, M = T.M, m = blockIdx.x;
-    const int p0 = T.bin_piece_off[m], p1 = T.bin_piece_off[m + 1];
     const double* part = T.partial + (size_t)blockIdx.y * T.n_pieces * 3 * k;
     for (int t = threadIdx.x; t < 3 * k; t += 256) {
-        double s = 0.0;
-        for (int j = p0; j < p1; ++j) s += part[(size_t)j * 3 * k + t];
+        const double s = pml_piece_sum(part + t, (size_t)3 * k, T.bin_piece_off[m], T.bin_piece_off[m + 1]);
         if (t < k) {
             if (m < M) T.times_out[((size_t)blockIdx.y * M + m) * k + t] = s;
         } else if (t < 2 * k) {
@@ -172,94 +122,30 @@ static __global__ void __launch_bounds__(256) history_time_vector_kernel(PmlHist
     }
 }
 
-// sum (x b) (x) v over the segments of one piece.  grid (piece, tile group, column), tiled as history_jump_kernel: a wavefront
-// owns the 16 rows i of one band and four bands of columns j; per step the four lane rows (hi) hold four consecutive segments:
-// A[m][kk] = x b_kk[i0 + m], B[kk][n] = v_kk[j0 + n] (v_mfma_f64_16x16x4_f64; D: col = lane & 15, row = (lane >> 4) + 4 reg).
-// States beyond k and segments beyond the piece enter as zeros.
-// WIDE = 0: up to 64 states, one tile group, the loop over the steps unrolled by four (the loads of 16 segments in flight).
+// sum (x b) (x) v over the segments of one piece of the plan: item i is segment i, on the node with the caller's id
+// seg_node[i]; its staged scalars are kept by segment, and the plan holds no root.  grid (piece, tile group, column)
+struct HistSegmentItems {
+    const int *seg_node, *new_of_old;
+    __device__ __forceinline__ void at(int i, int& n, int& stage_row) const {
+        const int id = seg_node[i];
+        n = new_of_old ? new_of_old[id] : id;
+        stage_row = i;
+    }
+    __device__ __forceinline__ bool valid(bool inside, int) const { return inside; }
+};
 template <int WIDE>
 __global__ void __launch_bounds__(256) history_time_jump_kernel(PmlHistTimeArgs T) {
-    const PmlHistArgs& A = T.h;
-    const int k = A.k, ks = A.ks;
-    const int TT = (k + 15) >> 4, TG = WIDE ? (TT + 3) >> 2 : 1;
-    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63, lo = lane & 15, hi = lane >> 4;
-    const int ga = blockIdx.y / TG, gb = blockIdx.y % TG;
-    const int ta = 4 * ga + wave;
-    if (ta >= TT) return;   // (no barrier below)
-    const int col = A.col0 + blockIdx.z;
-    const size_t colN = (size_t)col * A.N;
-    const int a = 16 * ta + lo;
-    const double pi_a = a < k ? A.pi[(size_t)col * ks + a] : 0.0;
-    pml_v4f64 acc[4];
-#pragma unroll
-    for (int t = 0; t < 4; ++t) acc[t] = pml_v4f64{0.0, 0.0, 0.0, 0.0};
-    const int i0 = T.jpiece_off[blockIdx.x], i1 = T.jpiece_off[blockIdx.x + 1];
-    const int a_c = min(a, k - 1);
-    auto step = [&](int base) {
-        // (segments beyond the piece read its last one and are zeroed by the selects below: no load waits for a test)
-        const int i = min(base + hi, i1 - 1);
-        const bool valid = base + hi < i1;
-        const int id = T.seg_node[i];
-        const int n = A.new_of_old ? A.new_of_old[id] : id;
-        const int pp = max(A.parent[n], 0);
-        const bool tip = A.n_children[n] == 0;
-        const size_t row = colN + n;
-        const double e_stored = A.E[row];
-        const double q = A.post[(colN + pp) * ks + a_c];
-        const double* st = T.stage + ((size_t)blockIdx.z * T.n_segments + i) * 3;
-        const double S = st[0], xoc1 = st[1], xe = st[2];
-        double w[4];
-#pragma unroll
-        for (int t = 0; t < 4; ++t) w[t] = hist_v(A, row, tip, 16 * (4 * gb + t) + lo);
-        double va = 0.0;
-        if (!WIDE) {   // up to 64 states: the four tiles are the whole row
-#pragma unroll
-            for (int t = 0; t < 4; ++t) va = t == wave ? w[t] : va;
-        } else {
-            va = hist_v(A, row, tip, a);
-        }
-        const double m = (1.0 - e_stored) * S + e_stored * va;
-        const double o = (valid && a < k && q > 0.0 && m > 0.0) ? q / m : 0.0;
-        const double u = valid ? pi_a * xoc1 + o * xe : 0.0;
-#pragma unroll
-        for (int t = 0; t < 4; ++t) acc[t] = __builtin_amdgcn_mfma_f64_16x16x4f64(u, valid ? w[t] : 0.0, acc[t], 0, 0, 0);
-    };
-    if (!WIDE) {
-        // (by hand: the MFMA is convergent, which keeps the compiler from unrolling a loop with a remainder; steps beyond the
-        // piece are all-zero operands)
-        for (int base = i0; base < i1; base += 16) {
-            step(base);
-            step(base + 4);
-            step(base + 8);
-            step(base + 12);
-        }
-    } else {
-        for (int base = i0; base < i1; base += 4) step(base);
-    }
-    double* out = T.jpartial + ((size_t)blockIdx.z * T.n_jpieces + blockIdx.x) * k * k;
-#pragma unroll
-    for (int t = 0; t < 4; ++t) {
-        const int b = 16 * (4 * gb + t) + lo;
-#pragma unroll
-        for (int reg = 0; reg < 4; ++reg) {
-            const int r = 16 * ta + hi + 4 * reg;
-            if (r < k && b < k) out[(size_t)r * k + b] = acc[t][reg];
-        }
-    }
+    hist_jump_product<WIDE>(T.h, HistSegmentItems{T.seg_node, T.h.new_of_old}, T.stage + (size_t)blockIdx.z * T.n_segments * 3,
+                            T.jpiece_off[blockIdx.x], T.jpiece_off[blockIdx.x + 1],
+                            T.jpartial + ((size_t)blockIdx.z * T.n_jpieces + blockIdx.x) * T.h.k * T.h.k);
 }
 
-// jumps[col][m][i][j] = pi_j (sum x a [m][i] + the products of bin m's pieces in piece order [i][j]), the diagonal 0.
-// grid (M ceil(k k / 256), column): the bin is the slow index of x (M may exceed what y holds)
+// jumps[col][m][i][j]: hist_jumps_entry over bin m's pieces and its sum x a.  grid (M ceil(k k / 256), column)
 static __global__ void __launch_bounds__(256) history_time_matrix_kernel(PmlHistTimeArgs T) {
-    const int k = T.h.k, M = T.M, per_bin = (k * k + 255) / 256;
-    const int m = blockIdx.x / per_bin;
-    const int idx = (blockIdx.x % per_bin) * 256 + threadIdx.x;
-    if (idx >= k * k) return;
-    const double* part = T.jpartial + (size_t)blockIdx.y * T.n_jpieces * k * k + idx;
-    double s = 0.0;
-    for (int j = T.bin_jpiece_off[m]; j < T.bin_jpiece_off[m + 1]; ++j) s += part[(size_t)j * k * k];
-    const int i = idx / k, j = idx % k;
-    const double pi_j = T.h.pi[(size_t)(T.h.col0 + blockIdx.y) * T.h.ks + j];
-    const size_t at = (size_t)blockIdx.y * M + m;
-    T.jumps_out[at * k * k + idx] = i == j ? 0.0 : pi_j * (T.xa[at * k + i] + s);
+    const int k = T.h.k;
+    int m, idx;
+    if (!pml_bin_entry(k, m, idx)) return;
+    const size_t at = (size_t)blockIdx.y * T.M + m;
+    T.jumps_out[at * k * k + idx] = hist_jumps_entry(T.h, blockIdx.y, idx, T.jpartial + (size_t)blockIdx.y * T.n_jpieces * k * k,
+                                                     T.bin_jpiece_off[m], T.bin_jpiece_off[m + 1], T.xa + at * k);
 }

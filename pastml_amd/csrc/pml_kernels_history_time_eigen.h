@@ -20,9 +20,10 @@
 //
 // heig_basis_kernel stages E_n, r_n, l_n and t'_n per branch as it does for the whole tree.  hte_segment_kernel forms ls, Ey, rs
 // once per segment (3 k exponentials, 3 ks doubles), for heig_basis_kernel's reason: no pair may cost a transcendental.
-// hte_pair_kernel is heig_pair_kernel over the segments of a piece of the plan (pml_cut_time_pieces by PML_HEIG_PIECE: no piece
-// straddles two bins), without the per-branch sums.  The partials are summed in piece order per bin (hte_reduce_kernel), and
-// times / jumps come from W_m by heig's two small products per bin (hte_t1_kernel, hte_times_kernel, hte_jumps_kernel).
+// hte_pair_kernel has heig_pair_kernel's tiles and epilogue (heig_tile, heig_tile_sums) and a walk of its own over the segments
+// of a piece of the plan (pml_cut_time_pieces by PML_HEIG_PIECE: no piece straddles two bins), without the per-branch sums.  The
+// partials are summed in piece order per bin (hte_reduce_kernel), and times / jumps come from W_m by the two small products of
+// pml_kernels_history_eigen_shared.h per bin (hte_t1_kernel, hte_times_kernel, hte_jumps_kernel).
 // hte_lineage_kernel takes the flagged segments of a boundary in tiles of 16 -- the two changes of basis Ainv^T (l o e^{d s t'})
 // and A (r o e^{d u t'}) by heig_product, on the FP64 matrix cores from 16 states on -- and adds the tiles of a piece of 512
 // in tile order; hte_lineage_sum_kernel adds the pieces of a boundary in piece order and clamps at 0.
@@ -33,7 +34,7 @@
 // has, and nothing depends on the grid, on the other columns, on the column's position or on which outputs are asked for (W_m
 // is formed in full either way).  The posteriors this reads are the eigen sweeps': their bits follow the schedule.
 #pragma once
-#include "pml_kernels_history_eigen.h"   // (PmlHeigArgs, heig_Phi, heig_owned, heig_product)
+#include "pml_kernels_history_eigen_shared.h"
 
 #define PML_HTE_TILE 16   // flagged segments per tile of the lineage kernel (the vectors of one MFMA operand)
 
@@ -83,107 +84,68 @@ static __global__ void __launch_bounds__(256) hte_segment_kernel(PmlHteArgs T) {
     if (c == 0) T.sy[(size_t)blockIdx.y * T.n_segments + i] = y;
 }
 
-// The pair sum of one piece and one tile of pairs: heig_pair_kernel's layout.  grid (piece, tile, column); tile = band of c (CR
-// values) x band of d (64).
+
+// The pair sum of one piece of the plan's segments and one tile of pairs (heig_tile).  grid (piece, tile, column)
 template <int CR>
 __global__ void __launch_bounds__(256) hte_pair_kernel(PmlHteArgs T) {
     __shared__ double buf[CR * 64];   // the wavefronts' sums
     const PmlHeigArgs& A = T.h;
     const int k = A.k, ks = A.ks;
-    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), lane = threadIdx.x & 63;
-    const int tile = blockIdx.y, c0 = (tile / A.td) * CR, d = (tile % A.td) * 64 + lane;
-    const bool d_in = d < k;
-    const int dcl = min(d, k - 1);
-    const double* ev = A.ev + (size_t)(A.col0 + blockIdx.z) * k;
-    const double ev_d = ev[dcl];
+    const HeigTile t = heig_tile<CR>(A);
     double acc[CR];
 #pragma unroll
     for (int j = 0; j < CR; ++j) acc[j] = 0.0;
     const int i0 = T.piece_off[blockIdx.x], i1 = T.piece_off[blockIdx.x + 1];
-    for (int i = i0 + wave; i < i1; i += 4) {
+    for (int i = i0 + t.wave; i < i1; i += 4) {
         const double* st = T.sstage + ((size_t)blockIdx.z * T.n_segments + i) * 3 * ks;
         const double y = T.sy[(size_t)blockIdx.z * T.n_segments + i];
-        const double E_d = st[dcl];
-        const double r_d = d_in ? st[ks + dcl] : 0.0;
+        const double E_d = st[t.dcl];
+        const double r_d = t.d_in ? st[ks + t.dcl] : 0.0;
 #pragma unroll
         for (int j = 0; j < CR; ++j) {
-            const int c = c0 + j, cc = min(c, k - 1);   // (uniform over the wavefront)
+            const int c = t.c0 + j, cc = min(c, k - 1);   // (uniform over the wavefront)
             const double l_c = c < k ? st[2 * ks + cc] : 0.0;
-            acc[j] += l_c * heig_Phi(y, ev[cc], ev_d, st[cc], E_d) * r_d;
+            acc[j] += l_c * heig_Phi(y, t.ev[cc], t.ev_d, st[cc], E_d) * r_d;
             // (one pair's chain at a time, as the branches of heig_pair_kernel's per-branch sum leave it there: scheduled as one
             // block, the CR chains take 217 registers at CR = 32 -- two wavefronts per SIMD -- where this takes 157, three)
             __builtin_amdgcn_sched_barrier(0);
         }
     }
-    // the wavefronts' sums in wavefront order
-    for (int w = 0; w < 4; ++w) {
-        if (wave == w) {
-#pragma unroll
-            for (int j = 0; j < CR; ++j) buf[j * 64 + lane] = w == 0 ? acc[j] : buf[j * 64 + lane] + acc[j];
-        }
-        __syncthreads();
-    }
-    double* out = T.partial + ((size_t)blockIdx.z * T.n_pieces + blockIdx.x) * k * k;
-    for (int e = threadIdx.x; e < CR * 64; e += 256) {
-        const int c = c0 + (e >> 6), dd = (tile % A.td) * 64 + (e & 63);
-        if (c < k && dd < k) out[(size_t)c * k + dd] = buf[e];
-    }
+    heig_tile_sums<CR>(t, buf, acc, k, T.partial + ((size_t)blockIdx.z * T.n_pieces + blockIdx.x) * k * k);
 }
 
-// The kernels per bin below: grid (M ceil(k k / 256), column), the bin the slow index of x (M may exceed what y holds).
-// W_m: the partials of bin m's pieces in piece order (an empty bin: exact zeros).
+// The kernels per bin below: grid (M ceil(k k / 256), column), the bin the slow index of x (pml_bin_entry), and heig's
+// transforms on bin m's W.  W_m: the partials of bin m's pieces in piece order (an empty bin: exact zeros).
 static __global__ void __launch_bounds__(256) hte_reduce_kernel(PmlHteArgs T) {
-    const int k = T.h.k, per_bin = (k * k + 255) / 256;
-    const int m = blockIdx.x / per_bin, idx = (blockIdx.x % per_bin) * 256 + threadIdx.x;
-    if (idx >= k * k) return;
-    const double* part = T.partial + (size_t)blockIdx.y * T.n_pieces * k * k + idx;
-    double s = 0.0;
-    for (int j = T.bin_piece_off[m]; j < T.bin_piece_off[m + 1]; ++j) s += part[(size_t)j * k * k];
-    T.Wsum[((size_t)blockIdx.y * T.M + m) * k * k + idx] = s;
+    const int k = T.h.k;
+    int m, idx;
+    if (!pml_bin_entry(k, m, idx)) return;
+    T.Wsum[((size_t)blockIdx.y * T.M + m) * k * k + idx] =
+        pml_piece_sum(T.partial + (size_t)blockIdx.y * T.n_pieces * k * k + idx, (size_t)k * k, T.bin_piece_off[m], T.bin_piece_off[m + 1]);
 }
 
-// T1_m[s][d] = sum_c Ainv[c][s] W_m[c][d], c ascending
 static __global__ void __launch_bounds__(256) hte_t1_kernel(PmlHteArgs T) {
-    const int k = T.h.k, per_bin = (k * k + 255) / 256;
-    const int m = blockIdx.x / per_bin, idx = (blockIdx.x % per_bin) * 256 + threadIdx.x;
-    if (idx >= k * k) return;
-    const int s = idx / k, d = idx % k;
-    const double* Ai = T.h.Ainv + (size_t)(T.h.col0 + blockIdx.y) * k * k;
-    const double* W = T.Wsum + ((size_t)blockIdx.y * T.M + m) * k * k;
-    double sum = 0.0;
-    for (int c = 0; c < k; ++c) sum = fma(Ai[(size_t)c * k + s], W[(size_t)c * k + d], sum);
-    T.T1[((size_t)blockIdx.y * T.M + m) * k * k + idx] = sum;
+    const int k = T.h.k;
+    int m, idx;
+    if (!pml_bin_entry(k, m, idx)) return;
+    const size_t at = ((size_t)blockIdx.y * T.M + m) * k * k;
+    heig_t1(T.h, blockIdx.y, idx, T.Wsum + at, T.T1 + at);
 }
 
-// times[m][s] = (1 / sf) sum_d T1_m[s][d] A[s][d], d ascending.  grid (M, column), thread s
-static __global__ void __launch_bounds__(256) hte_times_kernel(PmlHteArgs T) {
-    const int k = T.h.k, s = threadIdx.x;
-    if (s >= k) return;
-    const size_t col = T.h.col0 + blockIdx.y, at = (size_t)blockIdx.y * T.M + blockIdx.x;
-    const double* Am = T.h.A + col * k * k + (size_t)s * k;
-    const double* T1 = T.T1 + at * k * k + (size_t)s * k;
-    double sum = 0.0;
-    for (int d = 0; d < k; ++d) sum = fma(T1[d], Am[d], sum);
-    sum /= T.h.sf[col];
-    T.times_out[at * k + s] = sum > 0.0 ? sum : 0.0;
-}
-
-// jumps[m][i][j] = Q_ij sum_d T1_m[i][d] A[j][d], Q_ij = sum_n A[i][n] d_n Ainv[n][j]; the diagonal 0
 static __global__ void __launch_bounds__(256) hte_jumps_kernel(PmlHteArgs T) {
-    const int k = T.h.k, per_bin = (k * k + 255) / 256;
-    const int m = blockIdx.x / per_bin, idx = (blockIdx.x % per_bin) * 256 + threadIdx.x;
-    if (idx >= k * k) return;
-    const int i = idx / k, j = idx % k;
-    const size_t col = T.h.col0 + blockIdx.y, at = (size_t)blockIdx.y * T.M + m;
-    const double *ev = T.h.ev + col * k, *Am = T.h.A + col * k * k, *Ai = T.h.Ainv + col * k * k;
-    const double* T1 = T.T1 + at * k * k + (size_t)i * k;
-    double sum = 0.0, q = 0.0;
-    for (int d = 0; d < k; ++d) sum = fma(T1[d], Am[(size_t)j * k + d], sum);
-    for (int n = 0; n < k; ++n) q = fma(Am[(size_t)i * k + n] * ev[n], Ai[(size_t)n * k + j], q);
-    const double v = q * sum;
-    T.jumps_out[at * k * k + idx] = (i != j && v > 0.0) ? v : 0.0;
+    const int k = T.h.k;
+    int m, idx;
+    if (!pml_bin_entry(k, m, idx)) return;
+    const size_t at = ((size_t)blockIdx.y * T.M + m) * k * k;
+    heig_jumps(T.h, blockIdx.y, idx, T.T1 + at, T.jumps_out + at);
 }
 
+// grid (M, column), thread s
+static __global__ void __launch_bounds__(256) hte_times_kernel(PmlHteArgs T) {
+    const int k = T.h.k;
+    const size_t at = (size_t)blockIdx.y * T.M + blockIdx.x;
+    if ((int)threadIdx.x < k) heig_times(T.h, blockIdx.y, threadIdx.x, T.T1 + at * k * k, T.times_out + at * k);
+}
 // The posterior of the state at the flagged segments' points, added up over one piece.  grid (piece, column), 256 threads,
 // dynamic LDS: 16 (kp + 1) + 48 doubles and 16 ints, kp = k rounded up to 16; X[b][s] as in heig_basis_kernel.  Per tile of 16
 // segments: X = l o e^{d s t'}, a = Ainv^T X; X = r o e^{d u t'}, b = A X; X = a o b (q_p where t' = 0); thread j adds X[.][j]
@@ -257,8 +219,7 @@ __global__ void __launch_bounds__(256) hte_lineage_kernel(PmlHteArgs T) {
 static __global__ void __launch_bounds__(256) hte_lineage_sum_kernel(PmlHteArgs T) {
     const int k = T.h.k, j = threadIdx.x, m = blockIdx.x;
     if (j >= k) return;
-    const double* part = T.lpart + (size_t)blockIdx.y * T.n_lpieces * k + j;
-    double s = 0.0;
-    for (int p = T.bin_lpiece_off[m]; p < T.bin_lpiece_off[m + 1]; ++p) s += part[(size_t)p * k];
+    const double s = pml_piece_sum(T.lpart + (size_t)blockIdx.y * T.n_lpieces * k + j, k, T.bin_lpiece_off[m], T.bin_lpiece_off[m + 1]);
     T.lineages_out[((size_t)blockIdx.y * (T.M + 1) + m) * k + j] = s > 0.0 ? s : 0.0;
 }
+

@@ -2,6 +2,7 @@
 // (pml_launch_*.hip, one per kernel family, compiled in parallel): the dispatch functions, the cases of lane shapes they are
 // instantiated for (the shapes themselves: pml_columns.h) and the predicates that say which family a context's sweeps take.
 #pragma once
+#include <type_traits>
 #include "pml_host.h"
 #include "pml_time_segments.h"
 
@@ -213,14 +214,46 @@ PML_INTERNAL int launch_expected(pml_ctx* ctx, int cb, int ce, const unsigned ch
 // ---- pml_launch_gradient.hip: exact gradient of ln L of the F81 family for the columns [cb, ce) (pml_loglik_gradient); device
 //      arrays d_rates [cols][3], d_pi [cols][k], d_flat [cols]; queued only: the partials go into the caller's scope, which waits
 PML_INTERNAL int launch_gradient(pml_ctx* ctx, CallScope& mem, int cb, int ce, double* d_rates, double* d_pi, int* d_flat);
+//      The lane shape <G, R> of the passes that stream v_n and q_p once per branch (the gradient here, the two exact histories
+//      of the F81 family below) at k <= 512 states: f(G, R), the two as std::integral_constant
+template <class F>
+static inline void with_branch_shape(int k, const F& f) {
+    using std::integral_constant;
+    if (k <= 4) f(integral_constant<int, 1>{}, integral_constant<int, 4>{});
+    else if (k <= 16) f(integral_constant<int, 4>{}, integral_constant<int, 4>{});
+    else if (k <= 64) f(integral_constant<int, 16>{}, integral_constant<int, 4>{});
+    else if (k <= 256) f(integral_constant<int, 64>{}, integral_constant<int, 4>{});
+    else f(integral_constant<int, 64>{}, integral_constant<int, 8>{});
+}
 // ---- pml_launch_history.hip: exact expected dwell times and Markov jumps of the F81 family for the columns [cb, ce)
 //      (pml_expected_history); device arrays d_times [cols][k], d_jumps [cols][k][k] or null, d_branch [cols][N] in the caller's
 //      numbering or null; queued only: partials and staged scalars go into the caller's scope, which waits
+//      history_piece / history_jump_piece: ids (per time interval: segments) per piece of the branch pass and of the jump product;
+//      history_args: the fields of a that come from the context and from cb, everything else zeroed
+struct PmlHistArgs;
+PML_INTERNAL int history_piece(int k);
+PML_INTERNAL int history_jump_piece(int k);
+PML_INTERNAL void history_args(const pml_ctx* ctx, int cb, PmlHistArgs& a);
 PML_INTERNAL int launch_history(pml_ctx* ctx, CallScope& mem, int cb, int ce, double* d_times, double* d_jumps, double* d_branch);
 // ---- pml_launch_history_eigen.hip: the same for the eigen-decomposed models, 2 <= k <= 256 (pml_expected_history_eigen); the
 //      same device arrays; queued only: the staged vectors and the partials go into the caller's scope, which waits
-//      heig_rows: the values of c a lane of the pair sum keeps in registers at k states
+//      heig_rows: the values of c a lane of the pair sum keeps in registers at k states; with_heig_rows: f(CR), CR =
+//      heig_rows(k) as a std::integral_constant
+//      heig_args: the fields of a that come from the context and from cb, tc and td, everything else zeroed; launch_heig_basis:
+//      the changes of basis per branch into a.stage and a.tprime, which both entries of the eigen models begin with
+struct PmlHeigArgs;
 PML_INTERNAL int heig_rows(int k);
+template <class F>
+static inline void with_heig_rows(int k, const F& f) {
+    using std::integral_constant;
+    const int CR = heig_rows(k);
+    if (CR == 4) f(integral_constant<int, 4>{});
+    else if (CR == 16) f(integral_constant<int, 16>{});
+    else if (CR == 32) f(integral_constant<int, 32>{});
+    else f(integral_constant<int, 64>{});
+}
+PML_INTERNAL void heig_args(const pml_ctx* ctx, int cb, PmlHeigArgs& a);
+PML_INTERNAL void launch_heig_basis(pml_ctx* ctx, int cols, const PmlHeigArgs& a);
 PML_INTERNAL int launch_history_eigen(pml_ctx* ctx, CallScope& mem, int cb, int ce, double* d_times, double* d_jumps, double* d_branch);
 // ---- pml_launch_history_sample.hip: histories of column col drawn on the scenarios d_states [N][rs] that launch_scenarios left
 //      on the device (pml_sample_histories); device arrays d_times [n_rep][k], d_jumps [n_rep][k][k] (zeroed) or null, d_branch
@@ -230,11 +263,9 @@ PML_INTERNAL int launch_history_sample(pml_ctx* ctx, CallScope& mem, int col, in
                                        size_t rs, double* d_times, unsigned* d_jumps, unsigned short* d_branch,
                                        unsigned long long* d_skipped);
 // ---- pml_launch_history_time.hip: the same per time interval, with the lineages at every boundary (pml_history_through_time).
-//      plan: the segments (pml_time_segments.h); pieces / jpieces: its cut by history_time_piece(k) with the pseudo-bin and by
-//      history_time_jump_piece(k) without -- all three the caller's, alive until its scope has waited.  Device arrays d_times
+//      plan: the segments (pml_time_segments.h); pieces / jpieces: its cut by history_piece(k) with the pseudo-bin and by
+//      history_jump_piece(k) without -- all three the caller's, alive until its scope has waited.  Device arrays d_times
 //      [cols][M][k], d_jumps [cols][M][k][k] or null, d_lineages [cols][M + 1][k] or null; queued only
-PML_INTERNAL int history_time_piece(int k);
-PML_INTERNAL int history_time_jump_piece(int k);
 PML_INTERNAL int launch_history_time(pml_ctx* ctx, CallScope& mem, int cb, int ce, const PmlTimeSegments& plan, const PmlTimePieces& pieces,
                                      const PmlTimePieces& jpieces, double* d_times, double* d_jumps, double* d_lineages);
 // ---- pml_launch_history_time_eigen.hip: launch_history_time for the eigen-decomposed models, 2 <= k <= 256

@@ -38,13 +38,10 @@ PML_INTERNAL int launch_gradient(pml_ctx* ctx, CallScope& mem, int cb, int ce, d
     a.pi_out = d_pi;
     a.flat_out = d_flat;
     PML_TRY(mem.get(&a.partial, (size_t)cols * a.n_pieces * (k + 3)));
-    const dim3 grid(a.n_pieces, cols);
-    if (k <= 4) hipLaunchKernelGGL((gradient_f81_kernel<1, 4>), grid, dim3(256), 0, ctx->stream, a);
-    else if (k <= 16) hipLaunchKernelGGL((gradient_f81_kernel<4, 4>), grid, dim3(256), 0, ctx->stream, a);
-    else if (k <= 64) hipLaunchKernelGGL((gradient_f81_kernel<16, 4>), grid, dim3(256), 0, ctx->stream, a);
-    else if (k <= 256) hipLaunchKernelGGL((gradient_f81_kernel<64, 4>), grid, dim3(256), 0, ctx->stream, a);
-    else if (k <= 512) hipLaunchKernelGGL((gradient_f81_kernel<64, 8>), grid, dim3(256), 0, ctx->stream, a);
-    else return fail(PML_ERR_UNSUPPORTED, "k = %d: the F81 family holds at most 512 states", k);
+    if (k > 512) return fail(PML_ERR_UNSUPPORTED, "k = %d: the F81 family holds at most 512 states", k);
+    with_branch_shape(k, [&](auto G, auto R) {
+        hipLaunchKernelGGL((gradient_f81_kernel<G(), R()>), dim3(a.n_pieces, cols), dim3(256), 0, ctx->stream, a);
+    });
     hipLaunchKernelGGL(gradient_reduce_kernel, dim3(cols), dim3(256), 0, ctx->stream, a);
     HIP_TRY(hipGetLastError());
     return PML_OK;

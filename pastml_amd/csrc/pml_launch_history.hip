@@ -4,21 +4,18 @@
 #include "pml_launch.h"
 #include "pml_kernels_history.h"
 
-// Ids per piece: fixed by k, never by the grid (the sums' order, hence their bits, follows from it).
+// Ids -- per time interval: segments -- per piece: fixed by k, never by the grid or by the bins (the sums' order, hence their
+// bits, follows from it); a segment streams what a branch streams.
 // Branch pass: gradient_piece's sizes, for its reasons -- a piece's partial is 2 k doubles against the 2 k doubles EACH of its
 // branches streams in, under 1 % of the traffic everywhere, and a single column of a few thousand nodes still spreads over
 // several workgroups.
-static int history_piece(int k) { return k <= 4 ? 1024 : (k <= 64 ? 512 : 256); }
+int history_piece(int k) { return k <= 4 ? 1024 : (k <= 64 ? 512 : 256); }
 // Jump product: expected_piece's sizes, for its reasons -- a piece's partial (k^2 doubles) against what its branches stream in
 // (2 k doubles each): 2048 ids keep the partials under 2 % of the traffic at k = 64, 4096 under 7 % at k = 512.
-static int history_jump_piece(int k) { return k <= 64 ? 2048 : 4096; }
+int history_jump_piece(int k) { return k <= 64 ? 2048 : 4096; }
 
-// d_times [cols][k]; d_jumps [cols][k][k] or null; d_branch [cols][N] (caller's numbering) or null.  Queued only: partials and
-// staged scalars live in the caller's scope, which makes the call's one wait.
-PML_INTERNAL int launch_history(pml_ctx* ctx, CallScope& mem, int cb, int ce, double* d_times, double* d_jumps, double* d_branch) {
-    const int k = ctx->k, N = ctx->N, cols = ce - cb;
-    if (k > 512) return fail(PML_ERR_UNSUPPORTED, "k = %d: the F81 family holds at most 512 states", k);
-    PmlHistArgs a;
+void history_args(const pml_ctx* ctx, int cb, PmlHistArgs& a) {
+    a = PmlHistArgs{};   // (the pieces, the scratch and the outputs: the caller's)
     a.parent = ctx->d_parent;
     a.n_children = ctx->d_n_children;
     a.new_of_old = ctx->d_new_of_old;   // (null when the library works in the caller's numbering)
@@ -32,11 +29,20 @@ PML_INTERNAL int launch_history(pml_ctx* ctx, CallScope& mem, int cb, int ce, do
     a.sf = ctx->d_sf;
     a.tau = ctx->d_tau;
     a.tauf = ctx->d_tauf;
-    a.N = N;
-    a.k = k;
+    a.N = ctx->N;
+    a.k = ctx->k;
     a.ks = ctx->ks;
     a.W = ctx->W;
     a.col0 = cb;
+}
+
+// d_times [cols][k]; d_jumps [cols][k][k] or null; d_branch [cols][N] (caller's numbering) or null.  Queued only: partials and
+// staged scalars live in the caller's scope, which makes the call's one wait.
+PML_INTERNAL int launch_history(pml_ctx* ctx, CallScope& mem, int cb, int ce, double* d_times, double* d_jumps, double* d_branch) {
+    const int k = ctx->k, N = ctx->N, cols = ce - cb;
+    if (k > 512) return fail(PML_ERR_UNSUPPORTED, "k = %d: the F81 family holds at most 512 states", k);
+    PmlHistArgs a;
+    history_args(ctx, cb, a);
     a.piece = history_piece(k);
     a.n_pieces = (N + a.piece - 1) / a.piece;
     a.jpiece = history_jump_piece(k);
@@ -44,19 +50,15 @@ PML_INTERNAL int launch_history(pml_ctx* ctx, CallScope& mem, int cb, int ce, do
     a.times_out = d_times;
     a.jumps_out = d_jumps;
     a.branch_out = d_branch;
-    a.stage = a.jpartial = nullptr;
     PML_TRY(mem.get(&a.partial, (size_t)cols * a.n_pieces * 2 * k));
     PML_TRY(mem.get(&a.xa, (size_t)cols * k));
     if (d_jumps != nullptr) {
         PML_TRY(mem.get(&a.stage, (size_t)cols * N * 3));
         PML_TRY(mem.get(&a.jpartial, (size_t)cols * a.n_jpieces * k * k));
     }
-    const dim3 grid(a.n_pieces, cols);
-    if (k <= 4) hipLaunchKernelGGL((history_branch_kernel<1, 4>), grid, dim3(256), 0, ctx->stream, a);
-    else if (k <= 16) hipLaunchKernelGGL((history_branch_kernel<4, 4>), grid, dim3(256), 0, ctx->stream, a);
-    else if (k <= 64) hipLaunchKernelGGL((history_branch_kernel<16, 4>), grid, dim3(256), 0, ctx->stream, a);
-    else if (k <= 256) hipLaunchKernelGGL((history_branch_kernel<64, 4>), grid, dim3(256), 0, ctx->stream, a);
-    else hipLaunchKernelGGL((history_branch_kernel<64, 8>), grid, dim3(256), 0, ctx->stream, a);
+    with_branch_shape(k, [&](auto G, auto R) {
+        hipLaunchKernelGGL((history_branch_kernel<G(), R()>), dim3(a.n_pieces, cols), dim3(256), 0, ctx->stream, a);
+    });
     hipLaunchKernelGGL(history_vector_kernel, dim3(cols), dim3(256), 0, ctx->stream, a);
     if (d_jumps != nullptr) {
         const int T = (k + 15) / 16, TG = (T + 3) / 4;

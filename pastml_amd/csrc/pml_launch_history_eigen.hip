@@ -10,12 +10,8 @@
 // the number of tiles that read a branch's staged vectors again.  A pair's sum does not depend on the band it falls into.
 int heig_rows(int k) { return k <= 4 ? 4 : (k <= 16 ? 16 : (k <= 64 ? 32 : 64)); }
 
-// d_times [cols][k]; d_jumps [cols][k][k] or null; d_branch [cols][N] (caller's numbering) or null.  Queued only: the staged
-// vectors and the partials live in the caller's scope, which makes the call's one wait.
-PML_INTERNAL int launch_history_eigen(pml_ctx* ctx, CallScope& mem, int cb, int ce, double* d_times, double* d_jumps, double* d_branch) {
-    const int k = ctx->k, N = ctx->N, cols = ce - cb;
-    if (k < 2 || k > 256) return fail(PML_ERR_UNSUPPORTED, "k = %d: the eigen models' history takes 2 to 256 states", k);
-    PmlHeigArgs a;
+void heig_args(const pml_ctx* ctx, int cb, PmlHeigArgs& a) {
+    a = PmlHeigArgs{};   // (the pieces, the scratch and the outputs: the caller's)
     a.parent = ctx->d_parent;
     a.n_children = ctx->d_n_children;
     a.new_of_old = ctx->d_new_of_old;   // (null when the library works in the caller's numbering)
@@ -29,19 +25,35 @@ PML_INTERNAL int launch_history_eigen(pml_ctx* ctx, CallScope& mem, int cb, int 
     a.sf = ctx->d_sf;
     a.tau = ctx->d_tau;
     a.tauf = ctx->d_tauf;
-    a.N = N;
-    a.k = k;
+    a.N = ctx->N;
+    a.k = ctx->k;
     a.ks = ctx->ks;
     a.W = ctx->W;
     a.col0 = cb;
+    const int CR = heig_rows(ctx->k);
+    a.tc = (ctx->k + CR - 1) / CR;
+    a.td = (ctx->k + 63) / 64;
+}
+
+void launch_heig_basis(pml_ctx* ctx, int cols, const PmlHeigArgs& a) {
+    const int kp = (a.k + 15) & ~15;
+    const size_t lds = (size_t)(16 * (kp + 1) + 16) * sizeof(double);   // (35 KB at 256 states)
+    const dim3 tiles((a.N + 15) / 16, cols);
+    if (a.k >= 16) hipLaunchKernelGGL(heig_basis_kernel<true>, tiles, dim3(256), lds, ctx->stream, a);
+    else hipLaunchKernelGGL(heig_basis_kernel<false>, tiles, dim3(256), lds, ctx->stream, a);
+}
+
+// d_times [cols][k]; d_jumps [cols][k][k] or null; d_branch [cols][N] (caller's numbering) or null.  Queued only: the staged
+// vectors and the partials live in the caller's scope, which makes the call's one wait.
+PML_INTERNAL int launch_history_eigen(pml_ctx* ctx, CallScope& mem, int cb, int ce, double* d_times, double* d_jumps, double* d_branch) {
+    const int k = ctx->k, N = ctx->N, cols = ce - cb;
+    if (k < 2 || k > 256) return fail(PML_ERR_UNSUPPORTED, "k = %d: the eigen models' history takes 2 to 256 states", k);
+    PmlHeigArgs a;
+    heig_args(ctx, cb, a);
     a.n_pieces = (N + PML_HEIG_PIECE - 1) / PML_HEIG_PIECE;
-    const int CR = heig_rows(k);
-    a.tc = (k + CR - 1) / CR;
-    a.td = (k + 63) / 64;
     a.times_out = d_times;
     a.jumps_out = d_jumps;
     a.branch_out = d_branch;
-    a.qdiag = a.G = a.bpart = nullptr;
     const size_t kk = (size_t)k * k;
     PML_TRY(mem.get(&a.stage, (size_t)cols * N * 3 * ctx->ks));
     PML_TRY(mem.get(&a.tprime, (size_t)cols * N));
@@ -56,16 +68,10 @@ PML_INTERNAL int launch_history_eigen(pml_ctx* ctx, CallScope& mem, int cb, int 
         hipLaunchKernelGGL(heig_qdiag_kernel, dim3(cols), dim3(256), 0, ctx->stream, a);
         hipLaunchKernelGGL(heig_g_kernel, square, dim3(256), 0, ctx->stream, a);
     }
-    const int kp = (k + 15) & ~15;
-    const size_t lds = (size_t)(16 * (kp + 1) + 16) * sizeof(double);   // (35 KB at 256 states)
-    const dim3 tiles((N + 15) / 16, cols);
-    if (k >= 16) hipLaunchKernelGGL(heig_basis_kernel<true>, tiles, dim3(256), lds, ctx->stream, a);
-    else hipLaunchKernelGGL(heig_basis_kernel<false>, tiles, dim3(256), lds, ctx->stream, a);
-    const dim3 grid(a.n_pieces, a.tc * a.td, cols);
-    if (CR == 4) hipLaunchKernelGGL(heig_pair_kernel<4>, grid, dim3(256), 0, ctx->stream, a);
-    else if (CR == 16) hipLaunchKernelGGL(heig_pair_kernel<16>, grid, dim3(256), 0, ctx->stream, a);
-    else if (CR == 32) hipLaunchKernelGGL(heig_pair_kernel<32>, grid, dim3(256), 0, ctx->stream, a);
-    else hipLaunchKernelGGL(heig_pair_kernel<64>, grid, dim3(256), 0, ctx->stream, a);
+    launch_heig_basis(ctx, cols, a);
+    with_heig_rows(k, [&](auto CR) {
+        hipLaunchKernelGGL(heig_pair_kernel<CR()>, dim3(a.n_pieces, a.tc * a.td, cols), dim3(256), 0, ctx->stream, a);
+    });
     hipLaunchKernelGGL(heig_reduce_kernel, square, dim3(256), 0, ctx->stream, a);
     hipLaunchKernelGGL(heig_t1_kernel, square, dim3(256), 0, ctx->stream, a);
     hipLaunchKernelGGL(heig_times_kernel, dim3(cols), dim3(256), 0, ctx->stream, a);

@@ -33,31 +33,9 @@ PML_INTERNAL int launch_history_time_eigen(pml_ctx* ctx, CallScope& mem, int cb,
                                            double* d_times, double* d_jumps, double* d_lineages) {
     const int k = ctx->k, N = ctx->N, cols = ce - cb, M = host.plan.M;
     if (k < 2 || k > 256) return fail(PML_ERR_UNSUPPORTED, "k = %d: the eigen models' history takes 2 to 256 states", k);
-    PmlHteArgs t;
+    PmlHteArgs t{};   // (what the lineages alone need stays null without them)
     PmlHeigArgs& a = t.h;
-    a.parent = ctx->d_parent;
-    a.n_children = ctx->d_n_children;
-    a.new_of_old = ctx->d_new_of_old;   // (null when the library works in the caller's numbering)
-    a.dist = ctx->d_dist;
-    a.masks = ctx->d_masks;
-    a.bu = ctx->d_bu;
-    a.post = ctx->d_post;
-    a.ev = ctx->d_d;
-    a.A = ctx->d_A;
-    a.Ainv = ctx->d_Ainv;
-    a.sf = ctx->d_sf;
-    a.tau = ctx->d_tau;
-    a.tauf = ctx->d_tauf;
-    a.N = N;
-    a.k = k;
-    a.ks = ctx->ks;
-    a.W = ctx->W;
-    a.col0 = cb;
-    a.n_pieces = 0;   // (the pieces are the plan's, below)
-    const int CR = heig_rows(k);   // (pml_launch_history_eigen.hip has the reasons)
-    a.tc = (k + CR - 1) / CR;
-    a.td = (k + 63) / 64;
-    a.partial = a.Wsum = a.T1 = a.qdiag = a.G = a.bpart = a.times_out = a.branch_out = a.jumps_out = nullptr;
+    heig_args(ctx, cb, a);   // (its pieces stay 0: the pieces are the plan's, below)
     t.M = M;
     t.n_segments = host.plan.n_interval_segments();
     t.n_pieces = host.pieces.n_pieces();
@@ -65,9 +43,6 @@ PML_INTERNAL int launch_history_time_eigen(pml_ctx* ctx, CallScope& mem, int cb,
     t.times_out = d_times;
     t.jumps_out = d_jumps;
     t.lineages_out = d_lineages;
-    t.lin_node = t.lpiece_off = t.bin_lpiece_off = nullptr;
-    t.lin_frac = nullptr;
-    t.lpart = nullptr;
     const size_t kk = (size_t)k * k, S = (size_t)t.n_segments;
     int *d_node, *d_piece_off, *d_bin_piece_off;
     double* d_frac;
@@ -86,18 +61,12 @@ PML_INTERNAL int launch_history_time_eigen(pml_ctx* ctx, CallScope& mem, int cb,
     PML_TRY(mem.get(&t.partial, (size_t)cols * t.n_pieces * kk));
     PML_TRY(mem.get(&t.Wsum, (size_t)cols * M * kk));
     PML_TRY(mem.get(&t.T1, (size_t)cols * M * kk));
-    const int kp = (k + 15) & ~15;
-    const size_t lds = (size_t)(16 * (kp + 1) + 16) * sizeof(double);   // (35 KB at 256 states)
-    const dim3 tiles((N + 15) / 16, cols);
-    if (k >= 16) hipLaunchKernelGGL(heig_basis_kernel<true>, tiles, dim3(256), lds, ctx->stream, a);
-    else hipLaunchKernelGGL(heig_basis_kernel<false>, tiles, dim3(256), lds, ctx->stream, a);
+    launch_heig_basis(ctx, cols, a);
     if (t.n_pieces > 0) {
         hipLaunchKernelGGL(hte_segment_kernel, dim3((unsigned)((S * k + 255) / 256), cols), dim3(256), 0, ctx->stream, t);
-        const dim3 grid(t.n_pieces, a.tc * a.td, cols);
-        if (CR == 4) hipLaunchKernelGGL(hte_pair_kernel<4>, grid, dim3(256), 0, ctx->stream, t);
-        else if (CR == 16) hipLaunchKernelGGL(hte_pair_kernel<16>, grid, dim3(256), 0, ctx->stream, t);
-        else if (CR == 32) hipLaunchKernelGGL(hte_pair_kernel<32>, grid, dim3(256), 0, ctx->stream, t);
-        else hipLaunchKernelGGL(hte_pair_kernel<64>, grid, dim3(256), 0, ctx->stream, t);
+        with_heig_rows(k, [&](auto CR) {
+            hipLaunchKernelGGL(hte_pair_kernel<CR()>, dim3(t.n_pieces, a.tc * a.td, cols), dim3(256), 0, ctx->stream, t);
+        });
     }
     const dim3 square((unsigned)(M * ((kk + 255) / 256)), cols);
     hipLaunchKernelGGL(hte_reduce_kernel, square, dim3(256), 0, ctx->stream, t);
@@ -117,6 +86,7 @@ PML_INTERNAL int launch_history_time_eigen(pml_ctx* ctx, CallScope& mem, int cb,
         t.bin_lpiece_off = d_bin_lpiece_off;
         PML_TRY(mem.get(&t.lpart, (size_t)cols * t.n_lpieces * k));
         if (t.n_lpieces > 0) {
+            const int kp = (k + 15) & ~15;
             const size_t llds = (size_t)(16 * (kp + 1) + 48) * sizeof(double) + 16 * sizeof(int);
             const dim3 lgrid(t.n_lpieces, cols);
             if (k >= 16) hipLaunchKernelGGL(hte_lineage_kernel<true>, lgrid, dim3(256), llds, ctx->stream, t);

@@ -235,8 +235,8 @@ def test_200_bins_on_a_3_tip_tree():
 # pieces
 # ---------------------------------------------------------------------------------------------------------------------
 
-# (k, segments per piece): the segment pass's 1024, 512 and 256 (history_time_piece), the jump product's 2048 and 4096
-# (history_time_jump_piece; pml_launch_history_time.hip)
+# (k, segments per piece): the segment pass's 1024, 512 and 256 (history_piece), the jump product's 2048 and 4096
+# (history_jump_piece; pml_launch_history.hip)
 PIECES = [(4, 1024), (5, 512), (65, 256), (2, 2048), (65, 4096)]
 
 
